@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - image->first-token latency + decode tokens/s of the Vision-Zephyr hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): Zephyr-7B-beta
@@ -17,10 +17,16 @@ GPUs (RCCL all-reduce / all-gather over xGMI inside the per-token graph) + the i
 no data-path collective (the reference's own multi-GPU inference scheme, ref:script/eval/eval_qa.sh:21-47).  The TP engine is
 measured by child processes with a time limit; if RCCL fails there the line falls back to the replica numbers and says so.
 
-Extra objects: `roofline` (the dominant kernel by time: the decode weight-streaming GEMV, HBM-bound;
-HIP events on the launch stream in an instrumented replay of decode steps right after the timed
-region), `roofline_prefill` (MFMA tile GEMM of the prefill, same method) and `cpu_baseline` (the CPU
-oracle = port of the reference's fp32 CPU path, timed on this box's host cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the line (plus the outputs, with --dump-outputs).
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step returned to the caller - the greedy ids,
+[1, new_tokens] - as DIR/generated_ids.npy (float64).  The inputs are seeded, so two builds can be compared id for id.
+
+--full adds the extra objects, measured after the timed region: `roofline` (the dominant kernel by time: the decode
+weight-streaming GEMV, HBM-bound; HIP events on the launch stream in an instrumented replay of decode steps), `roofline_prefill`
+(MFMA tile GEMM of the prefill, same method), `parity` (the request against the reference's fixture), `streamer_path`,
+`persistent_kernel`, `fp8_weights` (the W8A16 engine, in a child process), `cpu_baseline` (the CPU oracle = port of the
+reference's fp32 CPU path, timed on the host cores on a bounded sample) and, in tensor-parallel mode, `xgmi` (per-collective
+times and the one-shot all-reduce probe).  Without --full those keys are absent or null.
 """
 import argparse
 import json
@@ -372,6 +378,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp8-leg", action="store_true", help="skip the extra W8A16 (e4m3 weight stream) measurement")
     ap.add_argument("--fp8-leg-only", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's generated ids to DIR/generated_ids.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs after the timed region: rooflines, reference parity, streamer and persistent paths, "
+                         "the W8A16 engine, the CPU baseline, the tensor-parallel xGMI timings and one-shot probe")
     args = ap.parse_args()
     if args.fp8_leg_only:
         return fp8_leg_only(args)
@@ -423,6 +434,8 @@ def main():
             dist.barrier()
         sync()
 
+    last_out = [None]      # what the latest step returned to its caller (--dump-outputs)
+
     def step():
         tm = {}
         t0 = time.perf_counter()
@@ -431,6 +444,7 @@ def main():
         sync()
         t2 = time.perf_counter()
         assert out.shape == (1, n_new)
+        last_out[0] = out
         return tm["t_first_token"] - t0, t2 - tm["t_first_token"]
 
     for _ in range(args.warmup):
@@ -448,11 +462,15 @@ def main():
     if dist is not None:
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
     elapsed, ttft_sum, dec_sum = stats.tolist()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "generated_ids.npy"), last_out[0].cpu().numpy().astype(np.float64))
 
-    # ---- tensor-parallel mode: per-collective time from HIP events (every rank runs the instrumented replay: the collectives need
-    # all of them), so that a multi-GPU run yields xGMI numbers ----
+    # ---- --full, tensor-parallel mode: per-collective time from HIP events (every rank runs the instrumented replay: the collectives
+    # need all of them), so that a multi-GPU run yields xGMI numbers ----
     xgmi = None
-    if tp_mode and not dry:
+    if tp_mode and not dry and args.full:
         emb = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, [tiles])[4]
         eng.prof_enable(True, B.K_COMM)
         _, last = eng.prefill(emb, [S])
@@ -530,9 +548,9 @@ def main():
                     pass
             xgmi["oneshot_probe"] = probe
 
-    # ---- roofline legs: instrumented replays of the same work, HIP events on the launch stream ----
+    # ---- --full, roofline legs: instrumented replays of the same work, HIP events on the launch stream ----
     roof, roof_prefill, parity, stream_leg, persist_leg = None, None, None, None, None
-    if rank == 0 and not tp_mode and not dry:          # (a tensor-parallel engine needs every rank inside each collective)
+    if args.full and rank == 0 and not tp_mode and not dry:          # (a tensor-parallel engine needs every rank inside each collective)
         w_bytes, pre_flops = algorithmic_work(cfg, S, n_tiles)
         emb = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, [tiles])[4]
         _, last = eng.prefill(emb, [S])
@@ -588,12 +606,12 @@ def main():
             stream_leg = streamer_leg(model, ids, tiles, n_new, args.steps)
             persist_leg = persistent_leg(model, ids, tiles, n_new)
 
-    # ---- extra leg (never `value`): the same request on the W8A16 engine of SURVEY config 5 - e4m3 weights with per-row
+    # ---- --full, extra leg (never `value`): the same request on the W8A16 engine of SURVEY config 5 - e4m3 weights with per-row
     # power-of-two scales streamed by the decode GEMV, bf16 activations, bf16 MFMA prefill on the dequantised weights.
     # Runs in a CHILD process with a time limit (as the tensor-parallel leg does): whatever happens there - an exception, a
     # stall while the second engine is built - the bf16 line of this process is printed. ----
     fp8_leg = None
-    if world == 1 and not args.no_fp8_leg and not dry:
+    if args.full and world == 1 and not args.no_fp8_leg and not dry:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--fp8-leg-only", "--steps", str(args.steps), "--layers", str(args.layers),
                "--new-tokens", str(args.new_tokens)]
@@ -625,6 +643,8 @@ def main():
             env.pop(k)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--steps", str(args.steps), "--warmup", str(max(1, args.warmup)),
                "--layers", str(args.layers), "--new-tokens", str(args.new_tokens), "--no-cpu-baseline", "--no-fp8-leg"]
+        if args.full:
+            cmd.append("--full")
         limit = int(os.environ.get("VZ_BENCH_TP_TIMEOUT", "300"))
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=limit)
@@ -649,7 +669,7 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and not dry:
+    if args.full and not args.no_cpu_baseline and world == 1 and not dry:
         try:
             cpu = cpu_baseline(cfg, S, n_tiles, n_new)
         except Exception as ex:   # the GPU numbers stand on their own; say why the CPU leg is missing

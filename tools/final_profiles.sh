@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end evidence, written under gpurun_out/final/ (copy what is to be judged into profiles/):
-#   bench_line.json                 default `python bench.py` line (cpu_baseline + fp8 leg included)
+#   bench_line.json                 `python bench.py --full` line (cpu_baseline + fp8 leg included)
 #   bench_kernel_stats.csv          rocprofv3 --kernel-trace --stats of the same command (summary only)
 #   bench_phase_breakdown.txt       per-kernel time inside image->first-token and decode (tools/analyze_trace.py)
 #   bench_line_under_rocprof.json   the line printed by the profiled run
@@ -8,10 +8,11 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/final
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py > $OUT/bench_line.json 2> $OUT/bench_stderr.log || exit 1
+REPO=$PWD
+timeout -k 10 500 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_stderr.log || exit 1
 echo "bench done"; cut -c1-200 $OUT/bench_line.json
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_final
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_final -o b --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > /tmp/prof_final.log 2>&1 || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_final -o b --output-format csv -- python3 "$REPO/bench.py" --full --no-cpu-baseline > /tmp/prof_final.log 2>&1 || exit 1
 grep "^{" /tmp/prof_final.log | tail -1 > $OUT/bench_line_under_rocprof.json
 cp $(find /tmp/prof_final -name "b_kernel_stats.csv") $OUT/bench_kernel_stats.csv
 python3 $GRAFT_REPO_ROOT/tools/analyze_trace.py $(find /tmp/prof_final -name "b_kernel_trace.csv") > $OUT/bench_phase_breakdown.txt
