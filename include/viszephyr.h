@@ -359,6 +359,26 @@ int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_pos, int ct
  * one call must not overlap (no destination equal to another move's source or destination). */
 int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const int* h_dst, const int* h_len, vz_stream stream);
 
+/* ---- beam search (hf:generation/utils.py `_beam_search`, do_sample=False; csrc/beam.hip; vz_hip/beam.py replays the records) ----
+ * K = max(2, 1 + n_eos) * nb candidates per group and step; equal scores go to the smaller flat index beam * V + token.
+ * vz_llm_decode_beam(enable=1): the tail of every decode step selects beams on the device.  The running decode batch holds `groups`
+ * prompts x `nb` (2..16) beam rows (row g * nb + j); d_scores [groups * nb] = the running beam scores, h_base[g] = prompt length of
+ * group g, d_hist = history records int32 [hist_steps][groups][K][3] = {fp32 score bits, token, parent beam}, appended at a
+ * device-side step index that restarts at 0 here.  After each selection the cache positions [h_base[g], slot) of every row whose
+ * parent is another row become the parent's (in place, bit-exact).  enable = 0: argmax / the sampler again.  tp_size > 1: unsupported.
+ * vz_op_beam_select: the same selection on fp32 logits [rows = groups * nb_in, cols] with running scores d_scores_in [rows] (NULL = 0):
+ * d_records [groups][K][3] and the next running beams d_next_tok / d_next_score / d_next_parent [groups * nb_out] (the first step:
+ * nb_in = 1 on the prefill logits).  vz_llm_kv_beam_reorder: the reorder alone, positions [h_base[g], h_end[g]) of group g, local parent
+ * indices d_parent [groups * nb] on the device. */
+int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, const int* h_eos, int n_eos, const int* h_base,
+                       const float* d_scores, int* d_hist, int hist_steps, vz_stream stream);
+int vz_op_beam_select(const float* d_logits, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                      const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent, vz_stream stream);
+int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, const int* h_end, const int* d_parent, vz_stream stream);
+/* device-to-device copy of the whole KV cache (bf16 [layer][K|V][max_batch][kv head][max_ctx][head_dim]) into d_out; *bytes = its
+ * size (d_out = NULL: the size only).  Tests. */
+int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* bytes, vz_stream stream);
+
 /* ---- anyres preprocessing on the device (ref:vis_zephyr/model/multi_scale_process.py:70-171) ----
  * vz_op_resample_u8: Pillow's 8-bit LANCZOS `Image.resize` (horizontal pass, 8-bit intermediate, vertical pass) of an
  * [h, w, 3] u8 image to [h2, w2, 3], bit-exact.  bounds int32 [out, 2] = (first tap, tap count), coefs int32 [out, k] at 22

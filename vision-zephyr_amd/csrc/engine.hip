@@ -270,6 +270,10 @@ struct vz_engine {
     std::vector<int> h_len, h_pos; std::vector<char> h_parked;
     // sampling tail (vz_llm_decode_sampling): off = greedy argmax
     int samp_on = 0, samp_top_k = 0, samp_ctr0 = 0; float samp_temp = 1.f, samp_top_p = 1.f; unsigned samp_seed[2] = {0, 0};
+    // beam tail (vz_llm_decode_beam): groups x nb rows; d_beam = [score (fp32) | parent | base | hidx, pad | base, end of a standalone
+    // reorder | candidate scores | candidate tokens] (BEAM_ROWS rows); beam_hist = the caller's history records, beam_hist_cap steps
+    static constexpr int BEAM_ROWS = 64, BEAM_K = 80;
+    int beam_on = 0, beam_nb = 0, beam_groups = 0, beam_hist_cap = 0; BeamEos beam_eos{0, {0, 0, 0, 0}}; int* beam_hist = nullptr; int* d_beam = nullptr;
     int* ring = nullptr; int ring_n = 0, ring_rows = 0;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [ring_rows][ring_n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_nsplit = 1;          // context splits of the decode attention for the steps being launched
@@ -284,7 +288,7 @@ struct vz_engine {
     bool use_tok = false;               // the steps being launched run on it (decided per vz_llm_decode_steps call)
     int tok_poke_word = -1; unsigned tok_poke_value = 0;      // TEST HOOK (vz_test_persist_poke): applied once, behind the next counter reset
     hipStream_t cap_stream = nullptr;   // stream capture is not allowed on the legacy null stream torch hands us
-    hipGraphExec_t dec_graph = nullptr; int dec_graph_B = 0, dec_graph_n = 0, dec_graph_nsplit = 0, dec_graph_tok = -1; long dec_graph_samp[6] = {0, 0, 0, 0, 0, 0}; int* dec_graph_out = nullptr; char* dec_graph_arena = nullptr;
+    hipGraphExec_t dec_graph = nullptr; int dec_graph_B = 0, dec_graph_n = 0, dec_graph_nsplit = 0, dec_graph_tok = -1; long dec_graph_samp[6] = {0, 0, 0, 0, 0, 0}; long dec_graph_beam[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int* dec_graph_out = nullptr; char* dec_graph_arena = nullptr;
     int* h_pinned = nullptr;     // pinned staging for small host->device uploads
     size_t h_pinned_ints = 0;
     // profiling
@@ -530,6 +534,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_ao_done) hipFree(e->d_ao_done);
     if (e->d_ferr) hipFree(e->d_ferr);
     if (e->d_xnorm) hipFree(e->d_xnorm);
+    if (e->d_beam) hipFree(e->d_beam);
     if (e->d_gather) (void)hipFree(e->d_gather);
     vz_decode_persist_destroy(e->tok);
     if (e->comm) (void)ncclCommDestroy(e->comm);
@@ -1271,7 +1276,18 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     }
     {
         ProfScope ps(e, K_OTHER, s);
-        if (e->samp_on)
+        if (e->beam_on) {
+            // beam tail (beam.hip): select, then the KV of rows whose parent is another row follows the parent, then the history index
+            const int nb = e->beam_nb, rows = e->beam_nb * e->beam_groups;
+            float* score = (float*)e->d_beam; int* parent = e->d_beam + vz_engine::BEAM_ROWS; int* base = parent + vz_engine::BEAM_ROWS;
+            int* hidx = base + vz_engine::BEAM_ROWS;
+            float* cand_s = (float*)(hidx + 4 + 2 * vz_engine::BEAM_ROWS); int* cand_t = (int*)cand_s + vz_engine::BEAM_ROWS * vz_engine::BEAM_K;
+            RC(vz_launch_beam_select(e->d_logits, rows, c.vocab, nb, nb, e->beam_eos, score, cand_s, cand_t, e->beam_hist, hidx, e->beam_hist_cap,
+                                     cur, score, parent, pos, slot, len, d_out_ids, out_stride, step, c.max_ctx, e->rope_max, s));
+            RC(vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, nb, e->beam_groups,
+                                         parent, base, nb, slot, nb, s));
+            RC(vz_launch_beam_advance(hidx, s));
+        } else if (e->samp_on)
             RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp_temp, e->samp_top_k, e->samp_top_p, (const unsigned*)(step + 2), step + 1, 0, cur, pos,
                                 slot, len, d_out_ids, out_stride, step, c.max_ctx, e->rope_max, e->ring, e->ring_n, s));
         else
@@ -1322,6 +1338,102 @@ extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float tem
                             nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s);
 }
 
+static int ensure_beam_state(vz_engine* e) {
+    if (e->d_beam) return VZ_OK;
+    const size_t ints = 4 + 5 * (size_t)vz_engine::BEAM_ROWS + 2 * (size_t)vz_engine::BEAM_ROWS * vz_engine::BEAM_K;
+    VZ_CHECK_HIP(hipMalloc((void**)&e->d_beam, ints * sizeof(int)));
+    VZ_CHECK_HIP(hipMemset(e->d_beam, 0, ints * sizeof(int)));
+    return VZ_OK;
+}
+
+static int beam_eos_of(const int* h_eos, int n_eos, BeamEos* out) {
+    VZ_CHECK_ARG(n_eos >= 0 && n_eos <= 4 && (n_eos == 0 || h_eos), "beam: 0..4 eos ids expected, got %d", n_eos);
+    out->n = n_eos;
+    for (int i = 0; i < 4; ++i) out->id[i] = i < n_eos ? h_eos[i] : -1;
+    return VZ_OK;
+}
+
+// Beam search (hf:generation/utils.py `_beam_search`, do_sample=False; beam.hip): after vz_llm_decode_beam(enable=1) the tail of every
+// decode step chooses beams instead of argmax.  The running batch (vz_llm_decode_begin) holds `groups` prompts x `nb` beam rows, row
+// g * nb + j; `d_scores` [groups * nb] are the running beam scores after the first step, h_base[g] the prompt length of group g (the
+// cache positions from there on follow the chosen parents), d_hist the history records [hist_steps][groups][K][3] ({score bits, token,
+// parent beam}; K = max(2, 1 + n_eos) * nb), written at a device-side index that restarts at 0 here.  enable = 0: the tail is argmax /
+// the sampler again.
+extern "C" int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, const int* h_eos, int n_eos, const int* h_base,
+                                  const float* d_scores, int* d_hist, int hist_steps, vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->beam_on = 0; e->beam_hist = nullptr; return VZ_OK; }
+    const vz_config& c = e->c;
+    if (e->tp > 1) { vz_set_error("decode_beam: beam search on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(nb >= 2 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, vz_engine::BEAM_ROWS) && h_base && d_scores &&
+                 d_hist && hist_steps >= 1, "decode_beam: %d groups x %d beams (2..16) must fit min(max_batch %d, 64) rows; base, scores and "
+                 "history needed", groups, nb, c.max_batch);
+    BeamEos eos;
+    RC(beam_eos_of(h_eos, n_eos, &eos));
+    for (int g = 0; g < groups; ++g) VZ_CHECK_ARG(h_base[g] >= 0 && h_base[g] < c.max_ctx, "decode_beam: base[%d] = %d outside [0, %d)", g, h_base[g], c.max_ctx);
+    RC(ensure_beam_state(e));
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = nb * groups, R = vz_engine::BEAM_ROWS;
+    std::vector<int> h(2 * R + 4, 0);            // [parent | base | hidx, pad]
+    for (int r = 0; r < rows; ++r) { h[r] = r % nb; h[R + r] = h_base[r / nb]; }
+    RC(upload_ints(e, h.data(), h.size(), e->d_beam + R, s));
+    VZ_CHECK_HIP(hipMemcpyAsync(e->d_beam, d_scores, rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    e->beam_on = 1; e->beam_nb = nb; e->beam_groups = groups; e->beam_eos = eos; e->beam_hist = d_hist; e->beam_hist_cap = hist_steps;
+    return VZ_OK;
+}
+
+// The beam tail's selection on given fp32 logits [rows, cols] (rows = groups * nb_in beam rows, running scores d_scores_in [rows] or
+// NULL = 0): the group's top K candidates -> d_records [groups][K][3] ({score bits, token, parent beam}), the first nb_out non-eos
+// ones -> d_next_tok / d_next_score / d_next_parent [groups * nb_out].  The first step of a beam search: nb_in = 1 on the prefill logits.
+extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                                 const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
+                                 vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_logits && d_records && d_next_tok && rows >= 1 && cols >= 1 && nb_in >= 1 && nb_in <= 16 && nb_out >= 1 && nb_out <= 16 &&
+                 rows % nb_in == 0, "beam_select: bad argument");
+    BeamEos eos;
+    RC(beam_eos_of(h_eos, n_eos, &eos));
+    const int K = vz_beam_k(nb_out, n_eos);
+    void* p = nullptr; size_t have = 0;
+    RC(vz_stream_ws(5, s, (size_t)rows * K * 2 * sizeof(int), false, &p, &have));
+    VZ_CHECK_ARG(p && have >= (size_t)rows * K * 2 * sizeof(int), "beam_select: first use of a stream inside a capture (call it once before capturing)");
+    float* cand_s = (float*)p; int* cand_t = (int*)p + (size_t)rows * K;
+    return vz_launch_beam_select(d_logits, rows, cols, nb_in, nb_out, eos, d_scores_in, cand_s, cand_t, d_records, nullptr, 1, d_next_tok,
+                                 d_next_score, d_next_parent, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, s);
+}
+
+// The beam tail's KV reorder on its own: for every group g of `nb` rows (row g * nb + j), cache positions [h_base[g], h_end[g]) of row j
+// become those of row d_parent[g * nb + j] of the same group (device ints, local beam indices), every layer, K and V, in place.
+extern "C" int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, const int* h_end, const int* d_parent, vz_stream stream) {
+    NEED_READY();
+    const vz_config& c = e->c;
+    VZ_CHECK_ARG(nb >= 1 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, vz_engine::BEAM_ROWS) && h_base && h_end && d_parent,
+                 "kv_beam_reorder: %d groups x %d rows must fit min(max_batch %d, 64)", groups, nb, c.max_batch);
+    for (int g = 0; g < groups; ++g)
+        VZ_CHECK_ARG(h_base[g] >= 0 && h_base[g] <= h_end[g] && h_end[g] <= c.max_ctx, "kv_beam_reorder: group %d range [%d, %d) outside [0, %d]", g, h_base[g], h_end[g], c.max_ctx);
+    RC(ensure_beam_state(e));
+    hipStream_t s = (hipStream_t)stream;
+    const int R = vz_engine::BEAM_ROWS;
+    int* tb = e->d_beam + 3 * R + 4;            // [base | end] per group
+    std::vector<int> h(2 * R, 0);
+    for (int g = 0; g < groups; ++g) { h[g] = h_base[g]; h[R + g] = h_end[g]; }
+    RC(upload_ints(e, h.data(), h.size(), tb, s));
+    return vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, nb, groups, d_parent,
+                                     tb, 1, tb + R, 1, s);
+}
+
+// A device-to-device copy of the whole KV cache ([layer][K|V][max_batch][kv head][max_ctx][head_dim] bf16) into d_out (tests):
+// *bytes receives its size; d_out = NULL only asks for it.
+extern "C" int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* bytes, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(bytes, "kv_copy_out: null size");
+    *bytes = e->kv_layer_elems * e->c.n_layers * sizeof(bf16_t);
+    if (!d_out) return VZ_OK;
+    VZ_CHECK_ARG(max_bytes >= *bytes, "kv_copy_out: %zu bytes do not hold the %zu-byte cache", max_bytes, *bytes);
+    VZ_CHECK_HIP(hipMemcpyAsync(d_out, e->kv, *bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return VZ_OK;
+}
+
 extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d_logits_dbg, vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
@@ -1330,6 +1442,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(n >= 1 && d_out_ids, "decode_steps: bad argument");
     const int B = e->dec_B;
     VZ_CHECK_ARG(!e->ring || B <= e->ring_rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring_rows, B);
+    VZ_CHECK_ARG(!e->beam_on || (B == e->beam_nb * e->beam_groups && !e->ring), "decode_steps: the beam tail needs a decode batch of exactly "
+                 "%d x %d rows (it has %d) and no token ring", e->beam_groups, e->beam_nb, B);
     const size_t need = ((size_t)B * (3 * c.hidden + (c.n_heads + 2 * c.n_kv_heads) * c.head_dim + c.inter)) * 2 + 8192;   // upper bound (tp = 1 sizes)
     RC(ensure_arena(e, need));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of
@@ -1402,8 +1516,14 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     // they change (seed and draw counter live in device memory and do not).
     long samp_key[6] = {e->samp_on, e->samp_top_k, 0, 0, (long)(uintptr_t)e->ring, e->ring_n};
     memcpy(&samp_key[2], &e->samp_temp, 4); memcpy(&samp_key[3], &e->samp_top_p, 4);
+    // the beam tail's mode, shape, eos ids and history buffer are kernel arguments too
+    long beam_key[8] = {e->beam_on, e->beam_on ? e->beam_nb : 0, e->beam_on ? e->beam_groups : 0, e->beam_on ? (long)(uintptr_t)e->beam_hist : 0,
+                        e->beam_on ? e->beam_hist_cap : 0, e->beam_on ? e->beam_eos.n : 0,
+                        e->beam_on ? ((long)(unsigned)e->beam_eos.id[0] << 32 | (unsigned)e->beam_eos.id[1]) : 0,
+                        e->beam_on ? ((long)(unsigned)e->beam_eos.id[2] << 32 | (unsigned)e->beam_eos.id[3]) : 0};
     if (!e->dec_graph || e->dec_graph_B != B || e->dec_graph_n != n || e->dec_graph_out != d_out_ids || e->dec_graph_arena != e->arena ||
-        e->dec_graph_nsplit != e->dec_nsplit || e->dec_graph_tok != ((int)e->use_tok | (g_attn_o << 1)) || memcmp(e->dec_graph_samp, samp_key, sizeof(samp_key)) != 0) {
+        e->dec_graph_nsplit != e->dec_nsplit || e->dec_graph_tok != ((int)e->use_tok | (g_attn_o << 1)) || memcmp(e->dec_graph_samp, samp_key, sizeof(samp_key)) != 0 ||
+        memcmp(e->dec_graph_beam, beam_key, sizeof(beam_key)) != 0) {
         if (e->dec_graph) { hipGraphExecDestroy(e->dec_graph); e->dec_graph = nullptr; }
         hipGraph_t graph;
         if (!e->cap_stream) VZ_CHECK_HIP(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
@@ -1426,7 +1546,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             for (int i = 0; i < n; ++i) RC(decode_step_launch(e, d_out_ids, n, nullptr, s));
             return VZ_OK;
         }
-        e->dec_graph_B = B; e->dec_graph_n = n; e->dec_graph_out = d_out_ids; e->dec_graph_arena = e->arena; e->dec_graph_nsplit = e->dec_nsplit; e->dec_graph_tok = (int)e->use_tok | (g_attn_o << 1); memcpy(e->dec_graph_samp, samp_key, sizeof(samp_key));
+        e->dec_graph_B = B; e->dec_graph_n = n; e->dec_graph_out = d_out_ids; e->dec_graph_arena = e->arena; e->dec_graph_nsplit = e->dec_nsplit; e->dec_graph_tok = (int)e->use_tok | (g_attn_o << 1); memcpy(e->dec_graph_samp, samp_key, sizeof(samp_key)); memcpy(e->dec_graph_beam, beam_key, sizeof(beam_key));
     }
     for (int i = 0; i < n; ++i) VZ_CHECK_HIP(hipGraphLaunch(e->dec_graph, s));
     return VZ_OK;

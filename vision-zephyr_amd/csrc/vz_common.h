@@ -333,6 +333,16 @@ struct KvMoves { int n; int src[16], dst[16], len[16]; };
 int vz_launch_kv_move_rows(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, const KvMoves& mv,
                            hipStream_t s);
 int vz_launch_step_advance(int* step, hipStream_t s);
+// beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
+struct BeamEos { int n; int id[4]; };
+int vz_beam_k(int nb, int n_eos);
+int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
+                          float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
+                          int* next_parent, int* pos, int* slot, int* len, int* out_ids, int out_stride, const int* step, int max_ctx,
+                          int rope_max, hipStream_t s);
+int vz_launch_beam_advance(int* hidx, hipStream_t s);
+int vz_launch_kv_beam_reorder(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, int nb, int groups,
+                              const int* parent, const int* base, int base_stride, const int* end, int end_stride, hipStream_t s);
 int vz_launch_repack_logits(const float* gathered, float* out, int rows, int Vp, int V, int tp, hipStream_t s);
 
 // ---- backward kernels of the Stage-1 training step (train.hip) ----

@@ -331,7 +331,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               num_beams: int = 1, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
                               sync_every: int = 16, timing: Optional[dict] = None, **unused):
         if num_beams != 1:
-            raise NotImplementedError("beam search is not on the reference's inference path (cli/eval use sampling/greedy)")
+            return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
+                                       eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing, **unused)
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         if max_new_tokens is None:
             max_new_tokens = 20 if max_length is None else max(1, max_length - S)
@@ -415,6 +416,121 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 done = done_at[:, chunk.shape[1] - 1]
             cols.append(chunk)
         return torch.cat(cols, dim=1).to(self.device)
+
+    # ---- beam search (hf:generation/utils.py `_beam_search`, do_sample=False; csrc/beam.hip + vz_hip/beam.py) ----------------
+    def _generate_beam(self, inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
+                       eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, length_penalty: float = 1.0,
+                       early_stopping=False, num_return_sequences: int = 1, return_dict_in_generate: bool = False,
+                       timing: Optional[dict] = None, **unused):
+        """Beam search over the prompts of a batch: `Bsz * num_return_sequences` rows of new tokens, HF's `sequences` of a
+        decoder-only model generating from inputs_embeds (shorter hypotheses filled as HF fills them, vz_hip.beam.fill_value).
+        Each prompt is prefilled once; its first step is chosen on the prefill logits (vz_op_beam_select), its prompt KV copied
+        into its num_beams cache rows, and then the decode steps run with the beam tail (selection + KV reorder on the device),
+        `sync_every` steps per host sync, whose history records the host replays (vz_hip.beam.BeamReplay) to keep HF's finished
+        hypotheses and to stop where HF stops."""
+        from vz_hip import beam as BM
+        from vz_hip import binding as B
+        eng = self.engine
+        nb = int(num_beams)
+        if do_sample:
+            raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not built: beam search here is deterministic")
+        if streamer is not None:
+            raise ValueError("`streamer` cannot be used with beam search (yet!). Make sure that `num_beams` is set to 1.")
+        if stopping_criteria is not None:
+            raise NotImplementedError("stopping_criteria with num_beams > 1: the beam tail stops on eos ids and the length limit only")
+        if eng.tp_size > 1:
+            raise NotImplementedError("beam search on a tensor-parallel engine (tp_size > 1) is not built")
+        if not 2 <= nb <= 16:
+            raise NotImplementedError(f"num_beams = {nb}: the device beam tail takes 2..16 beams")
+        if nb > min(eng.max_batch, 64):
+            raise ValueError(f"num_beams = {nb} exceeds the engine's max_batch ({eng.max_batch}): every beam needs a KV-cache row")
+        nrs = int(num_return_sequences)
+        if not 1 <= nrs <= nb:
+            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}.")
+        Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        if max_new_tokens is None:
+            max_new_tokens = 20 if max_length is None else max(1, max_length - S)
+        max_new = int(max_new_tokens)
+        if eos_token_id is None:
+            eos_token_id = self.generation_config.eos_token_id
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
+        if len(eos) > 4:
+            raise NotImplementedError(f"{len(eos)} eos ids: the beam tail takes up to 4")
+        if pad_token_id is None:
+            pad_token_id = self.generation_config.pad_token_id
+        fill = BM.fill_value(pad_token_id, eos)
+        inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
+        seqlens = self._seqlens(attention_mask, Bsz, S)
+        if max(seqlens) + max_new > eng.max_ctx:
+            raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
+        G = max(1, min(Bsz, min(eng.max_batch, 64) // nb))          # prompts per chunk: G * nb cache rows
+        hyps = []
+        for b0 in range(0, Bsz, G):
+            hyps += self._beam_chunk(inputs_embeds[b0:b0 + G], seqlens[b0:b0 + G],
+                                     None if position_ids is None else position_ids[b0:b0 + G], nb, max_new, eos,
+                                     float(length_penalty), early_stopping, nrs, max(1, int(sync_every)), timing)
+        n = max(len(t) for h in hyps for t, _ in h)
+        seqs = torch.full((Bsz * nrs, n), fill, dtype=torch.long)
+        scores = torch.empty(Bsz * nrs, dtype=torch.float32)
+        for b, h in enumerate(hyps):
+            for r, (t, sc) in enumerate(h):
+                seqs[b * nrs + r, :len(t)] = torch.tensor(t, dtype=torch.long)
+                scores[b * nrs + r] = sc
+        seqs = seqs.to(self.device)
+        if return_dict_in_generate:
+            return SimpleNamespace(sequences=seqs, sequences_scores=scores.to(self.device), scores=None, logits=None,
+                                   beam_indices=None, attentions=None, hidden_states=None, past_key_values=None)
+        return seqs
+
+    def _beam_chunk(self, embeds, seqlens, position_ids, nb, max_new, eos, length_penalty, early_stopping, nrs, sync_every, timing=None):
+        from vz_hip import beam as BM
+        from vz_hip import binding as B
+        eng = self.engine
+        G = embeds.shape[0]
+        R = G * nb
+        # every row parked (the cache moves below may only touch parked rows), then one prefill per prompt into its first beam row
+        eng.decode_begin(torch.zeros(R, dtype=torch.int32), [0] * R, [0] * R)
+        last = []
+        for g in range(G):
+            Sg = int(seqlens[g])
+            last.append(eng.prefill_rows(g * nb, embeds[g:g + 1, :Sg], [Sg],
+                                         None if position_ids is None else position_ids[g:g + 1, :Sg]))
+        last = torch.cat(last, 0).contiguous()
+        rec, tok, sc, _ = B.beam_select(last, None, 1, nb, eos)
+        replays = [BM.BeamReplay(nb, eos, max_new, length_penalty, early_stopping) for _ in range(G)]
+        s0, t0, p0 = BM.decode_records(rec)
+        if timing is not None:
+            import time
+            timing["t_first_token"] = time.perf_counter()        # the host holds every prompt's first step here
+        for g in range(G):
+            replays[g].step(s0[g], t0[g], p0[g])
+        if not all(r.done for r in replays):
+            src = [g * nb for g in range(G) for _ in range(1, nb)]
+            dst = [g * nb + j for g in range(G) for j in range(1, nb)]
+            eng.kv_move_rows(src, dst, [seqlens[d // nb] for d in dst])          # the prompt KV of each prompt into its beam rows
+            next_pos = [int(seqlens[r // nb]) if position_ids is None else int(position_ids[r // nb, seqlens[r // nb] - 1]) + 1
+                        for r in range(R)]
+            eng.decode_begin(tok, next_pos, [int(seqlens[r // nb]) for r in range(R)])
+            K = BM.beam_k(nb, len(eos))
+            hist = torch.empty(max(1, max_new - 1), G, K, 3, dtype=torch.int32, device=self.device)
+            eng.set_beam(True, nb, G, eos, [int(v) for v in seqlens], sc, hist)
+            try:
+                done_steps, remaining = 0, max_new - 1
+                while remaining > 0 and not all(r.done for r in replays):
+                    n = min(sync_every, remaining)
+                    eng.decode_steps(n)
+                    s, t, p = BM.decode_records(hist[done_steps:done_steps + n])      # the only host sync of the chunk
+                    done_steps += n
+                    remaining -= n
+                    for i in range(n):
+                        for g in range(G):
+                            if not replays[g].done:
+                                replays[g].step(s[i, g], t[i, g], p[i, g])
+            finally:
+                eng.set_beam(False)
+        return [r.best(nrs) for r in replays]
 
     # ---- continuous batching (SURVEY 8f rank 3): the 23 K-item eval loop without waiting for a batch's longest answer ----
     @torch.no_grad()

@@ -124,6 +124,10 @@ SYMBOLS = {
     "vz_train_adamw_step": (_I, [_P, _F, _F, _F, _F, _F, _P]),
     "vz_op_vip_point": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, _P]),
     "vz_op_sample": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P, _P]),
+    "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
+    "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "vz_llm_kv_copy_out": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -459,6 +463,33 @@ def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed:
                              float(1.0 if top_p is None else top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter), ptr(ids),
                              stream_ptr(logits.device)))
     return ids
+
+
+def beam_k(nb: int, n_eos: int) -> int:
+    """candidates per group and step (hf:generation/utils.py `_beam_search`: beams_to_keep)."""
+    return max(2, 1 + n_eos) * nb
+
+
+def beam_select(logits, scores, nb_in: int, nb_out: int, eos=()):
+    """the beam tail's selection on fp32 logits [groups * nb_in, V] with running scores [groups * nb_in] (None = 0) on the device
+    (beam.hip).  Returns (records int32 [groups, K, 3] = {fp32 score bits, token, parent beam}, next tokens int32, next scores fp32,
+    next parents int32 [groups * nb_out])."""
+    _need_cuda(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and logits.shape[0] % nb_in == 0
+    eos = [int(t) for t in eos]
+    groups, dev = logits.shape[0] // nb_in, logits.device
+    if scores is not None:
+        scores = scores.to(dev, torch.float32).contiguous()
+        assert scores.numel() == logits.shape[0]
+    K = beam_k(nb_out, len(eos))
+    rec = torch.empty(groups, K, 3, dtype=torch.int32, device=dev)
+    tok = torch.empty(groups * nb_out, dtype=torch.int32, device=dev)
+    sc = torch.empty(groups * nb_out, dtype=torch.float32, device=dev)
+    par = torch.empty(groups * nb_out, dtype=torch.int32, device=dev)
+    arr = (C.c_int * max(1, len(eos)))(*eos)
+    check(lib().vz_op_beam_select(ptr(logits), logits.shape[0], logits.shape[1], int(nb_in), int(nb_out), arr, len(eos), ptr(scores),
+                                  ptr(rec), ptr(tok), ptr(sc), ptr(par), stream_ptr(dev)))
+    return rec, tok, sc, par
 
 
 def op_async_error(device=None) -> int:

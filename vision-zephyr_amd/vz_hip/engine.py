@@ -591,6 +591,43 @@ class Engine:
         self._ring_keep = ring
         B.check(self.lib.vz_llm_decode_ring(self.h, B.ptr(ring), slots, rows))
 
+    def set_beam(self, on: bool, num_beams: int = 0, groups: int = 0, eos: Sequence[int] = (), base: Sequence[int] = (),
+                 scores: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None):
+        """tail of every decode step: beam selection on the device (beam.hip) for `groups` prompts x `num_beams` rows of the running
+        batch, running scores fp32 [groups * num_beams], prompt lengths `base` (the cache from there on follows the chosen parents),
+        history records hist int32 [steps, groups, K, 3] written at a device-side step index that restarts at 0 here.  off: argmax /
+        the sampler again."""
+        if not on:
+            self._beam_keep = None
+            B.check(self.lib.vz_llm_decode_beam(self.h, 0, 0, 0, None, 0, None, None, None, 0, self._s()))
+            return
+        eos = [int(t) for t in eos]
+        scores = scores.to(self.device, torch.float32).contiguous()
+        assert hist is not None and hist.dtype == torch.int32 and hist.is_contiguous() and hist.dim() == 4
+        self._beam_keep = (scores, hist)
+        ea = (C.c_int * max(1, len(eos)))(*eos)
+        ba = (C.c_int * len(base))(*[int(v) for v in base])
+        B.check(self.lib.vz_llm_decode_beam(self.h, 1, int(num_beams), int(groups), ea, len(eos), ba, B.ptr(scores), B.ptr(hist),
+                                            int(hist.shape[0]), self._s()))
+
+    def kv_beam_reorder(self, num_beams: int, groups: int, base: Sequence[int], end: Sequence[int], parent: torch.Tensor):
+        """for every group g: cache positions [base[g], end[g]) of row g * num_beams + j become those of row g * num_beams + parent[...]
+        (local beam indices, int32 on the device), every layer, K and V, in place - the beam tail's reorder on its own."""
+        parent = parent.to(self.device, torch.int32).contiguous()
+        arr = lambda v: (C.c_int * groups)(*[int(x) for x in v])    # noqa: E731
+        B.check(self.lib.vz_llm_kv_beam_reorder(self.h, int(num_beams), int(groups), arr(base), arr(end), B.ptr(parent), self._s()))
+
+    def kv_cache(self) -> torch.Tensor:
+        """a copy of the whole KV cache, bf16 [n_layers, 2 (K|V), max_batch, kv heads, max_ctx, head_dim] (tests)."""
+        n = C.c_size_t(0)
+        B.check(self.lib.vz_llm_kv_copy_out(self.h, None, 0, C.byref(n), self._s()))
+        cfg = self.cfg
+        out = torch.empty(cfg.n_layers, 2, self.max_batch, cfg.n_kv_heads // self.tp_size, self.max_ctx, cfg.head_dim,
+                          dtype=torch.bfloat16, device=self.device)
+        assert out.numel() * 2 == n.value
+        B.check(self.lib.vz_llm_kv_copy_out(self.h, B.ptr(out), n.value, C.byref(n), self._s()))
+        return out
+
     def check_async(self):
         """raise if a bounded device-side wait expired since the last check (outputs invalid): the stream-K fix-up of
         the 256^2 GEMM (its tile is NaN, never a stale sum)."""
