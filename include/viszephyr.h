@@ -426,6 +426,28 @@ int vz_train_comm_init(vz_trainer* t, const char* id128, int rank, int world);
 int vz_train_allreduce(vz_trainer* t, vz_stream stream);
 int vz_train_adamw_step(vz_trainer* t, float lr, float beta1, float beta2, float eps, float weight_decay, vz_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3b. Stage-2 LoRA finetune step (ref:script/finetune.sh; ref:vis_zephyr/train/train.py:224-243, 933-951)
+ *
+ * The Stage-1 trainer plus a peft LoRA branch on every decoder linear: y = W x + scaling * B (A dropout(x)), A [r, in],
+ * B [out, r], scaling = alpha / r, an independent dropout mask per module.  The frozen weights and the inference engine stay
+ * untouched; the branch exists inside the trainer only.  The projector stays trainable (one optimiser group with the factors).
+ *   vz_train_lora_enable        adds 2 x 7 x n_layers tensors to the parameter table AFTER the projector tensors (Stage-1
+ *       offsets and names unchanged), named "lora.{layer}.{q,k,v,o,gate,up,down}.{A,B}" (row-major A [r, in], B [out, r]),
+ *       with fp32 master / moments / gradient in the same arenas (vz_train_arenas: the pointers change) and a bf16 working copy.
+ *       Masters start at zero; vz_train_set_master on a LoRA tensor also rewrites its working copy.  r % 64 == 0, 0 <= dropout < 1.
+ *       vz_train_zero_grad / vz_train_allreduce / vz_train_adamw_step cover the factors; vz_train_stage1_accumulate runs the branch.
+ *   vz_train_lora_set_counter   dropout counter of the following micro-batches: Philox4x32-10, key = seed, counter = (column / 4,
+ *       (sample_base + sample in micro-batch) * row_stride + position, layer * 7 + module, optimiser_step), word column % 4; an
+ *       element is kept when the word >= floor(p * 2^32).  row_stride >= the micro-batch's S (the longest row of the optimiser
+ *       batch keeps every mask independent of the micro-batch split).
+ *   vz_op_lora_dropout          the dropout at op level: out = keep * x * scaling / (1 - p) (bf16), rows = B * S of one micro-batch.
+ * ------------------------------------------------------------------------------------------ */
+int vz_train_lora_enable(vz_trainer* t, int r, float alpha, float dropout, unsigned long long seed, vz_stream stream);
+int vz_train_lora_set_counter(vz_trainer* t, int optimiser_step, long sample_base, long row_stride);
+int vz_op_lora_dropout(const void* d_x, int ldx, void* d_out, int ldo, int rows, int cols, int S, long sample_base, long row_stride,
+                       int tag, int step, unsigned long long seed, float p, float scaling, vz_stream stream);
+
 /* ViP "point" overlay on the device (ref:vis_zephyr/model/vip_processor/conversation_generator.py:143-153,170-175: the
  * `vcr_qa` / `vcr_qar` visual prompt = `ImageDraw.ellipse(box, fill=rgba, outline=rgba)` on a transparent canvas +
  * `Image.alpha_composite` + convert("RGB")): composites one filled ellipse with the INTEGER box (x0, y0, x1, y1) - the

@@ -346,8 +346,10 @@ struct ProfScope {
 
 static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M,
                   int N, int K, const float* bias, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
-                  const float* norm_w = nullptr, float norm_eps = 0.f, const unsigned char* W8 = nullptr, const float* ws = nullptr) {
+                  const float* norm_w = nullptr, float norm_eps = 0.f, const unsigned char* W8 = nullptr, const float* ws = nullptr,
+                  int splitk_hint = 0) {
     LinearArgs a = mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, res, ldr, act, out_fp32);
+    a.splitk_hint = splitk_hint;          // 0 = the dispatcher's choice (the Stage-2 trainer's narrow LoRA shapes pass their own)
     a.norm_w = norm_w; a.norm_eps = norm_eps; a.err = e->d_ferr; e->last_stream = s;
     if (klass_hint == 1 && M >= 2 && ldw == K) {       // decode step: the fragment-tiled copy of this weight, if the caller registered one
         if (e->tiled_dirty) {

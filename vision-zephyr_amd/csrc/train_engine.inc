@@ -16,6 +16,16 @@
 // Memory: one bump arena per trainer (saved activations + scratch), sized by a dry run of the same carving code.
 struct ProjParam { std::string name; int dtype; long n; size_t off; void* work; };
 
+// Stage-2 LoRA adapters (ref:vis_zephyr/train/train.py:933-951, peft LoraConfig; see the block before vz_train_lora_enable)
+constexpr int LORA_MODS = 7;                                    // q k v o gate up down
+static const char* const LORA_MOD_NAMES[LORA_MODS] = {"q", "k", "v", "o", "gate", "up", "down"};
+struct LoraState {
+    int r = 0; float alpha = 0.f, p = 0.f, scaling = 0.f; unsigned long long seed = 0;
+    int first = -1;                                             // table index of lora.0.q.A; A / B of (layer, module) follow in order
+    bf16_t* work = nullptr;                                     // bf16 working copies of every factor (one block)
+    int step = 0; long sample_base = 0, row_stride = 0;         // dropout counter of the next micro-batch
+};
+
 struct vz_trainer {
     vz_engine* e = nullptr;
     std::vector<bf16_t*> t_qkv, t_o, t_gu, t_down;     // W^T of the frozen Zephyr linears: [H,QKV] [A,H] [H,2I] [I,H]
@@ -26,6 +36,7 @@ struct vz_trainer {
     float* d_loss_rows = nullptr; size_t loss_rows_cap = 0; long loss_rows_n = 0;
     int adam_t = 0;
     ncclComm_t dp_comm = nullptr; int dp_world = 1;
+    LoraState lora;
 };
 
 static float* G_(vz_trainer* tr, const std::string& name, long n, int* rc) {
@@ -45,7 +56,8 @@ extern "C" int vz_train_destroy(vz_trainer* tr) {
     if (!tr) return VZ_OK;
     (void)hipDeviceSynchronize();
     for (auto* v : {&tr->t_qkv, &tr->t_o, &tr->t_gu, &tr->t_down}) for (bf16_t* p : *v) if (p) (void)hipFree(p);
-    for (void* p : {(void*)tr->t_lm, (void*)tr->master, (void*)tr->m, (void*)tr->v, (void*)tr->grad, (void*)tr->ws, (void*)tr->d_loss_rows}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)tr->t_lm, (void*)tr->master, (void*)tr->m, (void*)tr->v, (void*)tr->grad, (void*)tr->ws, (void*)tr->d_loss_rows,
+                    (void*)tr->lora.work}) if (p) (void)hipFree(p);
     if (tr->dp_comm) (void)ncclCommDestroy(tr->dp_comm);
     delete tr;
     return VZ_OK;
@@ -117,7 +129,94 @@ extern "C" int vz_train_set_master(vz_trainer* tr, const char* name, const float
     VZ_CHECK_ARG(tr && name && d_values, "train_set_master: bad argument");
     auto it = tr->index.find(name);
     VZ_CHECK_ARG(it != tr->index.end() && tr->params[it->second].n == n, "train_set_master: no projector tensor '%s' of %ld elements", name, n);
-    VZ_CHECK_HIP(hipMemcpyAsync(tr->master + tr->params[it->second].off, d_values, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const ProjParam& pp = tr->params[it->second];
+    VZ_CHECK_HIP(hipMemcpyAsync(tr->master + pp.off, d_values, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    // a LoRA factor's working copy is the trainer's own: it follows the master at once (RNE, as vz_train_adamw_step writes it)
+    if (tr->lora.first >= 0 && it->second >= tr->lora.first) RC(vz_launch_f32_to_bf16(tr->master + pp.off, (bf16_t*)pp.work, n, (hipStream_t)stream));
+    return VZ_OK;
+}
+
+// ---- Stage-2 LoRA (ref:vis_zephyr/train/train.py:224-243 find_all_linear_names, :933-951 LoraConfig; ref:script/finetune.sh) ----
+// Every decoder linear gets an adapter: y = W x + scaling * B (A dropout(x)), A [r, in], B [out, r], scaling = alpha / r, dropout p
+// per module (peft's Linear.forward).  The factors join the parameter table AFTER the projector tensors - Stage-1 offsets, names and
+// results stay as they were - as lora.{layer}.{q,k,v,o,gate,up,down}.{A,B}, with fp32 master / moments / gradient in the same flat
+// arenas (so zero_grad / allreduce / adamw cover them) and a bf16 working copy owned here.  Masters start at zero (the branch adds
+// exactly nothing); the host writes peft's initial values (or a saved adapter) through vz_train_set_master.
+static void lora_dims(const vz_config& c, int mod, int* in, int* out) {
+    const int H = c.hidden, D = c.head_dim, A = c.n_heads * D, KV = c.n_kv_heads * D, I = c.inter;
+    static const int ins[LORA_MODS] = {0, 0, 0, 1, 0, 0, 2};
+    const int in_dims[3] = {H, A, I};
+    const int out_dims[LORA_MODS] = {A, KV, KV, H, I, I, H};
+    *in = in_dims[ins[mod]]; *out = out_dims[mod];
+}
+
+extern "C" int vz_train_lora_enable(vz_trainer* tr, int r, float alpha, float dropout, unsigned long long seed, vz_stream stream) {
+    VZ_CHECK_ARG(tr && tr->e, "train_lora_enable: null trainer");
+    VZ_CHECK_ARG(tr->lora.r == 0, "train_lora_enable: LoRA is already enabled on this trainer");
+    VZ_CHECK_ARG(r >= 64 && r % 64 == 0 && alpha > 0.f && dropout >= 0.f && dropout < 1.f,
+                 "train_lora_enable: r=%d (a multiple of 64: the rank is a GEMM contraction), alpha=%g, dropout=%g in [0, 1)", r, (double)alpha, (double)dropout);
+    hipStream_t s = (hipStream_t)stream;
+    const vz_config& c = tr->e->c;
+    const size_t old_total = tr->total;
+    size_t off = old_total, woff = 0;
+    std::vector<ProjParam> add;
+    std::vector<size_t> wo;
+    for (int i = 0; i < c.n_layers; ++i)
+        for (int mod = 0; mod < LORA_MODS; ++mod) {
+            int in, out;
+            lora_dims(c, mod, &in, &out);
+            for (int ab = 0; ab < 2; ++ab) {
+                const long n = (long)r * (ab == 0 ? in : out);
+                add.push_back(ProjParam{"lora." + std::to_string(i) + "." + LORA_MOD_NAMES[mod] + (ab == 0 ? ".A" : ".B"), 0, n, off, nullptr});
+                wo.push_back(woff);
+                off += (size_t)((n + 63) & ~63L); woff += (size_t)((n + 63) & ~63L);
+            }
+        }
+    bf16_t* work = nullptr;
+    float* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto release = [&]() {
+        if (work) (void)hipFree(work);
+        for (float* p : fresh) if (p) (void)hipFree(p);
+    };
+    bool ok = hipMalloc((void**)&work, woff * sizeof(bf16_t)) == hipSuccess;
+    for (int k = 0; k < 4 && ok; ++k) ok = hipMalloc((void**)&fresh[k], off * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        release();
+        vz_set_error("train_lora_enable: out of memory for %zu MiB of LoRA arenas", (off - old_total) * 16 >> 20);
+        return VZ_ERR_HIP;
+    }
+    float** arenas[4] = {&tr->master, &tr->m, &tr->v, &tr->grad};
+    hipError_t he = hipSuccess;
+    for (int k = 0; k < 4 && he == hipSuccess; ++k) {
+        he = hipMemcpyAsync(fresh[k], *arenas[k], old_total * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (he == hipSuccess) he = hipMemsetAsync(fresh[k] + old_total, 0, (off - old_total) * sizeof(float), s);
+    }
+    if (he == hipSuccess) he = hipMemsetAsync(work, 0, woff * sizeof(bf16_t), s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) {             // the trainer keeps its Stage-1 arenas; nothing of the new ones survives
+        (void)hipStreamSynchronize(s);
+        release();
+        vz_set_error("train_lora_enable: %s", hipGetErrorString(he));
+        return VZ_ERR_HIP;
+    }
+    for (int k = 0; k < 4; ++k) { (void)hipFree(*arenas[k]); *arenas[k] = fresh[k]; }
+    tr->lora.first = (int)tr->params.size();
+    for (size_t k = 0; k < add.size(); ++k) {
+        add[k].work = work + wo[k];
+        tr->index[add[k].name] = (int)tr->params.size();
+        tr->params.push_back(add[k]);
+    }
+    tr->total = off;
+    tr->lora.work = work; tr->lora.r = r; tr->lora.alpha = alpha; tr->lora.p = dropout; tr->lora.scaling = alpha / (float)r; tr->lora.seed = seed;
+    return VZ_OK;
+}
+
+// dropout counter of the following micro-batches: the optimiser step, the index of the micro-batch's first sample within the optimiser
+// batch, and the row stride of the counter (>= every micro-batch's S: the longest spliced row of the optimiser batch)
+extern "C" int vz_train_lora_set_counter(vz_trainer* tr, int optimiser_step, long sample_base, long row_stride) {
+    VZ_CHECK_ARG(tr && tr->lora.r > 0, "train_lora_set_counter: LoRA is not enabled");
+    VZ_CHECK_ARG(optimiser_step >= 0 && sample_base >= 0 && row_stride >= 1, "train_lora_set_counter: bad argument");
+    tr->lora.step = optimiser_step; tr->lora.sample_base = sample_base; tr->lora.row_stride = row_stride;
     return VZ_OK;
 }
 
@@ -249,7 +348,7 @@ static int attn_bwd_one(vz_engine* e, const AttnBwd& a, char* ws, size_t ws_byte
 
 // dW[N,K] (+)= dY^T X  and  db[N] += colsum(dY):  dY [R,N] bf16 (ld ldy), X [R,K] bf16 (ld ldx).  Scratch from `m`.
 static int weight_grad(vz_engine* e, Carver& m, const bf16_t* dY, int ldy, const bf16_t* X, int ldx, long R, int N, int K, float* dW, float* db,
-                       hipStream_t s) {
+                       hipStream_t s, int splitk_hint = 0) {
     const size_t save = m.off;
     const int Rp = pad64((int)R);
     bf16_t* dYt = m.take<bf16_t>((size_t)N * Rp);
@@ -264,7 +363,7 @@ static int weight_grad(vz_engine* e, Carver& m, const bf16_t* dY, int ldy, const
     { ProfScope ps(e, K_OTHER, s);
       RC(vz_launch_transpose(dY, ldy, 0, 0, dYt, Rp, 0, 0, (int)R, N, 1, 1, 0, s));
       RC(vz_launch_transpose(X, ldx, 0, 0, Xt, Rp, 0, 0, (int)R, K, 1, 1, 0, s)); }
-    RC(linear(e, 0, dYt, Rp, Xt, Rp, tmp, K, N, K, Rp, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s));
+    RC(linear(e, 0, dYt, Rp, Xt, Rp, tmp, K, N, K, Rp, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s, nullptr, 0.f, nullptr, nullptr, splitk_hint));
     { ProfScope ps(e, K_OTHER, s);
       RC(vz_launch_axpy_f32(dW, tmp, (long)N * K, s));
       if (db) RC(vz_launch_colsum(dY, ldy, R, N, part, db, s)); }
@@ -287,12 +386,101 @@ static int input_grad(vz_engine* e, Carver& m, const bf16_t* dY, int ldy, const 
 struct Blk { bf16_t *x_in, *y1, *qkv, *att_s, *x_a, *y2, *qc, *ckv, *att_c, *x_b, *y3, *ffh, *ff; };
 struct Lay { bf16_t *x_in, *y, *qrot, *att, *x_mid, *y2, *gu, *act; };
 struct TrainPlan {
+    bf16_t* lora_u;         // Stage 2: u = drop(x) A^T of every adapted module, [layer][module][B*S, r]
     bf16_t *feats, *fn, *x0, *y0, *kv0, *q0, *a0, *xs, *x_fin, *proj, *emb, *x_last, *y_last, *dlogits;
     float* logits; int* tile_map; int* zero_map; int* seq;
     std::vector<Blk> blk; std::vector<Lay> lay;
     bf16_t *kc, *vc;        // K/V of the micro-batch, cache layout [layer][B][Hkv][S][D]
     size_t scratch_off;
 };
+
+// ---- the LoRA branch of one adapted module (Stage 2) ----
+// forward:  xd = drop(x) * scaling / (1 - p) (lora.hip, mask from the counter);  u = xd A^T [rows, r], kept;  y += u B^T (the GEMM's
+//           residual epilogue, in place).  The scaling rides on xd, so neither GEMM needs a scale epilogue.
+// backward: v = g B [rows, r];  dX += drop(v A) (same mask and factor);  dB += g^T u;  dA += v^T xd (xd rebuilt from the counter).
+// Weight operands are the bf16 working copies; the backward's B^T / A^T are transposed into scratch per call (r x in, small).
+static int lora_call(const vz_trainer* tr, int layer, int mod, const bf16_t* x, long ldx, bf16_t* out, long ldo, const bf16_t* res, int B, int S,
+                     hipStream_t s) {
+    const LoraState& lo = tr->lora;
+    int in, outd;
+    lora_dims(tr->e->c, mod, &in, &outd);
+    ProfScope ps(tr->e, K_OTHER, s);
+    return vz_launch_lora_dropout(x, ldx, out, ldo, res, ldo, B * S, in, S, lo.sample_base, lo.row_stride, layer * LORA_MODS + mod, lo.step, lo.seed,
+                                  lo.p, lo.scaling, s);
+}
+// K-split of the LoRA contractions with N = r (x A^T, g B, dB = g^T u): a 128-column output has one column tile, so the dispatcher's own
+// split (4 slices when M > 512) leaves half of the 256 CUs idle at 4096 rows; cut K until ~512 workgroups exist, keeping >= 8 K-tiles per slice
+static int lora_splitk(int M, int N, int K) {
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128), nk = K / 64;
+    int sk = std::min(16, std::max(1, 512 / tiles));
+    while (sk > 1 && nk / sk < 8) --sk;
+    return sk;
+}
+static const ProjParam& lora_param(const vz_trainer* tr, int layer, int mod, int ab) { return tr->params[tr->lora.first + (layer * LORA_MODS + mod) * 2 + ab]; }
+
+static int lora_fwd(vz_trainer* tr, Carver m, int layer, int mod, const bf16_t* x, int ldx, bf16_t* y, int ldy, const TrainPlan& pl, int B, int S,
+                    hipStream_t s) {
+    vz_engine* e = tr->e;
+    const int r = tr->lora.r;
+    const long rows = (long)B * S;
+    int in, out;
+    lora_dims(e->c, mod, &in, &out);
+    bf16_t* xd = m.take<bf16_t>(rows * in);
+    if (!m.ok) { vz_set_error("train: LoRA forward scratch too small (internal sizing error)"); return VZ_ERR_STATE; }
+    bf16_t* u = pl.lora_u + ((size_t)layer * LORA_MODS + mod) * rows * r;
+    RC(lora_call(tr, layer, mod, x, ldx, xd, in, nullptr, B, S, s));
+    RC(linear(e, 0, xd, in, (const bf16_t*)lora_param(tr, layer, mod, 0).work, in, u, r, (int)rows, r, in, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s,
+              nullptr, 0.f, nullptr, nullptr, lora_splitk((int)rows, r, in)));
+    return linear(e, 0, u, r, (const bf16_t*)lora_param(tr, layer, mod, 1).work, r, y, ldy, (int)rows, out, r, nullptr, y, ldy, VZ_ACT_NONE, 0, s);
+}
+
+static int lora_bwd(vz_trainer* tr, Carver m, int layer, int mod, const bf16_t* g, int ldg, const bf16_t* x, int ldx, bf16_t* dX, int lddx,
+                    const TrainPlan& pl, int B, int S, hipStream_t s) {
+    vz_engine* e = tr->e;
+    const int r = tr->lora.r;
+    const long rows = (long)B * S;
+    int in, out;
+    lora_dims(e->c, mod, &in, &out);
+    const ProjParam &pa = lora_param(tr, layer, mod, 0), &pb = lora_param(tr, layer, mod, 1);
+    const bf16_t* u = pl.lora_u + ((size_t)layer * LORA_MODS + mod) * rows * r;
+    bf16_t* bt = m.take<bf16_t>((size_t)r * out);
+    bf16_t* at = m.take<bf16_t>((size_t)in * r);
+    bf16_t* v = m.take<bf16_t>(rows * r);
+    bf16_t* t = m.take<bf16_t>(rows * in);                   // v A, later xd
+    if (!m.ok) { vz_set_error("train: LoRA backward scratch too small (internal sizing error)"); return VZ_ERR_STATE; }
+    { ProfScope ps(e, K_OTHER, s);
+      RC(transpose2d((const bf16_t*)pb.work, out, r, bt, out, s));
+      RC(transpose2d((const bf16_t*)pa.work, r, in, at, r, s)); }
+    RC(linear(e, 0, g, ldg, bt, out, v, r, (int)rows, r, out, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s, nullptr, 0.f, nullptr, nullptr,
+              lora_splitk((int)rows, r, out)));
+    RC(linear(e, 0, v, r, at, r, t, in, (int)rows, in, r, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+    RC(lora_call(tr, layer, mod, t, in, dX, lddx, dX, B, S, s));
+    RC(weight_grad(e, m, g, ldg, u, r, rows, out, r, tr->grad + pb.off, nullptr, s, lora_splitk(out, r, pad64((int)rows))));
+    RC(lora_call(tr, layer, mod, x, ldx, t, in, nullptr, B, S, s));
+    return weight_grad(e, m, v, r, t, in, rows, r, in, tr->grad + pa.off, nullptr, s);
+}
+
+// scratch of the LoRA backward (the gate|up copy + the largest module's lora_bwd), as the carving above takes it
+static size_t lora_bwd_ws(const vz_config& c, int r, long rows) {
+    size_t need = 0;
+    const int Rp = pad64((int)rows);
+    for (int mod = 0; mod < LORA_MODS; ++mod) {
+        int in, out;
+        lora_dims(c, mod, &in, &out);
+        Carver m(nullptr, ~(size_t)0);
+        if (mod == 4 || mod == 5) m.take<bf16_t>(rows * 2 * c.inter);
+        m.take<bf16_t>((size_t)r * out); m.take<bf16_t>((size_t)in * r); m.take<bf16_t>(rows * r); m.take<bf16_t>(rows * in);
+        size_t wg = 0;
+        for (int k = 0; k < 2; ++k) {         // weight_grad of dB [out, r], then of dA [r, in]
+            const int N = k == 0 ? out : r, K = k == 0 ? r : in;
+            Carver w(nullptr, ~(size_t)0);
+            w.take<bf16_t>((size_t)N * Rp); w.take<bf16_t>((size_t)K * Rp); w.take<float>((size_t)N * K); w.take<float>((size_t)vz_colsum_groups(rows) * N);
+            wg = std::max(wg, w.off);
+        }
+        need = std::max(need, m.off + wg + 1024);
+    }
+    return need;
+}
 
 // Accumulates the gradients of ONE micro-batch into the trainer's gradient arena and the micro-batch's row losses (x inv_n) into
 // the loss buffer.  Inputs as the inference stages take them: d_images bf16 [T,3,336,336]; d_text bf16 [n_samples,Lmax,H] +
@@ -318,6 +506,9 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
     const long R = (long)T * NQ, TP = (long)T * Pv, rows = (long)B * S, R0 = (long)n_samples * N0, RS = (long)n_samples * NQ;
     const float qscale = 1.0f / sqrtf((float)QD), lscale = 1.0f / sqrtf((float)D);
     int rc = VZ_OK;
+    const LoraState& lo = tr->lora;
+    const int lr = lo.r;
+    VZ_CHECK_ARG(!lr || lo.row_stride >= S, "train: LoRA dropout row stride %ld < S=%d (vz_train_lora_set_counter)", lo.row_stride, S);
 
     // ---------------- memory: everything below is carved from one arena; the dry run sizes it ----------------
     TrainPlan pl;
@@ -343,6 +534,7 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         pl.kc = m.take<bf16_t>((size_t)L * B * Hkv * S * D); pl.vc = m.take<bf16_t>((size_t)L * B * Hkv * S * D);
         pl.x_last = m.take<bf16_t>(rows * H); pl.y_last = m.take<bf16_t>(rows * H);
         pl.logits = m.take<float>(rows * V); pl.dlogits = m.take<bf16_t>(rows * tr->Vpad);
+        pl.lora_u = lr ? m.take<bf16_t>((size_t)L * LORA_MODS * rows * lr) : nullptr;
         pl.tile_map = m.take<int>(T + 16); pl.zero_map = m.take<int>(n_samples + 16); pl.seq = m.take<int>(rows + B + 16);
         pl.scratch_off = (m.off + 255) & ~(size_t)255;
     };
@@ -367,6 +559,7 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         qz.take<bf16_t>(R0 * 2 * H); qz.take<bf16_t>(R0 * H); qz.take<bf16_t>(R0 * H); qz.take<float>(R0 * 2 * H); qz.take<bf16_t>(RS * H); qz.take<bf16_t>(RS * H); qz.take<bf16_t>(RS * H);
         qz.take<float>(std::max(vz_layernorm_bwd_scratch_floats(TP, KD), vz_layernorm_bwd_scratch_floats(std::max(R, R0), H)));
         qz.take<bf16_t>((size_t)KD * 2 * H);        // largest transposed projector weight (input_grad)
+        if (lr) sc = std::max(sc, lora_bwd_ws(c, lr, rows));
         sc_need = std::max(z.off, qz.off) + std::max(sc, wg) + (1 << 20);
         const size_t need = dry.off + 4096 + sc_need;
         if (need > tr->ws_bytes) {
@@ -462,6 +655,9 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         bf16_t* qkv = (bf16_t*)(tr->ws + scratch0);           // [rows, QKV] un-rotated projection: scratch
         RC(vz_launch_rmsnorm(l.x_in, H, l.y, H, WF(p + "in_norm", H), (int)rows, H, c.rms_eps, s));
         RC(linear(e, 0, l.y, H, WB(p + "qkv.w", (long)QKV * H), H, qkv, QKV, (int)rows, QKV, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        Carver lf(tr->ws, tr->ws_bytes);                       // LoRA forward scratch: after the un-rotated projection
+        lf.off = scratch0; lf.take<bf16_t>(rows * QKV);
+        if (lr) for (int mod = 0; mod < 3; ++mod) RC(lora_fwd(tr, lf, i, mod, l.y, H, qkv + (mod == 0 ? 0 : mod == 1 ? A : A + Hkv * D), QKV, pl, B, S, s));
         bf16_t* kc = pl.kc + (size_t)i * kvl; bf16_t* vc = pl.vc + (size_t)i * kvl;
         RC(vz_launch_rope_kv(qkv, QKV, l.qrot, kc, vc, e->cosT, e->sinT, d_pos, d_slot, B, S, Hq, Hkv, D, S, s));
         {
@@ -476,12 +672,24 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             RC(vz_launch_attention(a, s));
         }
         RC(linear(e, 0, l.att, A, WB(p + "o.w", (long)H * A), A, l.x_mid, H, (int)rows, H, A, nullptr, l.x_in, H, VZ_ACT_NONE, 0, s));
+        if (lr) RC(lora_fwd(tr, lf, i, 3, l.att, A, l.x_mid, H, pl, B, S, s));
         RC(vz_launch_rmsnorm(l.x_mid, H, l.y2, H, WF(p + "post_norm", H), (int)rows, H, c.rms_eps, s));
         // gate|up pre-activations are kept (SwiGLU backward needs both): N = 2I plain columns, then the SwiGLU as its own kernel
         RC(linear(e, 0, l.y2, H, WB(p + "gu.w", 2L * I * H), H, l.gu, 2 * I, (int)rows, 2 * I, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        if (lr) {
+            // the fused output interleaves gate and up in 16-column groups: add the two branches on a [gate | up] copy, then put it back
+            Carver lg = lf;
+            bf16_t* z = lg.take<bf16_t>(rows * 2 * I);
+            if (!lg.ok) { vz_set_error("train: LoRA forward scratch too small (internal sizing error)"); return VZ_ERR_STATE; }
+            { ProfScope ps(e, K_OTHER, s); RC(vz_launch_gu_permute(l.gu, z, rows, I, 1, s)); }
+            RC(lora_fwd(tr, lg, i, 4, l.y2, H, z, 2 * I, pl, B, S, s));
+            RC(lora_fwd(tr, lg, i, 5, l.y2, H, z + I, 2 * I, pl, B, S, s));
+            { ProfScope ps(e, K_OTHER, s); RC(vz_launch_gu_permute(z, l.gu, rows, I, 0, s)); }
+        }
         RC(vz_launch_swiglu_fwd(l.gu, l.act, rows, I, s));
         bf16_t* x_next = i + 1 < L ? pl.lay[i + 1].x_in : pl.x_last;
         RC(linear(e, 0, l.act, I, WB(p + "down.w", (long)I * H), I, x_next, H, (int)rows, H, I, nullptr, l.x_mid, H, VZ_ACT_NONE, 0, s));
+        if (lr) RC(lora_fwd(tr, lf, i, 6, l.act, I, x_next, H, pl, B, S, s));
         if (rc) return rc;
     }
     const float* fnw = WF("llm.norm", H);
@@ -507,11 +715,23 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         Lay& l = pl.lay[i];
         // x_out = x_mid + down(act):  dact = dx . W_down
         RC(linear(e, 0, dx, H, tr->t_down[i], H, dact, I, (int)rows, I, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        Carver lb(tr->ws, tr->ws_bytes);                       // LoRA backward scratch: the attention backward's region, used before / after it
+        lb.off = z_scratch;
+        if (lr) RC(lora_bwd(tr, lb, i, 6, dx, H, l.act, I, dact, I, pl, B, S, s));
         RC(vz_launch_swiglu_bwd(l.gu, dact, dgu, rows, I, s));
         RC(linear(e, 0, dgu, 2 * I, tr->t_gu[i], 2 * I, dy, H, (int)rows, H, 2 * I, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        if (lr) {
+            Carver lg = lb;
+            bf16_t* g = lg.take<bf16_t>(rows * 2 * I);         // d(gate | up) in [gate | up] halves
+            if (!lg.ok) { vz_set_error("train: LoRA backward scratch too small (internal sizing error)"); return VZ_ERR_STATE; }
+            { ProfScope ps(e, K_OTHER, s); RC(vz_launch_gu_permute(dgu, g, rows, I, 1, s)); }
+            RC(lora_bwd(tr, lg, i, 4, g, 2 * I, l.y2, H, dy, H, pl, B, S, s));
+            RC(lora_bwd(tr, lg, i, 5, g + I, 2 * I, l.y2, H, dy, H, pl, B, S, s));
+        }
         RC(vz_launch_rmsnorm_bwd(l.x_mid, WF(p + "post_norm", H), dy, dx, dx2, rows, H, c.rms_eps, s));       // dx2 = d x_mid
         // x_mid = x_in + o(att):  datt = dx2 . W_o
         RC(linear(e, 0, dx2, H, tr->t_o[i], H, datt, A, (int)rows, A, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        if (lr) RC(lora_bwd(tr, lb, i, 3, dx2, H, l.att, A, datt, A, pl, B, S, s));
         AttnBwd ab;
         ab.q = l.qrot; ab.k = pl.kc + (size_t)i * kvl; ab.v = pl.vc + (size_t)i * kvl; ab.dO = datt;
         ab.B = B; ab.Sq = S; ab.Sk = S; ab.Hq = Hq; ab.Hkv = Hkv; ab.D = D;
@@ -522,6 +742,7 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         RC(attn_bwd(e, ab, tr->ws + z_scratch, tr->ws_bytes - z_scratch, s));
         RC(vz_launch_rope_bwd_assemble(dq, dk, dv, dqkv, e->cosT, e->sinT, d_pos, B, S, Hq, Hkv, D, S, s));
         RC(linear(e, 0, dqkv, QKV, tr->t_qkv[i], QKV, dy, H, (int)rows, H, QKV, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        if (lr) for (int mod = 0; mod < 3; ++mod) RC(lora_bwd(tr, lb, i, mod, dqkv + (mod == 0 ? 0 : mod == 1 ? A : A + Hkv * D), QKV, l.y, H, dy, H, pl, B, S, s));
         RC(vz_launch_rmsnorm_bwd(l.x_in, WF(p + "in_norm", H), dy, dx2, dx, rows, H, c.rms_eps, s));          // dx = d x_in
         if (rc) return rc;
     }

@@ -27,6 +27,19 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     return (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): the counter-based generator of the sampling tail (sampling.hip) and of the LoRA dropout
+// masks (lora.hip).  Counter (c0..c3), key (k0, k1); returns the four output words.
+__device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
 // ---- wave-wide reductions on the VALU (gfx950) ----
 // Inside a 16-lane row: DPP moves (quad swaps, half-row mirror, row mirror) - after the four steps every lane of a row holds
 // its row's result.  Across the four rows: v_permlane16_swap (odd rows of one operand <-> even rows of the other) and
@@ -375,5 +388,11 @@ int vz_launch_add_bf16(bf16_t* y, const bf16_t* x, long n, hipStream_t s);
 int vz_launch_f32_to_bf16(const float* x, bf16_t* y, long n, hipStream_t s);
 int vz_launch_bf16_to_f32(const bf16_t* x, float* y, long n, hipStream_t s);
 int vz_launch_acc_rows_f32(float* out, const bf16_t* src, int n_batches, long stride, int rows, int cols, hipStream_t s);
+// ---- LoRA branch of the Stage-2 step (lora.hip) ----
+unsigned vz_lora_threshold(float p);
+float vz_lora_factor(float scaling, float p);
+int vz_launch_lora_dropout(const bf16_t* x, long ldx, bf16_t* out, long ldo, const bf16_t* res, long ldr, int rows, int cols, int S,
+                           long sample_base, long row_stride, int tag, int step, unsigned long long seed, float p, float scaling, hipStream_t s);
+int vz_launch_gu_permute(const bf16_t* src, bf16_t* dst, long rows, int I, int to_plain, hipStream_t s);
 int vz_launch_adamw(float* p, float* m, float* v, float* g, void* work, int work_bf16, long n, float lr, float b1, float b2, float eps, float wd,
                     int t, hipStream_t s);

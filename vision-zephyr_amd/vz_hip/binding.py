@@ -122,6 +122,9 @@ SYMBOLS = {
     "vz_train_comm_init": (_I, [_P, C.c_char_p, _I, _I]),
     "vz_train_allreduce": (_I, [_P, _P]),
     "vz_train_adamw_step": (_I, [_P, _F, _F, _F, _F, _F, _P]),
+    "vz_train_lora_enable": (_I, [_P, _I, _F, _F, C.c_ulonglong, _P]),
+    "vz_train_lora_set_counter": (_I, [_P, _I, _L, _L]),
+    "vz_op_lora_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _I, _I, C.c_ulonglong, _F, _F, _P]),
     "vz_op_vip_point": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, _P]),
     "vz_op_sample": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -490,6 +493,17 @@ def beam_select(logits, scores, nb_in: int, nb_out: int, eos=()):
     check(lib().vz_op_beam_select(ptr(logits), logits.shape[0], logits.shape[1], int(nb_in), int(nb_out), arr, len(eos), ptr(scores),
                                   ptr(rec), ptr(tok), ptr(sc), ptr(par), stream_ptr(dev)))
     return rec, tok, sc, par
+
+
+def lora_dropout(x, S: int, sample_base: int, row_stride: int, tag: int, step: int, seed: int, p: float, scaling: float):
+    """the Stage-2 LoRA dropout on the device (lora.hip): x bf16 [B*S, cols] -> keep * x * scaling / (1 - p), bf16; the mask is
+    vz_hip/lora.py::dropout_keep's."""
+    _need_cuda(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    check(lib().vz_op_lora_dropout(ptr(x), x.stride(0), ptr(out), out.stride(0), x.shape[0], x.shape[1], int(S), int(sample_base), int(row_stride),
+                                   int(tag), int(step), int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), float(scaling), stream_ptr(x.device)))
+    return out
 
 
 def op_async_error(device=None) -> int:

@@ -24,6 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import binding as B
+from . import lora as L
 
 IGNORE_INDEX, IMAGE_TOKEN_INDEX = -100, -200
 
@@ -69,6 +70,8 @@ def _ref_to_engine(cfg) -> Dict[str, tuple]:
 
 
 class Stage1Trainer:
+    base_lr = MM_PROJECTOR_LR
+
     def __init__(self, model):
         self.model = model
         self.eng = model.engine
@@ -77,6 +80,11 @@ class Stage1Trainer:
         h = C.c_void_p()
         B.check(self.lib.vz_train_create(self.eng.h, C.byref(h), self.eng._s()))
         self.h = h
+        self._load_table()
+        self.steps_done = 0
+
+    def _load_table(self):
+        """the trainer's tensor table and the device pointers of its flat fp32 arenas"""
         self.table = {}
         name, n, off, mat = C.c_char_p(), C.c_long(), C.c_long(), C.c_int()
         for i in range(self.lib.vz_train_param_count(self.h)):
@@ -86,7 +94,6 @@ class Stage1Trainer:
         B.check(self.lib.vz_train_arenas(self.h, C.byref(g), C.byref(ma), C.byref(m), C.byref(v), C.byref(tot)))
         self.total = tot.value
         self._grad_ptr, self._master_ptr = g.value, ma.value
-        self.steps_done = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -102,8 +109,10 @@ class Stage1Trainer:
     # ---- views of the flat fp32 arenas (device memory owned by the trainer) ----
     def _view(self, base_ptr: int, name: str) -> torch.Tensor:
         off, n, _ = self.table[name]
-        shape = tuple(self.eng.w[name].shape)
-        return _from_ptr(base_ptr + 4 * off, n, self.eng.device).view(shape)
+        return _from_ptr(base_ptr + 4 * off, n, self.eng.device).view(self._shape(name))
+
+    def _shape(self, name: str):
+        return tuple(self.eng.w[name].shape)
 
     def grad(self, name: str) -> torch.Tensor:
         """fp32 gradient of an ENGINE tensor (e.g. 'qf.3.ffn1.w'), a view of the arena"""
@@ -232,7 +241,7 @@ class Stage1Trainer:
         if len(tiles) != Bsz:
             raise ValueError("one image (tile stack) per sample expected in a Stage-1 batch")
         # valid targets of the WHOLE batch: labels shifted by one inside each spliced row; image positions are IGNORE, so only text labels count
-        n_valid = 0
+        n_valid, row_stride = 0, 1
         for b in range(Bsz):
             lab = lab_cpu[b][mask_cpu[b]]
             ids = ids_cpu[b][mask_cpu[b]]
@@ -245,6 +254,7 @@ class Stage1Trainer:
             max_len = getattr(self.model.config, "tokenizer_model_max_length", None)
             flat = flat if max_len is None else flat[:max_len]
             n_valid += sum(1 for v in flat[1:] if v != IGNORE_INDEX)
+            row_stride = max(row_stride, len(flat))
         if n_valid == 0:
             raise ValueError("no valid target in the batch")
         mb = Bsz if micro_batch is None else max(1, int(micro_batch))
@@ -252,8 +262,12 @@ class Stage1Trainer:
         total = 0.0
         for b0 in range(0, Bsz, mb):
             sl = slice(b0, min(Bsz, b0 + mb))
+            self._before_micro_batch(b0, row_stride)
             total += self._accumulate(ids_cpu[sl], mask_cpu[sl], lab_cpu[sl], tiles[sl], 1.0 / n_valid, Lmax_batch)
         return total / n_valid
+
+    def _before_micro_batch(self, sample_base: int, row_stride: int):
+        """hook of the Stage-2 trainer (the dropout counter); `row_stride` = the longest spliced row of the optimiser batch"""
 
     def all_reduce(self):
         B.check(self.lib.vz_train_allreduce(self.h, self.eng._s()))
@@ -268,10 +282,10 @@ class Stage1Trainer:
         the scheduled learning rate.  Either `lr` (explicit) or `total_steps` (the schedule's length: the Trainer knows it from the
         dataset and the epoch count; there is no sensible default) must be given."""
         if lr is None and total_steps is None:
-            raise ValueError("Stage1Trainer.step: pass lr=..., or total_steps=... for the cosine schedule around mm_projector_lr = 2e-3")
+            raise ValueError(f"{type(self).__name__}.step: pass lr=..., or total_steps=... for the cosine schedule around {self.base_lr:g}")
         loss = self.forward_backward(input_ids, attention_mask, labels, images, micro_batch)
         self.all_reduce()
-        self.optimizer_step(lr_at(self.steps_done, int(total_steps)) if lr is None else lr)
+        self.optimizer_step(lr_at(self.steps_done, int(total_steps), self.base_lr) if lr is None else lr)
         return loss
 
     def projector_state_dict(self) -> Dict[str, torch.Tensor]:
@@ -314,6 +328,86 @@ class Stage1Trainer:
         buf = C.create_string_buffer(128)
         B.check(self.lib.vz_comm_unique_id(buf))
         B.check(self.lib.vz_train_comm_init(self.h, bytes(buf.raw), 0, 1))
+
+
+class Stage2Trainer(Stage1Trainer):
+    """Stage-2 finetune step (ref:script/finetune.sh): Stage 1 plus a peft LoRA branch on every decoder linear, trained together
+    with the projector in one AdamW group at lr 2e-4 (finetune.sh sets no --mm_projector_lr).  The branch runs inside
+    `vz_train_stage1_accumulate` once `vz_train_lora_enable` has added the factors (lora.{layer}.{q,k,v,o,gate,up,down}.{A,B}) to
+    the trainer's table; the dropout masks follow (seed, optimiser step, sample index within the optimiser batch, position), so a
+    batch split into micro-batches trains the same masks.  The factors start at zero: call `init_lora` (peft's init) or
+    `set_lora_from_adapter` before the first step."""
+    base_lr = L.FINETUNE_LR
+
+    def __init__(self, model, r: int = 128, alpha: float = 256, dropout: float = 0.05, seed: int = 0):
+        super().__init__(model)
+        self.r, self.alpha, self.dropout, self.seed = int(r), float(alpha), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.scaling = self.alpha / self.r
+        try:
+            B.check(self.lib.vz_train_lora_enable(self.h, self.r, self.alpha, self.dropout, self.seed, self.eng._s()))
+        except Exception:
+            self.close()                        # the Stage-1 part was built: free it (W^T copies, projector arenas)
+            raise
+        self._load_table()                      # the arenas moved and grew
+        self.n_layers = self.eng.cfg.n_layers
+        self._peft = L.peft_to_engine(self.n_layers)
+
+    def _shape(self, name: str):
+        return L.shape(self.eng.cfg, name, self.r) if name.startswith("lora.") else super()._shape(name)
+
+    def _before_micro_batch(self, sample_base: int, row_stride: int):
+        B.check(self.lib.vz_train_lora_set_counter(self.h, self.steps_done, int(sample_base), int(row_stride)))
+
+    # ---- the factors ----
+    def set_lora(self, named):
+        """fp32 masters (and the bf16 working copies) of LoRA factors from (name, tensor) pairs: peft keys or trainer names"""
+        for k, v in (named.items() if isinstance(named, dict) else named):
+            name = self._peft.get(k, k)
+            if name not in self.table:
+                raise KeyError(f"no LoRA factor {k!r}")
+            v = v.to(self.eng.device, torch.float32).contiguous()
+            _, n, _ = self.table[name]
+            if v.numel() != n or tuple(v.shape) != self._shape(name):
+                raise ValueError(f"{k}: shape {tuple(v.shape)}, the trainer holds {self._shape(name)}")
+            B.check(self.lib.vz_train_set_master(self.h, name.encode(), B.ptr(v), n, self.eng._s()))
+        torch.cuda.current_stream(self.eng.device).synchronize()
+
+    def init_lora(self, generator: Optional[torch.Generator] = None):
+        """peft's initial values: A <- kaiming_uniform_(a=sqrt(5)), B <- 0 (so the first step has dA = 0 exactly)"""
+        self.set_lora(L.init_factors(self.eng.cfg, self.r, generator))
+
+    def set_lora_from_adapter(self, directory: str):
+        """resume from a saved adapter (adapter_config.json + adapter_model.*); r and alpha must match this trainer's"""
+        cfg, tensors = L.read_adapter(directory)
+        if int(cfg["r"]) != self.r or float(cfg["lora_alpha"]) != self.alpha:
+            raise ValueError(f"adapter r={cfg['r']} alpha={cfg['lora_alpha']}, trainer r={self.r} alpha={self.alpha}")
+        self.set_lora({k: v for k, v in tensors.items() if k in self._peft})
+
+    def lora_master(self, name: str) -> torch.Tensor:
+        return self.master(self._peft.get(name, name))
+
+    def lora_grad(self, name: str) -> torch.Tensor:
+        return self.grad(self._peft.get(name, name))
+
+    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
+        """fp32 masters of the factors under peft's saved keys"""
+        return {k: self.master(n).detach().to("cpu", torch.float32).clone() for k, n in self._peft.items()}
+
+    def reference_grads(self) -> Dict[str, torch.Tensor]:
+        """gradients of every trainable tensor under peft's names: the factors (saved-key form, `...lora_A.weight`) and the projector
+        (`base_model.model.model.mm_projector.*`)"""
+        out = {L.PEFT_PREFIX + k: v for k, v in super().reference_grads().items()}
+        out.update({k: self.grad(n) for k, n in self._peft.items()})
+        return out
+
+    def save(self, directory: str, dtype: torch.dtype = torch.bfloat16) -> str:
+        """the reference's Stage-2 output (ref:vis_zephyr/train/train.py:1037-1046): adapter_config.json, adapter_model.safetensors and
+        non_lora_trainables.bin - what `load_pretrained_model(directory, model_base, model_name="...lora...")` merges back"""
+        L.write_adapter(directory, self.r, self.alpha, self.dropout, self.lora_state_dict(), self.projector_state_dict(), dtype)
+        cfg = getattr(self.model, "config", None)
+        if hasattr(cfg, "save_pretrained"):         # the reference saves the model config beside the adapter (the loader reads it)
+            cfg.save_pretrained(directory)
+        return directory
 
 
 def _from_ptr(ptr: int, n: int, device) -> torch.Tensor:
