@@ -234,6 +234,27 @@ extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, v
 // ------------------------------------------------------------------------------------------------
 struct Weight { const void* p; int dtype; long n; };
 
+// The weight tables the stages read, filled by vz_engine_finalize from the name registry.  A linear: the bf16 matrix [N, K] and its
+// fragment-tiled copy ("<name>t" if registered: the 2..64-row decode streams read it), the e4m3 copy + fp32 row scales (weight_fp8
+// engines only) and the e4m3 copy's tiled copy, the fp32 bias; null = absent.
+struct LinW {
+    const bf16_t* w = nullptr; const bf16_t* wt = nullptr;
+    const unsigned char* w8 = nullptr; const unsigned char* w8t = nullptr; const float* ws = nullptr;
+    const float* b = nullptr;
+};
+static LinW bare(const bf16_t* w) { LinW l; l.w = w; return l; }      // a matrix with nothing attached (trainer operands)
+// rows r0.. of a linear's matrix [., K] and bias (Q-Former block 0 runs the K|V rows of sa_in on their own)
+static LinW lin_rows(const LinW& l, long r0, int K) { LinW s = bare(l.w + r0 * K); s.b = l.b + r0; return s; }
+struct NormW { const float* w = nullptr; const float* b = nullptr; };      // LayerNorm scale + shift
+struct ClipLayerW { NormW ln1, ln2; LinW qkv, o, fc1, fc2; };
+struct QfBlockW { NormW n1, n2, n3; LinW sa_in, sa_out, ca_q, ca_kv, ca_out, ffn1, ffn2; };
+struct LlmLayerW { const float* in_norm = nullptr; const float* post_norm = nullptr; LinW qkv, o, gu, down; };
+struct TopW {
+    const bf16_t *clip_patch_w = nullptr, *clip_cls = nullptr, *clip_pos = nullptr; NormW clip_pre_ln;
+    const bf16_t* qf_queries = nullptr; NormW qf_pre_norm, qf_norm;
+    const bf16_t* embed = nullptr; const float* norm = nullptr; LinW lm_head;
+};
+
 enum { K_GEMM = 0, K_GEMV = 1, K_ATTN = 2, K_ATTN_DEC = 3, K_NORM = 4, K_OTHER = 5, K_FUSED = 6, K_COMM = 7 };
 
 struct vz_engine {
@@ -247,11 +268,10 @@ struct vz_engine {
     static constexpr int OS_MAX_ELEMS = 64 * 4096;       // up to 64 decode rows of hidden 4096
     float* d_gather = nullptr;     // [tp][rows][Vp] all-gathered logits before the repack
     size_t gather_floats = 0;
-    std::unordered_map<std::string, Weight> w;
-    // row-major bf16 weight -> its fragment-tiled copy (registered as "<name>t", same element count): the 2..64-row decode
-    // linears stream the tiled copy (gemm_skinny.hip); rebuilt whenever the registry changes
-    std::unordered_map<const void*, const bf16_t*> tiled; bool tiled_dirty = true;
-    std::unordered_map<const void*, const unsigned char*> tiled8;      // e4m3 copy "<name>8" / "<name>.w8" -> its fragment-tiled copy "<..>t" (dtype 2)
+    std::unordered_map<std::string, Weight> w;     // by name (vz_engine_set_weight); only vz_engine_finalize reads it
+    // resolved by vz_engine_finalize; valid while `finalized`
+    TopW top; std::vector<ClipLayerW> clip; std::vector<QfBlockW> qf; std::vector<LlmLayerW> llm;
+    bool qf_kv_contig = false;     // > 1 Q-Former block and their ca_kv weights + biases lie back to back (block-major)
     bool finalized = false;
     // rope
     const float* cosT = nullptr; const float* sinT = nullptr; int rope_max = 0;
@@ -296,22 +316,6 @@ struct vz_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev; size_t prof_used = 0;
 };
 
-static const void* W_(vz_engine* e, const std::string& name, int dtype, long n, int* rc) {
-    auto it = e->w.find(name);
-    if (it == e->w.end()) { vz_set_error("weight '%s' was never registered", name.c_str()); *rc = VZ_ERR_STATE; return nullptr; }
-    if (it->second.dtype != dtype || it->second.n != n) {
-        vz_set_error("weight '%s': expected dtype %d n %ld, got dtype %d n %ld", name.c_str(), dtype, n, it->second.dtype,
-                     it->second.n);
-        *rc = VZ_ERR_STATE;
-        return nullptr;
-    }
-    return it->second.p;
-}
-#define WB(name, n) ((const bf16_t*)W_(e, name, 0, (long)(n), &rc))
-#define WF(name, n) ((const float*)W_(e, name, 1, (long)(n), &rc))
-// e4m3 copy + row scales of a decode-side weight (nullptr unless the engine was created with weight_fp8)
-#define W8(name, n) (e->c.weight_fp8 ? (const unsigned char*)W_(e, name, 2, (long)(n), &rc) : (const unsigned char*)nullptr)
-#define WS(name, n) (e->c.weight_fp8 ? (const float*)W_(e, name, 1, (long)(n), &rc) : (const float*)nullptr)
 #define RC(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 
 struct ProfScope {
@@ -344,35 +348,23 @@ struct ProfScope {
     }
 };
 
-static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M,
-                  int N, int K, const float* bias, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
-                  const float* norm_w = nullptr, float norm_eps = 0.f, const unsigned char* W8 = nullptr, const float* ws = nullptr,
-                  int splitk_hint = 0) {
-    LinearArgs a = mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, res, ldr, act, out_fp32);
+// One linear C = epi(A . W^T + W.b): the route follows the row count and what finalize attached to W (tiled copies, e4m3 copy).
+static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M,
+                  int N, int K, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
+                  const float* norm_w = nullptr, float norm_eps = 0.f, int splitk_hint = 0) {
+    LinearArgs a = mk_linear(A, lda, W.w, ldw, C, ldc, M, N, K, W.b, res, ldr, act, out_fp32);
     a.splitk_hint = splitk_hint;          // 0 = the dispatcher's choice (the Stage-2 trainer's narrow LoRA shapes pass their own)
     a.norm_w = norm_w; a.norm_eps = norm_eps; a.err = e->d_ferr; e->last_stream = s;
+    const bool fp8 = W.w8 && W.ws;
     if (klass_hint == 1 && M >= 2 && ldw == K) {       // decode step: the fragment-tiled copy of this weight, if the caller registered one
-        if (e->tiled_dirty) {
-            e->tiled.clear(); e->tiled8.clear();
-            for (const auto& kv : e->w) {
-                if ((kv.second.dtype != 0 && kv.second.dtype != 2) || kv.first.empty() || kv.first.back() != 't') continue;
-                auto base = e->w.find(kv.first.substr(0, kv.first.size() - 1));
-                if (base == e->w.end() || base->second.dtype != kv.second.dtype || base->second.n != kv.second.n) continue;
-                if (kv.second.dtype == 0) e->tiled[base->second.p] = (const bf16_t*)kv.second.p;
-                else e->tiled8[base->second.p] = (const unsigned char*)kv.second.p;
-            }
-            e->tiled_dirty = false;
-        }
-        auto it = e->tiled.find((const void*)W);
-        if (it != e->tiled.end()) a.Wt = it->second;
-        if (W8 && ws && M >= 17 && M <= 64) {
+        a.Wt = W.wt;
+        if (fp8 && M >= 17 && M <= 64) {
             // 17..64-row step of an e4m3-weight engine: every projection streams the e4m3 fragment-tiled copy (gemm_wide.hip, round 3) -
             // half the bytes of the bf16 routes these row counts took before (the row-major e4m3 stream of gemm_skinny.hip was slower than
             // bf16 at 17..32 rows and unused beyond).  The RMSNorm runs as its own launch.
-            auto it8 = e->tiled8.find((const void*)W8);
-            if (it8 != e->tiled8.end()) {
+            if (W.w8t) {
                 LinearArgs t = a;
-                t.W8t = it8->second; t.wscale = ws; t.W8 = nullptr; t.Wt = nullptr; t.wide_ok = true;
+                t.W8t = W.w8t; t.wscale = W.ws; t.W8 = nullptr; t.Wt = nullptr; t.wide_ok = true;
                 if (norm_w) { t.A = e->d_xnorm; t.lda = K; t.norm_w = nullptr; }
                 if (vz_wide_ok(t)) {
                     if (norm_w) {
@@ -387,13 +379,13 @@ static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const 
         }
     }
     a.wide_ok = klass_hint == 1;          // 1 = decode step: rows are independent sequences
-    if (W8 && ws) {                       // e4m3 copy of the same weights: only the weight-stream kernels (M <= 32) take it
-        a.W8 = W8; a.wscale = ws;
+    if (fp8) {                            // e4m3 copy of the same weights: only the weight-stream kernels (M <= 32) take it
+        a.W8 = W.w8; a.wscale = W.ws;
         LinearArgs t = a;
         if (M > 16) t.norm_w = nullptr;   // 17..32 rows: the norm runs as its own kernel below
         if (!vz_gemv_ok(t) && !(g_skinny_mode && vz_skinny_ok(t))) { a.W8 = nullptr; a.wscale = nullptr; }
     }
-    if (klass_hint == 1 && M >= 17 && M <= 64 && a.Wt && (!(W8 && ws) || M >= std::max(g_decode_tile_rows, 33))) {      // (e4m3 engines: from where they leave the e4m3 stream anyway)
+    if (klass_hint == 1 && M >= 17 && M <= 64 && a.Wt && (!fp8 || M >= std::max(g_decode_tile_rows, 33))) {      // (e4m3 engines: from where they leave the e4m3 stream anyway)
         // 17..64-row decode step on the tiled weight copy (gemm_wide.hip): weights straight to registers, the activations of a 512-k
         // chunk staged once per 128 weight rows - for the projections whose row blocks fill the chip without a K split (gate|up,
         // lm_head: measured 52.7 vs 62 us and 55 vs 91 us at 64 rows; the split shapes stay on the tile GEMM).  The RMSNorm runs
@@ -411,7 +403,7 @@ static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const 
             return vz_launch_wide(t, s);
         }
     }
-    if (klass_hint == 1 && M >= ((W8 && ws) ? std::max(g_decode_tile_rows, 33) : g_decode_tile_rows) && M <= 64 && g_skinny_mode && (K & 63) == 0) {     // (e4m3 stream: ahead up to 32 rows)
+    if (klass_hint == 1 && M >= (fp8 ? std::max(g_decode_tile_rows, 33) : g_decode_tile_rows) && M <= 64 && g_skinny_mode && (K & 63) == 0) {     // (e4m3 stream: ahead up to 32 rows)
         // 17..64-row decode step as a TILE GEMM: the 128^2 MFMA kernel streams every weight once at the rate its workgroups can pull
         // (gate-up 48 us = 4.9 TB/s whatever the row count), where the MFMA weight stream of gemm_skinny.hip re-reads the activations
         // per 16-row group and falls to 2.7 TB/s at 64 rows (tools/bench_rows.py, profiles/r02_rows.txt).  Projections with few column
@@ -567,7 +559,7 @@ extern "C" int vz_engine_set_weight(vz_engine* e, const char* name, const void* 
     VZ_CHECK_ARG(((uintptr_t)d_ptr & 15) == 0, "set_weight: '%s' must be 16-byte aligned", name);
     RC(drop_decode_graph(e));
     e->w[name] = Weight{d_ptr, dtype, n_elems};
-    e->finalized = false; e->tiled_dirty = true;
+    e->finalized = false;
     return VZ_OK;
 }
 
@@ -576,7 +568,7 @@ extern "C" int vz_engine_unset_weight(vz_engine* e, const char* name) {
     VZ_CHECK_ARG(e && name, "unset_weight: bad argument");
     RC(drop_decode_graph(e));
     e->w.erase(name);
-    e->finalized = false; e->tiled_dirty = true;
+    e->finalized = false;
     return VZ_OK;
 }
 
@@ -602,38 +594,75 @@ static int kpad_patch(const vz_config& c) { return (int)align_up((size_t)3 * c.c
 extern "C" int vz_engine_finalize(vz_engine* e) {
     VZ_CHECK_ARG(e, "finalize: null engine");
     const vz_config& c = e->c;
+    e->finalized = false;
     int rc = VZ_OK;
-    const long C = c.clip_hidden, H = c.hidden, tokens = (c.clip_image / c.clip_patch) * (c.clip_image / c.clip_patch) + 1;
-    WB("clip.patch_w", C * kpad_patch(c)); WB("clip.cls", C); WB("clip.pos", tokens * C);
-    WF("clip.pre_ln.w", C); WF("clip.pre_ln.b", C);
-    for (int i = 0; i < c.clip_layers && !rc; ++i) {
+    // a registered tensor of the expected dtype and element count; the first one that is missing or differs fails the call
+    auto get = [&](const std::string& name, int dtype, long n) -> const void* {
+        if (rc) return nullptr;
+        auto it = e->w.find(name);
+        if (it == e->w.end()) { vz_set_error("weight '%s' was never registered", name.c_str()); rc = VZ_ERR_STATE; return nullptr; }
+        if (it->second.dtype != dtype || it->second.n != n) {
+            vz_set_error("weight '%s': expected dtype %d n %ld, got dtype %d n %ld", name.c_str(), dtype, n, it->second.dtype,
+                         it->second.n);
+            rc = VZ_ERR_STATE;
+            return nullptr;
+        }
+        return it->second.p;
+    };
+    // the fragment-tiled copy of a matrix: "<name>t" with the same dtype and element count, else none
+    auto tiled = [&](const std::string& name, int dtype, long n) -> const void* {
+        auto it = e->w.find(name + "t");
+        return it != e->w.end() && it->second.dtype == dtype && it->second.n == n ? it->second.p : nullptr;
+    };
+    auto vec = [&](const std::string& name, long n) { return (const float*)get(name, 1, n); };
+    auto mat = [&](const std::string& name, long n) { return (const bf16_t*)get(name, 0, n); };
+    auto norm = [&](const std::string& p, long n) { NormW r; r.w = vec(p + ".w", n); r.b = vec(p + ".b", n); return r; };
+    auto lin = [&](const std::string& name, long n) { LinW l; l.w = mat(name, n); l.wt = (const bf16_t*)tiled(name, 0, n); return l; };
+    auto lin_b = [&](const std::string& p, long n, long nb) { LinW l = lin(p + ".w", n); l.b = vec(p + ".b", nb); return l; };
+    // weight_fp8: the e4m3 copy (and its tiled copy) + the row scales of a decode-side linear
+    auto fp8 = [&](LinW& l, const std::string& n8, const std::string& ns, long n, long rows) {
+        if (!c.weight_fp8) return;
+        l.w8 = (const unsigned char*)get(n8, 2, n); l.w8t = (const unsigned char*)tiled(n8, 2, n); l.ws = vec(ns, rows);
+    };
+    const long C = c.clip_hidden, H = c.hidden, KD = c.qf_kv_dim, tokens = (c.clip_image / c.clip_patch) * (c.clip_image / c.clip_patch) + 1;
+    TopW& t = e->top;
+    t.clip_patch_w = mat("clip.patch_w", C * kpad_patch(c)); t.clip_cls = mat("clip.cls", C); t.clip_pos = mat("clip.pos", tokens * C);
+    t.clip_pre_ln = norm("clip.pre_ln", C);
+    e->clip.assign(c.clip_layers, ClipLayerW());
+    for (int i = 0; i < c.clip_layers; ++i) {
         const std::string p = "clip." + std::to_string(i) + ".";
-        WF(p + "ln1.w", C); WF(p + "ln1.b", C); WB(p + "qkv.w", 3 * C * C); WF(p + "qkv.b", 3 * C);
-        WB(p + "o.w", C * C); WF(p + "o.b", C); WF(p + "ln2.w", C); WF(p + "ln2.b", C);
-        WB(p + "fc1.w", (long)c.clip_inter * C); WF(p + "fc1.b", c.clip_inter);
-        WB(p + "fc2.w", (long)c.clip_inter * C); WF(p + "fc2.b", C);
+        ClipLayerW& L = e->clip[i];
+        L.ln1 = norm(p + "ln1", C); L.qkv = lin_b(p + "qkv", 3 * C * C, 3 * C); L.o = lin_b(p + "o", C * C, C); L.ln2 = norm(p + "ln2", C);
+        L.fc1 = lin_b(p + "fc1", c.clip_inter * C, c.clip_inter); L.fc2 = lin_b(p + "fc2", c.clip_inter * C, C);
     }
-    WB("qf.queries", (long)c.qf_queries * H); WF("qf.pre_norm.w", c.qf_kv_dim); WF("qf.pre_norm.b", c.qf_kv_dim);
-    WF("qf.norm.w", H); WF("qf.norm.b", H);
-    for (int i = 0; i < c.qf_blocks && !rc; ++i) {
+    t.qf_queries = mat("qf.queries", c.qf_queries * H); t.qf_pre_norm = norm("qf.pre_norm", KD); t.qf_norm = norm("qf.norm", H);
+    e->qf.assign(c.qf_blocks, QfBlockW());
+    for (int i = 0; i < c.qf_blocks; ++i) {
         const std::string p = "qf." + std::to_string(i) + ".";
-        for (const char* n : {"n1", "n2", "n3"}) { WF(p + n + ".w", H); WF(p + n + ".b", H); }
-        WB(p + "sa_in.w", 3 * H * H); WF(p + "sa_in.b", 3 * H); WB(p + "sa_out.w", H * H); WF(p + "sa_out.b", H);
-        WB(p + "ca_q.w", H * H); WF(p + "ca_q.b", H); WB(p + "ca_kv.w", 2 * H * c.qf_kv_dim); WF(p + "ca_kv.b", 2 * H);
-        WB(p + "ca_out.w", H * H); WF(p + "ca_out.b", H);
-        WB(p + "ffn1.w", 2 * H * H); WF(p + "ffn1.b", 2 * H); WB(p + "ffn2.w", 2 * H * H); WF(p + "ffn2.b", H);
+        QfBlockW& Q = e->qf[i];
+        Q.n1 = norm(p + "n1", H); Q.n2 = norm(p + "n2", H); Q.n3 = norm(p + "n3", H);
+        Q.sa_in = lin_b(p + "sa_in", 3 * H * H, 3 * H); Q.sa_out = lin_b(p + "sa_out", H * H, H);
+        Q.ca_q = lin_b(p + "ca_q", H * H, H); Q.ca_kv = lin_b(p + "ca_kv", 2 * H * KD, 2 * H); Q.ca_out = lin_b(p + "ca_out", H * H, H);
+        Q.ffn1 = lin_b(p + "ffn1", 2 * H * H, 2 * H); Q.ffn2 = lin_b(p + "ffn2", 2 * H * H, H);
     }
-    const long qkv_n = (long)(e->Hq_l + 2 * e->Hkv_l) * c.head_dim;
-    WB("llm.embed", (long)c.vocab * H); WF("llm.norm", H); WB("llm.lm_head", (long)e->Vp * H);
-    W8("llm.lm_head8", (long)e->Vp * H); WS("llm.lm_heads", e->Vp);
-    for (int i = 0; i < c.n_layers && !rc; ++i) {
+    const long qkv_n = (long)(e->Hq_l + 2 * e->Hkv_l) * c.head_dim, A = (long)e->Hq_l * c.head_dim, I = e->I_l;
+    t.embed = mat("llm.embed", (long)c.vocab * H); t.norm = vec("llm.norm", H); t.lm_head = lin("llm.lm_head", (long)e->Vp * H);
+    fp8(t.lm_head, "llm.lm_head8", "llm.lm_heads", (long)e->Vp * H, e->Vp);
+    e->llm.assign(c.n_layers, LlmLayerW());
+    for (int i = 0; i < c.n_layers; ++i) {
         const std::string p = "llm." + std::to_string(i) + ".";
-        WF(p + "in_norm", H); WF(p + "post_norm", H); WB(p + "qkv.w", qkv_n * H); WB(p + "o.w", H * (long)e->Hq_l * c.head_dim);
-        WB(p + "gu.w", 2L * e->I_l * H); WB(p + "down.w", (long)e->I_l * H);
-        W8(p + "qkv.w8", qkv_n * H); WS(p + "qkv.ws", qkv_n); W8(p + "o.w8", H * (long)e->Hq_l * c.head_dim); WS(p + "o.ws", H);
-        W8(p + "gu.w8", 2L * e->I_l * H); WS(p + "gu.ws", 2L * e->I_l); W8(p + "down.w8", (long)e->I_l * H); WS(p + "down.ws", H);
+        LlmLayerW& L = e->llm[i];
+        L.in_norm = vec(p + "in_norm", H); L.post_norm = vec(p + "post_norm", H);
+        L.qkv = lin(p + "qkv.w", qkv_n * H); L.o = lin(p + "o.w", H * A); L.gu = lin(p + "gu.w", 2 * I * H); L.down = lin(p + "down.w", I * H);
+        fp8(L.qkv, p + "qkv.w8", p + "qkv.ws", qkv_n * H, qkv_n); fp8(L.o, p + "o.w8", p + "o.ws", H * A, H);
+        fp8(L.gu, p + "gu.w8", p + "gu.ws", 2 * I * H, 2 * I); fp8(L.down, p + "down.w8", p + "down.ws", I * H, H);
     }
     if (rc) return rc;
+    // vz_qformer runs the cross-attention K|V projections of all blocks as one product when their weights and biases are contiguous
+    // (vz_hip/engine.py allocates them so; a C-ABI caller may too)
+    e->qf_kv_contig = c.qf_blocks > 1;
+    for (int i = 1; i < c.qf_blocks && e->qf_kv_contig; ++i)
+        e->qf_kv_contig = e->qf[i].ca_kv.w == e->qf[0].ca_kv.w + (size_t)i * 2 * H * KD && e->qf[i].ca_kv.b == e->qf[0].ca_kv.b + (size_t)i * 2 * H;
     e->finalized = true;
     return VZ_OK;
 }
@@ -679,26 +708,26 @@ extern "C" int vz_clip_fused_features(vz_engine* e, const void* d_images, int T,
     bf16_t* qkv = m.take<bf16_t>(hs_layer * 3);
     bf16_t* att = m.take<bf16_t>(hs_layer);
     bf16_t* mlp = m.take<bf16_t>((size_t)rows * c.clip_inter);
-    int rc = VZ_OK;
+    const TopW& t = e->top;
     {
         ProfScope ps(e, K_OTHER, s);
         RC(vz_launch_im2col((const bf16_t*)d_images, T, c.clip_image, c.clip_patch, kpad, col, s));
     }
-    RC(linear(e, 0, col, kpad, WB("clip.patch_w", (long)C * kpad), kpad, pe, C, T * P, C, kpad, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+    RC(linear(e, 0, col, kpad, bare(t.clip_patch_w), kpad, pe, C, T * P, C, kpad, nullptr, 0, VZ_ACT_NONE, 0, s));
     {
         ProfScope ps(e, K_OTHER, s);
-        RC(vz_launch_clip_assemble(pe, WB("clip.cls", C), WB("clip.pos", (long)tokens * C), T, tokens, C, att, s));
+        RC(vz_launch_clip_assemble(pe, t.clip_cls, t.clip_pos, T, tokens, C, att, s));
     }
     {
         ProfScope ps(e, K_NORM, s);
-        RC(vz_launch_layernorm(att, C, hs, C, WF("clip.pre_ln.w", C), WF("clip.pre_ln.b", C), rows, C, c.clip_eps, s));
+        RC(vz_launch_layernorm(att, C, hs, C, t.clip_pre_ln.w, t.clip_pre_ln.b, rows, C, c.clip_eps, s));
     }
     for (int i = 0; i < L; ++i) {
-        const std::string p = "clip." + std::to_string(i) + ".";
+        const ClipLayerW& W = e->clip[i];
         bf16_t* x = hs + hs_layer * i;
         bf16_t* xn = hs + hs_layer * (i + 1);
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, C, y, C, WF(p + "ln1.w", C), WF(p + "ln1.b", C), rows, C, c.clip_eps, s)); }
-        RC(linear(e, 0, y, C, WB(p + "qkv.w", 3L * C * C), C, qkv, 3 * C, rows, 3 * C, C, WF(p + "qkv.b", 3 * C), nullptr, 0, VZ_ACT_NONE, 0, s));
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, C, y, C, W.ln1.w, W.ln1.b, rows, C, c.clip_eps, s)); }
+        RC(linear(e, 0, y, C, W.qkv, C, qkv, 3 * C, rows, 3 * C, C, nullptr, 0, VZ_ACT_NONE, 0, s));
         {
             ProfScope ps(e, K_ATTN, s);
             AttnArgs a;
@@ -709,20 +738,14 @@ extern "C" int vz_clip_fused_features(vz_engine* e, const void* d_images, int T,
             a.scale = 0.125f; a.causal = 0; a.q_pos0 = 0; a.window = 0; a.kv_len = nullptr;
             RC(vz_launch_attention(a, s));
         }
-        RC(linear(e, 0, att, C, WB(p + "o.w", (long)C * C), C, xn, C, rows, C, C, WF(p + "o.b", C), x, C, VZ_ACT_NONE, 0, s));
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(xn, C, y, C, WF(p + "ln2.w", C), WF(p + "ln2.b", C), rows, C, c.clip_eps, s)); }
-        RC(linear(e, 0, y, C, WB(p + "fc1.w", (long)c.clip_inter * C), C, mlp, c.clip_inter, rows, c.clip_inter, C,
-                  WF(p + "fc1.b", c.clip_inter), nullptr, 0, VZ_ACT_QUICK_GELU, 0, s));
-        RC(linear(e, 0, mlp, c.clip_inter, WB(p + "fc2.w", (long)c.clip_inter * C), c.clip_inter, xn, C, rows, C, c.clip_inter,
-                  WF(p + "fc2.b", C), xn, C, VZ_ACT_NONE, 0, s));
-        if (rc) return rc;
+        RC(linear(e, 0, att, C, W.o, C, xn, C, rows, C, C, x, C, VZ_ACT_NONE, 0, s));
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(xn, C, y, C, W.ln2.w, W.ln2.b, rows, C, c.clip_eps, s)); }
+        RC(linear(e, 0, y, C, W.fc1, C, mlp, c.clip_inter, rows, c.clip_inter, C, nullptr, 0, VZ_ACT_QUICK_GELU, 0, s));
+        RC(linear(e, 0, mlp, c.clip_inter, W.fc2, c.clip_inter, xn, C, rows, C, c.clip_inter, xn, C, VZ_ACT_NONE, 0, s));
     }
-    {
-        ProfScope ps(e, K_OTHER, s);
-        const int first = L - c.fusion_groups * c.fusion_layers_per_group;
-        RC(vz_launch_fusion(hs, (long)hs_layer, first, c.fusion_groups, c.fusion_layers_per_group, T, tokens, C, c.clip_keep_cls ? 0 : 1, (bf16_t*)d_out, s));
-    }
-    return rc;
+    ProfScope ps(e, K_OTHER, s);
+    const int first = L - c.fusion_groups * c.fusion_layers_per_group;
+    return vz_launch_fusion(hs, (long)hs_layer, first, c.fusion_groups, c.fusion_layers_per_group, T, tokens, C, c.clip_keep_cls ? 0 : 1, (bf16_t*)d_out, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -756,20 +779,12 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
     const int P = (c.clip_image / c.clip_patch) * (c.clip_image / c.clip_patch) + (c.clip_keep_cls ? 1 : 0);   // visual tokens per tile
     const int N0 = NQ + Lmax, FF = 2 * H;
     const size_t R = (size_t)T * NQ;  // query rows in flight after block 0's self-attention
-    int rc = VZ_OK;
     // The cross-attention K|V projections of all blocks read the same pre-normed features.  When their weights (and biases) lie back
-    // to back in memory (vz_hip/engine.py allocates them so; a C-ABI caller may too) they run as ONE product over N = blocks * 2H:
-    // 256 column tiles per row tile = whole residency rounds of the 256^2 kernel, no stream-K tail (8 x 217 us -> one launch).  The
-    // [T * P, blocks * 2H] result is capped at 2 GiB; larger tile batches fill the chip per block anyway.
+    // to back in memory (qf_kv_contig) they run as ONE product over N = blocks * 2H: 256 column tiles per row tile = whole residency
+    // rounds of the 256^2 kernel, no stream-K tail (8 x 217 us -> one launch).  The [T * P, blocks * 2H] result is capped at 2 GiB;
+    // larger tile batches fill the chip per block anyway.
     const int nb = c.qf_blocks;
-    const bf16_t* kvw0 = WB("qf.0.ca_kv.w", 2L * H * KD);
-    const float* kvb0 = WF("qf.0.ca_kv.b", 2 * H);
-    bool kv_all = nb > 1 && (size_t)T * P * nb * 2 * H * sizeof(bf16_t) <= ((size_t)2 << 30) && g_qf_kv_all;
-    for (int i = 1; i < nb && kv_all && !rc; ++i) {
-        const std::string p = "qf." + std::to_string(i) + ".";
-        kv_all = WB(p + "ca_kv.w", 2L * H * KD) == kvw0 + (size_t)i * 2 * H * KD && WF(p + "ca_kv.b", 2 * H) == kvb0 + (size_t)i * 2 * H;
-    }
-    if (rc) return rc;
+    const bool kv_all = e->qf_kv_contig && (size_t)T * P * nb * 2 * H * sizeof(bf16_t) <= ((size_t)2 << 30) && g_qf_kv_all;
     const int kv_ld = kv_all ? nb * 2 * H : 2 * H;
     size_t need;
     {
@@ -799,9 +814,8 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
     // key-split partials (96 keys per workgroup) of the cross-attention and of block 0's self-attention over [queries ; text]
     const size_t part_floats = std::max((size_t)T * ((P + 95) / 96), (size_t)n_samples * ((N0 + 95) / 96)) * c.qf_heads * NQ * (512 + 4);
     float* part = m.take<float>(part_floats);
-    { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm((const bf16_t*)d_feats, KD, fn, KD, WF("qf.pre_norm.w", KD), WF("qf.pre_norm.b", KD), T * P, KD, c.qf_eps, s)); }
-    const bf16_t* queries = WB("qf.queries", (long)NQ * H);
-    if (rc) return rc;
+    { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm((const bf16_t*)d_feats, KD, fn, KD, e->top.qf_pre_norm.w, e->top.qf_pre_norm.b, T * P, KD, c.qf_eps, s)); }
+    const bf16_t* queries = e->top.qf_queries;
     // ---- block 0 self-attention, once per sample, query rows only ----
     {
         ProfScope ps(e, K_OTHER, s);
@@ -812,42 +826,37 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
         }
     }
     {
-        const std::string p = "qf.0.";
-        const bf16_t* w_in = WB(p + "sa_in.w", 3L * H * H);
-        const float* b_in = WF(p + "sa_in.b", 3 * H);
-        if (rc) return rc;
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x0, H, y0, H, WF(p + "n1.w", H), WF(p + "n1.b", H), n_samples * N0, H, c.qf_eps, s)); }
-        RC(linear(e, 0, y0, H, w_in + (size_t)H * H, H, kv0, 2 * H, n_samples * N0, 2 * H, H, b_in + H, nullptr, 0, VZ_ACT_NONE, 0, s));
-        RC(linear(e, 0, y0, H, w_in, H, q0, H, NQ, H, H, b_in, nullptr, 0, VZ_ACT_NONE, 0, s));  // rows 0..31 of sample 0 = LN1(queries)
+        const QfBlockW& W = e->qf[0];
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x0, H, y0, H, W.n1.w, W.n1.b, n_samples * N0, H, c.qf_eps, s)); }
+        RC(linear(e, 0, y0, H, lin_rows(W.sa_in, H, H), H, kv0, 2 * H, n_samples * N0, 2 * H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, y0, H, W.sa_in, H, q0, H, NQ, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));  // rows 0..31 of sample 0 = LN1(queries)
         RC(qf_attn(e, q0, 0, H, kv0, kv0 + H, (long)N0 * 2 * H, 2 * H, a0, n_samples, NQ, N0, s, part, part_floats));
-        RC(linear(e, 0, a0, H, WB(p + "sa_out.w", (long)H * H), H, xs, H, n_samples * NQ, H, H, WF(p + "sa_out.b", H), xs, H, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, a0, H, W.sa_out, H, xs, H, n_samples * NQ, H, H, xs, H, VZ_ACT_NONE, 0, s));
         ProfScope ps(e, K_OTHER, s);
         for (int t = 0; t < T; ++t) RC(vz_launch_copy_rows(xs + (size_t)h_tile_sample[t] * NQ * H, H, x + (size_t)t * NQ * H, H, NQ, H, s));
     }
     for (int i = 0; i < c.qf_blocks; ++i) {
-        const std::string p = "qf." + std::to_string(i) + ".";
+        const QfBlockW& W = e->qf[i];
         if (i > 0) {
-            { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, WF(p + "n1.w", H), WF(p + "n1.b", H), (int)R, H, c.qf_eps, s)); }
-            RC(linear(e, 0, y, H, WB(p + "sa_in.w", 3L * H * H), H, qkv, 3 * H, (int)R, 3 * H, H, WF(p + "sa_in.b", 3 * H), nullptr, 0, VZ_ACT_NONE, 0, s));
+            { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, W.n1.w, W.n1.b, (int)R, H, c.qf_eps, s)); }
+            RC(linear(e, 0, y, H, W.sa_in, H, qkv, 3 * H, (int)R, 3 * H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
             RC(qf_attn(e, qkv, (long)NQ * 3 * H, 3 * H, qkv + H, qkv + 2 * H, (long)NQ * 3 * H, 3 * H, att, T, NQ, NQ, s));
-            RC(linear(e, 0, att, H, WB(p + "sa_out.w", (long)H * H), H, x, H, (int)R, H, H, WF(p + "sa_out.b", H), x, H, VZ_ACT_NONE, 0, s));
+            RC(linear(e, 0, att, H, W.sa_out, H, x, H, (int)R, H, H, x, H, VZ_ACT_NONE, 0, s));
         }
-        // cross-attention against the tile's 576 fused visual tokens
-        if (!kv_all) RC(linear(e, 0, fn, KD, WB(p + "ca_kv.w", 2L * H * KD), KD, ckv, 2 * H, T * P, 2 * H, KD, WF(p + "ca_kv.b", 2 * H), nullptr, 0, VZ_ACT_NONE, 0, s));
-        else if (i == 0) RC(linear(e, 0, fn, KD, kvw0, KD, ckv, kv_ld, T * P, kv_ld, KD, kvb0, nullptr, 0, VZ_ACT_NONE, 0, s));
+        // cross-attention against the tile's 576 fused visual tokens (kv_all: block 0's ca_kv heads the weights of every block)
+        if (!kv_all || i == 0) RC(linear(e, 0, fn, KD, W.ca_kv, KD, ckv, kv_ld, T * P, kv_ld, KD, nullptr, 0, VZ_ACT_NONE, 0, s));
         const bf16_t* ck = kv_all ? ckv + (size_t)i * 2 * H : ckv;
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, WF(p + "n2.w", H), WF(p + "n2.b", H), (int)R, H, c.qf_eps, s)); }
-        RC(linear(e, 0, y, H, WB(p + "ca_q.w", (long)H * H), H, qkv, H, (int)R, H, H, WF(p + "ca_q.b", H), nullptr, 0, VZ_ACT_NONE, 0, s));
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, W.n2.w, W.n2.b, (int)R, H, c.qf_eps, s)); }
+        RC(linear(e, 0, y, H, W.ca_q, H, qkv, H, (int)R, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         RC(qf_attn(e, qkv, (long)NQ * H, H, ck, ck + H, (long)P * kv_ld, kv_ld, att, T, NQ, P, s, part, part_floats));
-        RC(linear(e, 0, att, H, WB(p + "ca_out.w", (long)H * H), H, x, H, (int)R, H, H, WF(p + "ca_out.b", H), x, H, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, att, H, W.ca_out, H, x, H, (int)R, H, H, x, H, VZ_ACT_NONE, 0, s));
         // FFN
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, WF(p + "n3.w", H), WF(p + "n3.b", H), (int)R, H, c.qf_eps, s)); }
-        RC(linear(e, 0, y, H, WB(p + "ffn1.w", 2L * H * H), H, ff, FF, (int)R, FF, H, WF(p + "ffn1.b", FF), nullptr, 0, VZ_ACT_GELU_ERF, 0, s));
-        RC(linear(e, 0, ff, FF, WB(p + "ffn2.w", 2L * H * H), FF, x, H, (int)R, H, FF, WF(p + "ffn2.b", H), x, H, VZ_ACT_NONE, 0, s));
-        if (rc) return rc;
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, W.n3.w, W.n3.b, (int)R, H, c.qf_eps, s)); }
+        RC(linear(e, 0, y, H, W.ffn1, H, ff, FF, (int)R, FF, H, nullptr, 0, VZ_ACT_GELU_ERF, 0, s));
+        RC(linear(e, 0, ff, FF, W.ffn2, FF, x, H, (int)R, H, FF, x, H, VZ_ACT_NONE, 0, s));
     }
-    { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, (bf16_t*)d_out, H, WF("qf.norm.w", H), WF("qf.norm.b", H), (int)R, H, c.qf_eps, s)); }
-    return rc;
+    ProfScope ps(e, K_NORM, s);
+    return vz_launch_layernorm(x, H, (bf16_t*)d_out, H, e->top.qf_norm.w, e->top.qf_norm.b, (int)R, H, c.qf_eps, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -856,12 +865,9 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
 extern "C" int vz_embed_splice(vz_engine* e, const int* d_kind, const int* d_idx, int rows, const void* d_visual, void* d_out,
                                vz_stream stream) {
     NEED_READY();
-    int rc = VZ_OK;
-    const bf16_t* table = WB("llm.embed", (long)e->c.vocab * e->c.hidden);
-    if (rc) return rc;
     VZ_CHECK_ARG(d_idx && d_out && rows > 0, "splice: bad argument");
     ProfScope ps(e, K_OTHER, (hipStream_t)stream);
-    return vz_launch_gather_rows(d_kind, d_idx, rows, e->c.hidden, table, (const bf16_t*)d_visual, (bf16_t*)d_out, (hipStream_t)stream);
+    return vz_launch_gather_rows(d_kind, d_idx, rows, e->c.hidden, e->top.embed, (const bf16_t*)d_visual, (bf16_t*)d_out, (hipStream_t)stream);
 }
 
 
@@ -917,17 +923,12 @@ static int ensure_gather(vz_engine* e, int rows, hipStream_t s) {
 static int lm_head_logits(vz_engine* e, const bf16_t* h, int rows, float* out, hipStream_t s, const float* norm_w) {
     const vz_config& c = e->c;
     const int H = c.hidden;
-    int rc = VZ_OK;
-    const bf16_t* lm = WB("llm.lm_head", (long)e->Vp * H);
-    if (rc) return rc;
-    const unsigned char* lm8 = W8("llm.lm_head8", (long)e->Vp * H);
-    const float* lms = WS("llm.lm_heads", e->Vp);
-    if (rc) return rc;
-    if (tp_local(e)) return linear(e, norm_w ? 1 : 0, h, H, lm, H, out, c.vocab, rows, c.vocab, H, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s, norm_w, c.rms_eps, lm8, lms);
+    const LinW& lm = e->top.lm_head;
+    if (tp_local(e)) return linear(e, norm_w ? 1 : 0, h, H, lm, H, out, c.vocab, rows, c.vocab, H, nullptr, 0, VZ_ACT_NONE, 1, s, norm_w, c.rms_eps);
     const size_t local_off = ((size_t)e->tp * rows * e->Vp + 3) & ~(size_t)3;      // the GEMM wants a 16-byte-aligned output base
     { int r = ensure_gather(e, rows, s); if (r) return r; }
     float* local = e->d_gather + local_off;
-    RC(linear(e, norm_w ? 1 : 0, h, H, lm, H, local, e->Vp, rows, e->Vp, H, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s, norm_w, c.rms_eps, lm8, lms));
+    RC(linear(e, norm_w ? 1 : 0, h, H, lm, H, local, e->Vp, rows, e->Vp, H, nullptr, 0, VZ_ACT_NONE, 1, s, norm_w, c.rms_eps));
     if (!e->comm && !tp_skip(e)) { vz_set_error("tensor-parallel engine used before vz_comm_init"); return VZ_ERR_STATE; }
     if (tp_skip(e)) {     // rehearsal: this rank's shard goes to its own chunk, the others stay zero
         VZ_CHECK_HIP(hipMemsetAsync(e->d_gather, 0, (size_t)e->tp * rows * e->Vp * sizeof(float), s));
@@ -1063,37 +1064,31 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
         for (int b = 0; b < B; ++b) h[rows + b] = h_seqlens[b];
         RC(upload_ints(e, h.data(), h.size(), d_ints, s));
     }
-    int rc = VZ_OK;
     // one Zephyr prefill linear: bf16 tile GEMM, or - weight_fp8 engine with vz_engine_prefill_fp8 on - the input rows quantised to e4m3
     // (one power-of-two scale per row) and the product on the fp8 MFMA against the e4m3 weight copy (gemm_fp8.hip)
     // (below ~768 rows the quantiser launches and the shallow grids cost more than the fp8 MFMA saves: 330 rows 20.4 vs 18.6 ms, 1320 rows 37.5 vs 43.6)
     const bool f8 = e->prefill_fp8 && rows >= g_fp8_prefill_min_rows && tp_local(e) && vz_gemm_fp8_ok(rows, QKV, H, H, H) && vz_gemm_fp8_ok(rows, H, I, I, I) && vz_gemm_fp8_ok(rows, H, A, A, A);
     // norm_w != null: Ain is the residual stream and the RMSNorm belongs to this linear (fp8: norm + quantiser in one launch)
-    auto plin = [&](const bf16_t* Ain, const float* norm_w, const std::string& wname, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
-        const bf16_t* W = WB(wname + ".w", (long)N * K);
-        if (rc) return rc;
+    auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
         if (f8) {
-            const unsigned char* w8 = W8(wname + ".w8", (long)N * K);
-            const float* ws = WS(wname + ".ws", N);
-            if (rc) return rc;
             {
                 ProfScope ps(e, K_NORM, s);
                 if (norm_w) RC(vz_launch_rmsnorm_quant_fp8(Ain, K, norm_w, c.rms_eps, q8, K, qs, rows, K, s));
                 else RC(vz_launch_quant_rows_fp8(Ain, K, q8, K, qs, rows, K, s));
             }
             Fp8LinearArgs f;
-            f.A8 = q8; f.lda = K; f.ascale = qs; f.W8 = w8; f.ldw = K; f.wscale = ws; f.C = Cout; f.ldc = ldc; f.M = rows; f.N = N; f.K = K;
+            f.A8 = q8; f.lda = K; f.ascale = qs; f.W8 = W.w8; f.ldw = K; f.wscale = W.ws; f.C = Cout; f.ldc = ldc; f.M = rows; f.N = N; f.K = K;
             f.bias = nullptr; f.residual = res; f.ldr = H; f.act = act; f.out_fp32 = 0;
             ProfScope ps(e, K_GEMM, s);
             return vz_launch_gemm_fp8(f, s);
         }
         if (norm_w) { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(Ain, K, y, K, norm_w, rows, K, c.rms_eps, s)); }
-        return linear(e, 0, norm_w ? y : Ain, K, W, K, Cout, ldc, rows, N, K, nullptr, res, H, act, 0, s);
+        return linear(e, 0, norm_w ? y : Ain, K, bare(W.w), K, Cout, ldc, rows, N, K, res, H, act, 0, s);      // (the bf16 matrix only: prefill never streams the e4m3 copy)
     };
     { ProfScope ps(e, K_OTHER, s); RC(vz_launch_copy_rows((const bf16_t*)d_embeds, H, x, H, rows, H, s)); }
     for (int i = 0; i < c.n_layers; ++i) {
-        const std::string p = "llm." + std::to_string(i) + ".";
-        RC(plin(x, WF(p + "in_norm", H), p + "qkv", QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
+        const LlmLayerW& W = e->llm[i];
+        RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
         // RoPE of K + the KV append; the queries are rotated by the attention's own Q load (g_rope_in_attn; else a rotated copy q as before)
         const bool rope_q_late = g_rope_in_attn && D == 128 && vz_attn_version() != 1;
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, rope_q_late ? nullptr : q, kc_of(e, i) + row_off, vc_of(e, i) + row_off, e->cosT, e->sinT, d_pos, d_slot, B, S, Hq, Hkv, D, c.max_ctx, s)); }
@@ -1110,15 +1105,13 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
             a.causal = 1; a.q_pos0 = 0; a.window = c.sliding_window; a.kv_len = d_len;
             RC(vz_launch_attention(a, s));
         }
-        RC(plin(att, nullptr, p + "o", H, A, x, H, lead ? x : nullptr, VZ_ACT_NONE));
+        RC(plin(att, nullptr, W.o, H, A, x, H, lead ? x : nullptr, VZ_ACT_NONE));
         RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
-        RC(plin(x, WF(p + "post_norm", H), p + "gu", 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
-        RC(plin(act, nullptr, p + "down", H, I, x, H, lead ? x : nullptr, VZ_ACT_NONE));
+        RC(plin(x, W.post_norm, W.gu, 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
+        RC(plin(act, nullptr, W.down, H, I, x, H, lead ? x : nullptr, VZ_ACT_NONE));
         RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
-        if (rc) return rc;
     }
-    const float* fn = WF("llm.norm", H);
-    if (rc) return rc;
+    const float* fn = e->top.norm;
     if (d_logits_all) {
         { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(x, H, y, H, fn, rows, H, c.rms_eps, s)); }
         RC(lm_head_logits(e, y, rows, d_logits_all, s, nullptr));
@@ -1131,7 +1124,7 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
         { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(ylast, H, ylast + (size_t)B * H, H, fn, B, H, c.rms_eps, s)); }
         RC(lm_head_logits(e, ylast + (size_t)B * H, B, d_logits_last, s, nullptr));
     }
-    return rc;
+    return VZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1218,13 +1211,11 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     bf16_t* att = m.take<bf16_t>((size_t)B * A);
     bf16_t* act = m.take<bf16_t>((size_t)B * I);
     if (!m.ok) { vz_set_error("decode: workspace too small"); return VZ_ERR_STATE; }
-    int rc = VZ_OK;
     if (e->use_tok && e->tok) {
         // batch 1 on an MI355X: embedding row -> 32 layers -> logits as the phases of ONE resident grid (decode_persist.hip); same
         // arithmetic as the launches below, bit for bit
         VzTokArgs a;
-        a.embed = WB("llm.embed", (long)c.vocab * H); a.lm_head = WB("llm.lm_head", (long)e->Vp * H); a.final_norm = WF("llm.norm", H);
-        if (rc) return rc;
+        a.embed = e->top.embed; a.lm_head = e->top.lm_head.w; a.final_norm = e->top.norm;
         a.cur = cur; a.pos = pos; a.slot = slot; a.step = step;
         a.logits = e->d_logits; a.part = e->d_part; a.ticket = e->d_ticket; a.cosT = e->cosT; a.sinT = e->sinT; a.err = e->d_ferr;
         a.vocab = c.vocab; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.window = c.sliding_window; a.scale = 0.08838834764831845f; a.eps = c.rms_eps;
@@ -1232,13 +1223,12 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
         ProfScope ps(e, K_GEMV, s);
         RC(vz_launch_decode_token(e->tok, a, s));
     } else {
-        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(cur, B, H, WB("llm.embed", (long)c.vocab * H), x, s)); }
+        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
-            const std::string p = "llm." + std::to_string(i) + ".";
+            const LlmLayerW& W = e->llm[i];
             const bool fuse_ao = g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
-            RC(linear(e, 1, x, H, WB(p + "qkv.w", (long)QKV * H), H, qkv, QKV, B, QKV, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s, WF(p + "in_norm", H), c.rms_eps,
-                      W8(p + "qkv.w8", (long)QKV * H), WS(p + "qkv.ws", QKV)));
+            RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
             {
                 ProfScope ps(e, K_ATTN_DEC, s);
                 AttnDecodeFusedArgs a;
@@ -1248,30 +1238,21 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
                 a.scale = 0.08838834764831845f;
                 if (fuse_ao) {
                     // batch 1 (round 3): the O projection's workgroups ride in the attention's grid and stream their weights under its latency
-                    // chain (attn_o_fused.hip); same arithmetic as the two launches, bit for bit
-                    const bf16_t* ow = WB(p + "o.w", (long)H * A);
-                    const unsigned char* ow8 = W8(p + "o.w8", (long)H * A);        // a weight_fp8 engine: the e4m3 rows + scales (as linear() would take them)
-                    const float* ows = WS(p + "o.ws", H);
-                    if (rc) return rc;
-                    RC(vz_launch_attn_o_fused(a, ow, ow8, ows, att, x, e->d_ao_done, step, i, c.n_layers, e->d_ferr, s));
+                    // chain (attn_o_fused.hip); same arithmetic as the two launches, bit for bit (a weight_fp8 engine: the e4m3 rows +
+                    // scales, as linear() would take them)
+                    RC(vz_launch_attn_o_fused(a, W.o.w, W.o.w8, W.o.ws, att, x, e->d_ao_done, step, i, c.n_layers, e->d_ferr, s));
                 } else {
                     RC(vz_launch_attn_decode_fused(a, s));
                 }
             }
-            if (!fuse_ao)
-                RC(linear(e, 1, att, A, WB(p + "o.w", (long)H * A), A, x, H, B, H, A, nullptr, lead ? x : nullptr, H, VZ_ACT_NONE, 0, s, nullptr, 0.f,
-                          W8(p + "o.w8", (long)H * A), WS(p + "o.ws", H)));
+            if (!fuse_ao) RC(linear(e, 1, att, A, W.o, A, x, H, B, H, A, lead ? x : nullptr, H, VZ_ACT_NONE, 0, s));
             RC(tp_allreduce_bf16(e, x, (size_t)B * H, s, true));
-            RC(linear(e, 1, x, H, WB(p + "gu.w", 2L * I * H), H, act, I, B, 2 * I, H, nullptr, nullptr, 0, VZ_ACT_SWIGLU, 0, s, WF(p + "post_norm", H), c.rms_eps,
-                      W8(p + "gu.w8", 2L * I * H), WS(p + "gu.ws", 2L * I)));
-            RC(linear(e, 1, act, I, WB(p + "down.w", (long)I * H), I, x, H, B, H, I, nullptr, lead ? x : nullptr, H, VZ_ACT_NONE, 0, s, nullptr, 0.f,
-                      W8(p + "down.w8", (long)I * H), WS(p + "down.ws", H)));
+            RC(linear(e, 1, x, H, W.gu, H, act, I, B, 2 * I, H, nullptr, 0, VZ_ACT_SWIGLU, 0, s, W.post_norm, c.rms_eps));
+            RC(linear(e, 1, act, I, W.down, I, x, H, B, H, I, lead ? x : nullptr, H, VZ_ACT_NONE, 0, s));
             RC(tp_allreduce_bf16(e, x, (size_t)B * H, s, true));
-            if (rc) return rc;
         }
-        RC(lm_head_logits(e, x, B, e->d_logits, s, WF("llm.norm", H)));
+        RC(lm_head_logits(e, x, B, e->d_logits, s, e->top.norm));
     }
-    if (rc) return rc;
     if (d_logits_dbg) {
         // debug copy is indexed by the host (eager mode only)
         VZ_CHECK_HIP(hipMemcpyAsync(d_logits_dbg, e->d_logits, (size_t)B * c.vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1463,15 +1444,12 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         c.n_kv_heads == 8 && c.head_dim == 128 && c.vocab >= 256 && vz_decode_persist_supported()) {
         if (!e->tok) {
             std::vector<VzTokLayerHost> lt(c.n_layers);
-            int rc = VZ_OK;
-            const long H = c.hidden, QKV = (long)(c.n_heads + 2 * c.n_kv_heads) * c.head_dim, I = c.inter;
             for (int i = 0; i < c.n_layers; ++i) {
-                const std::string p = "llm." + std::to_string(i) + ".";
-                lt[i].qkv_w = WB(p + "qkv.w", QKV * H); lt[i].o_w = WB(p + "o.w", H * H); lt[i].gu_w = WB(p + "gu.w", 2 * I * H); lt[i].down_w = WB(p + "down.w", I * H);
-                lt[i].in_norm = WF(p + "in_norm", H); lt[i].post_norm = WF(p + "post_norm", H);
+                const LlmLayerW& W = e->llm[i];
+                lt[i].qkv_w = W.qkv.w; lt[i].o_w = W.o.w; lt[i].gu_w = W.gu.w; lt[i].down_w = W.down.w;
+                lt[i].in_norm = W.in_norm; lt[i].post_norm = W.post_norm;
                 lt[i].kc = kc_of(e, i); lt[i].vc = vc_of(e, i);
             }
-            if (rc) return rc;
             RC(vz_decode_persist_create(lt.data(), c.n_layers, &e->tok));
         }
         RC(vz_decode_persist_reset(e->tok, s));         // arrival counters restart with the step counter

@@ -26,6 +26,10 @@ struct LoraState {
     int step = 0; long sample_base = 0, row_stride = 0;         // dropout counter of the next micro-batch
 };
 
+// gradients of the projector tensors in the trainer's flat fp32 arena, by block: parallel to the engine's Q-Former table
+struct GradWB { float* w = nullptr; float* b = nullptr; };          // a linear's weight + bias, or a LayerNorm's scale + shift
+struct QfBlockG { GradWB n1, n2, n3, sa_in, sa_out, ca_q, ca_kv, ca_out, ffn1, ffn2; };
+
 struct vz_trainer {
     vz_engine* e = nullptr;
     std::vector<bf16_t*> t_qkv, t_o, t_gu, t_down;     // W^T of the frozen Zephyr linears: [H,QKV] [A,H] [H,2I] [I,H]
@@ -37,14 +41,34 @@ struct vz_trainer {
     int adam_t = 0;
     ncclComm_t dp_comm = nullptr; int dp_world = 1;
     LoraState lora;
+    std::vector<QfBlockG> g_qf; GradWB g_pre_norm, g_norm; float* g_queries = nullptr;     // into `grad` (bind_grads)
 };
 
-static float* G_(vz_trainer* tr, const std::string& name, long n, int* rc) {
-    auto it = tr->index.find(name);
-    if (it == tr->index.end() || tr->params[it->second].n != n) { vz_set_error("trainer: no projector tensor '%s' of %ld elements", name.c_str(), n); *rc = VZ_ERR_STATE; return nullptr; }
-    return tr->grad + tr->params[it->second].off;
+// points the projector gradient table into the current `grad` arena (vz_train_create; again when LoRA moves the arenas)
+static int bind_grads(vz_trainer* tr) {
+    const vz_config& c = tr->e->c;
+    const long H = c.hidden, KD = c.qf_kv_dim;
+    int rc = VZ_OK;
+    auto g = [&](const std::string& name, long n) -> float* {
+        auto it = tr->index.find(name);
+        if (it != tr->index.end() && tr->params[it->second].n == n) return tr->grad + tr->params[it->second].off;
+        if (!rc) vz_set_error("trainer: no projector tensor '%s' of %ld elements", name.c_str(), n);
+        rc = VZ_ERR_STATE;
+        return nullptr;
+    };
+    auto wb = [&](const std::string& p, long n, long nb) { GradWB r; r.w = g(p + ".w", n); r.b = g(p + ".b", nb); return r; };
+    tr->g_queries = g("qf.queries", c.qf_queries * H); tr->g_pre_norm = wb("qf.pre_norm", KD, KD); tr->g_norm = wb("qf.norm", H, H);
+    tr->g_qf.assign(c.qf_blocks, QfBlockG());
+    for (int i = 0; i < c.qf_blocks; ++i) {
+        const std::string p = "qf." + std::to_string(i) + ".";
+        QfBlockG& G = tr->g_qf[i];
+        G.n1 = wb(p + "n1", H, H); G.n2 = wb(p + "n2", H, H); G.n3 = wb(p + "n3", H, H);
+        G.sa_in = wb(p + "sa_in", 3 * H * H, 3 * H); G.sa_out = wb(p + "sa_out", H * H, H);
+        G.ca_q = wb(p + "ca_q", H * H, H); G.ca_kv = wb(p + "ca_kv", 2 * H * KD, 2 * H); G.ca_out = wb(p + "ca_out", H * H, H);
+        G.ffn1 = wb(p + "ffn1", 2 * H * H, 2 * H); G.ffn2 = wb(p + "ffn2", 2 * H * H, H);
+    }
+    return rc;
 }
-#define GR(name, n) G_(tr, name, (long)(n), &rc)
 
 static int pad64(int v) { return (v + 63) & ~63; }
 
@@ -73,10 +97,9 @@ extern "C" int vz_train_create(vz_engine* e, vz_trainer** out, vz_stream stream)
     const int H = c.hidden, D = c.head_dim, QKV = (c.n_heads + 2 * c.n_kv_heads) * D, A = c.n_heads * D, I = c.inter;
     vz_trainer* tr = new vz_trainer();
     tr->e = e;
-    int rc = VZ_OK;
     auto fail = [&](int r) { vz_train_destroy(tr); return r; };
     for (int i = 0; i < c.n_layers; ++i) {
-        const std::string p = "llm." + std::to_string(i) + ".";
+        const LlmLayerW& W = e->llm[i];
         bf16_t *a = nullptr, *b = nullptr, *g = nullptr, *d = nullptr;
         if (hipMalloc((void**)&a, (size_t)H * QKV * 2) != hipSuccess || hipMalloc((void**)&b, (size_t)A * H * 2) != hipSuccess ||
             hipMalloc((void**)&g, (size_t)H * 2 * I * 2) != hipSuccess || hipMalloc((void**)&d, (size_t)I * H * 2) != hipSuccess) {
@@ -84,16 +107,16 @@ extern "C" int vz_train_create(vz_engine* e, vz_trainer** out, vz_stream stream)
             return fail(VZ_ERR_HIP);
         }
         tr->t_qkv.push_back(a); tr->t_o.push_back(b); tr->t_gu.push_back(g); tr->t_down.push_back(d);
-        int r = transpose2d(WB(p + "qkv.w", (long)QKV * H), QKV, H, a, QKV, s);
-        if (!r) r = transpose2d(WB(p + "o.w", (long)H * A), H, A, b, H, s);
-        if (!r) r = transpose2d(WB(p + "gu.w", 2L * I * H), 2 * I, H, g, 2 * I, s);
-        if (!r) r = transpose2d(WB(p + "down.w", (long)I * H), H, I, d, H, s);
-        if (r || rc) return fail(r ? r : rc);
+        int r = transpose2d(W.qkv.w, QKV, H, a, QKV, s);
+        if (!r) r = transpose2d(W.o.w, H, A, b, H, s);
+        if (!r) r = transpose2d(W.gu.w, 2 * I, H, g, 2 * I, s);
+        if (!r) r = transpose2d(W.down.w, H, I, d, H, s);
+        if (r) return fail(r);
     }
     tr->Vpad = pad64(c.vocab);
     if (hipMalloc((void**)&tr->t_lm, (size_t)H * tr->Vpad * 2) != hipSuccess) { vz_set_error("train_create: out of memory"); return fail(VZ_ERR_HIP); }
     (void)hipMemsetAsync(tr->t_lm, 0, (size_t)H * tr->Vpad * 2, s);
-    { int r = transpose2d(WB("llm.lm_head", (long)c.vocab * H), c.vocab, H, tr->t_lm, tr->Vpad, s); if (r || rc) return fail(r ? r : rc); }
+    { int r = transpose2d(e->top.lm_head.w, c.vocab, H, tr->t_lm, tr->Vpad, s); if (r) return fail(r); }
     // projector tensors in a fixed order (sorted names): the flat arenas follow it
     std::vector<std::string> names;
     for (auto& kv : e->w) if (kv.first.rfind("qf.", 0) == 0) names.push_back(kv.first);
@@ -110,6 +133,7 @@ extern "C" int vz_train_create(vz_engine* e, vz_trainer** out, vz_stream stream)
         if (hipMalloc((void**)p, off * sizeof(float)) != hipSuccess) { vz_set_error("train_create: out of memory for the optimiser arenas"); return fail(VZ_ERR_HIP); }
         (void)hipMemsetAsync(*p, 0, off * sizeof(float), s);
     }
+    { int r = bind_grads(tr); if (r) return fail(r); }
     for (auto& pp : tr->params) {       // master <- working copy (exact for fp32 vectors; matrices: see vz_train_set_master)
         if (pp.dtype == 1) (void)hipMemcpyAsync(tr->master + pp.off, pp.work, pp.n * sizeof(float), hipMemcpyDeviceToDevice, s);
         else {
@@ -200,6 +224,7 @@ extern "C" int vz_train_lora_enable(vz_trainer* tr, int r, float alpha, float dr
         return VZ_ERR_HIP;
     }
     for (int k = 0; k < 4; ++k) { (void)hipFree(*arenas[k]); *arenas[k] = fresh[k]; }
+    RC(bind_grads(tr));                 // the projector tensors keep their offsets in the new gradient arena
     tr->lora.first = (int)tr->params.size();
     for (size_t k = 0; k < add.size(); ++k) {
         add[k].work = work + wo[k];
@@ -363,7 +388,7 @@ static int weight_grad(vz_engine* e, Carver& m, const bf16_t* dY, int ldy, const
     { ProfScope ps(e, K_OTHER, s);
       RC(vz_launch_transpose(dY, ldy, 0, 0, dYt, Rp, 0, 0, (int)R, N, 1, 1, 0, s));
       RC(vz_launch_transpose(X, ldx, 0, 0, Xt, Rp, 0, 0, (int)R, K, 1, 1, 0, s)); }
-    RC(linear(e, 0, dYt, Rp, Xt, Rp, tmp, K, N, K, Rp, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s, nullptr, 0.f, nullptr, nullptr, splitk_hint));
+    RC(linear(e, 0, dYt, Rp, bare(Xt), Rp, tmp, K, N, K, Rp, nullptr, 0, VZ_ACT_NONE, 1, s, nullptr, 0.f, splitk_hint));
     { ProfScope ps(e, K_OTHER, s);
       RC(vz_launch_axpy_f32(dW, tmp, (long)N * K, s));
       if (db) RC(vz_launch_colsum(dY, ldy, R, N, part, db, s)); }
@@ -378,7 +403,7 @@ static int input_grad(vz_engine* e, Carver& m, const bf16_t* dY, int ldy, const 
     bf16_t* Wt = m.take<bf16_t>((size_t)K * N);
     if (!m.ok) { vz_set_error("input_grad: workspace too small"); return VZ_ERR_STATE; }
     { ProfScope ps(e, K_OTHER, s); RC(transpose2d(W, N, K, Wt, N, s)); }
-    RC(linear(e, 0, dY, ldy, Wt, N, dX, ldx, (int)R, K, N, nullptr, res, ldx, VZ_ACT_NONE, 0, s));
+    RC(linear(e, 0, dY, ldy, bare(Wt), N, dX, ldx, (int)R, K, N, res, ldx, VZ_ACT_NONE, 0, s));
     m.off = save;
     return VZ_OK;
 }
@@ -429,9 +454,9 @@ static int lora_fwd(vz_trainer* tr, Carver m, int layer, int mod, const bf16_t* 
     if (!m.ok) { vz_set_error("train: LoRA forward scratch too small (internal sizing error)"); return VZ_ERR_STATE; }
     bf16_t* u = pl.lora_u + ((size_t)layer * LORA_MODS + mod) * rows * r;
     RC(lora_call(tr, layer, mod, x, ldx, xd, in, nullptr, B, S, s));
-    RC(linear(e, 0, xd, in, (const bf16_t*)lora_param(tr, layer, mod, 0).work, in, u, r, (int)rows, r, in, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s,
-              nullptr, 0.f, nullptr, nullptr, lora_splitk((int)rows, r, in)));
-    return linear(e, 0, u, r, (const bf16_t*)lora_param(tr, layer, mod, 1).work, r, y, ldy, (int)rows, out, r, nullptr, y, ldy, VZ_ACT_NONE, 0, s);
+    RC(linear(e, 0, xd, in, bare((const bf16_t*)lora_param(tr, layer, mod, 0).work), in, u, r, (int)rows, r, in, nullptr, 0, VZ_ACT_NONE, 0, s,
+              nullptr, 0.f, lora_splitk((int)rows, r, in)));
+    return linear(e, 0, u, r, bare((const bf16_t*)lora_param(tr, layer, mod, 1).work), r, y, ldy, (int)rows, out, r, y, ldy, VZ_ACT_NONE, 0, s);
 }
 
 static int lora_bwd(vz_trainer* tr, Carver m, int layer, int mod, const bf16_t* g, int ldg, const bf16_t* x, int ldx, bf16_t* dX, int lddx,
@@ -451,9 +476,8 @@ static int lora_bwd(vz_trainer* tr, Carver m, int layer, int mod, const bf16_t* 
     { ProfScope ps(e, K_OTHER, s);
       RC(transpose2d((const bf16_t*)pb.work, out, r, bt, out, s));
       RC(transpose2d((const bf16_t*)pa.work, r, in, at, r, s)); }
-    RC(linear(e, 0, g, ldg, bt, out, v, r, (int)rows, r, out, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s, nullptr, 0.f, nullptr, nullptr,
-              lora_splitk((int)rows, r, out)));
-    RC(linear(e, 0, v, r, at, r, t, in, (int)rows, in, r, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+    RC(linear(e, 0, g, ldg, bare(bt), out, v, r, (int)rows, r, out, nullptr, 0, VZ_ACT_NONE, 0, s, nullptr, 0.f, lora_splitk((int)rows, r, out)));
+    RC(linear(e, 0, v, r, bare(at), r, t, in, (int)rows, in, r, nullptr, 0, VZ_ACT_NONE, 0, s));
     RC(lora_call(tr, layer, mod, t, in, dX, lddx, dX, B, S, s));
     RC(weight_grad(e, m, g, ldg, u, r, rows, out, r, tr->grad + pb.off, nullptr, s, lora_splitk(out, r, pad64((int)rows))));
     RC(lora_call(tr, layer, mod, x, ldx, t, in, nullptr, B, S, s));
@@ -505,7 +529,6 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
     const int N0 = NQ + Lmax;
     const long R = (long)T * NQ, TP = (long)T * Pv, rows = (long)B * S, R0 = (long)n_samples * N0, RS = (long)n_samples * NQ;
     const float qscale = 1.0f / sqrtf((float)QD), lscale = 1.0f / sqrtf((float)D);
-    int rc = VZ_OK;
     const LoraState& lo = tr->lora;
     const int lr = lo.r;
     VZ_CHECK_ARG(!lr || lo.row_stride >= S, "train: LoRA dropout row stride %ld < S=%d (vz_train_lora_set_counter)", lo.row_stride, S);
@@ -599,9 +622,8 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
 
     // ================= forward =================
     RC(vz_clip_fused_features(e, d_images, T, pl.feats, nullptr, stream));
-    { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(pl.feats, KD, pl.fn, KD, WF("qf.pre_norm.w", KD), WF("qf.pre_norm.b", KD), (int)TP, KD, c.qf_eps, s)); }
-    const bf16_t* queries = WB("qf.queries", (long)NQ * H);
-    if (rc) return rc;
+    { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(pl.feats, KD, pl.fn, KD, e->top.qf_pre_norm.w, e->top.qf_pre_norm.b, (int)TP, KD, c.qf_eps, s)); }
+    const bf16_t* queries = e->top.qf_queries;
     for (int sm = 0; sm < n_samples; ++sm) {
         RC(vz_launch_copy_rows(queries, H, pl.x0 + (size_t)sm * N0 * H, H, NQ, H, s));
         if (Lmax > 0) RC(vz_launch_copy_rows((const bf16_t*)d_text + (size_t)sm * Lmax * H, H, pl.x0 + ((size_t)sm * N0 + NQ) * H, H, Lmax, H, s));
@@ -611,50 +633,46 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         return qf_attn(e, q, q_bs, q_ss, k, v, kv_bs, kv_ss, o, Bn, Sq, Sk, s);
     };
     {
-        const std::string p = "qf.0.";
-        const bf16_t* w_in = WB(p + "sa_in.w", 3L * H * H);
-        const float* b_in = WF(p + "sa_in.b", 3 * H);
-        if (rc) return rc;
-        RC(vz_launch_layernorm(pl.x0, H, pl.y0, H, WF(p + "n1.w", H), WF(p + "n1.b", H), (int)R0, H, c.qf_eps, s));
-        RC(linear(e, 0, pl.y0, H, w_in + (size_t)H * H, H, pl.kv0, 2 * H, (int)R0, 2 * H, H, b_in + H, nullptr, 0, VZ_ACT_NONE, 0, s));
-        RC(linear(e, 0, pl.y0, H, w_in, H, pl.q0, H, NQ, H, H, b_in, nullptr, 0, VZ_ACT_NONE, 0, s));
+        const QfBlockW& W = e->qf[0];
+        RC(vz_launch_layernorm(pl.x0, H, pl.y0, H, W.n1.w, W.n1.b, (int)R0, H, c.qf_eps, s));
+        RC(linear(e, 0, pl.y0, H, lin_rows(W.sa_in, H, H), H, pl.kv0, 2 * H, (int)R0, 2 * H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, pl.y0, H, W.sa_in, H, pl.q0, H, NQ, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         RC(qattn(pl.q0, 0, H, pl.kv0, pl.kv0 + H, (long)N0 * 2 * H, 2 * H, pl.a0, n_samples, NQ, N0));
-        RC(linear(e, 0, pl.a0, H, WB(p + "sa_out.w", (long)H * H), H, pl.xs, H, (int)RS, H, H, WF(p + "sa_out.b", H), pl.xs, H, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, pl.a0, H, W.sa_out, H, pl.xs, H, (int)RS, H, H, pl.xs, H, VZ_ACT_NONE, 0, s));
         for (int t = 0; t < T; ++t) RC(vz_launch_copy_rows(pl.xs + (size_t)h_tile_sample[t] * NQ * H, H, pl.blk[0].x_a + (size_t)t * NQ * H, H, NQ, H, s));
     }
     for (int i = 0; i < NB; ++i) {
-        const std::string p = "qf." + std::to_string(i) + ".";
+        const QfBlockW& W = e->qf[i];
         Blk& b = pl.blk[i];
         if (i > 0) {
-            RC(vz_launch_layernorm(b.x_in, H, b.y1, H, WF(p + "n1.w", H), WF(p + "n1.b", H), (int)R, H, c.qf_eps, s));
-            RC(linear(e, 0, b.y1, H, WB(p + "sa_in.w", 3L * H * H), H, b.qkv, 3 * H, (int)R, 3 * H, H, WF(p + "sa_in.b", 3 * H), nullptr, 0, VZ_ACT_NONE, 0, s));
+            RC(vz_launch_layernorm(b.x_in, H, b.y1, H, W.n1.w, W.n1.b, (int)R, H, c.qf_eps, s));
+            RC(linear(e, 0, b.y1, H, W.sa_in, H, b.qkv, 3 * H, (int)R, 3 * H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
             RC(qattn(b.qkv, (long)NQ * 3 * H, 3 * H, b.qkv + H, b.qkv + 2 * H, (long)NQ * 3 * H, 3 * H, b.att_s, T, NQ, NQ));
-            RC(linear(e, 0, b.att_s, H, WB(p + "sa_out.w", (long)H * H), H, b.x_a, H, (int)R, H, H, WF(p + "sa_out.b", H), b.x_in, H, VZ_ACT_NONE, 0, s));
+            RC(linear(e, 0, b.att_s, H, W.sa_out, H, b.x_a, H, (int)R, H, H, b.x_in, H, VZ_ACT_NONE, 0, s));
         }
-        RC(linear(e, 0, pl.fn, KD, WB(p + "ca_kv.w", 2L * H * KD), KD, b.ckv, 2 * H, (int)TP, 2 * H, KD, WF(p + "ca_kv.b", 2 * H), nullptr, 0, VZ_ACT_NONE, 0, s));
-        RC(vz_launch_layernorm(b.x_a, H, b.y2, H, WF(p + "n2.w", H), WF(p + "n2.b", H), (int)R, H, c.qf_eps, s));
-        RC(linear(e, 0, b.y2, H, WB(p + "ca_q.w", (long)H * H), H, b.qc, H, (int)R, H, H, WF(p + "ca_q.b", H), nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, pl.fn, KD, W.ca_kv, KD, b.ckv, 2 * H, (int)TP, 2 * H, KD, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(vz_launch_layernorm(b.x_a, H, b.y2, H, W.n2.w, W.n2.b, (int)R, H, c.qf_eps, s));
+        RC(linear(e, 0, b.y2, H, W.ca_q, H, b.qc, H, (int)R, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         RC(qattn(b.qc, (long)NQ * H, H, b.ckv, b.ckv + H, (long)Pv * 2 * H, 2 * H, b.att_c, T, NQ, Pv));
-        RC(linear(e, 0, b.att_c, H, WB(p + "ca_out.w", (long)H * H), H, b.x_b, H, (int)R, H, H, WF(p + "ca_out.b", H), b.x_a, H, VZ_ACT_NONE, 0, s));
-        RC(vz_launch_layernorm(b.x_b, H, b.y3, H, WF(p + "n3.w", H), WF(p + "n3.b", H), (int)R, H, c.qf_eps, s));
-        RC(linear(e, 0, b.y3, H, WB(p + "ffn1.w", 2L * H * H), H, b.ffh, FF, (int)R, FF, H, WF(p + "ffn1.b", FF), nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, b.att_c, H, W.ca_out, H, b.x_b, H, (int)R, H, H, b.x_a, H, VZ_ACT_NONE, 0, s));
+        RC(vz_launch_layernorm(b.x_b, H, b.y3, H, W.n3.w, W.n3.b, (int)R, H, c.qf_eps, s));
+        RC(linear(e, 0, b.y3, H, W.ffn1, H, b.ffh, FF, (int)R, FF, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         RC(vz_launch_gelu_fwd(b.ffh, b.ff, R * FF, s));
         bf16_t* x_next = i + 1 < NB ? pl.blk[i + 1].x_in : pl.x_fin;
-        RC(linear(e, 0, b.ff, FF, WB(p + "ffn2.w", 2L * H * H), FF, x_next, H, (int)R, H, FF, WF(p + "ffn2.b", H), b.x_b, H, VZ_ACT_NONE, 0, s));
-        if (rc) return rc;
+        RC(linear(e, 0, b.ff, FF, W.ffn2, FF, x_next, H, (int)R, H, FF, b.x_b, H, VZ_ACT_NONE, 0, s));
     }
-    RC(vz_launch_layernorm(pl.x_fin, H, pl.proj, H, WF("qf.norm.w", H), WF("qf.norm.b", H), (int)R, H, c.qf_eps, s));
+    RC(vz_launch_layernorm(pl.x_fin, H, pl.proj, H, e->top.qf_norm.w, e->top.qf_norm.b, (int)R, H, c.qf_eps, s));
     // splice + Zephyr forward with saved activations
     RC(vz_embed_splice(e, d_kind, d_idx, (int)rows, pl.proj, pl.emb, stream));
     const size_t kvl = (size_t)B * Hkv * S * D;
     for (int i = 0; i < L; ++i) {
-        const std::string p = "llm." + std::to_string(i) + ".";
+        const LlmLayerW& W = e->llm[i];
         Lay& l = pl.lay[i];
         const bf16_t* xin = i == 0 ? pl.emb : nullptr;
         if (i == 0) RC(vz_launch_copy_rows(xin, H, l.x_in, H, (int)rows, H, s));
         bf16_t* qkv = (bf16_t*)(tr->ws + scratch0);           // [rows, QKV] un-rotated projection: scratch
-        RC(vz_launch_rmsnorm(l.x_in, H, l.y, H, WF(p + "in_norm", H), (int)rows, H, c.rms_eps, s));
-        RC(linear(e, 0, l.y, H, WB(p + "qkv.w", (long)QKV * H), H, qkv, QKV, (int)rows, QKV, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(vz_launch_rmsnorm(l.x_in, H, l.y, H, W.in_norm, (int)rows, H, c.rms_eps, s));
+        RC(linear(e, 0, l.y, H, W.qkv, H, qkv, QKV, (int)rows, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         Carver lf(tr->ws, tr->ws_bytes);                       // LoRA forward scratch: after the un-rotated projection
         lf.off = scratch0; lf.take<bf16_t>(rows * QKV);
         if (lr) for (int mod = 0; mod < 3; ++mod) RC(lora_fwd(tr, lf, i, mod, l.y, H, qkv + (mod == 0 ? 0 : mod == 1 ? A : A + Hkv * D), QKV, pl, B, S, s));
@@ -671,11 +689,11 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             a.scale = lscale; a.causal = 1; a.q_pos0 = 0; a.window = c.sliding_window; a.kv_len = d_len;
             RC(vz_launch_attention(a, s));
         }
-        RC(linear(e, 0, l.att, A, WB(p + "o.w", (long)H * A), A, l.x_mid, H, (int)rows, H, A, nullptr, l.x_in, H, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, l.att, A, W.o, A, l.x_mid, H, (int)rows, H, A, l.x_in, H, VZ_ACT_NONE, 0, s));
         if (lr) RC(lora_fwd(tr, lf, i, 3, l.att, A, l.x_mid, H, pl, B, S, s));
-        RC(vz_launch_rmsnorm(l.x_mid, H, l.y2, H, WF(p + "post_norm", H), (int)rows, H, c.rms_eps, s));
+        RC(vz_launch_rmsnorm(l.x_mid, H, l.y2, H, W.post_norm, (int)rows, H, c.rms_eps, s));
         // gate|up pre-activations are kept (SwiGLU backward needs both): N = 2I plain columns, then the SwiGLU as its own kernel
-        RC(linear(e, 0, l.y2, H, WB(p + "gu.w", 2L * I * H), H, l.gu, 2 * I, (int)rows, 2 * I, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, l.y2, H, W.gu, H, l.gu, 2 * I, (int)rows, 2 * I, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         if (lr) {
             // the fused output interleaves gate and up in 16-column groups: add the two branches on a [gate | up] copy, then put it back
             Carver lg = lf;
@@ -688,15 +706,12 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         }
         RC(vz_launch_swiglu_fwd(l.gu, l.act, rows, I, s));
         bf16_t* x_next = i + 1 < L ? pl.lay[i + 1].x_in : pl.x_last;
-        RC(linear(e, 0, l.act, I, WB(p + "down.w", (long)I * H), I, x_next, H, (int)rows, H, I, nullptr, l.x_mid, H, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, l.act, I, W.down, I, x_next, H, (int)rows, H, I, l.x_mid, H, VZ_ACT_NONE, 0, s));
         if (lr) RC(lora_fwd(tr, lf, i, 6, l.act, I, x_next, H, pl, B, S, s));
-        if (rc) return rc;
     }
-    const float* fnw = WF("llm.norm", H);
-    if (rc) return rc;
+    const float* fnw = e->top.norm;
     RC(vz_launch_rmsnorm(pl.x_last, H, pl.y_last, H, fnw, (int)rows, H, c.rms_eps, s));
-    RC(linear(e, 0, pl.y_last, H, WB("llm.lm_head", (long)V * H), H, pl.logits, V, (int)rows, V, H, nullptr, nullptr, 0, VZ_ACT_NONE, 1, s));
-    if (rc) return rc;
+    RC(linear(e, 0, pl.y_last, H, e->top.lm_head, H, pl.logits, V, (int)rows, V, H, nullptr, 0, VZ_ACT_NONE, 1, s));
     RC(vz_launch_cross_entropy(pl.logits, V, d_labels, rows, S, inv_n, tr->d_loss_rows, pl.dlogits, tr->Vpad, s));
     tr->loss_rows_n = rows;
 
@@ -708,18 +723,18 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
     float* dk = m.take<float>(kvl); float* dv = m.take<float>(kvl);
     const size_t z_scratch = (m.off + 255) & ~(size_t)255;
     if (!m.ok) { vz_set_error("train: arena too small (internal sizing error)"); return VZ_ERR_STATE; }
-    RC(linear(e, 0, pl.dlogits, tr->Vpad, tr->t_lm, tr->Vpad, dy, H, (int)rows, H, tr->Vpad, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+    RC(linear(e, 0, pl.dlogits, tr->Vpad, bare(tr->t_lm), tr->Vpad, dy, H, (int)rows, H, tr->Vpad, nullptr, 0, VZ_ACT_NONE, 0, s));
     RC(vz_launch_rmsnorm_bwd(pl.x_last, fnw, dy, nullptr, dx, rows, H, c.rms_eps, s));
     for (int i = L - 1; i >= 0; --i) {
-        const std::string p = "llm." + std::to_string(i) + ".";
+        const LlmLayerW& W = e->llm[i];
         Lay& l = pl.lay[i];
         // x_out = x_mid + down(act):  dact = dx . W_down
-        RC(linear(e, 0, dx, H, tr->t_down[i], H, dact, I, (int)rows, I, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, dx, H, bare(tr->t_down[i]), H, dact, I, (int)rows, I, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         Carver lb(tr->ws, tr->ws_bytes);                       // LoRA backward scratch: the attention backward's region, used before / after it
         lb.off = z_scratch;
         if (lr) RC(lora_bwd(tr, lb, i, 6, dx, H, l.act, I, dact, I, pl, B, S, s));
         RC(vz_launch_swiglu_bwd(l.gu, dact, dgu, rows, I, s));
-        RC(linear(e, 0, dgu, 2 * I, tr->t_gu[i], 2 * I, dy, H, (int)rows, H, 2 * I, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, dgu, 2 * I, bare(tr->t_gu[i]), 2 * I, dy, H, (int)rows, H, 2 * I, nullptr, 0, VZ_ACT_NONE, 0, s));
         if (lr) {
             Carver lg = lb;
             bf16_t* g = lg.take<bf16_t>(rows * 2 * I);         // d(gate | up) in [gate | up] halves
@@ -728,9 +743,9 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             RC(lora_bwd(tr, lg, i, 4, g, 2 * I, l.y2, H, dy, H, pl, B, S, s));
             RC(lora_bwd(tr, lg, i, 5, g + I, 2 * I, l.y2, H, dy, H, pl, B, S, s));
         }
-        RC(vz_launch_rmsnorm_bwd(l.x_mid, WF(p + "post_norm", H), dy, dx, dx2, rows, H, c.rms_eps, s));       // dx2 = d x_mid
+        RC(vz_launch_rmsnorm_bwd(l.x_mid, W.post_norm, dy, dx, dx2, rows, H, c.rms_eps, s));       // dx2 = d x_mid
         // x_mid = x_in + o(att):  datt = dx2 . W_o
-        RC(linear(e, 0, dx2, H, tr->t_o[i], H, datt, A, (int)rows, A, H, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, dx2, H, bare(tr->t_o[i]), H, datt, A, (int)rows, A, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         if (lr) RC(lora_bwd(tr, lb, i, 3, dx2, H, l.att, A, datt, A, pl, B, S, s));
         AttnBwd ab;
         ab.q = l.qrot; ab.k = pl.kc + (size_t)i * kvl; ab.v = pl.vc + (size_t)i * kvl; ab.dO = datt;
@@ -741,10 +756,9 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
         ab.dk_bs = (long)Hkv * S * D; ab.dk_ss = D; ab.dk_hs = (long)S * D;
         RC(attn_bwd(e, ab, tr->ws + z_scratch, tr->ws_bytes - z_scratch, s));
         RC(vz_launch_rope_bwd_assemble(dq, dk, dv, dqkv, e->cosT, e->sinT, d_pos, B, S, Hq, Hkv, D, S, s));
-        RC(linear(e, 0, dqkv, QKV, tr->t_qkv[i], QKV, dy, H, (int)rows, H, QKV, nullptr, nullptr, 0, VZ_ACT_NONE, 0, s));
+        RC(linear(e, 0, dqkv, QKV, bare(tr->t_qkv[i]), QKV, dy, H, (int)rows, H, QKV, nullptr, 0, VZ_ACT_NONE, 0, s));
         if (lr) for (int mod = 0; mod < 3; ++mod) RC(lora_bwd(tr, lb, i, mod, dqkv + (mod == 0 ? 0 : mod == 1 ? A : A + Hkv * D), QKV, l.y, H, dy, H, pl, B, S, s));
-        RC(vz_launch_rmsnorm_bwd(l.x_in, WF(p + "in_norm", H), dy, dx2, dx, rows, H, c.rms_eps, s));          // dx = d x_in
-        if (rc) return rc;
+        RC(vz_launch_rmsnorm_bwd(l.x_in, W.in_norm, dy, dx2, dx, rows, H, c.rms_eps, s));          // dx = d x_in
     }
     // ================= backward: Q-Former, all parameter gradients =================
     m.off = scratch0;
@@ -758,40 +772,36 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
     if (!m.ok) { vz_set_error("train: arena too small (internal sizing error, projector backward)"); return VZ_ERR_STATE; }
     const size_t q_scratch = (m.off + 255) & ~(size_t)255;
     auto scratch = [&]() { Carver c2(tr->ws, tr->ws_bytes); c2.off = q_scratch; return c2; };
-    auto ln_bwd = [&](const bf16_t* x, const std::string& nm, const bf16_t* dyv, const bf16_t* dres, bf16_t* dxo, long nrows, int cols) -> int {
-        float* gw = GR(nm + ".w", cols); float* gb = GR(nm + ".b", cols);
-        const float* w = WF(nm + ".w", cols);
-        if (rc) return rc;
+    auto ln_bwd = [&](const bf16_t* x, const NormW& w, const GradWB& g, const bf16_t* dyv, const bf16_t* dres, bf16_t* dxo, long nrows, int cols) -> int {
         ProfScope ps(e, K_NORM, s);
-        return vz_launch_layernorm_bwd(x, w, dyv, dres, dxo, lnpart, gw, gb, nrows, cols, c.qf_eps, s);
+        return vz_launch_layernorm_bwd(x, w.w, dyv, dres, dxo, lnpart, g.w, g.b, nrows, cols, c.qf_eps, s);
     };
     auto wgrad = [&](const bf16_t* dY, int ldy, const bf16_t* X, int ldx, long nrows, int N, int K, float* dW, float* db) -> int {
-        if (rc) return rc;
         Carver c2 = scratch();
         return weight_grad(e, c2, dY, ldy, X, ldx, nrows, N, K, dW, db, s);
     };
     auto igrad = [&](const bf16_t* dY, int ldy, const bf16_t* W, long nrows, int N, int K, bf16_t* dX, int ldx, const bf16_t* res) -> int {
-        if (rc) return rc;
         Carver c2 = scratch();
         return input_grad(e, c2, dY, ldy, W, nrows, N, K, dX, ldx, res, s);
     };
     { ProfScope ps(e, K_OTHER, s); RC(vz_launch_gather_rows_idx(dx, d_vis_rows, dproj, R, H, s)); }
-    RC(ln_bwd(pl.x_fin, "qf.norm", dproj, nullptr, dxq, R, H));
+    RC(ln_bwd(pl.x_fin, e->top.qf_norm, tr->g_norm, dproj, nullptr, dxq, R, H));
     bool have_dfn = false;
     for (int i = NB - 1; i >= 0; --i) {
-        const std::string p = "qf." + std::to_string(i) + ".";
+        const QfBlockW& W = e->qf[i];
+        const QfBlockG& G = tr->g_qf[i];
         Blk& b = pl.blk[i];
         // FFN
-        RC(wgrad(dxq, H, b.ff, FF, R, H, FF, GR(p + "ffn2.w", 2L * H * H), GR(p + "ffn2.b", H)));
-        RC(igrad(dxq, H, WB(p + "ffn2.w", 2L * H * H), R, H, FF, dff, FF, nullptr));
+        RC(wgrad(dxq, H, b.ff, FF, R, H, FF, G.ffn2.w, G.ffn2.b));
+        RC(igrad(dxq, H, W.ffn2.w, R, H, FF, dff, FF, nullptr));
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_gelu_bwd(b.ffh, dff, dffh, R * FF, s)); }
-        RC(wgrad(dffh, FF, b.y3, H, R, FF, H, GR(p + "ffn1.w", 2L * H * H), GR(p + "ffn1.b", FF)));
-        RC(igrad(dffh, FF, WB(p + "ffn1.w", 2L * H * H), R, FF, H, dy_, H, nullptr));
-        RC(ln_bwd(b.x_b, p + "n3", dy_, dxq, dtmp, R, H));
+        RC(wgrad(dffh, FF, b.y3, H, R, FF, H, G.ffn1.w, G.ffn1.b));
+        RC(igrad(dffh, FF, W.ffn1.w, R, FF, H, dy_, H, nullptr));
+        RC(ln_bwd(b.x_b, W.n3, G.n3, dy_, dxq, dtmp, R, H));
         std::swap(dxq, dtmp);                                   // dxq = d x_b
         // cross-attention
-        RC(wgrad(dxq, H, b.att_c, H, R, H, H, GR(p + "ca_out.w", (long)H * H), GR(p + "ca_out.b", H)));
-        RC(igrad(dxq, H, WB(p + "ca_out.w", (long)H * H), R, H, H, datt_, H, nullptr));
+        RC(wgrad(dxq, H, b.att_c, H, R, H, H, G.ca_out.w, G.ca_out.b));
+        RC(igrad(dxq, H, W.ca_out.w, R, H, H, datt_, H, nullptr));
         {
             AttnBwd ab;
             ab.q = b.qc; ab.k = b.ckv; ab.v = b.ckv + H; ab.dO = datt_;
@@ -802,16 +812,16 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             ab.dk = dckv; ab.dv = dckv + H; ab.dkv_fp32 = 0; ab.dk_bs = (long)Pv * 2 * H; ab.dk_ss = 2 * H; ab.dk_hs = QD;
             RC(attn_bwd(e, ab, tr->ws + q_scratch, tr->ws_bytes - q_scratch, s));
         }
-        RC(wgrad(dqc, H, b.y2, H, R, H, H, GR(p + "ca_q.w", (long)H * H), GR(p + "ca_q.b", H)));
-        RC(igrad(dqc, H, WB(p + "ca_q.w", (long)H * H), R, H, H, dy_, H, nullptr));
-        RC(wgrad(dckv, 2 * H, pl.fn, KD, TP, 2 * H, KD, GR(p + "ca_kv.w", 2L * H * KD), GR(p + "ca_kv.b", 2 * H)));
-        RC(igrad(dckv, 2 * H, WB(p + "ca_kv.w", 2L * H * KD), TP, 2 * H, KD, dfn, KD, have_dfn ? dfn : nullptr));
+        RC(wgrad(dqc, H, b.y2, H, R, H, H, G.ca_q.w, G.ca_q.b));
+        RC(igrad(dqc, H, W.ca_q.w, R, H, H, dy_, H, nullptr));
+        RC(wgrad(dckv, 2 * H, pl.fn, KD, TP, 2 * H, KD, G.ca_kv.w, G.ca_kv.b));
+        RC(igrad(dckv, 2 * H, W.ca_kv.w, TP, 2 * H, KD, dfn, KD, have_dfn ? dfn : nullptr));
         have_dfn = true;
-        RC(ln_bwd(b.x_a, p + "n2", dy_, dxq, dtmp, R, H));
+        RC(ln_bwd(b.x_a, W.n2, G.n2, dy_, dxq, dtmp, R, H));
         std::swap(dxq, dtmp);                                   // dxq = d x_a
         if (i > 0) {
-            RC(wgrad(dxq, H, b.att_s, H, R, H, H, GR(p + "sa_out.w", (long)H * H), GR(p + "sa_out.b", H)));
-            RC(igrad(dxq, H, WB(p + "sa_out.w", (long)H * H), R, H, H, datt_, H, nullptr));
+            RC(wgrad(dxq, H, b.att_s, H, R, H, H, G.sa_out.w, G.sa_out.b));
+            RC(igrad(dxq, H, W.sa_out.w, R, H, H, datt_, H, nullptr));
             AttnBwd ab;
             ab.q = b.qkv; ab.k = b.qkv + H; ab.v = b.qkv + 2 * H; ab.dO = datt_;
             ab.B = T; ab.Sq = NQ; ab.Sk = NQ; ab.Hq = QH; ab.Hkv = QH; ab.D = QD;
@@ -820,19 +830,16 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             ab.dq = dqkv3; ab.dq_bs = (long)NQ * 3 * H; ab.dq_ss = 3 * H; ab.dq_hs = QD;
             ab.dk = dqkv3 + H; ab.dv = dqkv3 + 2 * H; ab.dkv_fp32 = 0; ab.dk_bs = (long)NQ * 3 * H; ab.dk_ss = 3 * H; ab.dk_hs = QD;
             RC(attn_bwd(e, ab, tr->ws + q_scratch, tr->ws_bytes - q_scratch, s));
-            RC(wgrad(dqkv3, 3 * H, b.y1, H, R, 3 * H, H, GR(p + "sa_in.w", 3L * H * H), GR(p + "sa_in.b", 3 * H)));
-            RC(igrad(dqkv3, 3 * H, WB(p + "sa_in.w", 3L * H * H), R, 3 * H, H, dy_, H, nullptr));
-            RC(ln_bwd(b.x_in, p + "n1", dy_, dxq, dtmp, R, H));
+            RC(wgrad(dqkv3, 3 * H, b.y1, H, R, 3 * H, H, G.sa_in.w, G.sa_in.b));
+            RC(igrad(dqkv3, 3 * H, W.sa_in.w, R, 3 * H, H, dy_, H, nullptr));
+            RC(ln_bwd(b.x_in, W.n1, G.n1, dy_, dxq, dtmp, R, H));
             std::swap(dxq, dtmp);                               // dxq = d x_in = d(output of block i - 1)
         } else {
             // block 0: its self-attention ran once per SAMPLE on the 32 query rows (keys / values over [queries ; text]); the gradient of a
             // sample's rows is the sum over its tiles, and everything below is linear in that gradient
-            const bf16_t* w_in = WB(p + "sa_in.w", 3L * H * H);
-            float* g_in = GR(p + "sa_in.w", 3L * H * H); float* gb_in = GR(p + "sa_in.b", 3 * H);
-            if (rc) return rc;
             { ProfScope ps(e, K_OTHER, s); RC(vz_launch_segment_sum_rows(dxq, pl.tile_map, T, NQ, dxs, n_samples, H, s)); }
-            RC(wgrad(dxs, H, pl.a0, H, RS, H, H, GR(p + "sa_out.w", (long)H * H), GR(p + "sa_out.b", H)));
-            RC(igrad(dxs, H, WB(p + "sa_out.w", (long)H * H), RS, H, H, da0, H, nullptr));
+            RC(wgrad(dxs, H, pl.a0, H, RS, H, H, G.sa_out.w, G.sa_out.b));
+            RC(igrad(dxs, H, W.sa_out.w, RS, H, H, da0, H, nullptr));
             AttnBwd ab;
             ab.q = pl.q0; ab.k = pl.kv0; ab.v = pl.kv0 + H; ab.dO = da0;
             ab.B = n_samples; ab.Sq = NQ; ab.Sk = N0; ab.Hq = QH; ab.Hkv = QH; ab.D = QD;
@@ -843,23 +850,19 @@ extern "C" int vz_train_stage1_accumulate(vz_trainer* tr, const void* d_images, 
             RC(attn_bwd(e, ab, tr->ws + q_scratch, tr->ws_bytes - q_scratch, s));
             // the query projection was computed once (rows 0..31 of sample 0 = LN1(queries), the same for every sample)
             { ProfScope ps(e, K_OTHER, s); RC(vz_launch_segment_sum_rows(dq0, pl.zero_map, n_samples, NQ, dq0sum, 1, H, s)); }
-            RC(wgrad(dq0sum, H, pl.y0, H, NQ, H, H, g_in, gb_in));
-            RC(wgrad(dkv0, 2 * H, pl.y0, H, R0, 2 * H, H, g_in + (size_t)H * H, gb_in + H));
-            RC(igrad(dkv0, 2 * H, w_in + (size_t)H * H, R0, 2 * H, H, dy0, H, nullptr));
-            RC(igrad(dq0sum, H, w_in, NQ, H, H, dy0, H, dy0));           // + dq . Wq into the query rows of sample 0
-            RC(ln_bwd(pl.x0, p + "n1", dy0, nullptr, dx0, R0, H));
+            RC(wgrad(dq0sum, H, pl.y0, H, NQ, H, H, G.sa_in.w, G.sa_in.b));
+            RC(wgrad(dkv0, 2 * H, pl.y0, H, R0, 2 * H, H, G.sa_in.w + (size_t)H * H, G.sa_in.b + H));
+            RC(igrad(dkv0, 2 * H, W.sa_in.w + (size_t)H * H, R0, 2 * H, H, dy0, H, nullptr));
+            RC(igrad(dq0sum, H, W.sa_in.w, NQ, H, H, dy0, H, dy0));           // + dq . Wq into the query rows of sample 0
+            RC(ln_bwd(pl.x0, W.n1, G.n1, dy0, nullptr, dx0, R0, H));
             // learned_queries: residual path of every sample (xs = queries + ...) + the query rows of every sample's [queries ; text]
-            float* gq = GR("qf.queries", (long)NQ * H);
-            if (rc) return rc;
             ProfScope ps(e, K_OTHER, s);
-            RC(vz_launch_acc_rows_f32(gq, dxs, n_samples, (long)NQ * H, NQ, H, s));
-            RC(vz_launch_acc_rows_f32(gq, dx0, n_samples, (long)N0 * H, NQ, H, s));
+            RC(vz_launch_acc_rows_f32(tr->g_queries, dxs, n_samples, (long)NQ * H, NQ, H, s));
+            RC(vz_launch_acc_rows_f32(tr->g_queries, dx0, n_samples, (long)N0 * H, NQ, H, s));
         }
-        if (rc) return rc;
     }
     // pre_norm (LayerNorm 5120 of the fused visual features): parameter gradients only - the features are constants (CLIP runs under no_grad)
-    RC(ln_bwd(pl.feats, "qf.pre_norm", dfn, nullptr, nullptr, TP, KD));
-    return rc;
+    return ln_bwd(pl.feats, e->top.qf_pre_norm, tr->g_pre_norm, dfn, nullptr, nullptr, TP, KD);
 }
 
 // sum over the rows of the last micro-batch of (logsumexp - target logit): the caller multiplies by inv_n and adds micro-batches
