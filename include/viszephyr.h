@@ -308,6 +308,8 @@ int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, i
 /* how the last vz_llm_decode_steps ran: *graph = 1 when a captured hipGraph was replayed; *comm_in_graph = 1 when the RCCL
  * collectives of a tensor-parallel engine are part of that graph (0 = eager steps, e.g. after RCCL refused the capture) */
 int vz_llm_decode_mode(vz_engine* e, int* graph, int* comm_in_graph);
+/* context splits of the last decode-steps call (its context bucket) and the graphs captured since the engine was created */
+int vz_llm_decode_info(vz_engine* e, int* nsplit, int* captures);
 /* Batch-1 decode on an MI355X (ABI 10): after vz_tune_set(28, 1), with one row, one GPU, bf16 weights and the Zephyr-7B geometry,
  * vz_llm_decode_steps runs every token as ONE resident grid (decode_persist.hip: the 161 launches of a step become phases with
  * in-launch hand-offs; bit-identical logits).  Opt-in: on MI355X it measured slower than the launch chain.  A phase hand-off that expires raises VZ_ASYNC_PERSIST (vz_engine_async_error).
@@ -378,6 +380,48 @@ int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, 
 /* device-to-device copy of the whole KV cache (bf16 [layer][K|V][max_batch][kv head][max_ctx][head_dim]) into d_out; *bytes = its
  * size (d_out = NULL: the size only).  Tests. */
 int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* bytes, vz_stream stream);
+
+/* ---- prompt-lookup speculative decoding of one greedy sequence (hf:generation/candidate_generator.py PromptLookupCandidateGenerator;
+ * csrc/spec.hip; vz_hip/spec.py) ----
+ * A verify step carries R = D + 1 rows (D in 1..7) of ONE sequence in cache row 0: row 0 = the last emitted token, rows 1..D = guessed
+ * continuations.  Row i runs at rotary position p + i, appends its K / V at cache slot L + i and sees keys [.., L + i]; g_i = argmax of
+ * row i (the argmax op's tie rule); the step emits g_0 .. g_a for the longest prefix with draft_(i+1) == g_i, stops at the first eos id
+ * among them (inclusive) and at `budget` ids, and advances the state by the number emitted.
+ * Control words (device int32 [VZ_SPEC_CTL_WORDS]): write index into d_out, history length, done flag (eos emitted / budget reached:
+ * later steps emit nothing), ids the current draft holds, steps run; words 8..15 = the last step's argmax ids.
+ * Arm it with a decode-begin call of R rows (tokens [t, any..], positions p + i, context lengths L + i), then the decode-spec call
+ * (enable=1): d_hist int32 [hist_cap] holds hist_len ids, one per position of the sequence so far INCLUDING the token of row 0 (-1 = a
+ * position without a text id: never matches, ends a proposal); d_out int32 [budget]; d_stats int32 [stats_cap][3] = {drafted, draft ids
+ * used, emitted} per step (NULL = none); source 0 = drafts by the n-gram rule (max_ngram 1..4), 1 = the step drafts
+ * d_stream[w .. w + D) where w = its write index (tests, benchmarks).  L + 1 + budget + D <= max_ctx is required.  The decode-steps call
+ * then runs verify steps (its d_out_ids argument is not written); enable = 0: the plain tail again.  tp_size > 1: unsupported.
+ * The op-level calls run the pieces on caller-provided buffers: the draft rule for a history (-> d_draft [D], count in
+ * d_ctl[VZ_SPEC_CTL_DRAFTED]); argmax + acceptance on logits [R, cols] with d_state = [cur | pos | slot | len] x R (d_stats [3]);
+ * RoPE + append of R fresh QKV rows (pos / slot [R]) + the verify attention over cache row [Hkv][max_ctx][D] -> o [R, Hq, D]
+ * (q_rot [R, Hq, D] scratch; ws from the part-floats call; ticket [Hkv] zeroed once; key_bound >= slot[0] + R keys, which fixes the
+ * absolute split positions: nsplit x 128-key multiples).
+ * A query's reduction order is a function of key positions only - and the output therefore bit-independent of the drafts - while a
+ * split is exactly 128 keys, i.e. while the context bucket has no more 128-key chunks than splits (<= 32 with the default split limit:
+ * max_ctx <= 4096).  Beyond that a split is a larger multiple of 128 that follows the host's worst-case bound, and results agree to
+ * bf16 rounding only. */
+#define VZ_SPEC_CTL_WRITE 0
+#define VZ_SPEC_CTL_HIST 1
+#define VZ_SPEC_CTL_DONE 2
+#define VZ_SPEC_CTL_DRAFTED 3
+#define VZ_SPEC_CTL_STEPS 4
+#define VZ_SPEC_CTL_IDS 8
+#define VZ_SPEC_CTL_WORDS 16
+int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram, int* d_hist, int hist_len, int hist_cap, const int* h_eos, int n_eos,
+                       int* d_out, int budget, int* d_ctl, int* d_stats, int stats_cap, int source, const int* d_stream, int stream_len,
+                       vz_stream stream);
+int vz_op_spec_draft(const int* d_hist, int hist_len, int D, int max_ngram, const int* h_eos, int n_eos, int* d_draft, int* d_ctl,
+                     vz_stream stream);
+int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist, int hist_cap,
+                      const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream);
+long vz_op_spec_part_floats(int R, int Hkv, int nsplit);
+int vz_op_attention_verify(const void* qkv, void* kc, void* vc, void* o, void* q_rot, float* ws, unsigned* ticket, const float* cosT,
+                           const float* sinT, const int* pos, const int* slot, int R, int Hq, int Hkv, int D, int max_ctx, int nsplit,
+                           int key_bound, int window, float scale, vz_stream stream);
 
 /* ---- anyres preprocessing on the device (ref:vis_zephyr/model/multi_scale_process.py:70-171) ----
  * vz_op_resample_u8: Pillow's 8-bit LANCZOS `Image.resize` (horizontal pass, 8-bit intermediate, vertical pass) of an

@@ -294,8 +294,14 @@ struct vz_engine {
     // reorder | candidate scores | candidate tokens] (BEAM_ROWS rows); beam_hist = the caller's history records, beam_hist_cap steps
     static constexpr int BEAM_ROWS = 64, BEAM_K = 80;
     int beam_on = 0, beam_nb = 0, beam_groups = 0, beam_hist_cap = 0; BeamEos beam_eos{0, {0, 0, 0, 0}}; int* beam_hist = nullptr; int* d_beam = nullptr;
+    // speculative tail (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0.  spec_base_len = keys visible to row 0 when
+    // the mode was armed; spec_key_bound = keys the steps being launched can reach (fixes the verify attention's absolute splits)
+    int spec_on = 0, spec_R = 0, spec_ngram = 2, spec_source = 0, spec_budget = 0, spec_hist_cap = 0, spec_stats_cap = 0, spec_stream_len = 0;
+    int spec_base_len = 0, spec_base_pos = 0, spec_key_bound = 0;
+    int *spec_hist = nullptr, *spec_out = nullptr, *spec_ctl = nullptr, *spec_stats = nullptr; const int* spec_stream = nullptr; BeamEos spec_eos{0, {0, 0, 0, 0}};
     int* ring = nullptr; int ring_n = 0, ring_rows = 0;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [ring_rows][ring_n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
+    int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)
     int dec_nsplit = 1;          // context splits of the decode attention for the steps being launched
     float* d_logits = nullptr;   // [max_batch, vocab] fp32
     bf16_t* d_xnorm = nullptr;   // [64, hidden]: normalised rows of a 5..16-row decode batch (the MFMA weight stream reads them from L2)
@@ -308,7 +314,7 @@ struct vz_engine {
     bool use_tok = false;               // the steps being launched run on it (decided per vz_llm_decode_steps call)
     int tok_poke_word = -1; unsigned tok_poke_value = 0;      // TEST HOOK (vz_test_persist_poke): applied once, behind the next counter reset
     hipStream_t cap_stream = nullptr;   // stream capture is not allowed on the legacy null stream torch hands us
-    hipGraphExec_t dec_graph = nullptr; int dec_graph_B = 0, dec_graph_n = 0, dec_graph_nsplit = 0, dec_graph_tok = -1; long dec_graph_samp[6] = {0, 0, 0, 0, 0, 0}; long dec_graph_beam[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int* dec_graph_out = nullptr; char* dec_graph_arena = nullptr;
+    hipGraphExec_t dec_graph = nullptr; int dec_graph_B = 0, dec_graph_n = 0, dec_graph_nsplit = 0, dec_graph_tok = -1; long dec_graph_samp[6] = {0, 0, 0, 0, 0, 0}; long dec_graph_beam[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long dec_graph_spec[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int* dec_graph_out = nullptr; char* dec_graph_arena = nullptr;
     int* h_pinned = nullptr;     // pinned staging for small host->device uploads
     size_t h_pinned_ints = 0;
     // profiling
@@ -1148,6 +1154,7 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     RC(upload_ints(e, h.data(), h.size(), e->d_state + mb, s));   // [pos | slot | len | step = 0, draw counter, seed lo, seed hi]
     VZ_CHECK_HIP(hipMemcpyAsync(e->d_state, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
     e->dec_B = B;
+    e->spec_on = 0;          // a new batch starts with the plain tail: vz_llm_decode_spec is armed AFTER this call
     e->h_len.assign(B, 0); e->h_pos.assign(B, 0); e->h_parked.assign(B, 0);
     for (int b = 0; b < B; ++b) { e->h_len[b] = h_ctx_len[b] + 1; e->h_pos[b] = h_next_pos[b]; e->h_parked[b] = h_ctx_len[b] == 0 && h_next_pos[b] == 0; }
     return VZ_OK;
@@ -1210,6 +1217,7 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     bf16_t* qkv = m.take<bf16_t>((size_t)B * QKV);
     bf16_t* att = m.take<bf16_t>((size_t)B * A);
     bf16_t* act = m.take<bf16_t>((size_t)B * I);
+    bf16_t* q_rot = e->spec_on ? m.take<bf16_t>((size_t)B * A) : nullptr;      // verify steps: the rotated queries of the R rows
     if (!m.ok) { vz_set_error("decode: workspace too small"); return VZ_ERR_STATE; }
     if (e->use_tok && e->tok) {
         // batch 1 on an MI355X: embedding row -> 32 layers -> logits as the phases of ONE resident grid (decode_persist.hip); same
@@ -1226,10 +1234,20 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
             const LlmLayerW& W = e->llm[i];
-            const bool fuse_ao = g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
+            const bool fuse_ao = !e->spec_on && g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
             RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
-            {
+            if (e->spec_on) {
+                // verify step (spec.hip): the B rows are consecutive positions of ONE sequence - RoPE + append of all of them to cache row 0
+                // (the stand-alone kernel: its bits), then one pass over that row for all B x 32 query heads
+                ProfScope ps(e, K_ATTN_DEC, s);
+                RC(vz_launch_rope_kv(qkv, QKV, q_rot, kc_of(e, i), vc_of(e, i), e->cosT, e->sinT, pos, slot, 1, B, Hq, Hkv, D, c.max_ctx, s));
+                SpecVerifyArgs a;
+                a.q = q_rot; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket; a.slot = slot;
+                a.R = B; a.Hq = Hq; a.Hkv = Hkv; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.key_bound = e->spec_key_bound;
+                a.window = c.sliding_window; a.scale = 0.08838834764831845f;
+                RC(vz_launch_spec_verify_attn(a, s));
+            } else {
                 ProfScope ps(e, K_ATTN_DEC, s);
                 AttnDecodeFusedArgs a;
                 a.qkv = qkv; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket;
@@ -1259,7 +1277,17 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     }
     {
         ProfScope ps(e, K_OTHER, s);
-        if (e->beam_on) {
+        if (e->spec_on) {
+            // speculative tail (spec.hip): per-row argmax, then acceptance + state advance + the next step's draft in one small launch
+            int* g = e->spec_ctl + VZ_SPEC_CTL_IDS;
+            RC(vz_launch_argmax(e->d_logits, B, c.vocab, g, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s));
+            SpecTailArgs t;
+            t.g = g; t.cur = cur; t.draft = cur + 1; t.pos = pos; t.slot = slot; t.len = len; t.ctl = e->spec_ctl; t.out = e->spec_out; t.budget = e->spec_budget;
+            t.hist = e->spec_hist; t.hist_cap = e->spec_hist_cap; t.stats = e->spec_stats; t.stats_cap = e->spec_stats_cap;
+            t.stream = e->spec_stream; t.stream_len = e->spec_stream_len; t.eos = e->spec_eos; t.R = B; t.max_ngram = e->spec_ngram;
+            t.source = e->spec_source; t.max_ctx = c.max_ctx; t.rope_max = e->rope_max; t.do_accept = 1; t.do_draft = 1;
+            RC(vz_launch_spec_tail(t, s));
+        } else if (e->beam_on) {
             // beam tail (beam.hip): select, then the KV of rows whose parent is another row follows the parent, then the history index
             const int nb = e->beam_nb, rows = e->beam_nb * e->beam_groups;
             float* score = (float*)e->d_beam; int* parent = e->d_beam + vz_engine::BEAM_ROWS; int* base = parent + vz_engine::BEAM_ROWS;
@@ -1405,6 +1433,93 @@ extern "C" int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const in
                                      tb, 1, tb + R, 1, s);
 }
 
+// Prompt-lookup speculative decoding (spec.hip; include/viszephyr.h has the contract): after vz_llm_decode_begin armed R = D + 1 rows of one
+// sequence (positions p + i, context lengths L + i), enable = 1 makes every decode step a verify step with the accept + draft tail and
+// writes the first draft into rows 1..D.  enable = 0: the plain tail again.
+extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram, int* d_hist, int hist_len, int hist_cap, const int* h_eos, int n_eos,
+                                  int* d_out, int budget, int* d_ctl, int* d_stats, int stats_cap, int source, const int* d_stream, int stream_len,
+                                  vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->spec_on = 0; return VZ_OK; }
+    const vz_config& c = e->c;
+    if (e->tp > 1) { vz_set_error("decode_spec: speculative decoding on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    const int R = D + 1;
+    VZ_CHECK_ARG(D >= 1 && D <= 7 && R <= c.max_batch && e->dec_B == R, "decode_spec: D = %d draft slots (1..7) need a running decode batch of D + 1 rows "
+                 "(it has %d; max_batch %d)", D, e->dec_B, c.max_batch);
+    VZ_CHECK_ARG(max_ngram >= 1 && max_ngram <= 4 && (source == 0 || source == 1) && d_out && d_ctl && budget >= 0 && stats_cap >= 0 && (d_stats || stats_cap == 0),
+                 "decode_spec: n-gram size 1..4, source 0 / 1, output and control buffers expected");
+    VZ_CHECK_ARG(source == 1 ? (d_stream != nullptr && stream_len >= 0) : (d_hist != nullptr && hist_len >= 1 && hist_len <= hist_cap),
+                 "decode_spec: source 0 needs a history of 1..hist_cap ids, source 1 an id stream");
+    VZ_CHECK_ARG(!d_hist || hist_len + budget <= hist_cap, "decode_spec: the history (%d ids) + %d new ids exceed its capacity %d", hist_len, budget, hist_cap);
+    for (int i = 0; i < R; ++i)
+        VZ_CHECK_ARG(e->h_len[i] == e->h_len[0] + i && e->h_pos[i] == e->h_pos[0] + i, "decode_spec: row %d must sit %d positions behind row 0 (vz_llm_decode_begin)", i, i);
+    VZ_CHECK_ARG(e->h_len[0] + budget + D <= c.max_ctx, "decode_spec: context %d + %d new ids + %d draft slots exceed max_ctx = %d", e->h_len[0], budget, D, c.max_ctx);
+    VZ_CHECK_ARG(e->h_pos[0] + budget + D < e->rope_max, "decode_spec: position %d + %d new ids + %d draft slots exceed the rotary tables (%d)", e->h_pos[0], budget, D, e->rope_max);
+    BeamEos eos;
+    RC(beam_eos_of(h_eos, n_eos, &eos));
+    hipStream_t s = (hipStream_t)stream;
+    int h[VZ_SPEC_CTL_WORDS] = {0};
+    h[VZ_SPEC_CTL_HIST] = d_hist ? hist_len : 0; h[VZ_SPEC_CTL_DONE] = budget == 0;
+    RC(upload_ints(e, h, VZ_SPEC_CTL_WORDS, d_ctl, s));
+    e->spec_on = 1; e->spec_R = R; e->spec_ngram = max_ngram; e->spec_source = source; e->spec_budget = budget; e->spec_hist = d_hist; e->spec_hist_cap = d_hist ? hist_cap : 0;
+    e->spec_out = d_out; e->spec_ctl = d_ctl; e->spec_stats = d_stats; e->spec_stats_cap = stats_cap; e->spec_stream = d_stream; e->spec_stream_len = stream_len;
+    e->spec_eos = eos; e->spec_base_len = e->h_len[0]; e->spec_base_pos = e->h_pos[0];
+    const int mb = c.max_batch;
+    SpecTailArgs t;
+    t.g = nullptr; t.cur = e->d_state; t.draft = t.cur + 1; t.pos = t.cur + mb; t.slot = t.pos + mb; t.len = t.slot + mb; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
+    t.hist = e->spec_hist; t.hist_cap = e->spec_hist_cap; t.stats = nullptr; t.stats_cap = 0; t.stream = d_stream; t.stream_len = stream_len; t.eos = eos;
+    t.R = R; t.max_ngram = max_ngram; t.source = source; t.max_ctx = c.max_ctx; t.rope_max = e->rope_max; t.do_accept = 0; t.do_draft = 1;
+    return vz_launch_spec_tail(t, s);
+}
+
+// the draft rule alone on a device history of hist_len ids: d_draft [D] (padded with 0), the count in d_ctl[VZ_SPEC_CTL_DRAFTED]
+extern "C" int vz_op_spec_draft(const int* d_hist, int hist_len, int D, int max_ngram, const int* h_eos, int n_eos, int* d_draft, int* d_ctl,
+                                vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_hist && d_draft && d_ctl && hist_len >= 0 && D >= 1 && D <= 7, "spec_draft: bad argument");
+    BeamEos eos;
+    RC(beam_eos_of(h_eos, n_eos, &eos));
+    VZ_CHECK_HIP(hipMemsetAsync(d_ctl, 0, VZ_SPEC_CTL_WORDS * sizeof(int), s));
+    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_ctl + VZ_SPEC_CTL_HIST), hist_len, 1, s));
+    SpecTailArgs t;
+    t.g = nullptr; t.cur = nullptr; t.draft = d_draft; t.pos = t.slot = t.len = nullptr; t.ctl = d_ctl; t.out = nullptr; t.budget = 0;
+    t.hist = (int*)d_hist; t.hist_cap = hist_len; t.stats = nullptr; t.stats_cap = 0; t.stream = nullptr; t.stream_len = 0; t.eos = eos;
+    t.R = D + 1; t.max_ngram = max_ngram; t.source = 0; t.max_ctx = 0; t.rope_max = 0; t.do_accept = 0; t.do_draft = 1;
+    return vz_launch_spec_tail(t, s);
+}
+
+// argmax of R logit rows + the acceptance step on caller-provided state: d_state = [cur | pos | slot | len] x R, d_ctl the control words
+// (the argmax ids land in words 8..), d_stats [3] = this step's record (NULL = none; the record index is the ctl step count)
+extern "C" int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist, int hist_cap,
+                                 const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_logits && d_state && d_ctl && d_out && R >= 2 && R <= 8 && cols >= 1 && budget >= 0 && max_ctx >= 1 && rope_max >= 1, "spec_accept: bad argument");
+    BeamEos eos;
+    RC(beam_eos_of(h_eos, n_eos, &eos));
+    int* g = d_ctl + VZ_SPEC_CTL_IDS;
+    RC(vz_launch_argmax(d_logits, R, cols, g, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s));
+    SpecTailArgs t;
+    t.g = g; t.cur = d_state; t.draft = d_state + 1; t.pos = d_state + R; t.slot = d_state + 2 * R; t.len = d_state + 3 * R; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
+    t.hist = d_hist; t.hist_cap = d_hist ? hist_cap : 0; t.stats = d_stats; t.stats_cap = d_stats ? 0x7fffffff / 4 : 0; t.stream = nullptr; t.stream_len = 0; t.eos = eos;
+    t.R = R; t.max_ngram = 1; t.source = 0; t.max_ctx = max_ctx; t.rope_max = rope_max; t.do_accept = 1; t.do_draft = 0;
+    return vz_launch_spec_tail(t, s);
+}
+
+extern "C" long vz_op_spec_part_floats(int R, int Hkv, int nsplit) { return (long)vz_spec_part_floats(R, Hkv, nsplit); }
+
+// RoPE + append of R fresh QKV rows of one sequence (the stand-alone kernel) + the verify attention over its cache row
+extern "C" int vz_op_attention_verify(const void* qkv, void* kc, void* vc, void* o, void* q_rot, float* ws, unsigned* ticket, const float* cosT,
+                                      const float* sinT, const int* pos, const int* slot, int R, int Hq, int Hkv, int D, int max_ctx, int nsplit,
+                                      int key_bound, int window, float scale, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(qkv && kc && vc && o && q_rot && ws && ticket && cosT && sinT && pos && slot && D == 128, "attention_verify: bad argument (head_dim 128)");
+    RC(vz_launch_rope_kv((const bf16_t*)qkv, (Hq + 2 * Hkv) * D, (bf16_t*)q_rot, (bf16_t*)kc, (bf16_t*)vc, cosT, sinT, pos, slot, 1, R, Hq, Hkv, D, max_ctx, s));
+    SpecVerifyArgs a;
+    a.q = (const bf16_t*)q_rot; a.kc = (const bf16_t*)kc; a.vc = (const bf16_t*)vc; a.o = (bf16_t*)o; a.part = ws; a.ticket = ticket; a.slot = slot;
+    a.R = R; a.Hq = Hq; a.Hkv = Hkv; a.max_ctx = max_ctx; a.nsplit = nsplit; a.key_bound = key_bound; a.window = window; a.scale = scale;
+    return vz_launch_spec_verify_attn(a, s);
+}
+
 // A device-to-device copy of the whole KV cache ([layer][K|V][max_batch][kv head][max_ctx][head_dim] bf16) into d_out (tests):
 // *bytes receives its size; d_out = NULL only asks for it.
 extern "C" int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* bytes, vz_stream stream) {
@@ -1427,6 +1542,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(!e->ring || B <= e->ring_rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring_rows, B);
     VZ_CHECK_ARG(!e->beam_on || (B == e->beam_nb * e->beam_groups && !e->ring), "decode_steps: the beam tail needs a decode batch of exactly "
                  "%d x %d rows (it has %d) and no token ring", e->beam_groups, e->beam_nb, B);
+    VZ_CHECK_ARG(!e->spec_on || (B == e->spec_R && !e->ring && !e->beam_on && !e->samp_on), "decode_steps: the speculative tail needs a decode batch of "
+                 "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec_R, B);
     const size_t need = ((size_t)B * (3 * c.hidden + (c.n_heads + 2 * c.n_kv_heads) * c.head_dim + c.inter)) * 2 + 8192;   // upper bound (tp = 1 sizes)
     RC(ensure_arena(e, need));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of
@@ -1459,7 +1576,11 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     // Capacity (the cache append writes slot = len - 1 of the row, the rotary tables are read at pos): every live row must still fit
     // after n steps.  Parked rows (continuous batching) are not checked: the step tail saturates their slot / position on the device.
     int len_max = 0;
+    // Verify steps advance by 1..R positions each, decided on the device: the host bounds by the worst case (n steps = n x R positions),
+    // itself bounded by the budget the mode was armed with (vz_llm_decode_spec checked base + budget + R against the cache).
+    const int spec_len_cap = e->spec_on ? e->spec_base_len + e->spec_budget : 0;
     for (int b = 0; b < B; ++b) {
+        if (e->spec_on) { len_max = std::max(len_max, std::min(e->h_len[b], c.max_ctx)); continue; }
         if (!e->h_parked[b]) {
             VZ_CHECK_ARG(e->h_len[b] + n - 1 <= c.max_ctx, "decode_steps: row %d would reach %d keys, the cache holds max_ctx = %d", b, e->h_len[b] + n - 1, c.max_ctx);
             VZ_CHECK_ARG(e->h_pos[b] + n - 1 < e->rope_max, "decode_steps: row %d would reach position %d, the rotary tables hold %d", b, e->h_pos[b] + n - 1, e->rope_max);
@@ -1473,6 +1594,11 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     {
         int keys = std::min(e->dec_len_max + n, c.max_ctx);
         if (c.sliding_window > 0) keys = std::min(keys, c.sliding_window);
+        if (e->spec_on) {
+            // keys the last of these n steps can see: row 0's worst-case length after n - 1 full steps, + R rows; no window cut - the verify
+            // attention's splits sit at absolute key positions
+            keys = std::min(std::min(e->h_len[0] + (n - 1) * B, spec_len_cap) + B - 1, c.max_ctx);
+        }
         const int need = (keys + 127) / 128;
         static const int buckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 24, 28, 32};
         int ns = e->nsplit;
@@ -1480,9 +1606,18 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         // many rows fill the chip by themselves: splitting their contexts as well only adds dispatch slots and a merge hop per (row, KV head)
         // (config-5 miniature, e4m3, ctx ~330: 64 rows x 3 splits -> x 1: decode 627 -> 597 ms per batch; 32 rows x 3 -> x 2: 459 -> 448) -
         // rows x KV heads x splits is held to ~512 workgroups; 1..2 rows keep every split (batch-1 numbers unchanged)
-        ns = std::min(ns, std::max(1, 512 / std::max(1, B * e->Hkv_l)));
+        if (!e->spec_on) ns = std::min(ns, std::max(1, 512 / std::max(1, B * e->Hkv_l)));      // (a verify step's rows share one cache row and its workgroups)
         e->dec_nsplit = g_attn_nsplit > 0 ? g_attn_nsplit : ns;
-        for (int b = 0; b < B; ++b) {       // what the device-side state will be after these n steps (the tail saturates, so do we)
+        if (e->spec_on) {
+            // the split positions follow the BUCKET, not the exact bound: one graph per bucket, as for the plain step
+            int chunks = need;
+            for (int bk : buckets) if (bk >= need) { chunks = bk; break; }
+            e->spec_key_bound = g_attn_nsplit > 0 ? c.max_ctx : std::min(chunks * 128, c.max_ctx);       // (a pinned split count: splits over the whole cache, one graph)
+            // worst case of the device-side state after these n steps (the device keeps the exact one): n x R positions, inside the budget
+            const int adv = std::min(e->h_len[0] - e->spec_base_len + n * B, e->spec_budget);
+            for (int b = 0; b < B; ++b) { e->h_len[b] = e->spec_base_len + adv + b; e->h_pos[b] = e->spec_base_pos + adv + b; }
+        }
+        for (int b = 0; b < B && !e->spec_on; ++b) {       // what the device-side state will be after these n steps (the tail saturates, so do we)
             if (e->h_parked[b]) { e->h_len[b] = std::min(e->h_len[b] + n, c.max_ctx); e->h_pos[b] = std::min(e->h_pos[b] + n, e->rope_max - 1); }
             else { e->h_len[b] += n; e->h_pos[b] += n; }      // a live row that is full is refused by the check above on the next call
         }
@@ -1501,7 +1636,15 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                         e->beam_on ? e->beam_hist_cap : 0, e->beam_on ? e->beam_eos.n : 0,
                         e->beam_on ? ((long)(unsigned)e->beam_eos.id[0] << 32 | (unsigned)e->beam_eos.id[1]) : 0,
                         e->beam_on ? ((long)(unsigned)e->beam_eos.id[2] << 32 | (unsigned)e->beam_eos.id[3]) : 0};
-    if (!e->dec_graph || e->dec_graph_B != B || e->dec_graph_n != n || e->dec_graph_out != d_out_ids || e->dec_graph_arena != e->arena ||
+    long spec_key[12] = {e->spec_on, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (e->spec_on) {
+        const long k[11] = {e->spec_ngram | (long)e->spec_source << 8 | (long)e->spec_eos.n << 16, e->spec_budget, (long)(uintptr_t)e->spec_hist, e->spec_hist_cap,
+                            (long)(uintptr_t)e->spec_out, (long)(uintptr_t)e->spec_ctl, (long)(uintptr_t)e->spec_stats, e->spec_stats_cap,
+                            (long)(uintptr_t)e->spec_stream, (long)e->spec_stream_len << 32 | (unsigned)e->spec_key_bound,
+                            ((long)(unsigned)e->spec_eos.id[0] << 32 | (unsigned)e->spec_eos.id[1]) ^ ((long)(unsigned)e->spec_eos.id[2] << 16) ^ ((long)(unsigned)e->spec_eos.id[3] << 48)};
+        memcpy(spec_key + 1, k, sizeof(k));
+    }
+    if (!e->dec_graph || memcmp(e->dec_graph_spec, spec_key, sizeof(spec_key)) != 0 || e->dec_graph_B != B || e->dec_graph_n != n || e->dec_graph_out != d_out_ids || e->dec_graph_arena != e->arena ||
         e->dec_graph_nsplit != e->dec_nsplit || e->dec_graph_tok != ((int)e->use_tok | (g_attn_o << 1)) || memcmp(e->dec_graph_samp, samp_key, sizeof(samp_key)) != 0 ||
         memcmp(e->dec_graph_beam, beam_key, sizeof(beam_key)) != 0) {
         if (e->dec_graph) { hipGraphExecDestroy(e->dec_graph); e->dec_graph = nullptr; }
@@ -1526,7 +1669,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             for (int i = 0; i < n; ++i) RC(decode_step_launch(e, d_out_ids, n, nullptr, s));
             return VZ_OK;
         }
-        e->dec_graph_B = B; e->dec_graph_n = n; e->dec_graph_out = d_out_ids; e->dec_graph_arena = e->arena; e->dec_graph_nsplit = e->dec_nsplit; e->dec_graph_tok = (int)e->use_tok | (g_attn_o << 1); memcpy(e->dec_graph_samp, samp_key, sizeof(samp_key)); memcpy(e->dec_graph_beam, beam_key, sizeof(beam_key));
+        e->dec_captures++;
+        e->dec_graph_B = B; e->dec_graph_n = n; e->dec_graph_out = d_out_ids; e->dec_graph_arena = e->arena; e->dec_graph_nsplit = e->dec_nsplit; e->dec_graph_tok = (int)e->use_tok | (g_attn_o << 1); memcpy(e->dec_graph_samp, samp_key, sizeof(samp_key)); memcpy(e->dec_graph_beam, beam_key, sizeof(beam_key)); memcpy(e->dec_graph_spec, spec_key, sizeof(spec_key));
     }
     for (int i = 0; i < n; ++i) VZ_CHECK_HIP(hipGraphLaunch(e->dec_graph, s));
     return VZ_OK;
@@ -1546,6 +1690,14 @@ extern "C" int vz_llm_decode_mode(vz_engine* e, int* graph, int* comm_in_graph) 
     VZ_CHECK_ARG(e && graph && comm_in_graph, "decode_mode: null argument");
     *graph = e->dec_graph != nullptr;
     *comm_in_graph = e->dec_graph != nullptr && !tp_local(e) && e->comm_graph_ok;
+    return VZ_OK;
+}
+
+// the last vz_llm_decode_steps call's context splits (the bucket its steps ran in) and the graphs captured so far (tests: a generation that
+// crosses a context bucket captures again)
+extern "C" int vz_llm_decode_info(vz_engine* e, int* nsplit, int* captures) {
+    VZ_CHECK_ARG(e && nsplit && captures, "decode_info: null argument");
+    *nsplit = e->dec_nsplit; *captures = e->dec_captures;
     return VZ_OK;
 }
 

@@ -356,6 +356,24 @@ int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, in
 int vz_launch_beam_advance(int* hidx, hipStream_t s);
 int vz_launch_kv_beam_reorder(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, int nb, int groups,
                               const int* parent, const int* base, int base_stride, const int* end, int end_stride, hipStream_t s);
+// prompt-lookup speculative decoding (spec.hip): the verify attention over one cache row and the accept + draft tail
+struct SpecVerifyArgs {
+    const bf16_t* q;       // [R][Hq][D] rotated queries
+    const bf16_t *kc, *vc; // the sequence's cache row of this layer [Hkv][max_ctx][D], the R new rows already appended
+    bf16_t* o;             // [R][Hq][D]
+    float* part;           // vz_spec_part_floats
+    unsigned* ticket;      // [Hkv], zeroed once
+    const int* slot;       // device: slot[0] = cache slot of row 0
+    int R, Hq, Hkv, max_ctx, nsplit, key_bound, window;
+    float scale;
+};
+int vz_launch_spec_verify_attn(const SpecVerifyArgs& a, hipStream_t s);
+size_t vz_spec_part_floats(int R, int Hkv, int nsplit);
+struct SpecTailArgs {
+    const int* g; int *cur, *draft, *pos, *slot, *len, *ctl, *out; int budget; int* hist; int hist_cap; int* stats; int stats_cap;
+    const int* stream; int stream_len; BeamEos eos; int R, max_ngram, source, max_ctx, rope_max, do_accept, do_draft;
+};
+int vz_launch_spec_tail(const SpecTailArgs& a, hipStream_t s);
 int vz_launch_repack_logits(const float* gathered, float* out, int rows, int Vp, int V, int tp, hipStream_t s);
 
 // ---- backward kernels of the Stage-1 training step (train.hip) ----

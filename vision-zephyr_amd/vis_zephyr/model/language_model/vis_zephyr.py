@@ -315,6 +315,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         attention_mask = kwargs.pop("attention_mask", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported in this generate function.")
+        mask_in = attention_mask
         if images is not None:
             (_, position_ids, attention_mask, _, inputs_embeds, _) = self.prepare_inputs_labels_for_multimodal(
                 input_ids, position_ids, attention_mask, None, None, images, images_size)
@@ -322,14 +323,35 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 inputs_embeds = self.get_model().embed_tokens(input_ids)
         else:
             inputs_embeds = self.get_model().embed_tokens(input_ids)
+        if kwargs.get("prompt_lookup_num_tokens") and input_ids is not None and input_ids.shape[0] == 1:
+            # built only once the call is known to run with drafts (_generate_from_embeds): every other call stays as it was
+            kwargs["_spec_history"] = lambda: self._spec_history(input_ids, mask_in, images, inputs_embeds.shape[1])
         return self._generate_from_embeds(inputs_embeds, attention_mask, position_ids, **kwargs)
+
+    def _spec_history(self, input_ids, attention_mask, images, n_positions: int) -> List[int]:
+        """one id per position of the (spliced) prompt for the prompt-lookup drafts (vz_hip.spec): text ids, -1 where a visual token sits."""
+        from vz_hip import spec
+        from vis_zephyr.constants import IMAGE_TOKEN_INDEX
+        ids = input_ids[0].detach().to("cpu", torch.long)
+        spliced = images is not None and self.get_vision_tower() is not None and input_ids.shape[1] != 1
+        if attention_mask is not None:          # the caller's mask: pads (left or right) hold no position of the sequence
+            ids = ids[attention_mask[0].detach().to("cpu").bool()]
+        if spliced:
+            tiles = [1 if x.ndim == 3 else int(x.shape[0]) for x in images] if isinstance(images, (list, tuple)) else \
+                [int(images[i].shape[0]) for i in range(images.shape[0])]
+            hist = spec.spliced_history(ids.tolist(), tiles, IMAGE_TOKEN_INDEX, self.arch.qf_queries,
+                                        getattr(self.config, "tokenizer_model_max_length", None))
+            assert len(hist) == n_positions, f"history of {len(hist)} ids for a spliced prompt of {n_positions} positions"
+            return hist
+        return ids.tolist()          # text only: the ids as given
 
     def _generate_from_embeds(self, inputs_embeds, attention_mask, position_ids, max_new_tokens: Optional[int] = None,
                               max_length: Optional[int] = None, do_sample: bool = False, temperature: float = 1.0,
                               top_p: Optional[float] = None, top_k: Optional[int] = -1, eos_token_id=None,
                               pad_token_id=None, streamer=None, stopping_criteria=None, use_cache: bool = True,
                               num_beams: int = 1, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
-                              sync_every: int = 16, timing: Optional[dict] = None, **unused):
+                              sync_every: int = 16, timing: Optional[dict] = None, prompt_lookup_num_tokens: Optional[int] = None,
+                              max_matching_ngram_size: Optional[int] = None, _spec_history=None, **unused):
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing, **unused)
@@ -353,6 +375,20 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                       device=generator.device if generator is not None else "cpu").item())
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
+        if prompt_lookup_num_tokens and _spec_history is not None:
+            # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
+            from vz_hip import spec
+            ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
+            D = spec.draft_slots(prompt_lookup_num_tokens, ngram, n_seq=Bsz, greedy=greedy, num_beams=num_beams, streamer=streamer,
+                                 stopping_criteria=stopping_criteria, tp_size=self.engine.tp_size, max_batch=self.engine.max_batch,
+                                 prompt_len=seqlens[0], max_new=max_new_tokens, max_ctx=self.engine.max_ctx, n_eos=len(eos),
+                                 heads_per_kv=self.arch.n_heads // max(1, self.arch.n_kv_heads))
+            if D:
+                _spec_history = _spec_history()
+                assert len(_spec_history) == seqlens[0], f"history of {len(_spec_history)} ids for a prompt of {seqlens[0]} positions"
+                out = self._generate_spec(inputs_embeds[0:1, :seqlens[0]], None if position_ids is None else position_ids[0:1, :seqlens[0]],
+                                          _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
+                return torch.tensor([out], dtype=torch.long, device=self.device)
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
             return self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing)
         outs = []
@@ -366,6 +402,25 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         for b, o in enumerate(outs):
             res[b, :len(o)] = torch.tensor(o, dtype=torch.long, device=self.device)
         return res
+
+    def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None) -> List[int]:
+        """One greedy sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
+        (csrc/spec.hip), `sync_every` per host sync."""
+        from vz_hip import binding as B
+        from vz_hip import spec
+        eng = self.engine
+        S = embeds.shape[1]
+        _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
+        next_pos = S if position_ids is None else int(position_ids[0, -1]) + 1
+        tok = int(B.argmax(last)[0])          # int(): the host holds the first token here
+        if timing is not None:
+            import time
+            timing["t_first_token"] = time.perf_counter()
+        report = {}
+        out = spec.decode(eng, tok, next_pos, S, history, D, max_new, eos, max_ngram, max(1, int(sync_every)), report=report)
+        if timing is not None:
+            timing["spec"] = report
+        return out
 
     def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step

@@ -21,6 +21,7 @@ VZ_ASYNC_PERSIST = 3
 VZ_ASYNC_ONESHOT = 4
 VZ_ASYNC_ATTN_O = 5
 ABI_VERSION = 10
+SPEC_CTL_WRITE, SPEC_CTL_HIST, SPEC_CTL_DONE, SPEC_CTL_DRAFTED, SPEC_CTL_STEPS, SPEC_CTL_IDS, SPEC_CTL_WORDS = 0, 1, 2, 3, 4, 8, 16
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF, ACT_SWIGLU = 0, 1, 2, 3
 K_GEMM, K_GEMV, K_ATTN, K_ATTN_DEC, K_NORM, K_OTHER, K_FUSED, K_COMM = range(8)
 
@@ -86,6 +87,7 @@ SYMBOLS = {
     "vz_llm_decode_begin": (_I, [_P, _I, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "vz_llm_decode_steps": (_I, [_P, _I, _P, _P, _P]),
     "vz_llm_decode_mode": (_I, [_P, _P, _P]),
+    "vz_llm_decode_info": (_I, [_P, _P, _P]),
     "vz_test_persist_poke": (_I, [_P, _I, C.c_uint, _P, _P]),
     "vz_prof_persist_stamps": (_I, [_P, _P, _I]),
     "vz_op_oneshot_area_bytes": (C.c_size_t, [_I, _I]),
@@ -131,6 +133,11 @@ SYMBOLS = {
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "vz_llm_kv_copy_out": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "vz_llm_decode_spec": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P]),
+    "vz_op_spec_draft": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "vz_op_spec_accept": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
+    "vz_op_spec_part_floats": (_L, [_I, _I, _I]),
+    "vz_op_attention_verify": (_I, [_P] * 11 + [_I] * 8 + [_F, _P]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -544,4 +551,50 @@ def attention_decode_fused(qkv, kcache, vcache, cos, sin, pos, slot, Hq, scale, 
     check(lib().vz_op_attention_decode_fused(ptr(qkv), ptr(kcache), ptr(vcache), ptr(o), ptr(ws), ptr(ticket), ptr(cos),
                                              ptr(sin), ptr(pos), ptr(slot), Bn, Hq, Hkv, D, max_ctx, nsplit, window,
                                              float(scale), stream_ptr(qkv.device)))
+    return o, ticket
+
+
+def _eos_arr(eos):
+    eos = [int(t) for t in eos]
+    return (C.c_int * max(1, len(eos)))(*eos), len(eos)
+
+
+def spec_draft(history, D: int, max_ngram: int = 2, eos=()):
+    """the prompt-lookup draft rule on the device (spec.hip) for an int32 history tensor: the proposed ids (a list, may be empty)."""
+    _need_cuda(history)
+    history = history.to(torch.int32).contiguous()
+    draft = torch.zeros(D, dtype=torch.int32, device=history.device)
+    ctl = torch.zeros(SPEC_CTL_WORDS, dtype=torch.int32, device=history.device)
+    arr, n_eos = _eos_arr(eos)
+    check(lib().vz_op_spec_draft(ptr(history), history.numel(), int(D), int(max_ngram), arr, n_eos, ptr(draft), ptr(ctl), stream_ptr(history.device)))
+    return draft[:int(ctl[SPEC_CTL_DRAFTED])].tolist()
+
+
+def spec_accept(logits, state, ctl, out, budget: int, hist=None, eos=(), stats=None, max_ctx: int = 1 << 20, rope_max: int = 1 << 20):
+    """argmax of the R logit rows + one acceptance step on caller-provided buffers, all updated in place: state int32 [4, R] =
+    cur | pos | slot | len, ctl int32 [SPEC_CTL_WORDS], out int32 [>= budget], hist int32 or None, stats int32 [3] or None."""
+    _need_cuda(logits, state, ctl, out)
+    R, V = logits.shape
+    assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 4 * R and ctl.numel() >= SPEC_CTL_WORDS and out.numel() >= budget
+    arr, n_eos = _eos_arr(eos)
+    check(lib().vz_op_spec_accept(ptr(logits), R, V, ptr(state), ptr(ctl), ptr(out), int(budget), ptr(hist), 0 if hist is None else hist.numel(),
+                                  arr, n_eos, ptr(stats), int(max_ctx), int(rope_max), stream_ptr(logits.device)))
+
+
+def attention_verify(qkv, kcache, vcache, cos, sin, pos, slot, Hq, scale, nsplit=8, key_bound=None, window=0, ticket=None):
+    """qkv bf16 [R, (Hq + 2 Hkv) * D]: R consecutive positions of ONE sequence; caches [Hkv, max_ctx, D] (its cache row); pos / slot int32
+    [R].  Appends the R rotated K / V rows in place, returns (o [R, Hq, D], ticket)."""
+    _need_cuda(qkv, kcache, vcache, cos, sin, pos, slot)
+    Hkv, max_ctx, D = kcache.shape
+    R = qkv.shape[0]
+    if key_bound is None:
+        key_bound = min(max_ctx, int(slot[0]) + R)
+    ws = torch.empty(lib().vz_op_spec_part_floats(R, Hkv, nsplit), dtype=torch.float32, device=qkv.device)
+    if ticket is None:
+        ticket = torch.zeros(Hkv, dtype=torch.int32, device=qkv.device)
+    o = torch.empty(R, Hq, D, dtype=torch.bfloat16, device=qkv.device)
+    q_rot = torch.empty(R, Hq, D, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().vz_op_attention_verify(ptr(qkv), ptr(kcache), ptr(vcache), ptr(o), ptr(q_rot), ptr(ws), ptr(ticket), ptr(cos), ptr(sin), ptr(pos),
+                                       ptr(slot), R, Hq, Hkv, D, max_ctx, int(nsplit), int(key_bound), int(window), float(scale),
+                                       stream_ptr(qkv.device)))
     return o, ticket

@@ -564,12 +564,26 @@ class Engine:
         np_ = (C.c_int * Bn)(*[int(v) for v in next_pos])
         cl = (C.c_int * Bn)(*[int(v) for v in ctx_len])
         self._dec_keep = ids
+        self._spec = None                  # a new batch starts with the plain tail (the library clears the mode too)
         B.check(self.lib.vz_llm_decode_begin(self.h, Bn, B.ptr(ids), np_, cl, self._s()))
         self._dec_B = Bn
 
     def decode_steps(self, n: int, out: Optional[torch.Tensor] = None, return_logits: bool = False):
-        """enqueue n greedy steps; returns int32 [B,n] (device; no host sync) (+ fp32 logits [n,B,V])."""
+        """enqueue n greedy steps; returns int32 [B,n] (device; no host sync) (+ fp32 logits [n,B,V]).  With the speculative tail
+        armed (`set_spec`): n verify steps, then ONE readback - returns the 1-D int32 ids (host) those n steps emitted."""
         Bn = self._dec_B
+        sp = getattr(self, "_spec", None)
+        if sp is not None:
+            lg = torch.empty(n, Bn, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logits else None
+            B.check(self.lib.vz_llm_decode_steps(self.h, n, B.ptr(sp["out"]), B.ptr(lg), self._s()))
+            host = sp["buf"][:sp["head"]].cpu()                  # control words | emitted ids | stats records: one copy, one sync
+            w0, w1 = sp["w"], int(host[B.SPEC_CTL_WRITE])
+            s0, s1 = sp["steps"], int(host[B.SPEC_CTL_STEPS])
+            sp["w"], sp["steps"], sp["done"] = w1, s1, bool(host[B.SPEC_CTL_DONE])
+            rec = host[B.SPEC_CTL_WORDS + sp["budget"]:].view(-1, 3)[s0:min(s1, sp["budget"])]
+            sp["records"].extend(rec.tolist())
+            ids = host[B.SPEC_CTL_WORDS + w0:B.SPEC_CTL_WORDS + w1].clone()
+            return (ids, lg) if return_logits else ids
         if out is None:
             out = torch.empty(Bn, n, dtype=torch.int32, device=self.device)
         lg = torch.empty(n, Bn, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logits else None
@@ -590,6 +604,35 @@ class Engine:
             rows, slots = (1 if ring.dim() == 1 else int(ring.shape[0])), int(ring.shape[-1])
         self._ring_keep = ring
         B.check(self.lib.vz_llm_decode_ring(self.h, B.ptr(ring), slots, rows))
+
+    def set_spec(self, on: bool, D: int = 0, max_ngram: int = 2, history: Sequence[int] = (), eos: Sequence[int] = (), budget: int = 0,
+                 source: int = 0, stream: Optional[Sequence[int]] = None):
+        """prompt-lookup speculative decoding (spec.hip) for the R = D + 1 rows `decode_begin` just armed (one sequence: row i at
+        position p + i, context L + i): every decode step becomes a verify step that emits 1..R ids, at most `budget` in all, and
+        stops at the first of `eos`.  history = one id per position of the sequence so far, the token of row 0 included (-1 = no text
+        id there).  source 0 drafts by the n-gram rule; 1 drafts the ids of `stream` that follow the step's own position (stream[t]
+        = the t-th id these steps are expected to emit: tests, benchmarks).  off: the plain tail again."""
+        if not on:
+            self._spec = None
+            B.check(self.lib.vz_llm_decode_spec(self.h, 0, 0, 0, None, 0, 0, None, 0, None, 0, None, None, 0, 0, None, 0, self._s()))
+            return
+        budget = int(budget)
+        head = B.SPEC_CTL_WORDS + 4 * budget                      # control words | out [budget] | stats [budget][3]
+        buf = torch.zeros(head + 1, dtype=torch.int32, device=self.device)
+        hist = torch.tensor(list(history) + [0] * budget, dtype=torch.int32).to(self.device) if source == 0 else None
+        sids = torch.tensor(list(stream if stream is not None else []) + [0], dtype=torch.int32).to(self.device) if source == 1 else None
+        ea = (C.c_int * max(1, len(eos)))(*[int(t) for t in eos])
+        out, stats = buf[B.SPEC_CTL_WORDS:], buf[B.SPEC_CTL_WORDS + budget:]
+        B.check(self.lib.vz_llm_decode_spec(self.h, 1, int(D), int(max_ngram), B.ptr(hist), len(history), 0 if hist is None else hist.numel(),
+                                            ea, len(eos), B.ptr(out), budget, B.ptr(buf), B.ptr(stats), budget, int(source), B.ptr(sids),
+                                            0 if sids is None else sids.numel() - 1, self._s()))
+        self._spec = {"buf": buf, "out": out, "hist": hist, "stream": sids, "head": head, "budget": budget, "D": int(D), "w": 0, "steps": 0,
+                      "done": budget == 0, "records": []}
+
+    def spec_state(self) -> dict:
+        """what the last readback of the speculative tail showed: done flag, steps run, ids emitted, per-step [drafted, used, emitted]."""
+        sp = self._spec
+        return {"done": sp["done"], "steps": sp["steps"], "tokens": sp["w"], "records": sp["records"], "D": sp["D"]}
 
     def set_beam(self, on: bool, num_beams: int = 0, groups: int = 0, eos: Sequence[int] = (), base: Sequence[int] = (),
                  scores: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None):
@@ -653,6 +696,12 @@ class Engine:
         g, c = C.c_int(0), C.c_int(0)
         B.check(self.lib.vz_llm_decode_mode(self.h, C.byref(g), C.byref(c)))
         return bool(g.value), bool(c.value)
+
+    def decode_info(self):
+        """(context splits of the last decode_steps call = its context bucket, graphs captured since the engine was created)."""
+        ns, cap = C.c_int(0), C.c_int(0)
+        B.check(self.lib.vz_llm_decode_info(self.h, C.byref(ns), C.byref(cap)))
+        return ns.value, cap.value
 
     # profiling hooks (bench.py roofline leg)
     def prof_enable(self, on: bool, klass: int = -1):
