@@ -502,7 +502,8 @@ int vz_op_vip_point(void* d_image_u8, int h, int w, int x0, int y0, int x1, int 
 /* argmax over fp32 logits rows: ids int32 [rows] (first maximal index) */
 int vz_op_argmax(const float* d_logits, int rows, int cols, int* d_ids, vz_stream stream);
 
-/* A/B hook of the bench tools (process-wide; production values in brackets).  Knobs:
+/* A/B hook of the bench tools (process-wide; production values in brackets).  A knob change takes effect on the next
+ * vz_llm_decode_steps, which captures its graph again.  Knobs:
  *   0  GEMV variant [0 = production choice; 1.. = alternatives compiled in: rows per wave, chunks in flight, non-temporal loads]
  *   1  tile GEMM choice [0 = by grid size; 1 = always 128^2; 2 = always 256^2]      2  prefill attention generation [3]
  *   3  split-K of M <= 512 linears [0 = auto; 1 = never]                             4  256^2 GEMM stream-K tail [1; 0 = whole tiles only; 2 = forced]

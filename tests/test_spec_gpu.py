@@ -428,3 +428,75 @@ def test_generate_prompt_lookup_edges(env):
     # a plain generate right after returns to the 1-row path, bit-identically to before
     after = model.generate(input_ids=ids, max_new_tokens=30, eos_token_id=None, **kw)
     assert torch.equal(after, before)
+
+
+# ------------------------------------------------------------------------------------------------
+# T8: the decode graph's key - whatever a captured step froze makes the next call capture again
+# ------------------------------------------------------------------------------------------------
+def test_knob_change_captures_again(env, B):
+    """a captured step froze the routes the vz_tune_set knobs chose: the first decode_steps after a knob change captures again,
+    even into the same output buffer, and then runs what an eager step runs under that knob."""
+    eng = env["bf16"].engine
+    S = 40
+    emb = eng.embed_tokens(_text_prompt(env, S, 31).unsqueeze(0))
+    _, last = eng.prefill(emb, [S], all_logits=False, last_logits=True)
+    first = last[0].argmax().to(torch.int32).view(1)
+    buf = torch.empty(1, 4, dtype=torch.int32, device=eng.device)
+    cap = lambda: eng.decode_info()[1]        # noqa: E731
+    eng.decode_begin(first, [S], [S])
+    eng.decode_steps(1)                       # whatever graph an earlier test left is replaced by one of another shape
+    c0 = cap()
+    eng.decode_steps(4, out=buf)
+    c1 = cap()
+    eng.decode_steps(4, out=buf)
+    assert (c1, cap()) == (c0 + 1, c0 + 1)
+    B.check(B.lib().vz_tune_set(9, 0))
+    try:
+        eng.decode_begin(first, [S], [S])
+        eng.decode_steps(4, out=buf)
+        assert eng.decode_mode()[0] and cap() == c0 + 2, "the knob change did not make the next call capture again"
+        eng.decode_begin(first, [S], [S])
+        eager, _ = eng.decode_steps(4, return_logits=True)
+        assert torch.equal(buf, eager)
+    finally:
+        B.check(B.lib().vz_tune_set(9, 1))
+
+
+def test_colliding_eos_sets_capture_again(env, B):
+    """the speculative tail's eos ids are kernel arguments: two eos sets that differ only in ids >= 65536 / their order run on two
+    graphs.  Every buffer is held here and the mode is armed through the C ABI, so nothing else differs between the two arms."""
+    import ctypes as C
+    eng, lib = env["bf16"].engine, B.lib()
+    D, budget, W = 3, 16, B.SPEC_CTL_WORDS
+    prompt = [1] + _text_prompt(env, 40, 37).tolist()
+    S = len(prompt)
+    _, last = eng.prefill(eng.embed_tokens(torch.tensor([prompt])), [S], all_logits=False, last_logits=True)
+    first = int(last[0].argmax())
+    first_ids = torch.tensor([first] + [0] * D, dtype=torch.int32)
+    hist0 = torch.tensor(prompt + [first] + [0] * budget, dtype=torch.int32).to(eng.device)
+    hist = hist0.clone()
+    buf = torch.zeros(W + 4 * budget + 1, dtype=torch.int32, device=eng.device)       # control words | out [budget] | stats [budget][3]
+    out, stats = buf[W:], buf[W + budget:]
+
+    def run(eos):
+        hist.copy_(hist0)
+        eng.decode_begin(first_ids, [S + i for i in range(D + 1)], [S + i for i in range(D + 1)])
+        ea = (C.c_int * 4)(*(list(eos) + [0] * (4 - len(eos))))
+        B.check(lib.vz_llm_decode_spec(eng.h, 1, D, 2, B.ptr(hist), S + 1, hist.numel(), ea, len(eos), B.ptr(out), budget, B.ptr(buf), B.ptr(stats),
+                                       budget, 0, None, 0, eng._s()))
+        try:
+            B.check(lib.vz_llm_decode_steps(eng.h, 2, B.ptr(out), None, eng._s()))
+            eng.check_async()
+            host = buf.cpu()
+        finally:
+            eng.set_spec(False)
+        assert eng.decode_mode()[0]
+        return host[W:W + int(host[B.SPEC_CTL_WRITE])].tolist(), eng.decode_info()[1]
+
+    free, _ = run(())
+    assert 2 <= len(free) <= 2 * (D + 1) and 0 not in free and 1 not in free, free       # (another prompt seed if this ever fires)
+    a = next(t for t in range(2, env["cfg"].vocab) if t not in free)
+    ids1, cap1 = run((a, 0x10000, 0))
+    ids2, cap2 = run((a, 0, 1))
+    assert ids1 == free and ids2 == free
+    assert cap2 == cap1 + 1, "a different eos set replayed the graph captured with the other one"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Decode rate of the bench request (BASELINE configs[2]: 5 tiles + 1889 ids -> S = 2048, 128 greedy tokens, 32 layers) under a
-list of vz_tune_set settings, ONE engine for all of them (the graph re-captures when a frozen knob changes).
+list of vz_tune_set settings, ONE engine for all of them (every vz_tune_set makes the next decode_steps capture its graph again).
     python tools/bench_decode.py "" "17=0" "17=24,18=40" ...      (VZ_FP8=1: the W8A16 engine; VZ_LAYERS, VZ_REPS)
 Each setting also prints the per-class launch times of 8 eager steps (GEMV / decode attention)."""
 import os

@@ -158,9 +158,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
                                                          int nb_in, int nb_out, int K, BeamEos eos, int groups,
                                                          int* __restrict__ hist, const int* __restrict__ hidx, int hist_cap,
                                                          int* __restrict__ next_tok, float* __restrict__ next_score,
-                                                         int* __restrict__ next_parent, int* __restrict__ pos, int* __restrict__ slot,
-                                                         int* __restrict__ len, int* __restrict__ out_ids, int out_stride,
-                                                         const int* __restrict__ step, int max_ctx, int rope_max) {
+                                                         int* __restrict__ next_parent, RowEmit emit) {
     __shared__ float ts[BEAM_KMAX];
     __shared__ int tt[BEAM_KMAX], tb[BEAM_KMAX];
     const int g = blockIdx.x, tid = threadIdx.x;
@@ -190,9 +188,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
             next_tok[row] = tt[i];
             if (next_score) next_score[row] = ts[i];
             if (next_parent) next_parent[row] = tb[i];
-            if (out_ids) out_ids[(size_t)row * out_stride + (step ? *step : 0)] = tt[i];
-            if (pos && pos[row] + 1 < rope_max) pos[row] += 1;
-            if (len && len[row] < max_ctx) { len[row] += 1; if (slot) slot[row] += 1; }
+            vz_emit_advance(emit, row, tt[i], 0u);          // (the beam tail runs without a token ring)
         }
     }
 }
@@ -270,11 +266,10 @@ int vz_beam_k(int nb, int n_eos) { return (n_eos + 1 > 2 ? n_eos + 1 : 2) * nb; 
 
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
-                          int* next_parent, int* pos, int* slot, int* len, int* out_ids, int out_stride, const int* step, int max_ctx,
-                          int rope_max, hipStream_t s) {
+                          int* next_parent, const RowEmit& emit, hipStream_t s) {
     const int K = vz_beam_k(nb_out, eos.n);
     VZ_CHECK_ARG(logits && cand_s && cand_t && next_tok && rows >= 1 && cols >= 1 && nb_in >= 1 && nb_in <= 16 && nb_out >= 1 &&
-                 nb_out <= 16 && rows % nb_in == 0 && eos.n >= 0 && eos.n <= 4 && K <= BEAM_KMAX,
+                 nb_out <= 16 && rows % nb_in == 0 && eos.n >= 0 && eos.n <= 4 && K <= BEAM_KMAX && !emit.ring,
                  "beam_select: bad argument (rows %d, nb_in %d, nb_out %d, %d eos ids)", rows, nb_in, nb_out, eos.n);
     VZ_CHECK_ARG(cols >= K, "beam_select: %d candidates per row exceed the vocabulary of %d", K, cols);
     { int r = init_beam_kernels(); if (r) return r; }
@@ -284,7 +279,7 @@ int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, in
         hipLaunchKernelGGL(beam_row_topk_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, K, scores_in, cand_s, cand_t);
     VZ_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_merge_kernel, dim3(rows / nb_in), dim3(256), 0, s, cand_s, cand_t, cols, nb_in, nb_out, K, eos, rows / nb_in,
-                       hist, hidx, hist_cap, next_tok, next_score, next_parent, pos, slot, len, out_ids, out_stride, step, max_ctx, rope_max);
+                       hist, hidx, hist_cap, next_tok, next_score, next_parent, emit);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

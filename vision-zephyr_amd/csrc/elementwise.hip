@@ -332,10 +332,7 @@ __global__ __launch_bounds__(256) void fusion_kernel(const bf16_t* __restrict__ 
 // loop the same kernel is the step's tail: it publishes the token for the next step, appends it to
 // the output ids and advances the per-slot position / context length kept on the device.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, int cols, int* __restrict__ ids,
-                                                      int* __restrict__ pos, int* __restrict__ slot, int* __restrict__ len,
-                                                      int* __restrict__ out_ids, int out_stride, const int* __restrict__ step,
-                                                      int max_ctx, int rope_max, int* __restrict__ ring, int ring_n) {
+__global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, int cols, int* __restrict__ ids, RowEmit emit) {
     __shared__ float sv[16];
     __shared__ int si[16];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -378,12 +375,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
         if (bi == 0x7fffffff) bi = 0;  // all-NaN row
         ids[row] = bi;
-        if (out_ids) out_ids[(size_t)row * out_stride + (step ? *step : 0)] = bi;
-        if (ring) ring[(size_t)row * ring_n + ((unsigned)step[1] % (unsigned)ring_n)] = bi;     // host-visible ring, slot = draw counter
-        // saturating advance: a live row is kept inside the cache by the host's capacity check (vz_llm_decode_steps); a parked row
-        // of a continuous batch steps for ever and must stay inside its own cache row / the rotary tables
-        if (pos && pos[row] + 1 < rope_max) pos[row] += 1;
-        if (len && len[row] < max_ctx) { len[row] += 1; if (slot) slot[row] += 1; }
+        vz_emit_advance(emit, row, bi, emit.ring ? (unsigned)emit.step[1] : 0u);      // ring slot = the draw counter behind the step index
     }
 }
 
@@ -505,10 +497,9 @@ int vz_launch_fusion(const bf16_t* hs_base, long layer_stride, int first_layer, 
     return VZ_OK;
 }
 
-int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, int* pos, int* slot, int* len, int* out_ids,
-                     int out_stride, const int* step, int max_ctx, int rope_max, int* ring, int ring_n, hipStream_t s) {
-    VZ_CHECK_ARG(logits && ids && rows > 0 && cols > 0 && (!ring || (step && ring_n > 0)), "argmax: bad argument");
-    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, ids, pos, slot, len, out_ids, out_stride, step, max_ctx, rope_max, ring, ring_n);
+int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const RowEmit& emit, hipStream_t s) {
+    VZ_CHECK_ARG(logits && ids && rows > 0 && cols > 0 && (!emit.ring || (emit.step && emit.ring_n > 0)), "argmax: bad argument");
+    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, ids, emit);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -226,7 +226,7 @@ extern "C" int vz_op_attention_decode_fused(const void* qkv, void* kc, void* vc,
     return vz_launch_attn_decode_fused(a, (hipStream_t)s);
 }
 extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, vz_stream s) {
-    return vz_launch_argmax(logits, rows, cols, ids, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, (hipStream_t)s);
+    return vz_launch_argmax(logits, rows, cols, ids, {}, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -257,6 +257,54 @@ struct TopW {
 
 enum { K_GEMM = 0, K_GEMV = 1, K_ATTN = 2, K_ATTN_DEC = 3, K_NORM = 4, K_OTHER = 5, K_FUSED = 6, K_COMM = 7 };
 
+static constexpr float ATTN_SCALE = 0.08838834764831845f;      // 128^-0.5 (vz_engine_create takes head_dim 128 only)
+
+// The device-side state of a decode batch of max_batch = mb rows: [cur | pos | slot | len], mb ints each (the row's input token, its
+// rotary position, the cache slot its keys are appended to, the keys it sees), then WORDS ints: the step index inside the running
+// vz_llm_decode_steps call, the draws since vz_llm_decode_begin, the sampler's seed (lo, hi).
+struct DecodeState {
+    static constexpr int ROW_ARRAYS = 4, WORDS = 4;
+    int *cur, *pos, *slot, *len, *step, *ctr; unsigned* seed;
+    static size_t ints(int mb) { return (size_t)ROW_ARRAYS * mb + WORDS; }
+};
+static DecodeState decode_state(int* base, int mb) {
+    int* w = base + DecodeState::ROW_ARRAYS * mb;
+    return {base, base + mb, base + 2 * mb, base + 3 * mb, w, w + 1, (unsigned*)(w + 2)};
+}
+
+// The tail of a decode step turns the logits into the next tokens: speculative verify > beam select > sampler > argmax, whichever
+// armed mode comes first (tail_kind).  The *Args of a mode are what its kernels take by value - a captured step freezes them, so
+// they go into the graph key as they are; they are laid out without padding (the key is compared with memcmp).
+enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC };
+struct SampleArgs { int top_k; float temp, top_p; };
+struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
+struct SpecArgs {
+    int *hist, *out, *ctl, *stats; const int* stream;
+    int ngram, source, budget, hist_cap, stats_cap, stream_len;
+    int key_bound;      // keys the steps being launched can reach (fixes the verify attention's absolute splits)
+    BeamEos eos;
+};
+// Everything decode_step_launch hands to a kernel that can differ between two vz_llm_decode_steps calls: a replayed graph is only
+// valid while all of it is unchanged.  The *Args of the modes that are off stay zero.
+struct DecodeGraphKey {
+    int B, n, nsplit, use_tok, kind; unsigned tune_epoch;
+    int* out; char* arena; int* ring; int ring_n;
+    SampleArgs samp; BeamArgs beam; SpecArgs spec;
+};
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) &&
+              sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
+
+// The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
+// scores | candidate tokens (BEAM_K per row)]
+static constexpr int BEAM_ROWS = 64, BEAM_K = 80;
+static constexpr size_t BEAM_INTS = 4 + 5 * (size_t)BEAM_ROWS + 2 * (size_t)BEAM_ROWS * BEAM_K;
+struct BeamView { float* score; int *parent, *base, *hidx, *re_base, *re_end; float* cand_s; int* cand_t; };
+static BeamView beam_view(int* d) {
+    const int R = BEAM_ROWS;
+    int* cand = d + 5 * R + 4;
+    return {(float*)d, d + R, d + 2 * R, d + 3 * R, d + 3 * R + 4, d + 4 * R + 4, (float*)cand, cand + R * BEAM_K};
+}
+
 struct vz_engine {
     vz_config c;
     // tensor parallelism: this rank's share of the 32 query heads / 8 KV heads / 14336 MLP columns and
@@ -280,7 +328,7 @@ struct vz_engine {
     // kv cache: [layer][2][B][Hkv][max_ctx][D]
     bf16_t* kv = nullptr; size_t kv_layer_elems = 0;
     // decode state (device)
-    int* d_state = nullptr;  // [cur_ids[B] | pos[B] | slot[B] | len[B] | step]
+    int* d_state = nullptr;  // DecodeState of max_batch rows
     int dec_B = 0;
     int prefill_fp8 = 0;         // vz_engine_prefill_fp8: the Zephyr prefill linears run e4m3 x e4m3 on the scaled MFMA (weight_fp8 engines)
     bool comm_graph_ok = true;   // RCCL collectives captured into the decode graph (cleared if a capture is refused -> eager steps)
@@ -288,18 +336,15 @@ struct vz_engine {
     // host mirror of the device-side decode state, per row: keys visible to the NEXT step, its rotary position, and whether the
     // row is parked (continuous batching: ctx_len 0, steps harmlessly, never checked against the capacity)
     std::vector<int> h_len, h_pos; std::vector<char> h_parked;
-    // sampling tail (vz_llm_decode_sampling): off = greedy argmax
-    int samp_on = 0, samp_top_k = 0, samp_ctr0 = 0; float samp_temp = 1.f, samp_top_p = 1.f; unsigned samp_seed[2] = {0, 0};
-    // beam tail (vz_llm_decode_beam): groups x nb rows; d_beam = [score (fp32) | parent | base | hidx, pad | base, end of a standalone
-    // reorder | candidate scores | candidate tokens] (BEAM_ROWS rows); beam_hist = the caller's history records, beam_hist_cap steps
-    static constexpr int BEAM_ROWS = 64, BEAM_K = 80;
-    int beam_on = 0, beam_nb = 0, beam_groups = 0, beam_hist_cap = 0; BeamEos beam_eos{0, {0, 0, 0, 0}}; int* beam_hist = nullptr; int* d_beam = nullptr;
-    // speculative tail (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0.  spec_base_len = keys visible to row 0 when
-    // the mode was armed; spec_key_bound = keys the steps being launched can reach (fixes the verify attention's absolute splits)
-    int spec_on = 0, spec_R = 0, spec_ngram = 2, spec_source = 0, spec_budget = 0, spec_hist_cap = 0, spec_stats_cap = 0, spec_stream_len = 0;
-    int spec_base_len = 0, spec_base_pos = 0, spec_key_bound = 0;
-    int *spec_hist = nullptr, *spec_out = nullptr, *spec_ctl = nullptr, *spec_stats = nullptr; const int* spec_stream = nullptr; BeamEos spec_eos{0, {0, 0, 0, 0}};
-    int* ring = nullptr; int ring_n = 0, ring_rows = 0;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [ring_rows][ring_n]
+    // the step's tail (tail_kind): each mode is armed on its own, so disarming one falls back to the next armed one
+    // sampling (vz_llm_decode_sampling): ctr0 / seed = the draw counter and the key the next vz_llm_decode_begin uploads
+    struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f}; } samp;
+    // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)
+    struct { int on = 0; BeamArgs a{}; int* d = nullptr; } beam;
+    // prompt-lookup speculation (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0; base_len / base_pos = keys visible
+    // to row 0 and its position when the mode was armed
+    struct { int on = 0, R = 0, base_len = 0, base_pos = 0; SpecArgs a{}; } spec;
+    struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)
     int dec_nsplit = 1;          // context splits of the decode attention for the steps being launched
@@ -314,13 +359,15 @@ struct vz_engine {
     bool use_tok = false;               // the steps being launched run on it (decided per vz_llm_decode_steps call)
     int tok_poke_word = -1; unsigned tok_poke_value = 0;      // TEST HOOK (vz_test_persist_poke): applied once, behind the next counter reset
     hipStream_t cap_stream = nullptr;   // stream capture is not allowed on the legacy null stream torch hands us
-    hipGraphExec_t dec_graph = nullptr; int dec_graph_B = 0, dec_graph_n = 0, dec_graph_nsplit = 0, dec_graph_tok = -1; long dec_graph_samp[6] = {0, 0, 0, 0, 0, 0}; long dec_graph_beam[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long dec_graph_spec[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int* dec_graph_out = nullptr; char* dec_graph_arena = nullptr;
+    hipGraphExec_t dec_graph = nullptr; DecodeGraphKey dec_graph_key{};      // the captured step and what it froze
     int* h_pinned = nullptr;     // pinned staging for small host->device uploads
     size_t h_pinned_ints = 0;
     // profiling
     int prof_on = 0, prof_class = -1;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev; size_t prof_used = 0;
 };
+
+static TailKind tail_kind(const vz_engine* e) { return e->spec.on ? TAIL_SPEC : e->beam.on ? TAIL_BEAM : e->samp.on ? TAIL_SAMPLE : TAIL_GREEDY; }
 
 #define RC(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 
@@ -500,7 +547,7 @@ extern "C" int vz_engine_create(const vz_config* cfg, vz_engine** out) {
     e->Vp = (c.vocab + c.tp_size - 1) / c.tp_size;
     e->kv_layer_elems = (size_t)2 * c.max_batch * e->Hkv_l * c.max_ctx * c.head_dim;
     hipError_t er = hipMalloc((void**)&e->kv, e->kv_layer_elems * c.n_layers * sizeof(bf16_t));
-    if (er == hipSuccess) er = hipMalloc((void**)&e->d_state, (4 * c.max_batch + 4) * sizeof(int));
+    if (er == hipSuccess) er = hipMalloc((void**)&e->d_state, DecodeState::ints(c.max_batch) * sizeof(int));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_logits, (size_t)c.max_batch * e->Vp * e->tp * sizeof(float));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_part, (size_t)c.max_batch * e->Hkv_l * 64 * (4 * 128 + 32) * sizeof(float));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_ticket, 4096);
@@ -534,7 +581,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_ao_done) hipFree(e->d_ao_done);
     if (e->d_ferr) hipFree(e->d_ferr);
     if (e->d_xnorm) hipFree(e->d_xnorm);
-    if (e->d_beam) hipFree(e->d_beam);
+    if (e->beam.d) hipFree(e->beam.d);
     if (e->d_gather) (void)hipFree(e->d_gather);
     vz_decode_persist_destroy(e->tok);
     if (e->comm) (void)ncclCommDestroy(e->comm);
@@ -583,8 +630,7 @@ extern "C" int vz_engine_resize_vocab(vz_engine* e, int new_vocab) {
     VZ_CHECK_ARG(e->tp == 1, "resize_vocab: not available on a tensor-parallel engine (rebuild it at the new vocabulary)");
     if (new_vocab == e->c.vocab) return VZ_OK;
     VZ_CHECK_HIP(hipDeviceSynchronize());
-    if (e->dec_graph) { (void)hipGraphExecDestroy(e->dec_graph); e->dec_graph = nullptr; }     // it holds the old logits width
-    if (e->tok) { vz_decode_persist_destroy(e->tok); e->tok = nullptr; }
+    RC(drop_decode_graph(e));     // it holds the old logits width
     if (e->d_logits) { VZ_CHECK_HIP(hipFree(e->d_logits)); e->d_logits = nullptr; }
     e->c.vocab = new_vocab;
     e->Vp = new_vocab;
@@ -884,6 +930,7 @@ extern "C" int vz_embed_splice(vz_engine* e, const int* d_kind, const int* d_idx
 static int g_force_comm = 0;
 static int g_rope_in_attn = 1;     // vz_tune_set(33, 0): the prefill writes a rotated copy of Q (rope_kv_kernel) for the attention again (A/B; bit-identical)
 static int g_flash_bwd = 1;               // vz_tune_set(32, 0): the training step's head-128 attention backward through the materialising batched-GEMM route again (A/B; train_engine.inc)
+static unsigned g_tune_epoch = 0;  // successful vz_tune_set calls so far: a captured decode step froze the routes the knobs chose, so it is part of the graph key
 static int g_attn_o = 1;           // vz_tune_set(30, 0): batch-1 decode attention and O projection as two launches again (attn_o_fused.hip off)
 static int g_persist_decode = 0;   // vz_tune_set(28, 1): batch-1 decode steps as one resident grid per token (decode_persist.hip) instead of the launch chain.
                                    // Off by default: measured 282 vs 339 tok/s (profiles/r03_persist_stamps.txt: the phase edges + the attention phase leave HBM idle longer than the launch boundaries they replace)
@@ -1107,7 +1154,7 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
             if (rope_q_late) { a.rope_cos = e->cosT; a.rope_sin = e->sinT; a.rope_pos = d_pos; }
             a.k_bs = a.v_bs = (long)Hkv * c.max_ctx * D; a.k_ss = a.v_ss = D; a.k_hs = a.v_hs = (long)c.max_ctx * D;
             a.o_bs = (long)S * A; a.o_ss = A; a.o_hs = D;
-            a.scale = 0.08838834764831845f;  // 128^-0.5
+            a.scale = ATTN_SCALE;
             a.causal = 1; a.q_pos0 = 0; a.window = c.sliding_window; a.kv_len = d_len;
             RC(vz_launch_attention(a, s));
         }
@@ -1143,18 +1190,19 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(B >= 1 && B <= c.max_batch && B <= 64 && d_first_ids && h_next_pos && h_ctx_len, "decode_begin: B=%d unsupported (1..min(64,max_batch))", B);
     const int mb = c.max_batch;
-    std::vector<int> h(3 * mb + 4, 0);
+    std::vector<int> h(DecodeState::ints(mb), 0);       // host image of the state: everything behind `cur` goes up in one copy
+    const DecodeState hs = decode_state(h.data(), mb), ds = decode_state(e->d_state, mb);
     for (int b = 0; b < B; ++b) {
         VZ_CHECK_ARG(h_ctx_len[b] >= 0 && h_ctx_len[b] < c.max_ctx, "decode_begin: ctx_len[%d]=%d outside [0,%d)", b, h_ctx_len[b], c.max_ctx);
-        h[b] = h_next_pos[b];            // pos
-        h[mb + b] = h_ctx_len[b];        // slot the next token is written to
-        h[2 * mb + b] = h_ctx_len[b] + 1;  // keys visible to the next token
+        hs.pos[b] = h_next_pos[b];
+        hs.slot[b] = h_ctx_len[b];         // slot the next token is written to
+        hs.len[b] = h_ctx_len[b] + 1;      // keys visible to the next token
     }
-    h[3 * mb + 1] = e->samp_ctr0; h[3 * mb + 2] = (int)e->samp_seed[0]; h[3 * mb + 3] = (int)e->samp_seed[1];
-    RC(upload_ints(e, h.data(), h.size(), e->d_state + mb, s));   // [pos | slot | len | step = 0, draw counter, seed lo, seed hi]
-    VZ_CHECK_HIP(hipMemcpyAsync(e->d_state, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    *hs.ctr = e->samp.ctr0; hs.seed[0] = e->samp.seed[0]; hs.seed[1] = e->samp.seed[1];      // (step = 0)
+    RC(upload_ints(e, hs.pos, h.size() - mb, ds.pos, s));
+    VZ_CHECK_HIP(hipMemcpyAsync(ds.cur, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
     e->dec_B = B;
-    e->spec_on = 0;          // a new batch starts with the plain tail: vz_llm_decode_spec is armed AFTER this call
+    e->spec.on = 0;          // a new batch starts with the plain tail: vz_llm_decode_spec is armed AFTER this call
     e->h_len.assign(B, 0); e->h_pos.assign(B, 0); e->h_parked.assign(B, 0);
     for (int b = 0; b < B; ++b) { e->h_len[b] = h_ctx_len[b] + 1; e->h_pos[b] = h_next_pos[b]; e->h_parked[b] = h_ctx_len[b] == 0 && h_next_pos[b] == 0; }
     return VZ_OK;
@@ -1168,15 +1216,16 @@ extern "C" int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_
     const vz_config& c = e->c;
     VZ_CHECK_ARG(e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row: row %d outside the running batch of %d", row, e->dec_B);
     VZ_CHECK_ARG(ctx_len >= 0 && ctx_len < c.max_ctx && next_pos >= 0, "decode_set_row: ctx_len %d / pos %d outside [0,%d)", ctx_len, next_pos, c.max_ctx);
-    const int mb = c.max_batch;
-    const int h[4] = {token, next_pos, ctx_len, ctx_len + 1};     // cur | pos | slot | len: one int in each of the four state arrays
+    const DecodeState ds = decode_state(e->d_state, c.max_batch);
+    const int h[DecodeState::ROW_ARRAYS] = {token, next_pos, ctx_len, ctx_len + 1};     // cur | pos | slot | len: one int in each of the four state arrays
     e->h_len[row] = ctx_len + 1; e->h_pos[row] = next_pos; e->h_parked[row] = ctx_len == 0 && next_pos == 0;
     hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(e->h_pinned && e->h_pinned_ints >= 4, "decode_set_row: no staging buffer (vz_llm_decode_begin allocates it)");
+    VZ_CHECK_ARG(e->h_pinned && e->h_pinned_ints >= DecodeState::ROW_ARRAYS, "decode_set_row: no staging buffer (vz_llm_decode_begin allocates it)");
     VZ_CHECK_HIP(hipStreamSynchronize(s));                        // previous use of the staging buffer has drained
     memcpy(e->h_pinned, h, sizeof(h));
     // a 4-row x 4-byte strided copy: row k lands in state array k at column `row`
-    VZ_CHECK_HIP(hipMemcpy2DAsync(e->d_state + row, (size_t)mb * sizeof(int), e->h_pinned, sizeof(int), sizeof(int), 4, hipMemcpyHostToDevice, s));
+    VZ_CHECK_HIP(hipMemcpy2DAsync(ds.cur + row, (size_t)(ds.pos - ds.cur) * sizeof(int), e->h_pinned, sizeof(int), sizeof(int), DecodeState::ROW_ARRAYS,
+                                  hipMemcpyHostToDevice, s));
     return VZ_OK;
 }
 
@@ -1205,60 +1254,74 @@ extern "C" int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const 
     return VZ_OK;
 }
 
+// the accept + draft launch of the armed speculative mode on the step's argmax ids g [R]; g = null: only the first draft (arming)
+static int launch_spec_tail(vz_engine* e, const int* g, hipStream_t s) {
+    const SpecArgs& a = e->spec.a;
+    const DecodeState st = decode_state(e->d_state, e->c.max_batch);
+    SpecTailArgs t;
+    t.g = g; t.cur = st.cur; t.draft = st.cur + 1; t.pos = st.pos; t.slot = st.slot; t.len = st.len; t.ctl = a.ctl; t.out = a.out; t.budget = a.budget;
+    t.hist = a.hist; t.hist_cap = a.hist_cap; t.stats = g ? a.stats : nullptr; t.stats_cap = g ? a.stats_cap : 0;
+    t.stream = a.stream; t.stream_len = a.stream_len; t.eos = a.eos; t.R = e->spec.R; t.max_ngram = a.ngram; t.source = a.source;
+    t.max_ctx = e->c.max_ctx; t.rope_max = e->rope_max; t.do_accept = g != nullptr; t.do_draft = 1;
+    return vz_launch_spec_tail(t, s);
+}
+
 // one decode step, all launches on `s`; every quantity that changes between steps lives in device memory
 static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, float* d_logits_dbg, hipStream_t s) {
     const vz_config& c = e->c;
-    const int B = e->dec_B, mb = c.max_batch;
+    const int B = e->dec_B;
     const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
     const bool lead = e->rank == 0;
-    int* cur = e->d_state; int* pos = cur + mb; int* slot = pos + mb; int* len = slot + mb; int* step = len + mb;
+    const DecodeState st = decode_state(e->d_state, c.max_batch);
+    const TailKind tail = tail_kind(e);
+    const bool spec = tail == TAIL_SPEC;
     Carver m(e->arena, e->arena_bytes);
     bf16_t* x = m.take<bf16_t>((size_t)B * H);
     bf16_t* qkv = m.take<bf16_t>((size_t)B * QKV);
     bf16_t* att = m.take<bf16_t>((size_t)B * A);
     bf16_t* act = m.take<bf16_t>((size_t)B * I);
-    bf16_t* q_rot = e->spec_on ? m.take<bf16_t>((size_t)B * A) : nullptr;      // verify steps: the rotated queries of the R rows
+    bf16_t* q_rot = spec ? m.take<bf16_t>((size_t)B * A) : nullptr;      // verify steps: the rotated queries of the R rows
     if (!m.ok) { vz_set_error("decode: workspace too small"); return VZ_ERR_STATE; }
     if (e->use_tok && e->tok) {
         // batch 1 on an MI355X: embedding row -> 32 layers -> logits as the phases of ONE resident grid (decode_persist.hip); same
         // arithmetic as the launches below, bit for bit
         VzTokArgs a;
         a.embed = e->top.embed; a.lm_head = e->top.lm_head.w; a.final_norm = e->top.norm;
-        a.cur = cur; a.pos = pos; a.slot = slot; a.step = step;
+        a.cur = st.cur; a.pos = st.pos; a.slot = st.slot; a.step = st.step;
         a.logits = e->d_logits; a.part = e->d_part; a.ticket = e->d_ticket; a.cosT = e->cosT; a.sinT = e->sinT; a.err = e->d_ferr;
-        a.vocab = c.vocab; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.window = c.sliding_window; a.scale = 0.08838834764831845f; a.eps = c.rms_eps;
+        a.vocab = c.vocab; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.window = c.sliding_window; a.scale = ATTN_SCALE; a.eps = c.rms_eps;
         e->last_stream = s;
         ProfScope ps(e, K_GEMV, s);
         RC(vz_launch_decode_token(e->tok, a, s));
     } else {
-        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(cur, B, H, e->top.embed, x, s)); }
+        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(st.cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
             const LlmLayerW& W = e->llm[i];
-            const bool fuse_ao = !e->spec_on && g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
+            const bool fuse_ao = !spec && g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
             RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
-            if (e->spec_on) {
+            if (spec) {
                 // verify step (spec.hip): the B rows are consecutive positions of ONE sequence - RoPE + append of all of them to cache row 0
                 // (the stand-alone kernel: its bits), then one pass over that row for all B x 32 query heads
                 ProfScope ps(e, K_ATTN_DEC, s);
-                RC(vz_launch_rope_kv(qkv, QKV, q_rot, kc_of(e, i), vc_of(e, i), e->cosT, e->sinT, pos, slot, 1, B, Hq, Hkv, D, c.max_ctx, s));
+                RC(vz_launch_rope_kv(qkv, QKV, q_rot, kc_of(e, i), vc_of(e, i), e->cosT, e->sinT, st.pos, st.slot, 1, B, Hq, Hkv, D, c.max_ctx, s));
                 SpecVerifyArgs a;
-                a.q = q_rot; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket; a.slot = slot;
-                a.R = B; a.Hq = Hq; a.Hkv = Hkv; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.key_bound = e->spec_key_bound;
-                a.window = c.sliding_window; a.scale = 0.08838834764831845f;
+                a.q = q_rot; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket; a.slot = st.slot;
+                a.R = B; a.Hq = Hq; a.Hkv = Hkv; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.key_bound = e->spec.a.key_bound;
+                a.window = c.sliding_window; a.scale = ATTN_SCALE;
                 RC(vz_launch_spec_verify_attn(a, s));
             } else {
                 ProfScope ps(e, K_ATTN_DEC, s);
                 AttnDecodeFusedArgs a;
                 a.qkv = qkv; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket;
-                a.cosT = e->cosT; a.sinT = e->sinT; a.pos = pos; a.slot = slot;
+                a.cosT = e->cosT; a.sinT = e->sinT; a.pos = st.pos; a.slot = st.slot;
                 a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.window = c.sliding_window;
-                a.scale = 0.08838834764831845f;
+                a.scale = ATTN_SCALE;
                 if (fuse_ao) {
                     // batch 1 (round 3): the O projection's workgroups ride in the attention's grid and stream their weights under its latency
                     // chain (attn_o_fused.hip); same arithmetic as the two launches, bit for bit (a weight_fp8 engine: the e4m3 rows +
                     // scales, as linear() would take them)
-                    RC(vz_launch_attn_o_fused(a, W.o.w, W.o.w8, W.o.ws, att, x, e->d_ao_done, step, i, c.n_layers, e->d_ferr, s));
+                    RC(vz_launch_attn_o_fused(a, W.o.w, W.o.w8, W.o.ws, att, x, e->d_ao_done, st.step, i, c.n_layers, e->d_ferr, s));
                 } else {
                     RC(vz_launch_attn_decode_fused(a, s));
                 }
@@ -1277,33 +1340,35 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     }
     {
         ProfScope ps(e, K_OTHER, s);
-        if (e->spec_on) {
-            // speculative tail (spec.hip): per-row argmax, then acceptance + state advance + the next step's draft in one small launch
-            int* g = e->spec_ctl + VZ_SPEC_CTL_IDS;
-            RC(vz_launch_argmax(e->d_logits, B, c.vocab, g, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s));
-            SpecTailArgs t;
-            t.g = g; t.cur = cur; t.draft = cur + 1; t.pos = pos; t.slot = slot; t.len = len; t.ctl = e->spec_ctl; t.out = e->spec_out; t.budget = e->spec_budget;
-            t.hist = e->spec_hist; t.hist_cap = e->spec_hist_cap; t.stats = e->spec_stats; t.stats_cap = e->spec_stats_cap;
-            t.stream = e->spec_stream; t.stream_len = e->spec_stream_len; t.eos = e->spec_eos; t.R = B; t.max_ngram = e->spec_ngram;
-            t.source = e->spec_source; t.max_ctx = c.max_ctx; t.rope_max = e->rope_max; t.do_accept = 1; t.do_draft = 1;
-            RC(vz_launch_spec_tail(t, s));
-        } else if (e->beam_on) {
-            // beam tail (beam.hip): select, then the KV of rows whose parent is another row follows the parent, then the history index
-            const int nb = e->beam_nb, rows = e->beam_nb * e->beam_groups;
-            float* score = (float*)e->d_beam; int* parent = e->d_beam + vz_engine::BEAM_ROWS; int* base = parent + vz_engine::BEAM_ROWS;
-            int* hidx = base + vz_engine::BEAM_ROWS;
-            float* cand_s = (float*)(hidx + 4 + 2 * vz_engine::BEAM_ROWS); int* cand_t = (int*)cand_s + vz_engine::BEAM_ROWS * vz_engine::BEAM_K;
-            RC(vz_launch_beam_select(e->d_logits, rows, c.vocab, nb, nb, e->beam_eos, score, cand_s, cand_t, e->beam_hist, hidx, e->beam_hist_cap,
-                                     cur, score, parent, pos, slot, len, d_out_ids, out_stride, step, c.max_ctx, e->rope_max, s));
-            RC(vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, nb, e->beam_groups,
-                                         parent, base, nb, slot, nb, s));
-            RC(vz_launch_beam_advance(hidx, s));
-        } else if (e->samp_on)
-            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp_temp, e->samp_top_k, e->samp_top_p, (const unsigned*)(step + 2), step + 1, 0, cur, pos,
-                                slot, len, d_out_ids, out_stride, step, c.max_ctx, e->rope_max, e->ring, e->ring_n, s));
-        else
-            RC(vz_launch_argmax(e->d_logits, B, c.vocab, cur, pos, slot, len, d_out_ids, out_stride, step, c.max_ctx, e->rope_max, e->ring, e->ring_n, s));
-        RC(vz_launch_step_advance(step, s));
+        // per row: the token into d_out_ids (and the ring), position / slot / length one further
+        const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
+        switch (tail) {
+        case TAIL_SPEC: {
+            // spec.hip: per-row argmax, then acceptance + state advance (its own, multi-row rule) + the next step's draft in one small launch
+            int* g = e->spec.a.ctl + VZ_SPEC_CTL_IDS;
+            RC(vz_launch_argmax(e->d_logits, B, c.vocab, g, {}, s));
+            RC(launch_spec_tail(e, g, s));
+            break;
+        }
+        case TAIL_BEAM: {
+            // beam.hip: select, then the KV of rows whose parent is another row follows the parent, then the history index
+            const BeamArgs& a = e->beam.a;
+            const BeamView v = beam_view(e->beam.d);
+            RC(vz_launch_beam_select(e->d_logits, a.nb * a.groups, c.vocab, a.nb, a.nb, a.eos, v.score, v.cand_s, v.cand_t, a.hist, v.hidx, a.hist_cap,
+                                     st.cur, v.score, v.parent, emit, s));
+            RC(vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, a.nb, a.groups,
+                                         v.parent, v.base, a.nb, st.slot, a.nb, s));
+            RC(vz_launch_beam_advance(v.hidx, s));
+            break;
+        }
+        case TAIL_SAMPLE:
+            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, st.seed, st.ctr, 0, st.cur, emit, s));
+            break;
+        case TAIL_GREEDY:
+            RC(vz_launch_argmax(e->d_logits, B, c.vocab, st.cur, emit, s));
+            break;
+        }
+        RC(vz_launch_step_advance(st.step, s));
     }
     return VZ_OK;
 }
@@ -1315,12 +1380,12 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
 extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperature, int top_k, float top_p, unsigned long long seed,
                                       int first_counter) {
     VZ_CHECK_ARG(e && first_counter >= 0, "decode_sampling: null engine / negative counter");
-    e->samp_ctr0 = first_counter;        // the draw counter also indexes the host-visible token ring of a greedy streamer loop
-    if (!enable) { e->samp_on = 0; return VZ_OK; }
+    e->samp.ctr0 = first_counter;        // the draw counter also indexes the host-visible token ring of a greedy streamer loop
+    if (!enable) { e->samp.on = 0; return VZ_OK; }
     VZ_CHECK_ARG(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f && first_counter >= 0,
                  "decode_sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
-    e->samp_on = 1; e->samp_temp = temperature; e->samp_top_k = top_k; e->samp_top_p = top_p;
-    e->samp_seed[0] = (unsigned)seed; e->samp_seed[1] = (unsigned)(seed >> 32); e->samp_ctr0 = first_counter;
+    e->samp.on = 1; e->samp.a = SampleArgs{top_k, temperature, top_p};
+    e->samp.seed[0] = (unsigned)seed; e->samp.seed[1] = (unsigned)(seed >> 32);
     return VZ_OK;
 }
 
@@ -1329,7 +1394,7 @@ extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperatur
 // read token t as soon as the event recorded behind step t fires, without a device-to-host copy per token.  NULL = off.
 extern "C" int vz_llm_decode_ring(vz_engine* e, int* ring, int ring_n, int ring_rows) {
     VZ_CHECK_ARG(e && (!ring || (ring_n >= 2 && ring_rows >= 1)), "decode_ring: ring_n >= 2 slots and ring_rows >= 1 rows expected");
-    e->ring = ring; e->ring_n = ring ? ring_n : 0; e->ring_rows = ring ? ring_rows : 0;
+    e->ring.p = ring; e->ring.n = ring ? ring_n : 0; e->ring.rows = ring ? ring_rows : 0;
     return VZ_OK;
 }
 
@@ -1345,15 +1410,13 @@ extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float tem
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)d_scratch, counter, 1, s));
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 1), (int)(unsigned)seed, 1, s));
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 2), (int)(unsigned)(seed >> 32), 1, s));
-    return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, nullptr,
-                            nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s);
+    return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
 }
 
 static int ensure_beam_state(vz_engine* e) {
-    if (e->d_beam) return VZ_OK;
-    const size_t ints = 4 + 5 * (size_t)vz_engine::BEAM_ROWS + 2 * (size_t)vz_engine::BEAM_ROWS * vz_engine::BEAM_K;
-    VZ_CHECK_HIP(hipMalloc((void**)&e->d_beam, ints * sizeof(int)));
-    VZ_CHECK_HIP(hipMemset(e->d_beam, 0, ints * sizeof(int)));
+    if (e->beam.d) return VZ_OK;
+    VZ_CHECK_HIP(hipMalloc((void**)&e->beam.d, BEAM_INTS * sizeof(int)));
+    VZ_CHECK_HIP(hipMemset(e->beam.d, 0, BEAM_INTS * sizeof(int)));
     return VZ_OK;
 }
 
@@ -1373,10 +1436,10 @@ static int beam_eos_of(const int* h_eos, int n_eos, BeamEos* out) {
 extern "C" int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, const int* h_eos, int n_eos, const int* h_base,
                                   const float* d_scores, int* d_hist, int hist_steps, vz_stream stream) {
     NEED_READY();
-    if (!enable) { e->beam_on = 0; e->beam_hist = nullptr; return VZ_OK; }
+    if (!enable) { e->beam.on = 0; e->beam.a.hist = nullptr; return VZ_OK; }
     const vz_config& c = e->c;
     if (e->tp > 1) { vz_set_error("decode_beam: beam search on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
-    VZ_CHECK_ARG(nb >= 2 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, vz_engine::BEAM_ROWS) && h_base && d_scores &&
+    VZ_CHECK_ARG(nb >= 2 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, BEAM_ROWS) && h_base && d_scores &&
                  d_hist && hist_steps >= 1, "decode_beam: %d groups x %d beams (2..16) must fit min(max_batch %d, 64) rows; base, scores and "
                  "history needed", groups, nb, c.max_batch);
     BeamEos eos;
@@ -1384,12 +1447,13 @@ extern "C" int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, 
     for (int g = 0; g < groups; ++g) VZ_CHECK_ARG(h_base[g] >= 0 && h_base[g] < c.max_ctx, "decode_beam: base[%d] = %d outside [0, %d)", g, h_base[g], c.max_ctx);
     RC(ensure_beam_state(e));
     hipStream_t s = (hipStream_t)stream;
-    const int rows = nb * groups, R = vz_engine::BEAM_ROWS;
-    std::vector<int> h(2 * R + 4, 0);            // [parent | base | hidx, pad]
-    for (int r = 0; r < rows; ++r) { h[r] = r % nb; h[R + r] = h_base[r / nb]; }
-    RC(upload_ints(e, h.data(), h.size(), e->d_beam + R, s));
-    VZ_CHECK_HIP(hipMemcpyAsync(e->d_beam, d_scores, rows * sizeof(float), hipMemcpyDeviceToDevice, s));
-    e->beam_on = 1; e->beam_nb = nb; e->beam_groups = groups; e->beam_eos = eos; e->beam_hist = d_hist; e->beam_hist_cap = hist_steps;
+    const int rows = nb * groups;
+    const BeamView v = beam_view(e->beam.d);
+    std::vector<int> h(v.re_base - v.parent, 0);            // [parent | base | hidx, pad] in one copy
+    for (int r = 0; r < rows; ++r) { h[r] = r % nb; h[(v.base - v.parent) + r] = h_base[r / nb]; }
+    RC(upload_ints(e, h.data(), h.size(), v.parent, s));
+    VZ_CHECK_HIP(hipMemcpyAsync(v.score, d_scores, rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    e->beam.on = 1; e->beam.a = BeamArgs{d_hist, nb, groups, hist_steps, eos};
     return VZ_OK;
 }
 
@@ -1410,7 +1474,7 @@ extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int 
     VZ_CHECK_ARG(p && have >= (size_t)rows * K * 2 * sizeof(int), "beam_select: first use of a stream inside a capture (call it once before capturing)");
     float* cand_s = (float*)p; int* cand_t = (int*)p + (size_t)rows * K;
     return vz_launch_beam_select(d_logits, rows, cols, nb_in, nb_out, eos, d_scores_in, cand_s, cand_t, d_records, nullptr, 1, d_next_tok,
-                                 d_next_score, d_next_parent, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, s);
+                                 d_next_score, d_next_parent, {}, s);
 }
 
 // The beam tail's KV reorder on its own: for every group g of `nb` rows (row g * nb + j), cache positions [h_base[g], h_end[g]) of row j
@@ -1418,19 +1482,18 @@ extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int 
 extern "C" int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, const int* h_end, const int* d_parent, vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
-    VZ_CHECK_ARG(nb >= 1 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, vz_engine::BEAM_ROWS) && h_base && h_end && d_parent,
+    VZ_CHECK_ARG(nb >= 1 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, BEAM_ROWS) && h_base && h_end && d_parent,
                  "kv_beam_reorder: %d groups x %d rows must fit min(max_batch %d, 64)", groups, nb, c.max_batch);
     for (int g = 0; g < groups; ++g)
         VZ_CHECK_ARG(h_base[g] >= 0 && h_base[g] <= h_end[g] && h_end[g] <= c.max_ctx, "kv_beam_reorder: group %d range [%d, %d) outside [0, %d]", g, h_base[g], h_end[g], c.max_ctx);
     RC(ensure_beam_state(e));
     hipStream_t s = (hipStream_t)stream;
-    const int R = vz_engine::BEAM_ROWS;
-    int* tb = e->d_beam + 3 * R + 4;            // [base | end] per group
-    std::vector<int> h(2 * R, 0);
-    for (int g = 0; g < groups; ++g) { h[g] = h_base[g]; h[R + g] = h_end[g]; }
-    RC(upload_ints(e, h.data(), h.size(), tb, s));
+    const BeamView v = beam_view(e->beam.d);
+    std::vector<int> h(2 * BEAM_ROWS, 0);       // [base | end] per group in one copy
+    for (int g = 0; g < groups; ++g) { h[g] = h_base[g]; h[(v.re_end - v.re_base) + g] = h_end[g]; }
+    RC(upload_ints(e, h.data(), h.size(), v.re_base, s));
     return vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, nb, groups, d_parent,
-                                     tb, 1, tb + R, 1, s);
+                                     v.re_base, 1, v.re_end, 1, s);
 }
 
 // Prompt-lookup speculative decoding (spec.hip; include/viszephyr.h has the contract): after vz_llm_decode_begin armed R = D + 1 rows of one
@@ -1440,7 +1503,7 @@ extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram
                                   int* d_out, int budget, int* d_ctl, int* d_stats, int stats_cap, int source, const int* d_stream, int stream_len,
                                   vz_stream stream) {
     NEED_READY();
-    if (!enable) { e->spec_on = 0; return VZ_OK; }
+    if (!enable) { e->spec.on = 0; return VZ_OK; }
     const vz_config& c = e->c;
     if (e->tp > 1) { vz_set_error("decode_spec: speculative decoding on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     const int R = D + 1;
@@ -1461,15 +1524,9 @@ extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram
     int h[VZ_SPEC_CTL_WORDS] = {0};
     h[VZ_SPEC_CTL_HIST] = d_hist ? hist_len : 0; h[VZ_SPEC_CTL_DONE] = budget == 0;
     RC(upload_ints(e, h, VZ_SPEC_CTL_WORDS, d_ctl, s));
-    e->spec_on = 1; e->spec_R = R; e->spec_ngram = max_ngram; e->spec_source = source; e->spec_budget = budget; e->spec_hist = d_hist; e->spec_hist_cap = d_hist ? hist_cap : 0;
-    e->spec_out = d_out; e->spec_ctl = d_ctl; e->spec_stats = d_stats; e->spec_stats_cap = stats_cap; e->spec_stream = d_stream; e->spec_stream_len = stream_len;
-    e->spec_eos = eos; e->spec_base_len = e->h_len[0]; e->spec_base_pos = e->h_pos[0];
-    const int mb = c.max_batch;
-    SpecTailArgs t;
-    t.g = nullptr; t.cur = e->d_state; t.draft = t.cur + 1; t.pos = t.cur + mb; t.slot = t.pos + mb; t.len = t.slot + mb; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
-    t.hist = e->spec_hist; t.hist_cap = e->spec_hist_cap; t.stats = nullptr; t.stats_cap = 0; t.stream = d_stream; t.stream_len = stream_len; t.eos = eos;
-    t.R = R; t.max_ngram = max_ngram; t.source = source; t.max_ctx = c.max_ctx; t.rope_max = e->rope_max; t.do_accept = 0; t.do_draft = 1;
-    return vz_launch_spec_tail(t, s);
+    e->spec.on = 1; e->spec.R = R; e->spec.base_len = e->h_len[0]; e->spec.base_pos = e->h_pos[0];
+    e->spec.a = SpecArgs{d_hist, d_out, d_ctl, d_stats, d_stream, max_ngram, source, budget, d_hist ? hist_cap : 0, stats_cap, stream_len, 0, eos};
+    return launch_spec_tail(e, nullptr, s);      // the first draft into rows 1..D
 }
 
 // the draft rule alone on a device history of hist_len ids: d_draft [D] (padded with 0), the count in d_ctl[VZ_SPEC_CTL_DRAFTED]
@@ -1497,9 +1554,10 @@ extern "C" int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_
     BeamEos eos;
     RC(beam_eos_of(h_eos, n_eos, &eos));
     int* g = d_ctl + VZ_SPEC_CTL_IDS;
-    RC(vz_launch_argmax(d_logits, R, cols, g, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, s));
+    RC(vz_launch_argmax(d_logits, R, cols, g, {}, s));
+    const DecodeState st = decode_state(d_state, R);
     SpecTailArgs t;
-    t.g = g; t.cur = d_state; t.draft = d_state + 1; t.pos = d_state + R; t.slot = d_state + 2 * R; t.len = d_state + 3 * R; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
+    t.g = g; t.cur = st.cur; t.draft = st.cur + 1; t.pos = st.pos; t.slot = st.slot; t.len = st.len; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
     t.hist = d_hist; t.hist_cap = d_hist ? hist_cap : 0; t.stats = d_stats; t.stats_cap = d_stats ? 0x7fffffff / 4 : 0; t.stream = nullptr; t.stream_len = 0; t.eos = eos;
     t.R = R; t.max_ngram = 1; t.source = 0; t.max_ctx = max_ctx; t.rope_max = rope_max; t.do_accept = 1; t.do_draft = 0;
     return vz_launch_spec_tail(t, s);
@@ -1532,6 +1590,22 @@ extern "C" int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, s
     return VZ_OK;
 }
 
+// what the steps vz_llm_decode_steps(n, d_out_ids) is about to launch would freeze in a capture (e->dec_nsplit, use_tok and the
+// speculative key bound are those of this call already)
+static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids) {
+    DecodeGraphKey k;
+    memset(&k, 0, sizeof(k));          // padding, and the modes that are off, compare equal
+    k.B = e->dec_B; k.n = n; k.nsplit = e->dec_nsplit; k.use_tok = e->use_tok; k.kind = tail_kind(e); k.tune_epoch = g_tune_epoch;
+    k.out = d_out_ids; k.arena = e->arena; k.ring = e->ring.p; k.ring_n = e->ring.n;
+    switch (k.kind) {
+    case TAIL_SPEC: k.spec = e->spec.a; break;
+    case TAIL_BEAM: k.beam = e->beam.a; break;
+    case TAIL_SAMPLE: k.samp = e->samp.a; break;
+    case TAIL_GREEDY: break;
+    }
+    return k;
+}
+
 extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d_logits_dbg, vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
@@ -1539,11 +1613,13 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(e->dec_B >= 1, "decode_steps: call vz_llm_decode_begin first");
     VZ_CHECK_ARG(n >= 1 && d_out_ids, "decode_steps: bad argument");
     const int B = e->dec_B;
-    VZ_CHECK_ARG(!e->ring || B <= e->ring_rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring_rows, B);
-    VZ_CHECK_ARG(!e->beam_on || (B == e->beam_nb * e->beam_groups && !e->ring), "decode_steps: the beam tail needs a decode batch of exactly "
-                 "%d x %d rows (it has %d) and no token ring", e->beam_groups, e->beam_nb, B);
-    VZ_CHECK_ARG(!e->spec_on || (B == e->spec_R && !e->ring && !e->beam_on && !e->samp_on), "decode_steps: the speculative tail needs a decode batch of "
-                 "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec_R, B);
+    VZ_CHECK_ARG(!e->ring.p || B <= e->ring.rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring.rows, B);
+    const TailKind tail = tail_kind(e);
+    const bool spec = tail == TAIL_SPEC;
+    VZ_CHECK_ARG(tail != TAIL_BEAM || (B == e->beam.a.nb * e->beam.a.groups && !e->ring.p), "decode_steps: the beam tail needs a decode batch of exactly "
+                 "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
+    VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
+                 "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
     const size_t need = ((size_t)B * (3 * c.hidden + (c.n_heads + 2 * c.n_kv_heads) * c.head_dim + c.inter)) * 2 + 8192;   // upper bound (tp = 1 sizes)
     RC(ensure_arena(e, need));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of
@@ -1551,8 +1627,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     bool use_graph = !e->prof_on && !d_logits_dbg && getenv("VZ_NO_GRAPH") == nullptr &&
                      (tp_local(e) || (e->comm_graph_ok && getenv("VZ_TP_NO_GRAPH") == nullptr));
     if (!tp_local(e)) RC(ensure_gather(e, B, s));
-    int* step = e->d_state + 4 * c.max_batch;
-    VZ_CHECK_HIP(hipMemsetAsync(step, 0, sizeof(int), s));
+    VZ_CHECK_HIP(hipMemsetAsync(decode_state(e->d_state, c.max_batch).step, 0, sizeof(int), s));
     VZ_CHECK_HIP(hipMemsetAsync(e->d_ao_done, 0, sizeof(unsigned), s));      // the attention + O launch's arrival word restarts with the step counter
     // vz_tune_set(28, 1) - batch 1, one GPU, bf16 weights, Zephyr-7B geometry on a 256-CU device: the steps run as ONE resident grid
     // per token (decode_persist.hip) instead of the launch chain.  Its pointer table is (re)built here, never inside a capture.
@@ -1578,9 +1653,9 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     int len_max = 0;
     // Verify steps advance by 1..R positions each, decided on the device: the host bounds by the worst case (n steps = n x R positions),
     // itself bounded by the budget the mode was armed with (vz_llm_decode_spec checked base + budget + R against the cache).
-    const int spec_len_cap = e->spec_on ? e->spec_base_len + e->spec_budget : 0;
+    const int spec_len_cap = spec ? e->spec.base_len + e->spec.a.budget : 0;
     for (int b = 0; b < B; ++b) {
-        if (e->spec_on) { len_max = std::max(len_max, std::min(e->h_len[b], c.max_ctx)); continue; }
+        if (spec) { len_max = std::max(len_max, std::min(e->h_len[b], c.max_ctx)); continue; }
         if (!e->h_parked[b]) {
             VZ_CHECK_ARG(e->h_len[b] + n - 1 <= c.max_ctx, "decode_steps: row %d would reach %d keys, the cache holds max_ctx = %d", b, e->h_len[b] + n - 1, c.max_ctx);
             VZ_CHECK_ARG(e->h_pos[b] + n - 1 < e->rope_max, "decode_steps: row %d would reach position %d, the rotary tables hold %d", b, e->h_pos[b] + n - 1, e->rope_max);
@@ -1594,7 +1669,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     {
         int keys = std::min(e->dec_len_max + n, c.max_ctx);
         if (c.sliding_window > 0) keys = std::min(keys, c.sliding_window);
-        if (e->spec_on) {
+        if (spec) {
             // keys the last of these n steps can see: row 0's worst-case length after n - 1 full steps, + R rows; no window cut - the verify
             // attention's splits sit at absolute key positions
             keys = std::min(std::min(e->h_len[0] + (n - 1) * B, spec_len_cap) + B - 1, c.max_ctx);
@@ -1606,18 +1681,18 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         // many rows fill the chip by themselves: splitting their contexts as well only adds dispatch slots and a merge hop per (row, KV head)
         // (config-5 miniature, e4m3, ctx ~330: 64 rows x 3 splits -> x 1: decode 627 -> 597 ms per batch; 32 rows x 3 -> x 2: 459 -> 448) -
         // rows x KV heads x splits is held to ~512 workgroups; 1..2 rows keep every split (batch-1 numbers unchanged)
-        if (!e->spec_on) ns = std::min(ns, std::max(1, 512 / std::max(1, B * e->Hkv_l)));      // (a verify step's rows share one cache row and its workgroups)
+        if (!spec) ns = std::min(ns, std::max(1, 512 / std::max(1, B * e->Hkv_l)));      // (a verify step's rows share one cache row and its workgroups)
         e->dec_nsplit = g_attn_nsplit > 0 ? g_attn_nsplit : ns;
-        if (e->spec_on) {
+        if (spec) {
             // the split positions follow the BUCKET, not the exact bound: one graph per bucket, as for the plain step
             int chunks = need;
             for (int bk : buckets) if (bk >= need) { chunks = bk; break; }
-            e->spec_key_bound = g_attn_nsplit > 0 ? c.max_ctx : std::min(chunks * 128, c.max_ctx);       // (a pinned split count: splits over the whole cache, one graph)
+            e->spec.a.key_bound = g_attn_nsplit > 0 ? c.max_ctx : std::min(chunks * 128, c.max_ctx);       // (a pinned split count: splits over the whole cache, one graph)
             // worst case of the device-side state after these n steps (the device keeps the exact one): n x R positions, inside the budget
-            const int adv = std::min(e->h_len[0] - e->spec_base_len + n * B, e->spec_budget);
-            for (int b = 0; b < B; ++b) { e->h_len[b] = e->spec_base_len + adv + b; e->h_pos[b] = e->spec_base_pos + adv + b; }
+            const int adv = std::min(e->h_len[0] - e->spec.base_len + n * B, e->spec.a.budget);
+            for (int b = 0; b < B; ++b) { e->h_len[b] = e->spec.base_len + adv + b; e->h_pos[b] = e->spec.base_pos + adv + b; }
         }
-        for (int b = 0; b < B && !e->spec_on; ++b) {       // what the device-side state will be after these n steps (the tail saturates, so do we)
+        for (int b = 0; b < B && !spec; ++b) {       // what the device-side state will be after these n steps (the tail saturates, so do we)
             if (e->h_parked[b]) { e->h_len[b] = std::min(e->h_len[b] + n, c.max_ctx); e->h_pos[b] = std::min(e->h_pos[b] + n, e->rope_max - 1); }
             else { e->h_len[b] += n; e->h_pos[b] += n; }      // a live row that is full is refused by the check above on the next call
         }
@@ -1627,26 +1702,9 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             RC(decode_step_launch(e, d_out_ids, n, d_logits_dbg ? d_logits_dbg + (size_t)i * B * c.vocab : nullptr, s));
         return VZ_OK;
     }
-    // Output pointer / stride, the workspace and the sampling parameters are kernel arguments frozen in the graph: re-capture when
-    // they change (seed and draw counter live in device memory and do not).
-    long samp_key[6] = {e->samp_on, e->samp_top_k, 0, 0, (long)(uintptr_t)e->ring, e->ring_n};
-    memcpy(&samp_key[2], &e->samp_temp, 4); memcpy(&samp_key[3], &e->samp_top_p, 4);
-    // the beam tail's mode, shape, eos ids and history buffer are kernel arguments too
-    long beam_key[8] = {e->beam_on, e->beam_on ? e->beam_nb : 0, e->beam_on ? e->beam_groups : 0, e->beam_on ? (long)(uintptr_t)e->beam_hist : 0,
-                        e->beam_on ? e->beam_hist_cap : 0, e->beam_on ? e->beam_eos.n : 0,
-                        e->beam_on ? ((long)(unsigned)e->beam_eos.id[0] << 32 | (unsigned)e->beam_eos.id[1]) : 0,
-                        e->beam_on ? ((long)(unsigned)e->beam_eos.id[2] << 32 | (unsigned)e->beam_eos.id[3]) : 0};
-    long spec_key[12] = {e->spec_on, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (e->spec_on) {
-        const long k[11] = {e->spec_ngram | (long)e->spec_source << 8 | (long)e->spec_eos.n << 16, e->spec_budget, (long)(uintptr_t)e->spec_hist, e->spec_hist_cap,
-                            (long)(uintptr_t)e->spec_out, (long)(uintptr_t)e->spec_ctl, (long)(uintptr_t)e->spec_stats, e->spec_stats_cap,
-                            (long)(uintptr_t)e->spec_stream, (long)e->spec_stream_len << 32 | (unsigned)e->spec_key_bound,
-                            ((long)(unsigned)e->spec_eos.id[0] << 32 | (unsigned)e->spec_eos.id[1]) ^ ((long)(unsigned)e->spec_eos.id[2] << 16) ^ ((long)(unsigned)e->spec_eos.id[3] << 48)};
-        memcpy(spec_key + 1, k, sizeof(k));
-    }
-    if (!e->dec_graph || memcmp(e->dec_graph_spec, spec_key, sizeof(spec_key)) != 0 || e->dec_graph_B != B || e->dec_graph_n != n || e->dec_graph_out != d_out_ids || e->dec_graph_arena != e->arena ||
-        e->dec_graph_nsplit != e->dec_nsplit || e->dec_graph_tok != ((int)e->use_tok | (g_attn_o << 1)) || memcmp(e->dec_graph_samp, samp_key, sizeof(samp_key)) != 0 ||
-        memcmp(e->dec_graph_beam, beam_key, sizeof(beam_key)) != 0) {
+    // the captured step is replayed while everything it froze is unchanged (seed, draw counter and the rows' state live in device memory)
+    const DecodeGraphKey key = decode_graph_key(e, n, d_out_ids);
+    if (!e->dec_graph || memcmp(&e->dec_graph_key, &key, sizeof(key)) != 0) {
         if (e->dec_graph) { hipGraphExecDestroy(e->dec_graph); e->dec_graph = nullptr; }
         hipGraph_t graph;
         if (!e->cap_stream) VZ_CHECK_HIP(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
@@ -1670,7 +1728,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             return VZ_OK;
         }
         e->dec_captures++;
-        e->dec_graph_B = B; e->dec_graph_n = n; e->dec_graph_out = d_out_ids; e->dec_graph_arena = e->arena; e->dec_graph_nsplit = e->dec_nsplit; e->dec_graph_tok = (int)e->use_tok | (g_attn_o << 1); memcpy(e->dec_graph_samp, samp_key, sizeof(samp_key)); memcpy(e->dec_graph_beam, beam_key, sizeof(beam_key)); memcpy(e->dec_graph_spec, spec_key, sizeof(spec_key));
+        memcpy(&e->dec_graph_key, &key, sizeof(key));
     }
     for (int i = 0; i < n; ++i) VZ_CHECK_HIP(hipGraphLaunch(e->dec_graph, s));
     return VZ_OK;
@@ -1744,7 +1802,7 @@ extern int g_attn_o_delay;
 extern int g_skinny_even;
 extern int g_gemm256_streamk, g_gemm256_skew, g_gemm256_stamps, g_gemm256_drain, g_gemm256_persist, g_attn_stamp_on, g_fp8_gemm_choice;
 int vz_gemm256_read_stamps(long long* host, int max_wgs, int* n_wgs);
-extern "C" int vz_tune_set(int knob, int value) {
+static int tune_set(int knob, int value) {
     if (knob == 0) { vz_set_gemv_variant(value); return VZ_OK; }
     if (knob == 1) { vz_set_gemm_choice(value); return VZ_OK; }
     if (knob == 2) { vz_set_attn_version(value); return VZ_OK; }
@@ -1777,6 +1835,11 @@ extern "C" int vz_tune_set(int knob, int value) {
     if (knob == 10) { if (value < 0 || value > 64) { vz_set_error("tune_set: decode attention splits must be 0..64"); return VZ_ERR_ARG; } g_attn_nsplit = value; return VZ_OK; }
     vz_set_error("tune_set: unknown knob %d", knob);
     return VZ_ERR_ARG;
+}
+extern "C" int vz_tune_set(int knob, int value) {
+    const int r = tune_set(knob, value);
+    if (r == VZ_OK) ++g_tune_epoch;          // the next vz_llm_decode_steps captures again
+    return r;
 }
 
 int vz_attn_read_stamps(long long* host16);

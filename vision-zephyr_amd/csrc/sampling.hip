@@ -66,10 +66,7 @@ __device__ __forceinline__ float block_max(float v, SampleShared& sh) {
 template <bool REG>
 __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ logits, int cols, float temperature, int top_k,
                                                       float top_p, const unsigned* __restrict__ seed, const int* __restrict__ ctr,
-                                                      int ctr_add, int* __restrict__ ids, int* __restrict__ pos, int* __restrict__ slot,
-                                                      int* __restrict__ len, int* __restrict__ out_ids, int out_stride,
-                                                      const int* __restrict__ step, int max_ctx, int rope_max, int* __restrict__ ring,
-                                                      int ring_n) {
+                                                      int ctr_add, int* __restrict__ ids, RowEmit emit) {
     __shared__ SampleShared sh;
     const int row = blockIdx.x, tid = threadIdx.x;
     const float* lr = logits + (size_t)row * cols;
@@ -183,11 +180,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ 
             if (sh.redf[w] > bv || (sh.redf[w] == bv && sh.redi[w] < bi)) { bv = sh.redf[w]; bi = sh.redi[w]; }
         if (bi == 0x7fffffff) bi = 0;     // all-NaN row
         ids[row] = bi;
-        if (out_ids) out_ids[(size_t)row * out_stride + (step ? *step : 0)] = bi;
-        if (ring) ring[(size_t)row * ring_n + (c2 % (unsigned)ring_n)] = bi;          // host-visible ring, slot = draw counter
-        // saturating advance (a parked row of a continuous batch steps for ever inside its own cache row)
-        if (pos && pos[row] + 1 < rope_max) pos[row] += 1;
-        if (len && len[row] < max_ctx) { len[row] += 1; if (slot) slot[row] += 1; }
+        vz_emit_advance(emit, row, bi, c2);          // ring slot = draw counter
     }
 }
 
@@ -204,17 +197,14 @@ int vz_init_sampling_kernels() {
 }
 
 int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const unsigned* seed,
-                     const int* ctr, int ctr_add, int* ids, int* pos, int* slot, int* len, int* out_ids, int out_stride,
-                     const int* step, int max_ctx, int rope_max, int* ring, int ring_n, hipStream_t s) {
-    VZ_CHECK_ARG(logits && ids && seed && ctr && rows > 0 && cols > 0 && (!ring || ring_n > 0), "sample: bad argument");
+                     const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s) {
+    VZ_CHECK_ARG(logits && ids && seed && ctr && rows > 0 && cols > 0 && (!emit.ring || emit.ring_n > 0), "sample: bad argument");
     VZ_CHECK_ARG(temperature > 0.f && top_p > 0.f, "sample: temperature %g and top_p %g must be positive (temperature 0 = greedy: use argmax)", (double)temperature, (double)top_p);
     { int r = vz_init_sampling_kernels(); if (r) return r; }
     if (cols <= 32768 && g_sample_lds_ok)
-        hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, pos,
-                           slot, len, out_ids, out_stride, step, max_ctx, rope_max, ring, ring_n);
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
     else
-        hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, pos,
-                           slot, len, out_ids, out_stride, step, max_ctx, rope_max, ring, ring_n);
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -330,11 +330,26 @@ int vz_launch_clip_assemble(const bf16_t* patch_out, const bf16_t* cls, const bf
                             bf16_t* out, hipStream_t s);
 int vz_launch_fusion(const bf16_t* hs_base, long layer_stride, int first_layer, int groups, int per_group, int T,
                      int tokens, int C, int skip, bf16_t* out, hipStream_t s);
-int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, int* pos, int* slot, int* len, int* out_ids,
-                     int out_stride, const int* step, int max_ctx, int rope_max, int* ring, int ring_n, hipStream_t s);
+// What the tail of a decode step does with a row's chosen token besides publishing it for the next step (argmax, sampler, beam select):
+// out_ids[row][*step] = token, the host-visible ring slot (ring: [rows][ring_n]), and the row's rotary position / cache slot / context
+// length move on by one.  Default = none of it (the kernels at op level).
+struct RowEmit {
+    int *pos = nullptr, *slot = nullptr, *len = nullptr;
+    int* out_ids = nullptr; int out_stride = 0; const int* step = nullptr;
+    int max_ctx = 0, rope_max = 0;
+    int* ring = nullptr; int ring_n = 0;
+};
+__device__ __forceinline__ void vz_emit_advance(const RowEmit& t, int row, int token, unsigned ring_slot) {
+    if (t.out_ids) t.out_ids[(size_t)row * t.out_stride + (t.step ? *t.step : 0)] = token;
+    if (t.ring) t.ring[(size_t)row * t.ring_n + ring_slot % (unsigned)t.ring_n] = token;
+    // saturating advance: a live row is kept inside the cache by the host's capacity check (vz_llm_decode_steps); a parked row
+    // of a continuous batch steps for ever and must stay inside its own cache row / the rotary tables
+    if (t.pos && t.pos[row] + 1 < t.rope_max) t.pos[row] += 1;
+    if (t.len && t.len[row] < t.max_ctx) { t.len[row] += 1; if (t.slot) t.slot[row] += 1; }
+}
+int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const unsigned* seed,
-                     const int* ctr, int ctr_add, int* ids, int* pos, int* slot, int* len, int* out_ids, int out_stride,
-                     const int* step, int max_ctx, int rope_max, int* ring, int ring_n, hipStream_t s);
+                     const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s);
 // set dynamic-LDS limits of every kernel up front (never inside a stream capture)
 int vz_init_gemm_kernels();
 int vz_init_attention_kernels();
@@ -351,8 +366,7 @@ struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
-                          int* next_parent, int* pos, int* slot, int* len, int* out_ids, int out_stride, const int* step, int max_ctx,
-                          int rope_max, hipStream_t s);
+                          int* next_parent, const RowEmit& emit, hipStream_t s);
 int vz_launch_beam_advance(int* hidx, hipStream_t s);
 int vz_launch_kv_beam_reorder(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, int nb, int groups,
                               const int* parent, const int* base, int base_stride, const int* end, int end_stride, hipStream_t s);
