@@ -112,6 +112,28 @@ int vz_op_linear_impl(int impl, const void* d_A, int lda, const void* d_W, int l
                       int M, int N, int K, const float* d_bias, const void* d_residual, int ldr,
                       int act, int out_fp32, vz_stream stream);
 
+/* Route query: the kernel family a linear of this shape runs on, without running it (touches no device; works without a GPU).
+ * Returns 0 GEMV, 1 SKINNY, 2 SKINNY_PERSIST, 3 SKINNY_WIDE (gemm_skinny.hip's three forms), 4 WIDE_BF16, 5 WIDE_E4M3 (gemm_wide.hip),
+ * 6 TILE128, 7 TILE256 - or -1 where the entry point would refuse the arguments.  `flags`: which copies of W exist and what the call
+ * fuses; `entry`: whose call it is.  Pointers count as 16-byte aligned, ldc / ldr as the output width.  *pre_norm (may be NULL) = 1 if
+ * the RMSNorm runs as its own launch before the linear, *splitk_hint (may be NULL) = the split-K factor handed to the 128^2 GEMM (0 = its own).
+ * The planner behind it (csrc/linear_route.hip) reads the tune knobs, so vz_tune_set changes the answer as it changes the launches. */
+#define VZ_ROUTE_WT 1u         /* the fragment-tiled bf16 copy exists (vz_op_tile_weights)           */
+#define VZ_ROUTE_W8 2u         /* the row-major e4m3 copy + row scales exist                          */
+#define VZ_ROUTE_W8T 4u        /* the fragment-tiled e4m3 copy + row scales exist                     */
+#define VZ_ROUTE_NORM 8u       /* an RMSNorm over A belongs to the call                               */
+#define VZ_ROUTE_BIAS 16u
+#define VZ_ROUTE_RESIDUAL 32u
+#define VZ_ROUTE_DECODE 64u    /* VZ_LINEAR_ENGINE only: the rows are the sequences of a decode step */
+#define VZ_LINEAR_ENGINE 0     /* a linear of an engine stage (prefill, CLIP, Q-Former; VZ_ROUTE_DECODE: a decode step) */
+#define VZ_LINEAR_OP 1         /* vz_op_linear, vz_op_linear_fp8 */
+#define VZ_LINEAR_RMSNORM 2    /* vz_op_linear_rmsnorm           */
+#define VZ_LINEAR_TILED 3      /* vz_op_linear_tiled             */
+#define VZ_LINEAR_TILED_FP8 4  /* vz_op_linear_tiled_fp8         */
+#define VZ_LINEAR_IMPL 8       /* + impl: vz_op_linear_impl      */
+int vz_op_linear_route(int M, int N, int K, int lda, int ldw, int act, int out_fp32, unsigned flags, int entry,
+                       int* pre_norm, int* splitk_hint);
+
 /* Causal-LM loss of forward(labels=...) (ref:vis_zephyr/model/language_model/vis_zephyr.py:51-98 hands labels to MistralForCausalLM.forward; hf:loss/loss_utils.py ForCausalLMLoss):
  * fp32 logits [B, S, V], int32 labels [B, S] (-100 = ignored), row (b, s) scored against labels[b][s + 1], mean over the valid targets.
  * d_loss_rows: B * S floats of scratch; d_out[0] = loss (NaN when no target is valid, as torch's mean), d_out[1] = number of valid targets. */

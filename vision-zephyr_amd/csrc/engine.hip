@@ -24,7 +24,7 @@
 
 #include <rccl/rccl.h>
 
-#include "vz_common.h"
+#include "linear_route.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -53,26 +53,54 @@ static LinearArgs mk_linear(const void* A, int lda, const void* W, int ldw, void
     return a;
 }
 
-// vz_tune_set(14, rows): from this many rows on a decode step's linears run on the 128^2 tile GEMM (65 = never)
-static int g_decode_tile_rows = 29;      // measured cross-over on the tiled weight copies (profiles/r02_rows.txt): MFMA weight stream 4.42 ms per step at 25 rows, 4.74 at 32; tile route 4.56 / 4.64
 static int g_fp8_prefill_min_rows = 768;   // vz_tune_set(22, rows): fewest prefill rows that take the fp8 MFMA path of a prefill_fp8 engine
-static int g_decode_sk_short = 8;      // vz_tune_set(15, v): split-K factor of the K = 4096 decode projections (QKV, O) on the tile-GEMM route
-static int vz_decode_splitk(int N, int K, int act) {
-    // In situ (rocprofv3 of a 64-row step, profiles/r02_rows.txt) the 128^2 kernel is bound by the bytes its workgroups keep in flight
-    // (32 KiB each): gate|up with 224 workgroups ran at 3.3 TB/s, down with 512 (split 16) at 4.4.  So every projection is cut along K
-    // until ~2 workgroups per CU are streaming: gate|up x2 (the SwiGLU pairs are formed by the finalize kernel), QKV / O x8, down x16.
-    if (N & 7) return 0;
-    const int tiles_n = (N + 127) / 128;
-    if (act == VZ_ACT_SWIGLU) return tiles_n < 384 ? 2 : 0;
-    if (K < 8192) return g_decode_sk_short;
-    int sk = (512 + tiles_n - 1) / tiles_n;
-    if (sk > 16) sk = 16;
-    return sk < 1 ? 1 : sk;
+
+// The op-level linear entry points: each names the kernels it exists for as the routes it admits (include/viszephyr.h: VZ_LINEAR_*); the
+// route itself is the planner's.  vz_op_linear_route asks the same function, so what it reports is what the entry point runs.
+static int op_plan(int entry, const LinearArgs& a, bool decode, LinPlan* p) {
+    const unsigned skinny = lin_bit(LIN_SKINNY) | lin_bit(LIN_SKINNY_PERSIST) | lin_bit(LIN_SKINNY_WIDE);
+    const int M = a.M, N = a.N, K = a.K;
+    switch (entry) {
+    case VZ_LINEAR_ENGINE:          // an engine's own call (route query only): its norm scratch has the linear's K columns
+        *p = vz_plan_linear(a, LinCaller{decode ? LIN_ROWS_DECODE : LIN_ROWS_COUPLED, K});
+        return VZ_OK;
+    case VZ_LINEAR_OP:              // vz_op_linear, vz_op_linear_fp8: 1 row: GEMV; 2..64 rows: MFMA weight stream (gemm_skinny.hip); tile GEMMs beyond
+        *p = vz_plan_linear(a, LinCaller{LIN_ROWS_FREE});
+        return VZ_OK;
+    case VZ_LINEAR_RMSNORM:
+        VZ_CHECK_ARG(a.norm_w && M >= 1 && M <= 16, "linear_rmsnorm: needs norm weights and 1 <= M <= 16 (the fused norm lives on the <= 16-row weight-stream kernels)");
+        *p = vz_plan_linear(a, LinCaller{LIN_ROWS_FREE, 0, lin_bit(LIN_GEMV) | skinny});
+        VZ_CHECK_ARG(p->route != LIN_NONE, "linear_rmsnorm: shape M=%d K=%d not supported by the weight-stream kernels", M, K);
+        return VZ_OK;
+    case VZ_LINEAR_TILED:           // 17..64 rows: gemm_wide.hip; else the MFMA weight stream on the tiled copy
+        VZ_CHECK_ARG(a.Wt && a.ldw == K && (N & 15) == 0, "linear_tiled: needs the tiled copy of a dense [N, K] weight with N %% 16 == 0");
+        *p = vz_plan_linear(a, LinCaller{LIN_ROWS_FREE, 0, lin_bit(LIN_WIDE_BF16) | skinny});
+        VZ_CHECK_ARG(p->route != LIN_NONE, "linear_tiled: the MFMA weight stream takes 2 <= M <= 64 (fused norm: <= 16), K %% 64 == 0 (M=%d K=%d)", M, K);
+        return VZ_OK;
+    case VZ_LINEAR_TILED_FP8:
+        VZ_CHECK_ARG(a.W8t && a.wscale && (N & 127) == 0, "linear_tiled_fp8: needs the tiled e4m3 copy + row scales of a dense [N, K] weight with N %% 128 == 0");
+        *p = vz_plan_linear(a, LinCaller{LIN_ROWS_FREE, 0, lin_bit(LIN_WIDE_E4M3)});
+        VZ_CHECK_ARG(p->route != LIN_NONE, "linear_tiled_fp8: needs 17 <= M <= 64, K %% 1024 == 0 (M=%d N=%d K=%d)", M, N, K);
+        return VZ_OK;
+    // vz_op_linear_impl: the route is forced, the launcher checks what it can take
+    case VZ_LINEAR_IMPL + 0: *p = vz_plan_forced(LIN_TILE128, a, false); return VZ_OK;
+    case VZ_LINEAR_IMPL + 1: *p = vz_plan_forced(LIN_GEMV, a, false); return VZ_OK;
+    case VZ_LINEAR_IMPL + 2: *p = vz_plan_forced(LIN_TILE256, a, false); return VZ_OK;
+    case VZ_LINEAR_IMPL + 3: *p = vz_plan_forced(LIN_SKINNY, a, false); return VZ_OK;
+    case VZ_LINEAR_IMPL + 4: *p = vz_plan_forced(LIN_TILE128, a, true); return VZ_OK;       // the 29..64-row decode route
+    }
+    vz_set_error("linear: unknown entry point %d", entry);
+    return VZ_ERR_ARG;
+}
+static int op_linear(int entry, const LinearArgs& a, vz_stream s) {
+    LinPlan p;
+    const int r = op_plan(entry, a, false, &p);
+    return r ? r : vz_run_linear(p, a, nullptr, (hipStream_t)s);
 }
 
 extern "C" int vz_op_linear(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                             const float* bias, const void* residual, int ldr, int act, int out_fp32, vz_stream s) {
-    return vz_launch_linear(mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32), (hipStream_t)s);
+    return op_linear(VZ_LINEAR_OP, mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32), s);
 }
 extern "C" int vz_op_linear_fp8(const void* A, int lda, const void* W8, int ldw, const float* wscale, void* C, int ldc, int M, int N,
                                 int K, const float* bias, const void* residual, int ldr, int act, int out_fp32,
@@ -80,7 +108,7 @@ extern "C" int vz_op_linear_fp8(const void* A, int lda, const void* W8, int ldw,
     VZ_CHECK_ARG(W8 && wscale, "linear_fp8: null weights / scales");
     LinearArgs a = mk_linear(A, lda, (const void*)W8, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32);
     a.W8 = (const unsigned char*)W8; a.wscale = wscale; a.norm_w = norm_w; a.norm_eps = norm_eps;
-    return vz_launch_linear(a, (hipStream_t)s);      // 1 row: GEMV; 2..16 rows: MFMA weight stream (gemm_skinny.hip)
+    return op_linear(VZ_LINEAR_OP, a, s);
 }
 extern "C" int vz_op_rmsnorm_quant_fp8(const void* x, int ldx, const float* w, float eps, void* q, int ldq, float* scale, int rows, int cols, vz_stream s) {
     return vz_launch_rmsnorm_quant_fp8((const bf16_t*)x, ldx, w, eps, (unsigned char*)q, ldq, scale, rows, cols, (hipStream_t)s);
@@ -97,11 +125,9 @@ extern "C" int vz_op_linear_fp8_mfma(const void* A8, int lda, const float* ascal
 }
 extern "C" int vz_op_linear_rmsnorm(const void* A, int lda, const float* norm_w, float norm_eps, const void* W, int ldw, void* C, int ldc,
                                     int M, int N, int K, const void* residual, int ldr, int act, int out_fp32, vz_stream s) {
-    VZ_CHECK_ARG(norm_w && M >= 1 && M <= 16, "linear_rmsnorm: needs norm weights and 1 <= M <= 16 (the fused norm lives on the <= 16-row weight-stream kernels)");
     LinearArgs a = mk_linear(A, lda, W, ldw, C, ldc, M, N, K, nullptr, residual, ldr, act, out_fp32);
     a.norm_w = norm_w; a.norm_eps = norm_eps;
-    VZ_CHECK_ARG((g_skinny_mode && vz_skinny_ok(a)) || vz_gemv_ok(a), "linear_rmsnorm: shape M=%d K=%d not supported by the weight-stream kernels", M, K);
-    return vz_launch_linear(a, (hipStream_t)s);
+    return op_linear(VZ_LINEAR_RMSNORM, a, s);
 }
 extern "C" int vz_op_tile_weights(const void* W, int N, int K, int ldw, void* Wt, vz_stream s) {
     return vz_launch_tile_weights((const bf16_t*)W, N, K, ldw, (bf16_t*)Wt, (hipStream_t)s);
@@ -109,12 +135,9 @@ extern "C" int vz_op_tile_weights(const void* W, int N, int K, int ldw, void* Wt
 extern "C" int vz_op_linear_tiled(const void* A, int lda, const void* W, const void* Wt, int ldw, void* C, int ldc, int M, int N, int K,
                                   const float* bias, const void* residual, int ldr, int act, int out_fp32, const float* norm_w,
                                   float norm_eps, vz_stream s) {
-    VZ_CHECK_ARG(Wt && ldw == K && (N & 15) == 0, "linear_tiled: needs the tiled copy of a dense [N, K] weight with N %% 16 == 0");
     LinearArgs a = mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32);
     a.Wt = (const bf16_t*)Wt; a.norm_w = norm_w; a.norm_eps = norm_eps;
-    if (M >= 17 && vz_wide_ok(a)) return vz_launch_wide(a, (hipStream_t)s);          // 17..64 rows: gemm_wide.hip
-    VZ_CHECK_ARG(g_skinny_mode && vz_skinny_ok(a), "linear_tiled: the MFMA weight stream takes 2 <= M <= 64 (fused norm: <= 16), K %% 64 == 0 (M=%d K=%d)", M, K);
-    return vz_launch_skinny(a, (hipStream_t)s);
+    return op_linear(VZ_LINEAR_TILED, a, s);
 }
 extern "C" int vz_op_tile_weights_fp8(const void* W8, int N, int K, int ldw, void* W8t, vz_stream s) {
     return vz_launch_tile_weights_fp8((const unsigned char*)W8, N, K, ldw, (unsigned char*)W8t, (hipStream_t)s);
@@ -122,23 +145,37 @@ extern "C" int vz_op_tile_weights_fp8(const void* W8, int N, int K, int ldw, voi
 // 17..64 rows on the e4m3 fragment-tiled copy (gemm_wide.hip's W8A16 stream): C = epi((A . dequant(W8)^T)), bf16 activations
 extern "C" int vz_op_linear_tiled_fp8(const void* A, int lda, const void* W8t, const float* wscale, void* C, int ldc, int M, int N, int K,
                                       const float* bias, const void* residual, int ldr, int act, int out_fp32, vz_stream s) {
-    VZ_CHECK_ARG(W8t && wscale && (N & 127) == 0, "linear_tiled_fp8: needs the tiled e4m3 copy + row scales of a dense [N, K] weight with N %% 128 == 0");
     LinearArgs a = mk_linear(A, lda, W8t, K, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32);      // (W is unused on this route: any aligned pointer)
     a.W8t = (const unsigned char*)W8t; a.wscale = wscale;
-    VZ_CHECK_ARG(vz_wide_ok(a), "linear_tiled_fp8: needs 17 <= M <= 64, K %% 1024 == 0 (M=%d N=%d K=%d)", M, N, K);
-    return vz_launch_wide(a, (hipStream_t)s);
+    return op_linear(VZ_LINEAR_TILED_FP8, a, s);
 }
 extern "C" int vz_op_linear_impl(int impl, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N,
                                  int K, const float* bias, const void* residual, int ldr, int act, int out_fp32,
                                  vz_stream s) {
-    LinearArgs a = mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32);
-    if (impl == 0) return vz_launch_gemm128(a, (hipStream_t)s);
-    if (impl == 1) return vz_launch_gemv(a, (hipStream_t)s);
-    if (impl == 2) return vz_launch_gemm256(a, (hipStream_t)s);
-    if (impl == 3) return vz_launch_skinny(a, (hipStream_t)s);
-    if (impl == 4) { a.splitk_hint = vz_decode_splitk(N, K, act); return vz_launch_gemm128(a, (hipStream_t)s); }     // the 17..64-row decode route
-    vz_set_error("linear: unknown impl %d", impl);
-    return VZ_ERR_ARG;
+    VZ_CHECK_ARG(impl >= 0 && impl <= 4, "linear: unknown impl %d", impl);
+    return op_linear(VZ_LINEAR_IMPL + impl, mk_linear(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, out_fp32), s);
+}
+// Which kernel family a linear of this shape runs on (LinRoute of csrc/linear_route.h; -1 = none): `flags` say which copies of W exist and
+// what is fused (VZ_ROUTE_*), `entry` whose call it is (VZ_LINEAR_*).  Pointers count as aligned, ldc = the output width.  Touches no device.
+extern "C" int vz_op_linear_route(int M, int N, int K, int lda, int ldw, int act, int out_fp32, unsigned flags, int entry,
+                                  int* pre_norm, int* splitk_hint) {
+    alignas(16) static const float some[4] = {0.f, 0.f, 0.f, 0.f};       // stands for every pointer that exists: nothing is read
+    const int n_out = act == VZ_ACT_SWIGLU ? N / 2 : N;
+    LinearArgs a = mk_linear(some, lda, some, ldw, (void*)some, n_out, M, N, K, (flags & VZ_ROUTE_BIAS) ? some : nullptr,
+                             (flags & VZ_ROUTE_RESIDUAL) ? some : nullptr, n_out, act, out_fp32);
+    if (flags & VZ_ROUTE_WT) a.Wt = (const bf16_t*)some;
+    if (flags & VZ_ROUTE_W8) a.W8 = (const unsigned char*)some;
+    if (flags & VZ_ROUTE_W8T) a.W8t = (const unsigned char*)some;
+    if (flags & (VZ_ROUTE_W8 | VZ_ROUTE_W8T)) a.wscale = some;
+    if (flags & VZ_ROUTE_NORM) { a.norm_w = some; a.norm_eps = 1e-5f; }
+    LinPlan p;
+    const std::string err = g_err;          // a query reports through its result: the checks it shares with the launches leave no message behind
+    const bool none = vz_linear_check_common(a) || op_plan(entry, a, (flags & VZ_ROUTE_DECODE) != 0, &p) || !vz_route_takes(p, a);
+    vz_set_error("%s", err.c_str());
+    if (none) return LIN_NONE;
+    if (pre_norm) *pre_norm = p.pre_norm;
+    if (splitk_hint) *splitk_hint = p.splitk_hint;
+    return p.route;
 }
 extern "C" int vz_op_causal_lm_loss(const float* logits, int B, int S, int V, const int* labels, float* loss_rows, float* out, vz_stream s) {
     return vz_launch_causal_lm_loss(logits, B, S, V, labels, loss_rows, out, (hipStream_t)s);
@@ -254,8 +291,6 @@ struct TopW {
     const bf16_t* qf_queries = nullptr; NormW qf_pre_norm, qf_norm;
     const bf16_t* embed = nullptr; const float* norm = nullptr; LinW lm_head;
 };
-
-enum { K_GEMM = 0, K_GEMV = 1, K_ATTN = 2, K_ATTN_DEC = 3, K_NORM = 4, K_OTHER = 5, K_FUSED = 6, K_COMM = 7 };
 
 static constexpr float ATTN_SCALE = 0.08838834764831845f;      // 128^-0.5 (vz_engine_create takes head_dim 128 only)
 
@@ -401,89 +436,26 @@ struct ProfScope {
     }
 };
 
-// One linear C = epi(A . W^T + W.b): the route follows the row count and what finalize attached to W (tiled copies, e4m3 copy).
-static int linear(vz_engine* e, int klass_hint, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M,
+// One linear C = epi(A . W^T + W.b) of the engine: the route follows the row count, the caller (decode = the rows are the independent
+// sequences of a decode step) and what finalize attached to W - vz_plan_linear picks the copy the kernel reads.
+static LinearArgs linear_args(vz_engine* e, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M, int N, int K,
+                              const bf16_t* res, int ldr, int act, int out_fp32, const float* norm_w, float norm_eps, int splitk_hint) {
+    LinearArgs a = mk_linear(A, lda, W.w, ldw, C, ldc, M, N, K, W.b, res, ldr, act, out_fp32);
+    a.W8 = W.w8; a.wscale = W.ws; a.Wt = W.wt; a.W8t = W.w8t;
+    a.splitk_hint = splitk_hint;          // 0 = the dispatcher's choice (the Stage-2 trainer's narrow LoRA shapes pass their own)
+    a.norm_w = norm_w; a.norm_eps = norm_eps; a.err = e->d_ferr;
+    return a;
+}
+static LinCaller linear_caller(const vz_engine* e, int decode) { return LinCaller{decode ? LIN_ROWS_DECODE : LIN_ROWS_COUPLED, e->c.hidden}; }
+static int linear(vz_engine* e, int decode, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M,
                   int N, int K, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
                   const float* norm_w = nullptr, float norm_eps = 0.f, int splitk_hint = 0) {
-    LinearArgs a = mk_linear(A, lda, W.w, ldw, C, ldc, M, N, K, W.b, res, ldr, act, out_fp32);
-    a.splitk_hint = splitk_hint;          // 0 = the dispatcher's choice (the Stage-2 trainer's narrow LoRA shapes pass their own)
-    a.norm_w = norm_w; a.norm_eps = norm_eps; a.err = e->d_ferr; e->last_stream = s;
-    const bool fp8 = W.w8 && W.ws;
-    if (klass_hint == 1 && M >= 2 && ldw == K) {       // decode step: the fragment-tiled copy of this weight, if the caller registered one
-        a.Wt = W.wt;
-        if (fp8 && M >= 17 && M <= 64) {
-            // 17..64-row step of an e4m3-weight engine: every projection streams the e4m3 fragment-tiled copy (gemm_wide.hip, round 3) -
-            // half the bytes of the bf16 routes these row counts took before (the row-major e4m3 stream of gemm_skinny.hip was slower than
-            // bf16 at 17..32 rows and unused beyond).  The RMSNorm runs as its own launch.
-            if (W.w8t) {
-                LinearArgs t = a;
-                t.W8t = W.w8t; t.wscale = W.ws; t.W8 = nullptr; t.Wt = nullptr; t.wide_ok = true;
-                if (norm_w) { t.A = e->d_xnorm; t.lda = K; t.norm_w = nullptr; }
-                if (vz_wide_ok(t)) {
-                    if (norm_w) {
-                        ProfScope ps(e, K_NORM, s);
-                        int r = vz_launch_rmsnorm(A, lda, e->d_xnorm, K, norm_w, M, K, norm_eps, s);
-                        if (r) return r;
-                    }
-                    ProfScope ps(e, K_GEMV, s);
-                    return vz_launch_wide(t, s);
-                }
-            }
-        }
-    }
-    a.wide_ok = klass_hint == 1;          // 1 = decode step: rows are independent sequences
-    if (fp8) {                            // e4m3 copy of the same weights: only the weight-stream kernels (M <= 32) take it
-        a.W8 = W.w8; a.wscale = W.ws;
-        LinearArgs t = a;
-        if (M > 16) t.norm_w = nullptr;   // 17..32 rows: the norm runs as its own kernel below
-        if (!vz_gemv_ok(t) && !(g_skinny_mode && vz_skinny_ok(t))) { a.W8 = nullptr; a.wscale = nullptr; }
-    }
-    if (klass_hint == 1 && M >= 17 && M <= 64 && a.Wt && (!fp8 || M >= std::max(g_decode_tile_rows, 33))) {      // (e4m3 engines: from where they leave the e4m3 stream anyway)
-        // 17..64-row decode step on the tiled weight copy (gemm_wide.hip): weights straight to registers, the activations of a 512-k
-        // chunk staged once per 128 weight rows - for the projections whose row blocks fill the chip without a K split (gate|up,
-        // lm_head: measured 52.7 vs 62 us and 55 vs 91 us at 64 rows; the split shapes stay on the tile GEMM).  The RMSNorm runs
-        // as its own launch.
-        LinearArgs t = a;
-        t.W8 = nullptr; t.wscale = nullptr;          // (a weight_fp8 engine's bf16 tensors - and their tiled copies - hold the same dequantised values)
-        if (norm_w) { t.A = e->d_xnorm; t.lda = K; t.norm_w = nullptr; }
-        if (vz_wide_engine_ok(t)) {
-            if (norm_w) {
-                ProfScope ps(e, K_NORM, s);
-                int r = vz_launch_rmsnorm(A, lda, e->d_xnorm, K, norm_w, M, K, norm_eps, s);
-                if (r) return r;
-            }
-            ProfScope ps(e, K_GEMV, s);
-            return vz_launch_wide(t, s);
-        }
-    }
-    if (klass_hint == 1 && M >= (fp8 ? std::max(g_decode_tile_rows, 33) : g_decode_tile_rows) && M <= 64 && g_skinny_mode && (K & 63) == 0) {     // (e4m3 stream: ahead up to 32 rows)
-        // 17..64-row decode step as a TILE GEMM: the 128^2 MFMA kernel streams every weight once at the rate its workgroups can pull
-        // (gate-up 48 us = 4.9 TB/s whatever the row count), where the MFMA weight stream of gemm_skinny.hip re-reads the activations
-        // per 16-row group and falls to 2.7 TB/s at 64 rows (tools/bench_rows.py, profiles/r02_rows.txt).  Projections with few column
-        // tiles (QKV 48, O / down 32) are cut along K until ~512 workgroups are in flight.  The RMSNorm runs as its own launch.
-        if (norm_w) {
-            ProfScope ps(e, K_NORM, s);
-            int r = vz_launch_rmsnorm(A, lda, e->d_xnorm, K, norm_w, M, K, norm_eps, s);
-            if (r) return r;
-            a.A = e->d_xnorm; a.lda = K; a.norm_w = nullptr;
-        }
-        a.W8 = nullptr; a.wscale = nullptr;          // (a weight_fp8 engine's bf16 tensors hold the same dequantised values)
-        a.splitk_hint = vz_decode_splitk(N, K, act);
-        ProfScope ps(e, K_GEMV, s);
-        return vz_launch_gemm128(a, s);
-    }
-    if (norm_w && M > 4 && M <= 64 && K == e->c.hidden && g_skinny_mode && !(vz_skinny_ok(a) && vz_skinny_fused_norm_ok(a))) {
-        // 5..16 rows without the persistent fused-norm kernel (knob 9 = 2, or a K it does not take): normalise once into an
-        // L2-resident scratch and let the one-group-per-workgroup MFMA weight stream take its B fragments from there
-        { ProfScope ps(e, K_NORM, s); int r = vz_launch_rmsnorm(A, lda, e->d_xnorm, K, norm_w, M, K, norm_eps, s); if (r) return r; }
-        a.A = e->d_xnorm; a.lda = K; a.norm_w = nullptr;
-        if (vz_skinny_ok(a)) { ProfScope ps(e, K_GEMV, s); return vz_launch_skinny(a, s); }
-        a.A = A; a.lda = lda; a.norm_w = norm_w;
-    }
-    if (norm_w) { ProfScope ps(e, K_GEMV, s); return vz_launch_linear(a, s); }     // skinny MFMA stream or GEMV: both fuse the norm
-    const bool gemv = vz_gemv_ok(a) || (g_skinny_mode && vz_skinny_ok(a));
-    ProfScope ps(e, gemv ? K_GEMV : K_GEMM, s);
-    return vz_launch_linear(a, s);
+    const LinearArgs a = linear_args(e, A, lda, W, ldw, C, ldc, M, N, K, res, ldr, act, out_fp32, norm_w, norm_eps, splitk_hint);
+    const LinPlan p = vz_plan_linear(a, linear_caller(e, decode));
+    e->last_stream = s;
+    if (p.pre_norm) { ProfScope ps(e, K_NORM, s); RC(vz_run_prenorm(a, e->d_xnorm, s)); }
+    ProfScope ps(e, p.klass, s);
+    return vz_run_route(p, a, e->d_xnorm, s);
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -1590,6 +1562,26 @@ extern "C" int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, s
     return VZ_OK;
 }
 
+// Does a linear of the B-row step decode_step_launch is about to issue (its four projections, the lm_head) leave the <= 16-row
+// weight-stream kernels?  Those routes - the tile GEMMs, gemm_wide.hip and the 17..64-row kernel beside them - are the ones whose launches
+// may take per-stream split-K scratch, which cannot be allocated inside a capture.
+static bool decode_step_past_16_row_kernels(vz_engine* e, int B) {
+    const vz_config& c = e->c;
+    const int H = c.hidden, QKV = (e->Hq_l + 2 * e->Hkv_l) * c.head_dim, I = e->I_l, A = e->Hq_l * c.head_dim, V = tp_local(e) ? c.vocab : e->Vp;
+    const LlmLayerW& W = e->llm[0];
+    const bf16_t* x = e->d_xnorm;          // stands for the activations and outputs: nothing is launched
+    const LinearArgs step[] = {
+        linear_args(e, x, H, W.qkv, H, (void*)x, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, W.in_norm, c.rms_eps, 0),
+        linear_args(e, x, A, W.o, A, (void*)x, H, B, H, A, x, H, VZ_ACT_NONE, 0, nullptr, 0.f, 0),
+        linear_args(e, x, H, W.gu, H, (void*)x, I, B, 2 * I, H, nullptr, 0, VZ_ACT_SWIGLU, 0, W.post_norm, c.rms_eps, 0),
+        linear_args(e, x, I, W.down, I, (void*)x, H, B, H, I, x, H, VZ_ACT_NONE, 0, nullptr, 0.f, 0),
+        linear_args(e, x, H, e->top.lm_head, H, (void*)x, V, B, V, H, nullptr, 0, VZ_ACT_NONE, 1, e->top.norm, c.rms_eps, 0),
+    };
+    for (const LinearArgs& a : step)
+        if (vz_plan_linear(a, linear_caller(e, 1)).route >= LIN_SKINNY_WIDE) return true;
+    return false;
+}
+
 // what the steps vz_llm_decode_steps(n, d_out_ids) is about to launch would freeze in a capture (e->dec_nsplit, use_tok and the
 // speculative key bound are those of this call already)
 static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids) {
@@ -1708,7 +1700,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         if (e->dec_graph) { hipGraphExecDestroy(e->dec_graph); e->dec_graph = nullptr; }
         hipGraph_t graph;
         if (!e->cap_stream) VZ_CHECK_HIP(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
-        if (B >= 17) {     // split-K scratch of the capture stream (128^2 tile route, gemm_wide K splits): never allocated inside a capture
+        if (decode_step_past_16_row_kernels(e, B)) {     // split-K scratch of the capture stream (128^2 tile route, gemm_wide K splits): never allocated inside a capture
             void* p = nullptr; size_t have = 0;
             RC(vz_stream_ws(0, e->cap_stream, (size_t)96 << 20, false, &p, &have));
             RC(vz_wide_reserve(e->cap_stream));
@@ -1803,36 +1795,21 @@ extern int g_skinny_even;
 extern int g_gemm256_streamk, g_gemm256_skew, g_gemm256_stamps, g_gemm256_drain, g_gemm256_persist, g_attn_stamp_on, g_fp8_gemm_choice;
 int vz_gemm256_read_stamps(long long* host, int max_wgs, int* n_wgs);
 static int tune_set(int knob, int value) {
-    if (knob == 0) { vz_set_gemv_variant(value); return VZ_OK; }
-    if (knob == 1) { vz_set_gemm_choice(value); return VZ_OK; }
-    if (knob == 2) { vz_set_attn_version(value); return VZ_OK; }
-    if (knob == 3) { vz_set_splitk_mode(value); return VZ_OK; }
-    if (knob == 4) { g_gemm256_streamk = value; return VZ_OK; }
-    if (knob == 5) { g_gemm256_skew = value; return VZ_OK; }
-    if (knob == 6) { g_gemm256_stamps = value; return VZ_OK; }
-    if (knob == 7) { g_force_comm = value; return VZ_OK; }
-    if (knob == 9) { g_skinny_mode = value; return VZ_OK; }
-    if (knob == 11) { g_gemm256_drain = value; return VZ_OK; }
-    if (knob == 14) { g_decode_tile_rows = value; return VZ_OK; }
-    if (knob == 19) { g_wide_mode = value; return VZ_OK; }
-    if (knob == 21) { g_fp8_gemm_choice = value; return VZ_OK; }
-    if (knob == 22) { g_fp8_prefill_min_rows = value; return VZ_OK; }
-    if (knob == 23) { vz_set_attn_split(value); return VZ_OK; }
-    if (knob == 24) { vz_set_splitk_cap(value); return VZ_OK; }
-    if (knob == 25) { g_qf_kv_all = value; return VZ_OK; }
-    if (knob == 27) { g_wide_fp8_splits = value; return VZ_OK; }
-    if (knob == 28) { g_persist_decode = value; return VZ_OK; }
-    if (knob == 29) { g_oneshot = value; return VZ_OK; }
-    if (knob == 30) { g_attn_o = value; return VZ_OK; }
-    if (knob == 31) { g_attn_o_delay = value; return VZ_OK; }
-    if (knob == 32) { g_flash_bwd = value; return VZ_OK; }
-    if (knob == 33) { g_rope_in_attn = value; return VZ_OK; }
-    if (knob == 34) { g_gemm256_persist = value; return VZ_OK; }
-    if (knob == 35) { g_skinny_even = value; return VZ_OK; }
-    if (knob == 26) { vz_set_splitk_mid(value); return VZ_OK; }
-    if (knob == 15) { g_decode_sk_short = value; return VZ_OK; }
-    if (knob == 16) { g_attn_stamp_on = value; return VZ_OK; }
     if (knob == 10) { if (value < 0 || value > 64) { vz_set_error("tune_set: decode attention splits must be 0..64"); return VZ_ERR_ARG; } g_attn_nsplit = value; return VZ_OK; }
+    // knob number -> the int it sets, or its setter
+    static const struct { int knob; int* var; void (*set)(int); } knobs[] = {
+        {0, nullptr, vz_set_gemv_variant}, {1, nullptr, vz_set_gemm_choice}, {2, nullptr, vz_set_attn_version}, {3, nullptr, vz_set_splitk_mode},
+        {4, &g_gemm256_streamk}, {5, &g_gemm256_skew}, {6, &g_gemm256_stamps}, {7, &g_force_comm}, {9, &g_skinny_mode},
+        {11, &g_gemm256_drain}, {14, &g_decode_tile_rows}, {15, &g_decode_sk_short}, {16, &g_attn_stamp_on}, {19, &g_wide_mode}, {21, &g_fp8_gemm_choice},
+        {22, &g_fp8_prefill_min_rows}, {23, nullptr, vz_set_attn_split}, {24, nullptr, vz_set_splitk_cap}, {25, &g_qf_kv_all}, {26, nullptr, vz_set_splitk_mid},
+        {27, &g_wide_fp8_splits}, {28, &g_persist_decode}, {29, &g_oneshot}, {30, &g_attn_o}, {31, &g_attn_o_delay}, {32, &g_flash_bwd}, {33, &g_rope_in_attn},
+        {34, &g_gemm256_persist}, {35, &g_skinny_even},
+    };
+    for (const auto& k : knobs) {
+        if (k.knob != knob) continue;
+        if (k.var) *k.var = value; else k.set(value);
+        return VZ_OK;
+    }
     vz_set_error("tune_set: unknown knob %d", knob);
     return VZ_ERR_ARG;
 }

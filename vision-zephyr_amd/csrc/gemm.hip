@@ -456,13 +456,12 @@ void vz_set_splitk_cap(int v) { g_splitk_cap = v < 1 ? 1 : (v > 16 ? 16 : v); }
 // Tile choice: the 256x256 8-phase kernel runs one workgroup per CU, so it needs enough 256^2 tiles to fill the
 // 256 CUs several times over (>= 512 tiles: measured cross-over on MI355X, tools/bench_kernels.py); smaller grids keep the
 // 128x128 kernel (2 workgroups per CU, 4x the tiles).
-int vz_launch_gemm(const LinearArgs& a, hipStream_t s) {
+bool vz_gemm_use256(const LinearArgs& a) {
     const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
     // measured on MI355X (tools/bench_kernels.py gemm): the 256^2 kernel wins once it has >= 160 tiles (QKV 192: 100 vs 118 us,
     // gate-up 896: 373 vs 506 us) or, with its stream-K tail, >= 96 tiles of long K (down-proj 128 tiles x 224 K-tiles:
     // 190 vs 252 us); the 128^2 kernel keeps short K (CLIP, K = 1024) and small grids (O-proj 128 tiles x 64: 68 vs 80 us)
-    const bool use256 = g_gemm_choice == 2 || (g_gemm_choice == 0 && a.K >= 1024 && (t256 >= 160 || (t256 >= 96 && a.K >= 8192)));
-    return use256 ? vz_launch_gemm256(a, s) : vz_launch_gemm128(a, s);
+    return g_gemm_choice == 2 || (g_gemm_choice == 0 && a.K >= 1024 && (t256 >= 160 || (t256 >= 96 && a.K >= 8192)));
 }
 
 int vz_launch_gemm128(const LinearArgs& a, hipStream_t s) {
@@ -484,7 +483,6 @@ int vz_launch_gemm128(const LinearArgs& a, hipStream_t s) {
     // The factor depends on N and K only, never on M: a row's result must not change with the number of rows beside it
     // (the Q-Former computes block 0's self-attention once per sample and relies on it being bit-identical to the
     // per-tile computation, tests/test_stages_gpu.py::test_qformer).
-    (void)tiles;
     if (g_splitk_mode != 1 && a.M <= 512 && p.tiles_n < 128 && a.act != VZ_ACT_SWIGLU && (a.N & 3) == 0) {
         // ~256 workgroups per row tile, rounded DOWN: two row tiles (the Q-Former's 160 rows) then fit the 512 slots in one round
         // (N = 12288: 96 column tiles x 3 slices x 2 row tiles = 576 workgroups ran a second round - 57 us; x 2 slices: 47 us)
@@ -550,13 +548,4 @@ int vz_launch_gemm_batched(const BatchedGemmArgs& b, hipStream_t s) {
     hipLaunchKernelGGL(gemm_bf16_kernel, dim3(p.tiles_m * p.tiles_n, b.n_outer * b.n_inner), dim3(256), GEMM_LDS, s, p);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
-}
-
-int vz_launch_linear(const LinearArgs& a, hipStream_t s) {
-    // 2 rows: the GEMV with both rows in LDS streams the weights like the 1-row launch (3.12 vs 3.48 ms per 2-row step); 3..64 rows
-    // (batched decode): one MFMA per KiB of weights
-    if (g_skinny_mode && vz_skinny_ok(a) && !(a.M == 2 && g_skinny_mode != 7 && vz_gemv_ok(a))) return vz_launch_skinny(a, s);
-    if (vz_gemv_ok(a)) return vz_launch_gemv(a, s);
-    VZ_CHECK_ARG(!a.W8, "linear: e4m3 weights are streamed by the M <= 16 kernels only (M=%d K=%d)", a.M, a.K);
-    return vz_launch_gemm(a, s);
 }

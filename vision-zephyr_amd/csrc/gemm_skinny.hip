@@ -18,7 +18,7 @@
 //     resident, and rides in the same prefetch ring as the weights.
 //   * FP8 weights (W8A16, vz_hip/quant.py): a lane's 16 bytes are the same 16 k of the step; they are widened to the two bf16
 //     fragments in registers (exact) and the row's power-of-two scale multiplies the fp32 result once.
-#include "vz_common.h"
+#include "linear_route.h"
 
 int g_skinny_even = 1;          // vz_tune_set(35, 0): one persistent workgroup per CU whatever the group count (A/B)
 namespace {
@@ -528,8 +528,8 @@ int g_num_cu_skinny = 0;
 template <bool SWIGLU, bool FP8>
 int launch_persist(const SkinnyParams& p, int n_groups, size_t lds, hipStream_t s) {
     // ONE workgroup per CU even where LDS would hold two (5..7 rows): measured 3.85 / 3.88 / 3.94 ms per 5 / 6 / 7-row step
-    // against 3.98 / 4.03 / 4.08 with two (knob 9 = 4) - the eight waves' synchronised bursts again
-    const int per_cu = g_skinny_mode == 4 ? ((160 * 1024) / (int)lds >= 2 ? 2 : 1) : 1;
+    // against 3.98 / 4.03 / 4.08 with two (knob 9 = SKINNY_PERSIST_2_PER_CU) - the eight waves' synchronised bursts again
+    const int per_cu = g_skinny_mode == SKINNY_PERSIST_2_PER_CU ? ((160 * 1024) / (int)lds >= 2 ? 2 : 1) : 1;
     const int cap = g_num_cu_skinny * per_cu;
     // the launch lasts as long as its busiest workgroup: ceil(n_groups / cap) groups.  With that many groups on EVERY workgroup fewer of them
     // are needed (QKV: 384 groups = 2 per workgroup on 192 CUs instead of 2 on 128 + 1 on 128; the waves' bursts then share HBM with fewer
@@ -565,14 +565,14 @@ int launch(const SkinnyParams& p, int blocks, size_t lds, hipStream_t s) {
 
 }  // namespace
 
-int g_skinny_mode = 1;   // vz_tune_set(9, v): 1 = 2..16-row linears use the MFMA weight stream (default), 0 = GEMV / tile GEMM as before
+int g_skinny_mode = SKINNY_ON;   // vz_tune_set(9, v): SkinnyMode (linear_route.h)
 
 // 5..16 rows with the RMSNorm fused: only the persistent form holds the normalised rows in LDS at one workgroup per CU
-bool vz_skinny_fused_norm_ok(const LinearArgs& a) { return g_skinny_mode != 2 && a.M >= 2 && a.M <= 16 && skinny_persist_ok(a); }
+bool vz_skinny_fused_norm_ok(const LinearArgs& a) { return g_skinny_mode != SKINNY_NO_PERSIST && a.M >= 2 && a.M <= 16 && skinny_persist_ok(a); }
 
 bool vz_skinny_ok(const LinearArgs& a) {
     if (a.M < 2 || a.M > 64 || (a.K & 63) != 0 || a.K < 512) return false;
-    if (a.M > 16 && (a.norm_w || !a.wide_ok)) return false;                                       // 17..64 rows: the caller normalises (no LDS staging)
+    if (a.M > 16 && (a.norm_w || !a.rows_free)) return false;                                       // 17..64 rows: the caller normalises (no LDS staging)
     if (a.W8 && (!a.wscale || (a.ldw & 15) != 0 || ((uintptr_t)a.W8 & 15) != 0)) return false;
     if (a.act == VZ_ACT_SWIGLU && (a.N % 32) != 0) return false;
     if ((a.lda & 7) != 0 || (a.ldw & 7) != 0) return false;                       // 16-byte fragment loads
@@ -613,6 +613,14 @@ int vz_launch_tile_weights(const bf16_t* W, int N, int K, int ldw, bf16_t* Wt, h
     return VZ_OK;
 }
 
+// which of the three forms: 17..64 rows have their own kernel; the persistent fused-norm form from 3 rows (3..4 rows joined in round 2:
+// 3.59 / 3.61 vs 3.69 / 3.68 ms per step on the tiled weights), from 2 with SKINNY_PERSIST_FROM_2, never with SKINNY_NO_PERSIST
+LinRoute vz_skinny_route(const LinearArgs& a) {
+    if (a.M > 16) return LIN_SKINNY_WIDE;
+    if (g_skinny_mode != SKINNY_NO_PERSIST && skinny_persist_ok(a) && (a.M >= 3 || g_skinny_mode == SKINNY_PERSIST_FROM_2)) return LIN_SKINNY_PERSIST;
+    return LIN_SKINNY;
+}
+
 int vz_launch_skinny(const LinearArgs& a, hipStream_t s) {
     int rc = vz_linear_check_common(a);
     if (rc) return rc;
@@ -621,12 +629,13 @@ int vz_launch_skinny(const LinearArgs& a, hipStream_t s) {
     SkinnyParams p;
     p.A = a.A; p.W = a.W; p.C = a.C; p.bias = a.bias; p.residual = a.residual; p.norm_w = a.norm_w;
     p.W8 = a.W8; p.wscale = a.wscale;
-    p.Wt = (!a.W8 && (a.N & 15) == 0 && g_skinny_mode != 5) ? a.Wt : nullptr;        // (knob 9 = 5: ignore the tiled copies, A/B)
+    p.Wt = (!a.W8 && (a.N & 15) == 0) ? a.Wt : nullptr;         // (the route plan passes the tiled copy only where it is to be read)
     p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldw = a.ldw; p.ldc = a.ldc; p.ldr = a.ldr;
     p.act = a.act; p.out_fp32 = a.out_fp32; p.norm_eps = a.norm_eps;
     const bool sw = a.act == VZ_ACT_SWIGLU;
     const int blocks = sw ? a.N / 32 : (a.N + 15) / 16;
-    if (a.M > 16) {          // 17..64 rows: two / four B operands per weight fragment
+    const LinRoute form = vz_skinny_route(a);
+    if (form == LIN_SKINNY_WIDE) {          // 17..64 rows: two / four B operands per weight fragment
         const bool four = blocks >= 512 && (p.K >> 6) >= 16;
 #define VZ_WIDE(SW, NWV, F8, MHV) do { \
             static VzDeviceOnce attr; \
@@ -641,7 +650,7 @@ int vz_launch_skinny(const LinearArgs& a, hipStream_t s) {
 #undef VZ_WIDE_MH
 #undef VZ_WIDE
     }
-    if (g_skinny_mode != 2 && skinny_persist_ok(a) && (a.M >= 3 || g_skinny_mode == 3)) {      // knob 9: 2 = never (3..4 rows joined in round 2: 3.59 / 3.61 vs 3.69 / 3.68 ms per step on the tiled weights)
+    if (form == LIN_SKINNY_PERSIST) {
         const size_t pl = skinny_persist_lds(a);
         if (p.W8) return sw ? launch_persist<true, true>(p, blocks, pl, s) : launch_persist<false, true>(p, blocks, pl, s);
         return sw ? launch_persist<true, false>(p, blocks, pl, s) : launch_persist<false, false>(p, blocks, pl, s);

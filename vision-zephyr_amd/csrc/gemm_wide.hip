@@ -19,7 +19,7 @@
 // Measured at 64 rows inside a 32-layer step (tools/prof_batched.sh, profiles/r02_rows.txt): gate|up (224 workgroups, no split) 52.7 us
 // against 57.1 + 5.2 (tile GEMM + finalize), lm_head 55 against 79 + 12; the split shapes do NOT win - down (P = 7) 38.5 against
 // 28.9 + 6.2, O (P = 8 / 4) 22.9 against 14.2 + 6.2, QKV (P = 4) 22.2 against 17.0 + 4.9 - so the engine takes this kernel where
-// pick_splits() = 1 and keeps the tile GEMM elsewhere (vz_wide_engine_ok).  The stream alone (MFMAs and LDS reads removed) ran
+// pick_splits() = 1 and keeps the tile GEMM elsewhere (vz_plan_linear, linear_route.hip).  The stream alone (MFMAs and LDS reads removed) ran
 // at the same rate: what bounds it is the load side of one 8-wave workgroup per CU, not the compute.
 // k assignment inside a 64-k step is gemm_skinny.hip's (lane (r, g): k = 16 g .. 16 g + 7 | + 8 .. + 15), so the tiled copies are shared.
 // The split-K workspace (partials + tickets) exists per (device, stream) (vz_stream_ws, gemm.hip): launches that share it are
@@ -469,10 +469,7 @@ int pick_splits(int row_blocks, int chunks, bool fp8 = false) {
 int g_wide_mode = 1;       // vz_tune_set(19, v): 0 = off (17..64-row decode steps keep the earlier routes)
 int g_wide_fp8_splits = 0; // vz_tune_set(27, P): force the K split of the e4m3 stream (0 = pick_splits; A/B)
 
-// what the engine's decode steps use it for: shapes that need no K split (measured faster than the tile GEMM + finalize there only)
-bool vz_wide_engine_ok(const LinearArgs& a);
-
-static int wide_splits(const LinearArgs& a) {
+int vz_wide_splits(const LinearArgs& a) {
     const int rbs = a.N >> 7, chunks = a.K >> 9;
     const bool f8 = a.W8t != nullptr;
     if (f8 && g_wide_fp8_splits > 0 && chunks % g_wide_fp8_splits == 0 && ((chunks / g_wide_fp8_splits) & 1) == 0) return g_wide_fp8_splits;
@@ -480,7 +477,7 @@ static int wide_splits(const LinearArgs& a) {
 }
 
 bool vz_wide_ok(const LinearArgs& a) {
-    if (!g_wide_mode || a.norm_w || !a.wide_ok) return false;
+    if (!g_wide_mode || a.norm_w || !a.rows_free) return false;
     if (a.W8t) { if (!a.wscale || ((uintptr_t)a.W8t & 15) != 0 || ((uintptr_t)a.wscale & 15) != 0 || ((a.K >> 9) & 1)) return false; }
     else if (!a.Wt || a.W8) return false;
     if (a.M < 17 || a.M > 64 || (a.N & 127) != 0 || (a.K & 511) != 0 || a.ldw != a.K) return false;
@@ -488,12 +485,10 @@ bool vz_wide_ok(const LinearArgs& a) {
     if (a.act == VZ_ACT_SWIGLU && a.bias) return false;
     if (((uintptr_t)a.bias & 15) != 0) return false;
     const int rbs = a.N >> 7;
-    const int P = wide_splits(a);
+    const int P = vz_wide_splits(a);
     const int mh = a.M <= 32 ? 2 : 4;
     return (size_t)rbs * P * NWV * mh * 1024 <= WIDE_PART_BYTES && rbs <= WIDE_TICKETS;
 }
-
-bool vz_wide_engine_ok(const LinearArgs& a) { return vz_wide_ok(a) && (a.W8t || pick_splits(a.N >> 7, a.K >> 9) == 1); }
 
 int vz_init_wide_kernels() {
     static VzDeviceOnce once;
@@ -544,7 +539,7 @@ int vz_launch_wide(const LinearArgs& a, hipStream_t s) {
     p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldc = a.ldc; p.ldr = a.ldr;
     p.act = a.act; p.out_fp32 = a.out_fp32;
     const int rbs = a.N >> 7, chunks = a.K >> 9;
-    p.P = wide_splits(a); p.cps = chunks / p.P;
+    p.P = vz_wide_splits(a); p.cps = chunks / p.P;
     p.part = nullptr; p.ticket = nullptr;
     if (p.P > 1) {
         void* part = nullptr; void* tick = nullptr; size_t hp = 0, ht = 0;

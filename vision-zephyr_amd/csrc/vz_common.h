@@ -139,7 +139,7 @@ struct LinearArgs {
     const float* bias;
     const bf16_t* residual; int ldr;
     int act; int out_fp32;
-    // optional fused RMSNorm prologue (GEMV path only): x <- bf16(norm_w * x * rsqrt(mean(x^2)+eps))
+    // optional fused RMSNorm prologue (GEMV and the <= 16-row MFMA weight stream; the tile GEMMs have none): x <- bf16(norm_w * x * rsqrt(mean(x^2)+eps))
     const float* norm_w; float norm_eps;
     // optional e4m3 copy of W (rows [N][ldw] bytes) + one fp32 power-of-two scale per row: GEMV path streams these instead
     const unsigned char* W8 = nullptr; const float* wscale = nullptr;
@@ -148,17 +148,16 @@ struct LinearArgs {
     const bf16_t* Wt = nullptr;
     // optional fragment-tiled copy of W8 (vz_launch_tile_weights_fp8: [N/16][K/64][64 lanes][16]): the 17..64-row e4m3 stream of gemm_wide.hip
     const unsigned char* W8t = nullptr;
-    // 17..64 rows may take the MFMA weight stream (rows = independent sequences of a decode batch).  Off for the engine's prefill /
-    // Q-Former linears: there a row's result must not depend on how many rows sit beside it (the tile GEMM's split-K is a
-    // function of N and K only; tests/test_stages_gpu.py::test_qformer), and 32 / 64 / 96 rows must all take the same kernel.
-    bool wide_ok = true;
+    // the rows are independent of each other: 17..64 of them may take the weight-stream kernels.  Set from LinCaller::rows by the route
+    // plan (linear_route.h), read by the kernels' eligibility checks.
+    bool rows_free = true;
     // 128^2 tile GEMM only: split-K factor to use instead of the batch-invariant default (0 = default).  A decode batch of 17..64 rows
     // (independent sequences, weight-stream bound) cuts K finer so that N / 128 column tiles fill the 256 CUs
     int splitk_hint = 0;
     // async error word of the caller (an engine's); nullptr = the launch stream's own (vz_op_async_error)
     int* err = nullptr;
 };
-int vz_launch_gemm(const LinearArgs& a, hipStream_t s);
+bool vz_gemm_use256(const LinearArgs& a);      // the 256^2 pipeline beats the 128^2 tiles on this shape (gemm.hip)
 int vz_launch_tile_weights(const bf16_t* W, int N, int K, int ldw, bf16_t* Wt, hipStream_t s);
 // gemm_fp8.hip: e4m3 x e4m3 MFMA GEMM (per-row power-of-two scales on both operands) + the activation quantiser
 struct Fp8LinearArgs {
@@ -174,7 +173,7 @@ int vz_launch_gemm_fp8(const Fp8LinearArgs& a, hipStream_t s);
 int vz_launch_gemm256_fp8(const Fp8LinearArgs& a, hipStream_t s);      // gemm256.hip's pipeline on e4m3 operands
 // gemm_wide.hip: 17..64 rows on the tiled weight copy, activations staged once per 128 weight rows (needs a.Wt, no fused norm)
 bool vz_wide_ok(const LinearArgs& a);
-bool vz_wide_engine_ok(const LinearArgs& a);     // the shapes an engine's decode step routes there (no K split)
+int vz_wide_splits(const LinearArgs& a);         // K splits a launch on these arguments would use (1 = none)
 int vz_launch_wide(const LinearArgs& a, hipStream_t s);
 int vz_launch_tile_weights_fp8(const unsigned char* W8, int N, int K, int ldw, unsigned char* W8t, hipStream_t s);
 int vz_wide_reserve(hipStream_t s);             // K-split scratch of a stream, allocated outside a capture
@@ -186,10 +185,12 @@ bool vz_gemv_ok(const LinearArgs& a);
 bool vz_skinny_ok(const LinearArgs& a);      // 2..16 rows: MFMA weight stream (gemm_skinny.hip)
 int vz_launch_skinny(const LinearArgs& a, hipStream_t s);
 int vz_init_skinny_kernels();
-extern int g_skinny_mode;
+extern int g_skinny_mode;                    // vz_tune_set(9, v): SkinnyMode (linear_route.h)
 bool vz_skinny_fused_norm_ok(const LinearArgs& a);
 int vz_init_gemv_kernels();
 void vz_set_gemv_variant(int v);
+// Profiling classes of vz_prof_enable / vz_prof_read
+enum { K_GEMM = 0, K_GEMV = 1, K_ATTN = 2, K_ATTN_DEC = 3, K_NORM = 4, K_OTHER = 5, K_FUSED = 6, K_COMM = 7 };
 // Profiling: when set, the next GEMM/GEMV launch is issued through hipExtLaunchKernelGGL with these events, which
 // the runtime stamps at the kernel's own start and end on the GPU (no launch gap inside the bracket).
 extern thread_local hipEvent_t g_vz_prof_start, g_vz_prof_stop;
@@ -217,11 +218,10 @@ int vz_launch_gemm256(const LinearArgs& a, hipStream_t s);
 int vz_init_gemm256_kernel();
 int vz_gemm256_async_error(hipStream_t s, int* err, bool reset_only);
 int vz_gemm256_corrupt_tickets(hipStream_t s, int tr, int arrive, int ready);
-void vz_set_gemm_choice(int v);
+void vz_set_gemm_choice(int v);  // 0 auto, 1 force 128x128, 2 force 256x256
 void vz_set_splitk_mode(int v);
 void vz_set_splitk_cap(int v);
-void vz_set_splitk_mid(int v);   // 0 auto, 1 force 128x128, 2 force 256x256
-int vz_launch_linear(const LinearArgs& a, hipStream_t s);  // picks by M
+void vz_set_splitk_mid(int v);   // 1: K slices for small grids with M > 512 (default), 0 off
 
 int vz_launch_layernorm(const bf16_t* x, int ldx, bf16_t* y, int ldy, const float* w, const float* b, int rows,
                         int cols, float eps, hipStream_t s);

@@ -57,6 +57,7 @@ SYMBOLS = {
     "vz_op_quant_rows_fp8": (_I, [_P, _I, _P, _I, _P, _I, _I, _P]),
     "vz_op_linear_fp8_mfma": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P]),
     "vz_op_linear_impl": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "vz_op_linear_route": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_uint, _I, _P, _P]),
     "vz_op_causal_lm_loss": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "vz_op_layernorm": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _F, _P]),
     "vz_op_rmsnorm": (_I, [_P, _I, _P, _I, _P, _I, _I, _F, _P]),
@@ -320,6 +321,20 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, bias=None
                                  ptr(bias), ptr(residual), 0 if residual is None else residual.stride(0), act, int(out_fp32),
                                  ptr(norm_w), float(norm_eps), stream_ptr(x.device)))
     return out
+
+
+LIN_ROUTES = ("GEMV", "SKINNY", "SKINNY_PERSIST", "SKINNY_WIDE", "WIDE_BF16", "WIDE_E4M3", "TILE128", "TILE256")
+ROUTE_WT, ROUTE_W8, ROUTE_W8T, ROUTE_NORM, ROUTE_BIAS, ROUTE_RESIDUAL, ROUTE_DECODE = 1, 2, 4, 8, 16, 32, 64
+LINEAR_ENGINE, LINEAR_OP, LINEAR_RMSNORM, LINEAR_TILED, LINEAR_TILED_FP8, LINEAR_IMPL = 0, 1, 2, 3, 4, 8
+
+
+def linear_route(M: int, N: int, K: int, lda: Optional[int] = None, ldw: Optional[int] = None, act: int = ACT_NONE, out_fp32=False,
+                 flags: int = 0, entry: int = LINEAR_ENGINE):
+    """(route name | "NONE", pre_norm, splitk_hint) of a linear of this shape under the current knobs; needs no GPU (vz_op_linear_route)."""
+    pre, sk = C.c_int(0), C.c_int(0)
+    r = lib().vz_op_linear_route(M, N, K, K if lda is None else lda, K if ldw is None else ldw, act, int(out_fp32), flags, entry,
+                                 C.byref(pre), C.byref(sk))
+    return (LIN_ROUTES[r] if 0 <= r < len(LIN_ROUTES) else "NONE"), bool(pre.value), sk.value
 
 
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor):
