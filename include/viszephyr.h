@@ -184,6 +184,51 @@ int vz_op_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const
 int vz_op_transpose(const void* d_src, long src_ld, void* d_dst, long dst_ld, int R, int C, vz_stream stream);
 int vz_op_colsum(const void* d_y, int ld, long rows, int cols, float* d_part, long part_floats, float* d_out, vz_stream stream);
 int vz_op_colsum_groups(long rows);
+/* The other kernels of the training step at op level (train.hip; the parity tests of tests/test_train_ops_gpu.py).  bf16 unless said otherwise;
+ * every launcher refuses null pointers, non-positive sizes and what its kernel cannot address (VZ_ERR_ARG), it never falls back.
+ *   transpose_batched  dst[o][i][c][col0 + r] = src[o][i][r][c] for o < n_outer, i < n_inner (element strides *_rs row, *_so outer, *_si inner):
+ *                      128- / 64-wide tiles when R, C, col0 and all strides are multiples of 8 and the bases 16-byte aligned, else 32 x 32
+ *   softmax_fwd        P[row][j] = softmax_j(scale S[row][j]) over the visible keys, exactly 0 elsewhere and in the padding up to ldp; S fp32;
+ *                      row = (b * H + h) * Sq + i; causal: key j <= i, window > 0: j > i - window; d_kv_len[b] (optional) caps the keys
+ *   softmax_bwd        dS = P (dP - sum_j P dP) scale, exactly 0 (and dP unread) where P == 0 and in the padding up to ldds; dP fp32
+ *   rmsnorm_bwd        dx = r (dy w - xh mean(dy w xh)) [+ dres], contiguous [rows, cols]; w fp32
+ *   layernorm_bwd      dx = rstd (g - mean g - xh mean(g xh)) [+ dres] (d_dx may be NULL), d_dw += sum_rows dy xh, d_db += sum_rows dy (fp32, fixed
+ *                      order); cols % 8 == 0, 16-byte-aligned rows; d_part >= vz_op_layernorm_bwd_scratch_floats(rows, cols) floats and ends
+ *                      with the (mean, rstd) pair of every row
+ *   gelu_* / swiglu_*  exact-erf GELU and silu(g) u on saved pre-activations and their derivatives; SwiGLU reads gu [rows, 2I] in the GEMM's
+ *                      interleaved column order [16 g | 16 u] (I % 16 == 0) and writes dgu in the same order
+ *   rope_bwd_assemble  fused-QKV gradient rows [Hq D | Hkv D | Hkv D] from dq [B*S,Hq,D] bf16 and dk, dv [B,Hkv,Sk_ld,D] fp32: Q and K parts rotated
+ *                      back by the angles of d_pos (tables [pos][D/2] fp32), V copied; D even
+ *   cross_entropy      row (b, s) against labels[b][s + 1]: d_loss_rows = lse - logit[target], d_dlogits (optional, leading dimension ldd >= V,
+ *                      padding zeroed) = (softmax - onehot) inv_n; a row whose target is < 0, >= V (torch would raise) or beyond the sequence
+ *                      is ignored: loss 0, zero gradient row
+ *   gather_rows_idx    dst[r] = src[idx[r]], zeros where idx[r] < 0 (cols % 8 == 0, 16-byte-aligned bases)
+ *   segment_sum_rows   dst[r][q] = sum over k < n_src with map[k] == r of src[k][q] (blocks of rows_per rows; fp32 sum, bf16 out)
+ *   acc_rows_f32       d_out[i] += sum_b src[b * stride + i] for i < rows * cols (fp32)
+ *   adamw              torch.optim.AdamW step t >= 1 on fp32 master / moments / gradient; writes the working copy (bf16 or fp32), clears d_g */
+int vz_op_transpose_batched(const void* d_src, long src_rs, long src_so, long src_si, void* d_dst, long dst_rs, long dst_so, long dst_si, int R, int C,
+                            int n_outer, int n_inner, int col0, vz_stream stream);
+int vz_op_softmax_fwd(const float* d_S, int lds, void* d_P, int ldp, long rows, int H, int Sq, int Sk, float scale, int causal, int window,
+                      const int* d_kv_len, vz_stream stream);
+int vz_op_softmax_bwd(const void* d_P, int ldp, const float* d_dP, int lddp, void* d_dS, int ldds, long rows, int Sk, float scale, vz_stream stream);
+int vz_op_rmsnorm_bwd(const void* d_x, const float* d_w, const void* d_dy, const void* d_dres, void* d_dx, long rows, int cols, float eps,
+                      vz_stream stream);
+long vz_op_layernorm_bwd_scratch_floats(long rows, int cols);
+int vz_op_layernorm_bwd(const void* d_x, const float* d_w, const void* d_dy, const void* d_dres, void* d_dx, float* d_part, long part_floats,
+                        float* d_dw, float* d_db, long rows, int cols, float eps, vz_stream stream);
+int vz_op_gelu_fwd(const void* d_h, void* d_y, long n, vz_stream stream);
+int vz_op_gelu_bwd(const void* d_h, const void* d_dy, void* d_dh, long n, vz_stream stream);
+int vz_op_swiglu_fwd(const void* d_gu, void* d_act, long rows, int I, vz_stream stream);
+int vz_op_swiglu_bwd(const void* d_gu, const void* d_dact, void* d_dgu, long rows, int I, vz_stream stream);
+int vz_op_rope_bwd_assemble(const void* d_dq, const float* d_dk, const float* d_dv, void* d_dqkv, const float* d_cos, const float* d_sin,
+                            const int* d_pos, int B, int S, int Hq, int Hkv, int head_dim, int Sk_ld, vz_stream stream);
+int vz_op_cross_entropy(const float* d_logits, int V, const int* d_labels, long rows, int S, float inv_n, float* d_loss_rows, void* d_dlogits, int ldd,
+                        vz_stream stream);
+int vz_op_gather_rows_idx(const void* d_src, const int* d_idx, void* d_dst, long rows, int cols, vz_stream stream);
+int vz_op_segment_sum_rows(const void* d_src, const int* d_map, int n_src, int rows_per, void* d_dst, int n_dst, int cols, vz_stream stream);
+int vz_op_acc_rows_f32(float* d_out, const void* d_src, int n_batches, long stride, int rows, int cols, vz_stream stream);
+int vz_op_adamw(float* d_p, float* d_m, float* d_v, float* d_g, void* d_work, int work_bf16, long n, float lr, float beta1, float beta2, float eps,
+                float weight_decay, int t, vz_stream stream);
 /* RoPE (rotate-half, hf:models/mistral/modeling_mistral.py:51-81) on the Q and K heads of a fused QKV row
  * [B*S, (Hq+2Hkv)*D] + append of K/V to the cache [B][Hkv][max_ctx][D].  d_pos / d_slot: int32 [B*S] position
  * id and cache slot of every token (slot < 0: token not cached).  d_q_out bf16 [B*S,Hq,D].  D = 128. */

@@ -223,6 +223,61 @@ extern "C" int vz_op_colsum(const void* y, int ld, long rows, int cols, float* p
     return vz_launch_colsum((const bf16_t*)y, ld, rows, cols, part, out, (hipStream_t)s);
 }
 extern "C" int vz_op_colsum_groups(long rows) { return vz_colsum_groups(rows); }
+// the remaining kernels of train.hip at op level (parity tests, tests/test_train_ops_gpu.py): thin casts, every check is the launcher's
+extern "C" int vz_op_transpose_batched(const void* src, long src_rs, long src_so, long src_si, void* dst, long dst_rs, long dst_so, long dst_si, int R,
+                                       int C, int n_outer, int n_inner, int col0, vz_stream s) {
+    return vz_launch_transpose((const bf16_t*)src, src_rs, src_so, src_si, (bf16_t*)dst, dst_rs, dst_so, dst_si, R, C, n_outer, n_inner, col0, (hipStream_t)s);
+}
+extern "C" int vz_op_softmax_fwd(const float* S, int lds, void* P, int ldp, long rows, int H, int Sq, int Sk, float scale, int causal, int window,
+                                 const int* kv_len, vz_stream s) {
+    return vz_launch_softmax_fwd(S, lds, (bf16_t*)P, ldp, rows, H, Sq, Sk, scale, causal, window, kv_len, (hipStream_t)s);
+}
+extern "C" int vz_op_softmax_bwd(const void* P, int ldp, const float* dP, int lddp, void* dS, int ldds, long rows, int Sk, float scale, vz_stream s) {
+    return vz_launch_softmax_bwd((const bf16_t*)P, ldp, dP, lddp, (bf16_t*)dS, ldds, rows, Sk, scale, (hipStream_t)s);
+}
+extern "C" int vz_op_rmsnorm_bwd(const void* x, const float* w, const void* dy, const void* dres, void* dx, long rows, int cols, float eps, vz_stream s) {
+    return vz_launch_rmsnorm_bwd((const bf16_t*)x, w, (const bf16_t*)dy, (const bf16_t*)dres, (bf16_t*)dx, rows, cols, eps, (hipStream_t)s);
+}
+extern "C" long vz_op_layernorm_bwd_scratch_floats(long rows, int cols) {
+    return rows > 0 && cols > 0 ? (long)vz_layernorm_bwd_scratch_floats(rows, cols) : 0;
+}
+extern "C" int vz_op_layernorm_bwd(const void* x, const float* w, const void* dy, const void* dres, void* dx, float* part, long part_floats, float* dw,
+                                   float* db, long rows, int cols, float eps, vz_stream s) {
+    VZ_CHECK_ARG(rows > 0 && cols > 0 && part_floats >= (long)vz_layernorm_bwd_scratch_floats(rows, cols), "layernorm_bwd: scratch of %ld floats is too small",
+                 part_floats);
+    return vz_launch_layernorm_bwd((const bf16_t*)x, w, (const bf16_t*)dy, (const bf16_t*)dres, (bf16_t*)dx, part, dw, db, rows, cols, eps, (hipStream_t)s);
+}
+extern "C" int vz_op_gelu_fwd(const void* h, void* y, long n, vz_stream s) { return vz_launch_gelu_fwd((const bf16_t*)h, (bf16_t*)y, n, (hipStream_t)s); }
+extern "C" int vz_op_gelu_bwd(const void* h, const void* dy, void* dh, long n, vz_stream s) {
+    return vz_launch_gelu_bwd((const bf16_t*)h, (const bf16_t*)dy, (bf16_t*)dh, n, (hipStream_t)s);
+}
+extern "C" int vz_op_swiglu_fwd(const void* gu, void* act, long rows, int I, vz_stream s) {
+    return vz_launch_swiglu_fwd((const bf16_t*)gu, (bf16_t*)act, rows, I, (hipStream_t)s);
+}
+extern "C" int vz_op_swiglu_bwd(const void* gu, const void* dact, void* dgu, long rows, int I, vz_stream s) {
+    return vz_launch_swiglu_bwd((const bf16_t*)gu, (const bf16_t*)dact, (bf16_t*)dgu, rows, I, (hipStream_t)s);
+}
+extern "C" int vz_op_rope_bwd_assemble(const void* dq, const float* dk, const float* dv, void* dqkv, const float* cosT, const float* sinT, const int* pos,
+                                       int B, int S, int Hq, int Hkv, int head_dim, int Sk_ld, vz_stream s) {
+    return vz_launch_rope_bwd_assemble((const bf16_t*)dq, dk, dv, (bf16_t*)dqkv, cosT, sinT, pos, B, S, Hq, Hkv, head_dim, Sk_ld, (hipStream_t)s);
+}
+extern "C" int vz_op_cross_entropy(const float* logits, int V, const int* labels, long rows, int S, float inv_n, float* loss_rows, void* dlogits, int ldd,
+                                   vz_stream s) {
+    return vz_launch_cross_entropy(logits, V, labels, rows, S, inv_n, loss_rows, (bf16_t*)dlogits, ldd, (hipStream_t)s);
+}
+extern "C" int vz_op_gather_rows_idx(const void* src, const int* idx, void* dst, long rows, int cols, vz_stream s) {
+    return vz_launch_gather_rows_idx((const bf16_t*)src, idx, (bf16_t*)dst, rows, cols, (hipStream_t)s);
+}
+extern "C" int vz_op_segment_sum_rows(const void* src, const int* map, int n_src, int rows_per, void* dst, int n_dst, int cols, vz_stream s) {
+    return vz_launch_segment_sum_rows((const bf16_t*)src, map, n_src, rows_per, (bf16_t*)dst, n_dst, cols, (hipStream_t)s);
+}
+extern "C" int vz_op_acc_rows_f32(float* out, const void* src, int n_batches, long stride, int rows, int cols, vz_stream s) {
+    return vz_launch_acc_rows_f32(out, (const bf16_t*)src, n_batches, stride, rows, cols, (hipStream_t)s);
+}
+extern "C" int vz_op_adamw(float* p, float* m, float* v, float* g, void* work, int work_bf16, long n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int t, vz_stream s) {
+    return vz_launch_adamw(p, m, v, g, work, work_bf16, n, lr, beta1, beta2, eps, weight_decay, t, (hipStream_t)s);
+}
 extern "C" int vz_op_attention_bwd(const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk, void* dv, int dkv_fp32, int B,
                                    int Sq, int Sk, int Hq, int Hkv, int head_dim, float scale, int causal, int window, const int* kv_len,
                                    float* ws, long ws_floats, vz_stream s) {

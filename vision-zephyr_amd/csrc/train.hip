@@ -551,13 +551,13 @@ int vz_launch_transpose(const bf16_t* src, long src_rs, long src_so, long src_si
 }
 int vz_launch_softmax_fwd(const float* S, int lds_, bf16_t* P, int ldp, long rows, int H, int Sq, int Sk, float scale, int causal, int window,
                           const int* kv_len, hipStream_t s) {
-    VZ_CHECK_ARG(S && P && rows > 0 && Sk <= lds_ && Sk <= ldp, "softmax_fwd: bad argument");
+    VZ_CHECK_ARG(S && P && rows > 0 && H > 0 && Sq > 0 && Sk > 0 && Sk <= lds_ && Sk <= ldp, "softmax_fwd: bad argument");
     hipLaunchKernelGGL(softmax_fwd_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, S, lds_, P, ldp, rows, H, Sq, Sk, scale, causal, window, kv_len);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
 int vz_launch_softmax_bwd(const bf16_t* P, int ldp, const float* dP, int lddp, bf16_t* dS, int ldds, long rows, int Sk, float scale, hipStream_t s) {
-    VZ_CHECK_ARG(P && dP && dS && rows > 0, "softmax_bwd: bad argument");
+    VZ_CHECK_ARG(P && dP && dS && rows > 0 && Sk > 0 && Sk <= ldp && Sk <= lddp && Sk <= ldds, "softmax_bwd: bad argument");
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, P, ldp, dP, lddp, dS, ldds, rows, Sk, scale);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -579,6 +579,7 @@ size_t vz_layernorm_bwd_scratch_floats(long rows, int cols) { return (size_t)vz_
 int vz_launch_layernorm_bwd(const bf16_t* x, const float* w, const bf16_t* dy, const bf16_t* dres, bf16_t* dx, float* part, float* dw, float* db,
                             long rows, int cols, float eps, hipStream_t s) {
     VZ_CHECK_ARG(x && w && dy && part && dw && db && rows > 0 && cols > 0 && (cols & 7) == 0, "layernorm_bwd: bad argument (cols %% 8)");
+    VZ_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx) & 15) == 0, "layernorm_bwd: x, dy, dres and dx must be 16-byte aligned");
     const int G = vz_layernorm_bwd_groups(rows);
     float* stats = part + (size_t)G * 2 * cols;
     hipLaunchKernelGGL(ln_bwd_dx_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, x, w, dy, dres, dx, stats, rows, cols, eps);
@@ -590,21 +591,26 @@ int vz_launch_layernorm_bwd(const bf16_t* x, const float* w, const bf16_t* dy, c
     return VZ_OK;
 }
 int vz_launch_gelu_fwd(const bf16_t* h, bf16_t* y, long n, hipStream_t s) {
+    VZ_CHECK_ARG(h && y && n > 0, "gelu_fwd: bad argument");
     hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, h, y, n);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
 int vz_launch_gelu_bwd(const bf16_t* h, const bf16_t* dy, bf16_t* dh, long n, hipStream_t s) {
+    VZ_CHECK_ARG(h && dy && dh && n > 0, "gelu_bwd: bad argument");
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, h, dy, dh, n);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
 int vz_launch_swiglu_fwd(const bf16_t* gu, bf16_t* act, long rows, int I, hipStream_t s) {
+    VZ_CHECK_ARG(gu && act && rows > 0 && I > 0, "swiglu_fwd: bad argument");
+    VZ_CHECK_ARG(I % 16 == 0, "swiglu_fwd: I %% 16");
     hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid_for(rows * I)), dim3(256), 0, s, gu, act, rows, I);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
 int vz_launch_swiglu_bwd(const bf16_t* gu, const bf16_t* dact, bf16_t* dgu, long rows, int I, hipStream_t s) {
+    VZ_CHECK_ARG(gu && dact && dgu && rows > 0 && I > 0, "swiglu_bwd: bad argument");
     VZ_CHECK_ARG(I % 16 == 0, "swiglu_bwd: I %% 16");
     hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(rows * I)), dim3(256), 0, s, gu, dact, dgu, rows, I);
     VZ_LAUNCH_CHECK();
@@ -612,6 +618,8 @@ int vz_launch_swiglu_bwd(const bf16_t* gu, const bf16_t* dact, bf16_t* dgu, long
 }
 int vz_launch_rope_bwd_assemble(const bf16_t* dq, const float* dk, const float* dv, bf16_t* dqkv, const float* cosT, const float* sinT, const int* pos,
                                 int B, int S, int Hq, int Hkv, int D, int Sk_ld, hipStream_t s) {
+    VZ_CHECK_ARG(dq && dk && dv && dqkv && cosT && sinT && pos && B > 0 && S > 0 && Hq > 0 && Hkv > 0 && D > 0 && Sk_ld >= S, "rope_bwd_assemble: bad argument");
+    VZ_CHECK_ARG(D % 2 == 0, "rope_bwd_assemble: odd head_dim %d", D);
     hipLaunchKernelGGL(rope_bwd_assemble_kernel, dim3(grid_for((long)B * S * (Hq + 2 * Hkv) * (D / 2))), dim3(256), 0, s, dq, dk, dv, dqkv, cosT, sinT,
                        pos, B, S, Hq, Hkv, D, Sk_ld);
     VZ_LAUNCH_CHECK();
@@ -619,7 +627,7 @@ int vz_launch_rope_bwd_assemble(const bf16_t* dq, const float* dk, const float* 
 }
 int vz_launch_cross_entropy(const float* logits, int V, const int* labels, long rows, int S, float inv_n, float* loss_rows, bf16_t* dlogits, int ldd,
                             hipStream_t s) {
-    VZ_CHECK_ARG(logits && labels && loss_rows && rows > 0 && (!dlogits || ldd >= V), "cross_entropy: bad argument");
+    VZ_CHECK_ARG(logits && labels && loss_rows && rows > 0 && rows <= INT_MAX && S > 0 && V > 0 && (!dlogits || ldd >= V), "cross_entropy: bad argument");
     hipLaunchKernelGGL(cross_entropy_kernel, dim3((int)rows), dim3(256), 0, s, logits, V, labels, S, inv_n, loss_rows, dlogits, ldd);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -627,7 +635,7 @@ int vz_launch_cross_entropy(const float* logits, int V, const int* labels, long 
 // hf:loss/loss_utils.py ForCausalLMLoss on fp32 logits [B, S, V] and labels [B, S] (ignore_index -100, shift by one, mean over
 // the valid targets): d_loss_rows = B * S floats of scratch, d_out[0] = loss, d_out[1] = number of valid targets
 int vz_launch_causal_lm_loss(const float* logits, int B, int S, int V, const int* labels, float* loss_rows, float* out, hipStream_t s) {
-    VZ_CHECK_ARG(logits && labels && loss_rows && out && B > 0 && S > 0 && V > 0, "causal_lm_loss: bad argument");
+    VZ_CHECK_ARG(logits && labels && loss_rows && out && B > 0 && S > 0 && V > 0 && (long)B * S <= INT_MAX, "causal_lm_loss: bad argument");
     const long rows = (long)B * S;
     hipLaunchKernelGGL(cross_entropy_kernel, dim3((int)rows), dim3(256), 0, s, logits, V, labels, S, 1.0f, loss_rows, (bf16_t*)nullptr, 0);
     VZ_LAUNCH_CHECK();
@@ -650,12 +658,15 @@ int vz_launch_colsum(const bf16_t* y, int ld, long rows, int cols, float* part, 
     return VZ_OK;
 }
 int vz_launch_gather_rows_idx(const bf16_t* src, const int* idx, bf16_t* dst, long rows, int cols, hipStream_t s) {
+    VZ_CHECK_ARG(src && idx && dst && rows > 0 && cols > 0, "gather_rows_idx: bad argument");
     VZ_CHECK_ARG(cols % 8 == 0, "gather_rows_idx: cols %% 8");
+    VZ_CHECK_ARG((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "gather_rows_idx: src and dst must be 16-byte aligned");
     hipLaunchKernelGGL(gather_rows_idx_kernel, dim3(grid_for(rows * (cols / 8))), dim3(256), 0, s, src, idx, dst, rows, cols);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
 int vz_launch_segment_sum_rows(const bf16_t* src, const int* map, int n_src, int rows_per, bf16_t* dst, int n_dst, int cols, hipStream_t s) {
+    VZ_CHECK_ARG(src && map && dst && n_src > 0 && rows_per > 0 && n_dst > 0 && cols > 0, "segment_sum_rows: bad argument");
     hipLaunchKernelGGL(segment_sum_rows_kernel, dim3(grid_for((long)n_dst * rows_per * cols)), dim3(256), 0, s, src, map, n_src, rows_per, dst, n_dst, cols);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -676,6 +687,7 @@ int vz_launch_bf16_to_f32(const bf16_t* x, float* y, long n, hipStream_t s) {
     return VZ_OK;
 }
 int vz_launch_acc_rows_f32(float* out, const bf16_t* src, int n_batches, long stride, int rows, int cols, hipStream_t s) {
+    VZ_CHECK_ARG(out && src && n_batches > 0 && stride >= 0 && rows > 0 && cols > 0, "acc_rows_f32: bad argument");
     hipLaunchKernelGGL(acc_rows_f32_kernel, dim3(grid_for((long)rows * cols)), dim3(256), 0, s, out, src, n_batches, stride, (long)rows * cols);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -688,7 +700,8 @@ int vz_launch_f32_to_bf16(const float* x, bf16_t* y, long n, hipStream_t s) {
 int vz_launch_adamw(float* p, float* m, float* v, float* g, void* work, int work_bf16, long n, float lr, float b1, float b2, float eps, float wd,
                     int t, hipStream_t s) {
     VZ_CHECK_ARG(p && m && v && g && work && n > 0 && t >= 1, "adamw: bad argument");
-    const float bc1 = 1.f - powf(b1, (float)t), bc2s = sqrtf(1.f - powf(b2, (float)t));
+    // in double, as torch.optim.AdamW does: 1 - b2^t cancels (t = 2: 0.002 out of 0.998), in fp32 that cost the step 1e-5 of its size
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2s = (float)sqrt(1.0 - pow((double)b2, (double)t));
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, m, v, g, work, work_bf16, n, lr, b1, b2, eps, wd, bc1, bc2s);
     VZ_LAUNCH_CHECK();
     return VZ_OK;

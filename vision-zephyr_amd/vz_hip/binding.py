@@ -139,6 +139,22 @@ SYMBOLS = {
     "vz_op_spec_accept": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "vz_op_spec_part_floats": (_L, [_I, _I, _I]),
     "vz_op_attention_verify": (_I, [_P] * 11 + [_I] * 8 + [_F, _P]),
+    "vz_op_transpose_batched": (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _I, _I, _P]),
+    "vz_op_softmax_fwd": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _F, _I, _I, _P, _P]),
+    "vz_op_softmax_bwd": (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _F, _P]),
+    "vz_op_rmsnorm_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
+    "vz_op_layernorm_bwd_scratch_floats": (_L, [_L, _I]),
+    "vz_op_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _F, _P]),
+    "vz_op_gelu_fwd": (_I, [_P, _P, _L, _P]),
+    "vz_op_gelu_bwd": (_I, [_P, _P, _P, _L, _P]),
+    "vz_op_swiglu_fwd": (_I, [_P, _P, _L, _I, _P]),
+    "vz_op_swiglu_bwd": (_I, [_P, _P, _P, _L, _I, _P]),
+    "vz_op_rope_bwd_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "vz_op_cross_entropy": (_I, [_P, _I, _P, _L, _I, _F, _P, _P, _I, _P]),
+    "vz_op_gather_rows_idx": (_I, [_P, _P, _P, _L, _I, _P]),
+    "vz_op_segment_sum_rows": (_I, [_P, _P, _I, _I, _P, _I, _I, _P]),
+    "vz_op_acc_rows_f32": (_I, [_P, _P, _I, _L, _I, _I, _P]),
+    "vz_op_adamw": (_I, [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -422,6 +438,124 @@ def colsum(y, out):
     part = torch.empty(lib().vz_op_colsum_groups(rows) * cols, dtype=torch.float32, device=y.device)
     check(lib().vz_op_colsum(ptr(y), y.stride(0), rows, cols, ptr(part), part.numel(), ptr(out), stream_ptr(y.device)))
     return out
+
+
+# ---- the kernels of the training step (train.hip) one by one: the wrappers type-check, allocate scratch and pass the caller's tensors through
+# as they are (outputs are the caller's, so a test can pre-fill them); eligibility is the launchers' business, a refusal raises ValueError ----
+def _bf(*ts):
+    for t in ts:
+        assert t is None or t.dtype == torch.bfloat16, "bf16 tensor expected"
+
+
+def _f32(*ts):
+    for t in ts:
+        assert t is None or t.dtype == torch.float32, "fp32 tensor expected"
+
+
+def _i32(*ts):
+    for t in ts:
+        assert t is None or t.dtype == torch.int32, "int32 tensor expected"
+
+
+def transpose_batched(src, src_rs, src_so, src_si, dst, dst_rs, dst_so, dst_si, R, C, n_outer, n_inner, col0):
+    """dst[o][i][c][col0 + r] = src[o][i][r][c] (vz_op_transpose_batched): src / dst are the bf16 base tensors, strides in elements"""
+    _need_cuda(src, dst)
+    _bf(src, dst)
+    check(lib().vz_op_transpose_batched(ptr(src), src_rs, src_so, src_si, ptr(dst), dst_rs, dst_so, dst_si, R, C, n_outer, n_inner, col0,
+                                        stream_ptr(src.device)))
+
+
+def softmax_fwd(S, P, rows, H, Sq, Sk, scale, causal=False, window=0, kv_len=None):
+    """P bf16 [rows, ldp] <- masked softmax of the fp32 scores S [rows, lds] (vz_op_softmax_fwd)"""
+    _need_cuda(S, P, kv_len)
+    _f32(S); _bf(P); _i32(kv_len)
+    check(lib().vz_op_softmax_fwd(ptr(S), S.stride(0), ptr(P), P.stride(0), rows, H, Sq, Sk, float(scale), int(causal), int(window), ptr(kv_len),
+                                  stream_ptr(S.device)))
+
+
+def softmax_bwd(P, dP, dS, rows, Sk, scale):
+    """dS bf16 [rows, ldds] <- P o (dP - sum P dP) scale (vz_op_softmax_bwd); P bf16 [rows, ldp], dP fp32 [rows, lddp]"""
+    _need_cuda(P, dP, dS)
+    _bf(P, dS); _f32(dP)
+    check(lib().vz_op_softmax_bwd(ptr(P), P.stride(0), ptr(dP), dP.stride(0), ptr(dS), dS.stride(0), rows, Sk, float(scale), stream_ptr(P.device)))
+
+
+def rmsnorm_bwd(x, w, dy, dres, dx, rows, cols, eps):
+    """dx <- RMSNorm backward of contiguous bf16 [rows, cols] (vz_op_rmsnorm_bwd); w fp32 [cols]; dres optional"""
+    _need_cuda(x, w, dy, dres, dx)
+    _bf(x, dy, dres, dx); _f32(w)
+    check(lib().vz_op_rmsnorm_bwd(ptr(x), ptr(w), ptr(dy), ptr(dres), ptr(dx), rows, cols, float(eps), stream_ptr(x.device)))
+
+
+def layernorm_bwd(x, w, dy, dres, dx, dw, db, rows, cols, eps):
+    """dx (or None) <- LayerNorm backward, dw / db fp32 [cols] += the parameter gradients (vz_op_layernorm_bwd); returns the fp32 [rows, 2]
+    (mean, rstd) statistics the kernels left at the end of their scratch"""
+    _need_cuda(x, w, dy, dres, dx, dw, db)
+    _bf(x, dy, dres, dx); _f32(w, dw, db)
+    part = torch.empty(max(int(lib().vz_op_layernorm_bwd_scratch_floats(rows, cols)), 1), dtype=torch.float32, device=x.device)
+    check(lib().vz_op_layernorm_bwd(ptr(x), ptr(w), ptr(dy), ptr(dres), ptr(dx), ptr(part), part.numel(), ptr(dw), ptr(db), rows, cols, float(eps),
+                                    stream_ptr(x.device)))
+    return part[part.numel() - 2 * rows:].view(rows, 2)
+
+
+def gelu_fwd(h, y, n):
+    _need_cuda(h, y); _bf(h, y)
+    check(lib().vz_op_gelu_fwd(ptr(h), ptr(y), n, stream_ptr(h.device)))
+
+
+def gelu_bwd(h, dy, dh, n):
+    _need_cuda(h, dy, dh); _bf(h, dy, dh)
+    check(lib().vz_op_gelu_bwd(ptr(h), ptr(dy), ptr(dh), n, stream_ptr(h.device)))
+
+
+def swiglu_fwd(gu, act, rows, I):
+    """act [rows, I] <- silu(g) u of gu [rows, 2I] in the interleaved [16 g | 16 u] column order (vz_op_swiglu_fwd)"""
+    _need_cuda(gu, act); _bf(gu, act)
+    check(lib().vz_op_swiglu_fwd(ptr(gu), ptr(act), rows, I, stream_ptr(gu.device)))
+
+
+def swiglu_bwd(gu, dact, dgu, rows, I):
+    _need_cuda(gu, dact, dgu); _bf(gu, dact, dgu)
+    check(lib().vz_op_swiglu_bwd(ptr(gu), ptr(dact), ptr(dgu), rows, I, stream_ptr(gu.device)))
+
+
+def rope_bwd_assemble(dq, dk, dv, dqkv, cos, sin, pos, B, S, Hq, Hkv, D, Sk_ld):
+    """dqkv bf16 [B*S, (Hq+2Hkv) D] <- dq bf16 [B*S,Hq,D], dk / dv fp32 [B,Hkv,Sk_ld,D]; cos / sin fp32 [n_pos, D/2]; pos int32 [B*S]"""
+    _need_cuda(dq, dk, dv, dqkv, cos, sin, pos)
+    _bf(dq, dqkv); _f32(dk, dv, cos, sin); _i32(pos)
+    check(lib().vz_op_rope_bwd_assemble(ptr(dq), ptr(dk), ptr(dv), ptr(dqkv), ptr(cos), ptr(sin), ptr(pos), B, S, Hq, Hkv, D, Sk_ld,
+                                        stream_ptr(dqkv.device)))
+
+
+def cross_entropy(logits, labels, rows, S, V, inv_n, loss_rows, dlogits=None):
+    """loss_rows fp32 [rows], dlogits bf16 [rows, ldd] (optional) <- fp32 logits [rows, V], int32 labels [rows] (vz_op_cross_entropy)"""
+    _need_cuda(logits, labels, loss_rows, dlogits)
+    _f32(logits, loss_rows); _i32(labels); _bf(dlogits)
+    check(lib().vz_op_cross_entropy(ptr(logits), V, ptr(labels), rows, S, float(inv_n), ptr(loss_rows), ptr(dlogits),
+                                    0 if dlogits is None else dlogits.stride(0), stream_ptr(logits.device)))
+
+
+def gather_rows_idx(src, idx, dst, rows, cols):
+    _need_cuda(src, idx, dst); _bf(src, dst); _i32(idx)
+    check(lib().vz_op_gather_rows_idx(ptr(src), ptr(idx), ptr(dst), rows, cols, stream_ptr(dst.device)))
+
+
+def segment_sum_rows(src, seg_map, n_src, rows_per, dst, n_dst, cols):
+    _need_cuda(src, seg_map, dst); _bf(src, dst); _i32(seg_map)
+    check(lib().vz_op_segment_sum_rows(ptr(src), ptr(seg_map), n_src, rows_per, ptr(dst), n_dst, cols, stream_ptr(dst.device)))
+
+
+def acc_rows_f32(out, src, n_batches, stride, rows, cols):
+    _need_cuda(out, src); _f32(out); _bf(src)
+    check(lib().vz_op_acc_rows_f32(ptr(out), ptr(src), n_batches, stride, rows, cols, stream_ptr(out.device)))
+
+
+def adamw(p, m, v, g, work, n, lr, beta1, beta2, eps, weight_decay, t):
+    """one fused AdamW step on fp32 p / m / v / g (vz_op_adamw); work: the bf16 or fp32 working copy"""
+    _need_cuda(p, m, v, g, work); _f32(p, m, v, g)
+    assert work is None or work.dtype in (torch.bfloat16, torch.float32)
+    check(lib().vz_op_adamw(ptr(p), ptr(m), ptr(v), ptr(g), ptr(work), int(work is not None and work.dtype == torch.bfloat16), n, float(lr),
+                            float(beta1), float(beta2), float(eps), float(weight_decay), int(t), stream_ptr(p.device)))
 
 
 def attention_bwd(q, k, v, dO, scale, causal=False, window=0, kv_len=None, dkv_fp32=True):
