@@ -520,6 +520,8 @@ int vz_op_anyres_tiles(const void* d_global, const void* d_resized, int nh, int 
  *                               DeepSpeed / HF Trainer reduce them) of the flat gradient arena, 256 MiB buckets; no-op without vz_train_comm_init
  *   vz_train_adamw_step         torch.optim.AdamW (no amsgrad) on every projector tensor; rewrites the engine's working copies,
  *                               clears the gradients
+ *   vz_train_ws_info            bytes of the activation + scratch arena, and the high-water mark of the last
+ *                               vz_train_stage1_accumulate in it (equal when that call sized the arena; smaller after a smaller shape)
  * ------------------------------------------------------------------------------------------ */
 typedef struct vz_trainer vz_trainer;
 int vz_train_create(vz_engine* e, vz_trainer** out, vz_stream stream);
@@ -536,6 +538,7 @@ int vz_train_zero_grad(vz_trainer* t, vz_stream stream);
 int vz_train_comm_init(vz_trainer* t, const char* id128, int rank, int world);
 int vz_train_allreduce(vz_trainer* t, vz_stream stream);
 int vz_train_adamw_step(vz_trainer* t, float lr, float beta1, float beta2, float eps, float weight_decay, vz_stream stream);
+int vz_train_ws_info(vz_trainer* t, size_t* arena_bytes, size_t* peak_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. Stage-2 LoRA finetune step (ref:script/finetune.sh; ref:vis_zephyr/train/train.py:224-243, 933-951)

@@ -186,6 +186,26 @@ def test_micro_batches_allreduce_adamw_and_second_step(env):
         tr.close()
 
 
+def test_arena_is_sized_by_the_step_itself_with_lora(env):
+    """tests/test_train_gpu.py::test_arena_is_sized_by_the_step_itself with the LoRA branches' buffers in the carving: the step that
+    sizes the arena uses all of it, the smaller micro-batches after it fit inside."""
+    ids, mask, lab, images = env["batch"]
+    tr = _trainer(env, 0.05)
+    try:
+        tr.init_lora(torch.Generator().manual_seed(1))
+        tr.zero_grad()
+        tr.forward_backward(ids, mask, lab, images)
+        arena, peak = tr.ws_info()
+        assert peak == arena > 0, (arena, peak)
+        tr.zero_grad()
+        tr.forward_backward(ids, mask, lab, images, micro_batch=1)
+        arena_mb, peak_mb = tr.ws_info()
+        assert arena_mb == arena and 0 < peak_mb <= arena, (arena_mb, peak_mb, arena)
+        record("stage2 step arena", batch_bytes=arena, last_micro_batch_bytes=peak_mb)
+    finally:
+        tr.close()
+
+
 def test_save_then_load_pretrained_model_round_trip(tmp_path, monkeypatch):
     """save() -> load_pretrained_model(dir, model_base=base, model_name="...-lora"), the reference's LoRA load mode, on a tiny on-disk
     base checkpoint (tests/test_loader_gpu.py::_write_checkpoint).  The reloaded model merges W += B A alpha / r of the saved factors

@@ -86,6 +86,65 @@ def test_loss_and_all_projector_gradients(env):
     record("stage1 gradients vs oracle", worst_tensor=worst[0], e_hip=worst[1], e_oracle_bf16=worst[2], loss_oracle_bf16=float(loss16))
 
 
+def test_arena_is_sized_by_the_step_itself(env):
+    """The step arena is sized by a launch-free pass of the step's own carving (train_engine.hip, "the step's memory"), so a call that
+    sizes the arena uses all of it: peak == arena.  A smaller shape after a larger one reuses the arena and reports the peak the same
+    shape has on a fresh sizing.  Shapes: the second sample alone as forward_backward(micro_batch=1) runs it (text padded to the
+    batch's longest), the Stage-1 batch, then the micro-batch-of-1 path, whose last call is that first shape again."""
+    from vz_hip.train import IMAGE_TOKEN_INDEX, Stage1Trainer
+    ids, mask, lab, images = env["batch"]
+    ids_cpu = ids.cpu().long()
+    Lmax = max(int((ids_cpu[b] != IMAGE_TOKEN_INDEX).sum()) for b in range(ids_cpu.shape[0]))
+    last = slice(ids_cpu.shape[0] - 1, ids_cpu.shape[0])
+    tr = Stage1Trainer(env["model"])          # its first step sizes the arena
+    try:
+        assert tr.ws_info() == (0, 0)
+        tr.zero_grad()
+        tr._accumulate(ids_cpu[last], mask.cpu().bool()[last], lab.cpu().long()[last], list(images)[last], 1.0, Lmax)
+        arena_one, peak_one = tr.ws_info()
+        assert peak_one == arena_one > 0, (arena_one, peak_one)
+        tr.zero_grad()
+        tr.forward_backward(ids, mask, lab, images)
+        arena, peak = tr.ws_info()
+        assert peak == arena > arena_one, (arena, peak, arena_one)
+        tr.zero_grad()
+        tr.forward_backward(ids, mask, lab, images, micro_batch=1)
+        arena_mb, peak_mb = tr.ws_info()
+        assert arena_mb == arena and peak_mb == peak_one <= arena, (arena_mb, peak_mb, arena, peak_one)
+        record("stage1 step arena", batch_bytes=arena, one_sample_bytes=arena_one)
+    finally:
+        tr.close()
+
+
+def test_attention_backward_routes_size_their_own_scratch(env):
+    """vz_tune_set(32, 0) sends the Zephyr layers' attention backward through the materialising batched-GEMM route, (32, 1) back to the
+    tile-resident one.  The route depends on the knob alone and each carves its own scratch: both steps succeed, the materialising
+    step's arena is at least the tile-resident step's need, and both losses are the fixture's."""
+    from vz_hip import binding as B
+    from vz_hip.train import Stage1Trainer
+    ids, mask, lab, images = env["batch"]
+    ref_loss = float(env["gold"]["loss"])
+    tr = Stage1Trainer(env["model"])
+    try:
+        B.check(B.lib().vz_tune_set(32, 0))
+        tr.zero_grad()
+        loss_gemm = tr.forward_backward(ids, mask, lab, images)
+        arena_gemm, peak_gemm = tr.ws_info()
+        B.check(B.lib().vz_tune_set(32, 1))
+        tr.zero_grad()
+        loss_flash = tr.forward_backward(ids, mask, lab, images)
+        arena_flash, peak_flash = tr.ws_info()
+    finally:
+        B.check(B.lib().vz_tune_set(32, 1))
+        tr.close()
+    record("stage1 attention backward routes", loss_batched_gemm=loss_gemm, loss_tile_resident=loss_flash, arena_batched_gemm=arena_gemm,
+           peak_tile_resident=peak_flash)
+    assert peak_gemm == arena_gemm > 0, (arena_gemm, peak_gemm)
+    assert arena_flash == arena_gemm and 0 < peak_flash <= arena_flash, (arena_flash, peak_flash, arena_gemm)
+    assert abs(loss_gemm - ref_loss) <= 2e-3 * ref_loss, (loss_gemm, ref_loss)
+    assert abs(loss_flash - ref_loss) <= 2e-3 * ref_loss, (loss_flash, ref_loss)
+
+
 def test_adamw_step_and_second_step(env):
     tr, T, sd = env["tr"], env["T"], env["sd"]
     ids, mask, lab, images = env["batch"]
@@ -220,7 +279,7 @@ def test_long_sequence_step_against_the_reference(env):
     """The length the reference trains up to (ref:script/pretrain.sh:44 --model_max_length 2048, with FlashAttention-2 and gradient
     checkpointing, ref:vis_zephyr/train/train_mem.py:8-10): one sample of 5 tiles + a 900-id caption -> S = 1059 spliced rows, against
     the reference's own loss.backward() at that length (tests/golden/stage1_long.npz, oracle/pin_train_step.py --long).  The attention
-    backward of the frozen Zephyr layers runs at S > 1024; its scratch is bounded per pass (train_engine.inc ATTN_BWD_CAP), not per batch."""
+    backward of the frozen Zephyr layers runs at S > 1024; its scratch is bounded per pass (train_engine.hip ATTN_BWD_CAP), not per batch."""
     import os
     from oracle import pin_train_step
     from util import GOLDEN

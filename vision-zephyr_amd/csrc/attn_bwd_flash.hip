@@ -16,7 +16,7 @@
 // A operand (the streamed tile transposed) comes from the row-major LDS image through ds_read_b64_tr_b16.  P and dS are rounded to bf16
 // once, before their products (as the materialising path's softmax kernels round them); statistics in fp32.
 // Cost: 5 + 4 tile products against the minimum of 5 (a single kernel needs float atomics for dQ); Stage-1 captions are ~200 tokens, the
-// form is there for the long-sequence case where the materialised P of train_engine.inc would be gigabytes per layer.
+// form is there for the long-sequence case where the materialised P of train_engine.hip would be gigabytes per layer.
 #include "vz_common.h"
 
 namespace {
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dkv_kernel(FlashBwdParams p)
 
 size_t vz_flash_bwd_scratch_bytes(int B, int Sq, int Hq) { return (size_t)2 * B * Hq * Sq * sizeof(float) + 256; }
 
-bool vz_flash_bwd_ok(const FlashBwdArgs& a) {
+bool vz_flash_bwd_ok(const AttnBwdArgs& a) {
     auto al = [](long v) { return (v & 7) == 0; };
     return a.D == FB_D && a.Hq % a.Hkv == 0 && a.Sq >= 1 && a.Sk >= 1 && al(a.q_bs) && al(a.q_ss) && al(a.q_hs) && al(a.k_bs) && al(a.k_ss) && al(a.k_hs) &&
            al(a.v_bs) && al(a.v_ss) && al(a.v_hs) && al(a.o_bs) && al(a.o_ss) && al(a.o_hs) && al(a.dq_bs) && al(a.dq_ss) && al(a.dq_hs) &&
@@ -339,7 +339,7 @@ bool vz_flash_bwd_ok(const FlashBwdArgs& a) {
            (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.dO | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15) == 0;
 }
 
-int vz_launch_flash_bwd(const FlashBwdArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s) {
+int vz_launch_flash_bwd(const AttnBwdArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s) {
     VZ_CHECK_ARG(a.q && a.k && a.v && a.dO && a.dq && a.dk && a.dv && scratch, "flash_bwd: null argument");
     VZ_CHECK_ARG(vz_flash_bwd_ok(a), "flash_bwd: head_dim 128, strides in multiples of 8 elements, 16-byte aligned tensors");
     VZ_CHECK_ARG(scratch_bytes >= vz_flash_bwd_scratch_bytes(a.B, a.Sq, a.Hq), "flash_bwd: scratch too small");

@@ -18,13 +18,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include <rccl/rccl.h>
-
-#include "linear_route.h"
+#include "engine_internal.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -283,7 +277,7 @@ extern "C" int vz_op_attention_bwd(const void* q, const void* k, const void* v, 
                                    float* ws, long ws_floats, vz_stream s) {
     VZ_CHECK_ARG(B > 0 && Sq > 0 && Sk > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "attention_bwd: bad shape");
     VZ_CHECK_ARG(head_dim == 128, "attention_bwd: the tile-resident backward is built for head_dim 128 (the Zephyr layers), got %d", head_dim);
-    FlashBwdArgs f;
+    AttnBwdArgs f;
     f.q = (const bf16_t*)q; f.k = (const bf16_t*)k; f.v = (const bf16_t*)v; f.dO = (const bf16_t*)dO; f.B = B; f.Sq = Sq; f.Sk = Sk; f.Hq = Hq; f.Hkv = Hkv; f.D = head_dim;
     const long A = (long)Hq * head_dim;
     f.q_bs = f.o_bs = f.dq_bs = (long)Sq * A; f.q_ss = f.o_ss = f.dq_ss = A; f.q_hs = f.o_hs = f.dq_hs = head_dim;
@@ -324,172 +318,7 @@ extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, v
 // ------------------------------------------------------------------------------------------------
 // engine
 // ------------------------------------------------------------------------------------------------
-struct Weight { const void* p; int dtype; long n; };
-
-// The weight tables the stages read, filled by vz_engine_finalize from the name registry.  A linear: the bf16 matrix [N, K] and its
-// fragment-tiled copy ("<name>t" if registered: the 2..64-row decode streams read it), the e4m3 copy + fp32 row scales (weight_fp8
-// engines only) and the e4m3 copy's tiled copy, the fp32 bias; null = absent.
-struct LinW {
-    const bf16_t* w = nullptr; const bf16_t* wt = nullptr;
-    const unsigned char* w8 = nullptr; const unsigned char* w8t = nullptr; const float* ws = nullptr;
-    const float* b = nullptr;
-};
-static LinW bare(const bf16_t* w) { LinW l; l.w = w; return l; }      // a matrix with nothing attached (trainer operands)
-// rows r0.. of a linear's matrix [., K] and bias (Q-Former block 0 runs the K|V rows of sa_in on their own)
-static LinW lin_rows(const LinW& l, long r0, int K) { LinW s = bare(l.w + r0 * K); s.b = l.b + r0; return s; }
-struct NormW { const float* w = nullptr; const float* b = nullptr; };      // LayerNorm scale + shift
-struct ClipLayerW { NormW ln1, ln2; LinW qkv, o, fc1, fc2; };
-struct QfBlockW { NormW n1, n2, n3; LinW sa_in, sa_out, ca_q, ca_kv, ca_out, ffn1, ffn2; };
-struct LlmLayerW { const float* in_norm = nullptr; const float* post_norm = nullptr; LinW qkv, o, gu, down; };
-struct TopW {
-    const bf16_t *clip_patch_w = nullptr, *clip_cls = nullptr, *clip_pos = nullptr; NormW clip_pre_ln;
-    const bf16_t* qf_queries = nullptr; NormW qf_pre_norm, qf_norm;
-    const bf16_t* embed = nullptr; const float* norm = nullptr; LinW lm_head;
-};
-
-static constexpr float ATTN_SCALE = 0.08838834764831845f;      // 128^-0.5 (vz_engine_create takes head_dim 128 only)
-
-// The device-side state of a decode batch of max_batch = mb rows: [cur | pos | slot | len], mb ints each (the row's input token, its
-// rotary position, the cache slot its keys are appended to, the keys it sees), then WORDS ints: the step index inside the running
-// vz_llm_decode_steps call, the draws since vz_llm_decode_begin, the sampler's seed (lo, hi).
-struct DecodeState {
-    static constexpr int ROW_ARRAYS = 4, WORDS = 4;
-    int *cur, *pos, *slot, *len, *step, *ctr; unsigned* seed;
-    static size_t ints(int mb) { return (size_t)ROW_ARRAYS * mb + WORDS; }
-};
-static DecodeState decode_state(int* base, int mb) {
-    int* w = base + DecodeState::ROW_ARRAYS * mb;
-    return {base, base + mb, base + 2 * mb, base + 3 * mb, w, w + 1, (unsigned*)(w + 2)};
-}
-
-// The tail of a decode step turns the logits into the next tokens: speculative verify > beam select > sampler > argmax, whichever
-// armed mode comes first (tail_kind).  The *Args of a mode are what its kernels take by value - a captured step freezes them, so
-// they go into the graph key as they are; they are laid out without padding (the key is compared with memcmp).
-enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC };
-struct SampleArgs { int top_k; float temp, top_p; };
-struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
-struct SpecArgs {
-    int *hist, *out, *ctl, *stats; const int* stream;
-    int ngram, source, budget, hist_cap, stats_cap, stream_len;
-    int key_bound;      // keys the steps being launched can reach (fixes the verify attention's absolute splits)
-    BeamEos eos;
-};
-// Everything decode_step_launch hands to a kernel that can differ between two vz_llm_decode_steps calls: a replayed graph is only
-// valid while all of it is unchanged.  The *Args of the modes that are off stay zero.
-struct DecodeGraphKey {
-    int B, n, nsplit, use_tok, kind; unsigned tune_epoch;
-    int* out; char* arena; int* ring; int ring_n;
-    SampleArgs samp; BeamArgs beam; SpecArgs spec;
-};
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) &&
-              sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
-
-// The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
-// scores | candidate tokens (BEAM_K per row)]
-static constexpr int BEAM_ROWS = 64, BEAM_K = 80;
-static constexpr size_t BEAM_INTS = 4 + 5 * (size_t)BEAM_ROWS + 2 * (size_t)BEAM_ROWS * BEAM_K;
-struct BeamView { float* score; int *parent, *base, *hidx, *re_base, *re_end; float* cand_s; int* cand_t; };
-static BeamView beam_view(int* d) {
-    const int R = BEAM_ROWS;
-    int* cand = d + 5 * R + 4;
-    return {(float*)d, d + R, d + 2 * R, d + 3 * R, d + 3 * R + 4, d + 4 * R + 4, (float*)cand, cand + R * BEAM_K};
-}
-
-struct vz_engine {
-    vz_config c;
-    // tensor parallelism: this rank's share of the 32 query heads / 8 KV heads / 14336 MLP columns and
-    // of the vocabulary (Vp = ceil(vocab / tp) rows of lm_head, zero padded); tp == 1: everything.
-    int tp = 1, rank = 0, Hq_l = 0, Hkv_l = 0, I_l = 0, Vp = 0;
-    ncclComm_t comm = nullptr;
-    // one-shot all-reduce of the decode step (comm_oneshot.hip): this rank's receive area, every rank's area (peer-mapped), sequence words
-    void* os_area = nullptr; void* os_areas[8] = {nullptr}; int os_ranks = 0; unsigned* os_seq = nullptr;
-    static constexpr int OS_MAX_ELEMS = 64 * 4096;       // up to 64 decode rows of hidden 4096
-    float* d_gather = nullptr;     // [tp][rows][Vp] all-gathered logits before the repack
-    size_t gather_floats = 0;
-    std::unordered_map<std::string, Weight> w;     // by name (vz_engine_set_weight); only vz_engine_finalize reads it
-    // resolved by vz_engine_finalize; valid while `finalized`
-    TopW top; std::vector<ClipLayerW> clip; std::vector<QfBlockW> qf; std::vector<LlmLayerW> llm;
-    bool qf_kv_contig = false;     // > 1 Q-Former block and their ca_kv weights + biases lie back to back (block-major)
-    bool finalized = false;
-    // rope
-    const float* cosT = nullptr; const float* sinT = nullptr; int rope_max = 0;
-    // workspace (one arena, carved per stage; stages never overlap in time on a stream)
-    char* arena = nullptr; size_t arena_bytes = 0;
-    // kv cache: [layer][2][B][Hkv][max_ctx][D]
-    bf16_t* kv = nullptr; size_t kv_layer_elems = 0;
-    // decode state (device)
-    int* d_state = nullptr;  // DecodeState of max_batch rows
-    int dec_B = 0;
-    int prefill_fp8 = 0;         // vz_engine_prefill_fp8: the Zephyr prefill linears run e4m3 x e4m3 on the scaled MFMA (weight_fp8 engines)
-    bool comm_graph_ok = true;   // RCCL collectives captured into the decode graph (cleared if a capture is refused -> eager steps)
-    int dec_len_max = 0;         // host-side bound on the longest row's visible keys (grows by one per launched step)
-    // host mirror of the device-side decode state, per row: keys visible to the NEXT step, its rotary position, and whether the
-    // row is parked (continuous batching: ctx_len 0, steps harmlessly, never checked against the capacity)
-    std::vector<int> h_len, h_pos; std::vector<char> h_parked;
-    // the step's tail (tail_kind): each mode is armed on its own, so disarming one falls back to the next armed one
-    // sampling (vz_llm_decode_sampling): ctr0 / seed = the draw counter and the key the next vz_llm_decode_begin uploads
-    struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f}; } samp;
-    // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)
-    struct { int on = 0; BeamArgs a{}; int* d = nullptr; } beam;
-    // prompt-lookup speculation (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0; base_len / base_pos = keys visible
-    // to row 0 and its position when the mode was armed
-    struct { int on = 0, R = 0, base_len = 0, base_pos = 0; SpecArgs a{}; } spec;
-    struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
-    hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
-    int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)
-    int dec_nsplit = 1;          // context splits of the decode attention for the steps being launched
-    float* d_logits = nullptr;   // [max_batch, vocab] fp32
-    bf16_t* d_xnorm = nullptr;   // [64, hidden]: normalised rows of a 5..16-row decode batch (the MFMA weight stream reads them from L2)
-    float* d_part = nullptr;     // decode attention partials
-    unsigned* d_ticket = nullptr; // arrival counters of the fused decode attention
-    unsigned* d_ao_done = nullptr; // arrival word of the attention + O-projection launch (attn_o_fused.hip); zeroed with the step counter
-    int* d_ferr = nullptr;        // raised by a bounded device-side wait that expired
-    int nsplit = 32;                 // upper bound: a split takes >= 128 keys, the splits beyond ceil(len / 128) leave at once
-    VzTokState* tok = nullptr;          // persistent decode-token kernel (decode_persist.hip): per-layer pointer table + hand-off vectors + arrival counters
-    bool use_tok = false;               // the steps being launched run on it (decided per vz_llm_decode_steps call)
-    int tok_poke_word = -1; unsigned tok_poke_value = 0;      // TEST HOOK (vz_test_persist_poke): applied once, behind the next counter reset
-    hipStream_t cap_stream = nullptr;   // stream capture is not allowed on the legacy null stream torch hands us
-    hipGraphExec_t dec_graph = nullptr; DecodeGraphKey dec_graph_key{};      // the captured step and what it froze
-    int* h_pinned = nullptr;     // pinned staging for small host->device uploads
-    size_t h_pinned_ints = 0;
-    // profiling
-    int prof_on = 0, prof_class = -1;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev; size_t prof_used = 0;
-};
-
 static TailKind tail_kind(const vz_engine* e) { return e->spec.on ? TAIL_SPEC : e->beam.on ? TAIL_BEAM : e->samp.on ? TAIL_SAMPLE : TAIL_GREEDY; }
-
-#define RC(expr) do { int _r = (expr); if (_r) return _r; } while (0)
-
-struct ProfScope {
-    vz_engine* e; hipStream_t s; bool on; size_t idx; bool ext = false;
-    ProfScope(vz_engine* e_, int klass, hipStream_t s_) : e(e_), s(s_), on(false), idx(0) {
-        if (e->prof_on && klass == e->prof_class) {
-            if (e->prof_used == e->prof_ev.size()) {
-                hipEvent_t a, b;
-                if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-                e->prof_ev.push_back({a, b});
-            }
-            idx = e->prof_used++;
-            on = true;
-            if (klass == K_GEMM || klass == K_GEMV) {      // stamped by the launch itself (kernel-only duration)
-                g_vz_prof_start = e->prof_ev[idx].first;
-                g_vz_prof_stop = e->prof_ev[idx].second;
-                ext = true;
-            } else {
-                (void)hipEventRecord(e->prof_ev[idx].first, s);
-            }
-        }
-    }
-    ~ProfScope() {
-        if (!on) return;
-        if (ext) {
-            if (g_vz_prof_start) { g_vz_prof_start = nullptr; g_vz_prof_stop = nullptr; e->prof_used--; }   // launch never happened
-        } else {
-            (void)hipEventRecord(e->prof_ev[idx].second, s);
-        }
-    }
-};
 
 // One linear C = epi(A . W^T + W.b) of the engine: the route follows the row count, the caller (decode = the rows are the independent
 // sequences of a decode step) and what finalize attached to W - vz_plan_linear picks the copy the kernel reads.
@@ -502,9 +331,9 @@ static LinearArgs linear_args(vz_engine* e, const bf16_t* A, int lda, const LinW
     return a;
 }
 static LinCaller linear_caller(const vz_engine* e, int decode) { return LinCaller{decode ? LIN_ROWS_DECODE : LIN_ROWS_COUPLED, e->c.hidden}; }
-static int linear(vz_engine* e, int decode, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M,
-                  int N, int K, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
-                  const float* norm_w = nullptr, float norm_eps = 0.f, int splitk_hint = 0) {
+int linear(vz_engine* e, int decode, const bf16_t* A, int lda, const LinW& W, int ldw, void* C, int ldc, int M,
+           int N, int K, const bf16_t* res, int ldr, int act, int out_fp32, hipStream_t s,
+           const float* norm_w, float norm_eps, int splitk_hint) {
     const LinearArgs a = linear_args(e, A, lda, W, ldw, C, ldc, M, N, K, res, ldr, act, out_fp32, norm_w, norm_eps, splitk_hint);
     const LinPlan p = vz_plan_linear(a, linear_caller(e, decode));
     e->last_stream = s;
@@ -512,20 +341,6 @@ static int linear(vz_engine* e, int decode, const bf16_t* A, int lda, const LinW
     ProfScope ps(e, p.klass, s);
     return vz_run_route(p, a, e->d_xnorm, s);
 }
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Carver {
-    char* base; size_t off, cap; bool ok;
-    Carver(char* b, size_t c) : base(b), off(0), cap(c), ok(true) {}
-    template <typename T> T* take(size_t n) {
-        off = align_up(off, 256);
-        T* p = (T*)(base + off);
-        off += n * sizeof(T);
-        if (off > cap) ok = false;
-        return p;
-    }
-};
 
 static int ensure_arena(vz_engine* e, size_t bytes) {
     if (bytes <= e->arena_bytes) return VZ_OK;
@@ -535,7 +350,7 @@ static int ensure_arena(vz_engine* e, size_t bytes) {
     return VZ_OK;
 }
 
-static int upload_ints(vz_engine* e, const int* h, size_t n, int* d, hipStream_t s) {
+int upload_ints(vz_engine* e, const int* h, size_t n, int* d, hipStream_t s) {
     // small host arrays go through a pinned staging buffer; the copy is enqueued on the stream
     if (n > e->h_pinned_ints) {
         if (e->h_pinned) { VZ_CHECK_HIP(hipStreamSynchronize(s)); VZ_CHECK_HIP(hipHostFree(e->h_pinned)); }
@@ -621,7 +436,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
 
 // The captured decode graph freezes every pointer its kernels take (weights, rotary tables, the gathered-logits buffer, the
 // workspace): whoever replaces one of them drops the graph, the next vz_llm_decode_steps captures again.
-static int drop_decode_graph(vz_engine* e) {
+int drop_decode_graph(vz_engine* e) {
     if (e->tok) {                               // the persistent kernel's layer table freezes weight / cache pointers too
         VZ_CHECK_HIP(hipDeviceSynchronize());
         vz_decode_persist_destroy(e->tok);
@@ -753,11 +568,6 @@ extern "C" int vz_engine_set_rope(vz_engine* e, const float* d_cos, const float*
     return VZ_OK;
 }
 
-#define NEED_READY()                                                                                         \
-    do {                                                                                                     \
-        if (!e || !e->finalized) { vz_set_error("engine not finalized (register every weight, then vz_engine_finalize)"); return VZ_ERR_STATE; } \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------
 // a8-a10: CLIP tower + fusion
 // ------------------------------------------------------------------------------------------------
@@ -831,8 +641,8 @@ extern "C" int vz_clip_fused_features(vz_engine* e, const void* d_images, int T,
 // a11: Q-Former
 // ------------------------------------------------------------------------------------------------
 static int g_qf_kv_all = 1;     // vz_tune_set(25, 0): the Q-Former's cross-attention K|V projections one block at a time (A/B)
-static int qf_attn(vz_engine* e, const bf16_t* q, long q_bs, long q_ss, const bf16_t* k, const bf16_t* v, long kv_bs, long kv_ss,
-                   bf16_t* o, int B, int Sq, int Sk, hipStream_t s, float* part = nullptr, size_t part_floats = 0) {
+int qf_attn(vz_engine* e, const bf16_t* q, long q_bs, long q_ss, const bf16_t* k, const bf16_t* v, long kv_bs, long kv_ss,
+            bf16_t* o, int B, int Sq, int Sk, hipStream_t s, float* part, size_t part_floats) {
     ProfScope ps(e, K_ATTN, s);
     AttnArgs a;
     a.part = part; a.part_floats = part_floats;
@@ -956,7 +766,6 @@ extern "C" int vz_embed_splice(vz_engine* e, const int* d_kind, const int* d_idx
 // dtypes, in-place buffers, stream order, the vocab-parallel gather + repack - runs on a single GPU.
 static int g_force_comm = 0;
 static int g_rope_in_attn = 1;     // vz_tune_set(33, 0): the prefill writes a rotated copy of Q (rope_kv_kernel) for the attention again (A/B; bit-identical)
-static int g_flash_bwd = 1;               // vz_tune_set(32, 0): the training step's head-128 attention backward through the materialising batched-GEMM route again (A/B; train_engine.inc)
 static unsigned g_tune_epoch = 0;  // successful vz_tune_set calls so far: a captured decode step froze the routes the knobs chose, so it is part of the graph key
 static int g_attn_o = 1;           // vz_tune_set(30, 0): batch-1 decode attention and O projection as two launches again (attn_o_fused.hip off)
 static int g_persist_decode = 0;   // vz_tune_set(28, 1): batch-1 decode steps as one resident grid per token (decode_persist.hip) instead of the launch chain.
@@ -1847,6 +1656,7 @@ extern "C" int vz_test_corrupt_streamk(vz_stream stream, int tile, int arrive, i
 
 extern int g_attn_o_delay;
 extern int g_skinny_even;
+extern int g_flash_bwd;      // train_engine.hip
 extern int g_gemm256_streamk, g_gemm256_skew, g_gemm256_stamps, g_gemm256_drain, g_gemm256_persist, g_attn_stamp_on, g_fp8_gemm_choice;
 int vz_gemm256_read_stamps(long long* host, int max_wgs, int* n_wgs);
 static int tune_set(int knob, int value) {
@@ -1905,4 +1715,3 @@ extern "C" int vz_prof_read(vz_engine* e, long* n_launches, double* total_ms) {
     return VZ_OK;
 }
 
-#include "train_engine.inc"

@@ -1,4 +1,4 @@
-// LoRA branch of the Stage-2 finetune step (train_engine.inc): the dropout of the adapter's input and the gate|up column permutation.
+// LoRA branch of the Stage-2 finetune step (train_engine.hip): the dropout of the adapter's input and the gate|up column permutation.
 //
 // peft's adapted linear (ref:vis_zephyr/train/train.py:933-951 -> peft `Linear.forward`): y = W x + scaling * B (A dropout(x)), each
 // adapted module with its own nn.Dropout(p).  The trainer never stores a mask: the kernel below writes

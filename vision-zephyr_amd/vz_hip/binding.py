@@ -125,6 +125,7 @@ SYMBOLS = {
     "vz_train_comm_init": (_I, [_P, C.c_char_p, _I, _I]),
     "vz_train_allreduce": (_I, [_P, _P]),
     "vz_train_adamw_step": (_I, [_P, _F, _F, _F, _F, _F, _P]),
+    "vz_train_ws_info": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vz_train_lora_enable": (_I, [_P, _I, _F, _F, C.c_ulonglong, _P]),
     "vz_train_lora_set_counter": (_I, [_P, _I, _L, _L]),
     "vz_op_lora_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _I, _I, C.c_ulonglong, _F, _F, _P]),

@@ -269,6 +269,12 @@ class Stage1Trainer:
     def _before_micro_batch(self, sample_base: int, row_stride: int):
         """hook of the Stage-2 trainer (the dropout counter); `row_stride` = the longest spliced row of the optimiser batch"""
 
+    def ws_info(self):
+        """(bytes of the activation + scratch arena, high-water mark of the last micro-batch in it)"""
+        arena, peak = C.c_size_t(), C.c_size_t()
+        B.check(self.lib.vz_train_ws_info(self.h, C.byref(arena), C.byref(peak)))
+        return arena.value, peak.value
+
     def all_reduce(self):
         B.check(self.lib.vz_train_allreduce(self.h, self.eng._s()))
 
