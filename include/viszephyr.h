@@ -163,7 +163,7 @@ int vz_op_attention(const void* d_q, const void* d_k, const void* d_v, void* d_o
  * head_dim 512 and many keys (the Q-Former cross-attention of ref:vis_zephyr/model/multimodal_projector/builder.py:34-39,
  * 32 queries x 576 visual tokens per tile) gives every 96 keys their own workgroup and merges the partial softmaxes in a second
  * kernel (the split depends on Sk only: a row's result is independent of B).  Needs B*Hq*ceil(Sk/96)*Sq*516 floats; with less
- * (or any other shape) it runs as vz_op_attention. */
+ * (or any other shape) it runs as vz_op_attention, which is this call without a workspace. */
 int vz_op_attention_split(const void* d_q, const void* d_k, const void* d_v, void* d_o,
                           int B, int Sq, int Sk, int Hq, int Hkv, int head_dim,
                           long q_bs, long q_ss, long q_hs, long k_bs, long k_ss, long k_hs,
@@ -288,6 +288,26 @@ typedef struct vz_config {
 
 int vz_engine_create(const vz_config* cfg, vz_engine** out);
 int vz_engine_destroy(vz_engine* e);
+
+/* The stage workspace.  An engine owns one arena; each stage call (CLIP, Q-Former, prefill, decode steps) lays its buffers out in it with
+ * that stage's one carving function, which also sizes the arena (it only grows).  vz_engine_ws_info: the arena's bytes and the mark the
+ * last stage call's carving reached (equal on the call that sized the arena).  vz_op_stage_ws_bytes: the bytes that carving takes for a
+ * call of the given dimensions on an engine of `cfg` - this rank's shard sizes, the current tune knobs - from the same function, without
+ * a device (works without a GPU); -1 for a config vz_engine_create or a shape the stage would refuse.
+ *   VZ_STAGE_CLIP     n = T tiles;  VZ_WS_CALLER_HIDDEN: the caller supplies d_hidden_dbg
+ *   VZ_STAGE_QFORMER  n = T, n2 = n_samples, Lmax;  VZ_WS_QF_KV_CONTIG: the blocks' ca_kv weights lie back to back (vz_qformer's layout
+ *                     hint), so the K|V projections of all blocks share one buffer unless the 2 GiB cap or knob 25 says otherwise
+ *   VZ_STAGE_PREFILL  n = B, n2 = S
+ *   VZ_STAGE_DECODE   n = B rows of the running batch;  VZ_WS_SPEC_TAIL: verify steps of the speculative tail (B = R in 2..8) */
+#define VZ_STAGE_CLIP 0
+#define VZ_STAGE_QFORMER 1
+#define VZ_STAGE_PREFILL 2
+#define VZ_STAGE_DECODE 3
+#define VZ_WS_CALLER_HIDDEN 1u
+#define VZ_WS_QF_KV_CONTIG 2u
+#define VZ_WS_SPEC_TAIL 4u
+int vz_engine_ws_info(vz_engine* e, size_t* arena_bytes, size_t* peak_bytes);
+long vz_op_stage_ws_bytes(const vz_config* cfg, int stage, int n, int n2, int Lmax, unsigned flags);
 
 /* Register one weight under its engine name (see vz_hip/weights.py for the packing from the
  * reference's state-dict keys).  dtype: 0 = bf16, 1 = fp32, 2 = u8 (e4m3 bytes).  The pointer is borrowed until destroy. */

@@ -1019,3 +1019,79 @@ def test_fp8_mfma_prefill_matches_quantized_oracle(env):
     assert torch.equal(again, bf16_prefill)
     del model
     torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------
+# the stage arena: one carving per stage sizes it and is used (csrc/engine.hip: carve_stage; tests/test_stage_ws_cpu.py holds the
+# carving functions themselves to the sizes the stages reserved before)
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small():
+    """a fresh small engine (the module's has run stages already): the smoke configuration, two cache rows"""
+    from vz_hip import synth
+    from vz_hip.engine import Engine
+    cfg = synth.ArchConfig(n_layers=1, vocab=4096)
+    eng = Engine(cfg, max_batch=2, max_ctx=128, max_tiles=2, max_text=16)
+    eng.load_synthetic(0)
+    eng.finalize()
+    yield dict(eng=eng, cfg=cfg, synth=synth)
+    eng.close()
+
+
+def _small_prefill(small, Bn, S):
+    """(B, S) text rows through the small engine's prefill: the last-position logits"""
+    eng, cfg, synth = small["eng"], small["cfg"], small["synth"]
+    ids = torch.stack([synth.synth_ids(S, cfg.vocab, image_pos=-1, seed=40 + b) for b in range(Bn)])
+    return eng.prefill(eng.embed_tokens(ids), [S] * Bn)[1]
+
+
+def test_arena_is_sized_by_the_stage_itself(small):
+    from vz_hip import binding as B
+    eng, cfg, synth = small["eng"], small["cfg"], small["synth"]
+    assert eng.ws_info() == (0, 0)
+    tiles = synth.synth_tiles(2, seed=1)
+    eng.clip_fused_features(tiles[:1])
+    arena1, peak1 = eng.ws_info()
+    assert peak1 == arena1 == eng.stage_ws_bytes(B.STAGE_CLIP, 1) > 0
+    feats = eng.clip_fused_features(tiles)
+    arena2, peak2 = eng.ws_info()
+    assert peak2 == arena2 == eng.stage_ws_bytes(B.STAGE_CLIP, 2) and arena2 > arena1
+    eng.clip_fused_features(tiles[:1])
+    assert eng.ws_info() == (arena2, peak1)                     # the arena only grows; the mark is the call's own
+    text = eng.embed_tokens(synth.synth_ids(8, cfg.vocab, image_pos=-1, seed=2)).unsqueeze(0)
+    eng.qformer(feats, text, [0, 0])
+    arena, peak = eng.ws_info()
+    assert peak == eng.stage_ws_bytes(B.STAGE_QFORMER, 2, 1, 8) and peak <= arena
+    last = _small_prefill(small, 2, 24)
+    arena, peak = eng.ws_info()
+    assert peak == eng.stage_ws_bytes(B.STAGE_PREFILL, 2, 24) and peak <= arena
+    eng.decode_begin(last.argmax(-1).to(torch.int32), [24, 24], [24, 24])
+    out = torch.empty(2, 2, dtype=torch.int32, device=eng.device)      # (a captured step freezes where its ids go)
+    eng.decode_steps(2, out=out)
+    arena, peak = eng.ws_info()
+    assert peak == eng.stage_ws_bytes(B.STAGE_DECODE, 2) and peak <= arena
+    assert eng.decode_mode()[0], "the steps were not captured"
+    captures = eng.decode_info()[1]
+    eng.decode_steps(2, out=out)                                # same shape, same bucket: the captured step is replayed
+    assert eng.decode_info()[1] == captures and eng.ws_info() == (arena, peak)
+    torch.cuda.synchronize()
+    eng.check_async()
+
+
+def test_speculative_tail_takes_one_q_rot_more(small):
+    from vz_hip import binding as B
+    eng, cfg = small["eng"], small["cfg"]
+    S, R = 24, 2
+    last = _small_prefill(small, 1, S)
+    first = int(last[0].argmax())
+    eng.decode_begin(torch.tensor([first, 0], dtype=torch.int32), [S, S + 1], [S, S + 1])
+    eng.set_spec(True, D=R - 1, history=[-1] * S + [first], budget=4)
+    try:
+        eng.decode_steps(1)
+        eng.check_async()
+        arena, peak = eng.ws_info()
+    finally:
+        eng.set_spec(False)
+    plain = eng.stage_ws_bytes(B.STAGE_DECODE, R)
+    assert peak == eng.stage_ws_bytes(B.STAGE_DECODE, R, flags=B.WS_SPEC_TAIL) and peak <= arena
+    assert peak - plain == R * cfg.n_heads * cfg.head_dim * 2       # q_rot: bf16 [R, Hq * D]

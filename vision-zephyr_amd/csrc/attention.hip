@@ -829,6 +829,21 @@ void vz_set_attn_version(int v) { g_attn_version = v; }
 int vz_attn_version() { return g_attn_version; }
 void vz_set_attn_split(int v) { g_attn_split = v; }
 
+// Key splits of an un-masked head_dim-512 launch with Sq query rows over Sk keys under knob 23 (1 = none).  A function of Sk alone
+// (three 32-key tiles per workgroup): a query row's result never depends on how many tiles or samples share the launch
+// (tests/test_stages_gpu.py::test_continuous_batching_matches_static_batches)
+static int split512(int Sq, int Sk) {
+    if (g_attn_split == 1 || Sq > 64) return 1;
+    const int ntiles = (Sk + 31) / 32;
+    const int nsplit = g_attn_split >= 2 ? std::min(g_attn_split, ntiles) : (ntiles >= 6 ? (ntiles + 2) / 3 : 1);
+    return nsplit <= 1024 ? nsplit : 1;
+}
+// fp32 scratch (AttnArgs::part) such a launch on (B, Hq, Sq, Sk) wants for its partial softmaxes; 0 = it would not split
+size_t vz_attn_split_floats(int B, int Hq, int Sq, int Sk) {
+    const int nsplit = split512(Sq, Sk);
+    return nsplit >= 2 ? (size_t)B * Hq * nsplit * Sq * (512 + 4) : 0;
+}
+
 int vz_init_attention_kernels() {
     static VzDeviceOnce once;
     if (!vz_device_first(once)) return VZ_OK;
@@ -867,14 +882,11 @@ int vz_launch_attention(const AttnArgs& a, hipStream_t s) {
     p.rope_cos = a.rope_cos; p.rope_sin = a.rope_sin; p.rope_pos = a.rope_pos;
     VZ_CHECK_ARG(!a.rope_cos || (a.head_dim == 128 && a.rope_sin && a.rope_pos && g_attn_version != 1 && !a.part),
                  "attention: RoPE at the query load is built into the head_dim-128 v2 kernel only");
-    if (a.head_dim == 512 && a.part && g_attn_split != 1 && a.Sq <= 64 && !a.causal && !a.kv_len) {
-        // the split is a function of Sk alone (three 32-key tiles per workgroup): a query row's result never depends on how many
-        // tiles or samples share the launch (tests/test_stages_gpu.py::test_continuous_batching_matches_static_batches)
-        const int ntiles = (a.Sk + 31) / 32;
-        const int nsplit = g_attn_split >= 2 ? std::min(g_attn_split, ntiles) : (ntiles >= 6 ? (ntiles + 2) / 3 : 1);
-        if (nsplit >= 2 && nsplit <= 1024 && (size_t)a.B * a.Hq * nsplit * a.Sq * (512 + 4) <= a.part_floats) {
+    if (a.head_dim == 512 && a.part && !a.causal && !a.kv_len) {
+        const size_t want = vz_attn_split_floats(a.B, a.Hq, a.Sq, a.Sk);
+        if (want && want <= a.part_floats) {          // (a smaller workspace: unsplit, the op-level contract of vz_op_attention_split)
             p.part = a.part;
-            return launch_flash_split<512, 32>(p, nsplit, s);
+            return launch_flash_split<512, 32>(p, split512(a.Sq, a.Sk), s);
         }
     }
     if (g_attn_version != 1) {

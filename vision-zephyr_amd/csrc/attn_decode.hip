@@ -31,6 +31,8 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(FusedParams p) {
 
 }  // namespace
 
+size_t vz_attn_decode_part_floats(int B, int Hkv, int nsplit) { return (size_t)B * Hkv * nsplit * attn_dec::PW; }
+
 int vz_launch_attn_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t s) {
     VZ_CHECK_ARG(a.D == D && a.Hq == a.Hkv * G, "attn_decode_fused: needs head_dim 128 and 4 query heads per KV head");
     VZ_CHECK_ARG(a.nsplit >= 1 && a.nsplit <= 64 && a.qkv && a.kc && a.vc && a.o && a.part && a.ticket, "attn_decode_fused: bad argument");

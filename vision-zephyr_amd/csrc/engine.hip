@@ -186,13 +186,9 @@ extern "C" int vz_op_attention(const void* q, const void* k, const void* v, void
                                int head_dim, long q_bs, long q_ss, long q_hs, long k_bs, long k_ss, long k_hs, long v_bs,
                                long v_ss, long v_hs, long o_bs, long o_ss, long o_hs, float scale, int causal, int q_pos0,
                                int window, const int* kv_len, vz_stream s) {
-    AttnArgs a;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
-    a.B = B; a.Sq = Sq; a.Sk = Sk; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = head_dim;
-    a.q_bs = q_bs; a.q_ss = q_ss; a.q_hs = q_hs; a.k_bs = k_bs; a.k_ss = k_ss; a.k_hs = k_hs;
-    a.v_bs = v_bs; a.v_ss = v_ss; a.v_hs = v_hs; a.o_bs = o_bs; a.o_ss = o_ss; a.o_hs = o_hs;
-    a.scale = scale; a.causal = causal; a.q_pos0 = q_pos0; a.window = window; a.kv_len = kv_len;
-    return vz_launch_attention(a, (hipStream_t)s);
+    // one fill for both forms: without a workspace the launcher never splits
+    return vz_op_attention_split(q, k, v, o, B, Sq, Sk, Hq, Hkv, head_dim, q_bs, q_ss, q_hs, k_bs, k_ss, k_hs, v_bs, v_ss, v_hs, o_bs, o_ss, o_hs, scale,
+                                 causal, q_pos0, window, kv_len, nullptr, 0, s);
 }
 extern "C" int vz_op_attention_split(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int Hq, int Hkv,
                                      int head_dim, long q_bs, long q_ss, long q_hs, long k_bs, long k_ss, long k_hs, long v_bs,
@@ -350,6 +346,20 @@ static int ensure_arena(vz_engine* e, size_t bytes) {
     return VZ_OK;
 }
 
+// A stage's workspace: its ONE carve function (carve_clip, carve_qformer, carve_prefill, carve_decode below; each takes dimensions, not
+// the engine, so vz_op_stage_ws_bytes asks the same function without a device) sizes the arena over a null base and then lays out the
+// real one; the mark it reaches is the stage's need (vz_engine_ws_info).
+template <typename Ws, typename Carve> static int carve_stage(vz_engine* e, const char* stage, Carve carve, Ws* ws) {
+    Carver dry(nullptr, ~(size_t)0);
+    carve(dry);
+    RC(ensure_arena(e, dry.off));
+    Carver m(e->arena, e->arena_bytes);
+    *ws = carve(m);
+    e->arena_peak = m.off;
+    if (!m.ok || m.off != dry.off) { vz_set_error("%s: the carving took %zu bytes of the arena, its sizing pass %zu (internal sizing error)", stage, m.off, dry.off); return VZ_ERR_STATE; }
+    return VZ_OK;
+}
+
 int upload_ints(vz_engine* e, const int* h, size_t n, int* d, hipStream_t s) {
     // small host arrays go through a pinned staging buffer; the copy is enqueued on the stream
     if (n > e->h_pinned_ints) {
@@ -364,9 +374,11 @@ int upload_ints(vz_engine* e, const int* h, size_t n, int* d, hipStream_t s) {
     return VZ_OK;
 }
 
-extern "C" int vz_engine_create(const vz_config* cfg, vz_engine** out) {
-    VZ_CHECK_ARG(cfg && out, "engine_create: null argument");
-    const vz_config& c = *cfg;
+// this rank's share of the query heads / KV heads / MLP columns (tp_size 1: everything)
+struct Shard { int Hq, Hkv, I; };
+static Shard shard_of(const vz_config& c) { return {c.n_heads / c.tp_size, c.n_kv_heads / c.tp_size, c.inter / c.tp_size}; }
+
+static int check_config(const vz_config& c) {
     VZ_CHECK_ARG(c.head_dim == 128 && c.hidden % 512 == 0 && c.inter % 512 == 0 && c.n_heads % c.n_kv_heads == 0 &&
                      c.n_heads * c.head_dim == c.hidden, "engine_create: unsupported Zephyr geometry");
     VZ_CHECK_ARG(c.clip_hidden % 512 == 0 && c.clip_hidden / c.clip_heads == 64 && c.clip_image % c.clip_patch == 0,
@@ -381,17 +393,28 @@ extern "C" int vz_engine_create(const vz_config* cfg, vz_engine** out) {
     VZ_CHECK_ARG(c.n_kv_heads % c.tp_size == 0 && c.n_heads % c.tp_size == 0 && (c.inter / c.tp_size) % 64 == 0 && c.inter % c.tp_size == 0,
                  "engine_create: tp_size %d must divide the KV heads (%d) and leave MLP shards that are multiples of 64", c.tp_size, c.n_kv_heads);
     VZ_CHECK_ARG((c.n_heads / c.tp_size) == 4 * (c.n_kv_heads / c.tp_size), "engine_create: 4 query heads per KV head expected");
+    return VZ_OK;
+}
+
+extern "C" int vz_engine_create(const vz_config* cfg, vz_engine** out) {
+    VZ_CHECK_ARG(cfg && out, "engine_create: null argument");
+    const vz_config& c = *cfg;
+    RC(check_config(c));
     { int r = vz_init_gemm_kernels(); if (r) return r; r = vz_init_attention_kernels(); if (r) return r; }
     vz_engine* e = new vz_engine();
     e->c = c;
     e->tp = c.tp_size; e->rank = c.tp_rank;
-    e->Hq_l = c.n_heads / c.tp_size; e->Hkv_l = c.n_kv_heads / c.tp_size; e->I_l = c.inter / c.tp_size;
+    const Shard sh = shard_of(c);
+    e->Hq_l = sh.Hq; e->Hkv_l = sh.Hkv; e->I_l = sh.I;
     e->Vp = (c.vocab + c.tp_size - 1) / c.tp_size;
     e->kv_layer_elems = (size_t)2 * c.max_batch * e->Hkv_l * c.max_ctx * c.head_dim;
     hipError_t er = hipMalloc((void**)&e->kv, e->kv_layer_elems * c.n_layers * sizeof(bf16_t));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_state, DecodeState::ints(c.max_batch) * sizeof(int));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_logits, (size_t)c.max_batch * e->Vp * e->tp * sizeof(float));
-    if (er == hipSuccess) er = hipMalloc((void**)&e->d_part, (size_t)c.max_batch * e->Hkv_l * 64 * (4 * 128 + 32) * sizeof(float));
+    // the partials of whichever decode attention runs: the fused step's records at up to 64 context splits (knob 10; attn_o_fused.hip and
+    // decode_persist.hip run the same body on the same records), or the speculative tail's verify attention over its <= 8 rows
+    const size_t part_floats = std::max(vz_attn_decode_part_floats(c.max_batch, e->Hkv_l, 64), vz_spec_part_floats(std::min(8, c.max_batch), e->Hkv_l, e->nsplit));
+    if (er == hipSuccess) er = hipMalloc((void**)&e->d_part, part_floats * sizeof(float));
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_ticket, 4096);
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_xnorm, (size_t)64 * c.hidden * sizeof(bf16_t));
     if (er == hipSuccess) er = hipMemset(e->d_ticket, 0, 4096);
@@ -571,32 +594,35 @@ extern "C" int vz_engine_set_rope(vz_engine* e, const float* d_cos, const float*
 // ------------------------------------------------------------------------------------------------
 // a8-a10: CLIP tower + fusion
 // ------------------------------------------------------------------------------------------------
+static int clip_tokens(const vz_config& c) { return (c.clip_image / c.clip_patch) * (c.clip_image / c.clip_patch) + 1; }
+static bool clip_shape_ok(const vz_config& c, int T) { return T >= 1 && T <= c.max_tiles; }
+struct ClipWs { bf16_t *col, *pe, *hs, *y, *qkv, *att, *mlp; };
+// own_hs = false: the caller supplies the buffer of every layer's hidden states (d_hidden_dbg)
+static ClipWs carve_clip(Carver& m, const vz_config& c, int T, bool own_hs) {
+    const size_t P = clip_tokens(c) - 1, hs_layer = (size_t)T * (P + 1) * c.clip_hidden;
+    ClipWs w;
+    w.col = m.take<bf16_t>((size_t)T * P * kpad_patch(c));
+    w.pe = m.take<bf16_t>((size_t)T * P * c.clip_hidden);
+    w.hs = own_hs ? m.take<bf16_t>(hs_layer * (c.clip_layers + 1)) : nullptr;
+    w.y = m.take<bf16_t>(hs_layer);
+    w.qkv = m.take<bf16_t>(hs_layer * 3);
+    w.att = m.take<bf16_t>(hs_layer);
+    w.mlp = m.take<bf16_t>((size_t)T * (P + 1) * c.clip_inter);
+    return w;
+}
+
 extern "C" int vz_clip_fused_features(vz_engine* e, const void* d_images, int T, void* d_out, void* d_hidden_dbg,
                                       vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
     hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(d_images && d_out && T >= 1 && T <= c.max_tiles, "clip: T=%d outside [1,%d]", T, c.max_tiles);
-    const int C = c.clip_hidden, g = c.clip_image / c.clip_patch, P = g * g, tokens = P + 1, kpad = kpad_patch(c);
+    VZ_CHECK_ARG(d_images && d_out && clip_shape_ok(c, T), "clip: T=%d outside [1,%d]", T, c.max_tiles);
+    const int C = c.clip_hidden, tokens = clip_tokens(c), P = tokens - 1, kpad = kpad_patch(c);
     const int L = c.clip_layers, rows = T * tokens;
     const size_t hs_layer = (size_t)rows * C;
-    size_t need = 0;
-    {
-        Carver m(nullptr, ~(size_t)0);
-        m.take<bf16_t>((size_t)T * P * kpad); m.take<bf16_t>((size_t)T * P * C);
-        if (!d_hidden_dbg) m.take<bf16_t>(hs_layer * (L + 1));
-        m.take<bf16_t>(hs_layer); m.take<bf16_t>(hs_layer * 3); m.take<bf16_t>(hs_layer); m.take<bf16_t>((size_t)rows * c.clip_inter);
-        need = m.off + 256;
-    }
-    RC(ensure_arena(e, need));
-    Carver m(e->arena, e->arena_bytes);
-    bf16_t* col = m.take<bf16_t>((size_t)T * P * kpad);
-    bf16_t* pe = m.take<bf16_t>((size_t)T * P * C);
-    bf16_t* hs = d_hidden_dbg ? (bf16_t*)d_hidden_dbg : m.take<bf16_t>(hs_layer * (L + 1));
-    bf16_t* y = m.take<bf16_t>(hs_layer);
-    bf16_t* qkv = m.take<bf16_t>(hs_layer * 3);
-    bf16_t* att = m.take<bf16_t>(hs_layer);
-    bf16_t* mlp = m.take<bf16_t>((size_t)rows * c.clip_inter);
+    ClipWs w;
+    RC(carve_stage(e, "clip", [&](Carver& m) { return carve_clip(m, c, T, !d_hidden_dbg); }, &w));
+    bf16_t *col = w.col, *pe = w.pe, *hs = d_hidden_dbg ? (bf16_t*)d_hidden_dbg : w.hs, *y = w.y, *qkv = w.qkv, *att = w.att, *mlp = w.mlp;
     const TopW& t = e->top;
     {
         ProfScope ps(e, K_OTHER, s);
@@ -655,6 +681,40 @@ int qf_attn(vz_engine* e, const bf16_t* q, long q_bs, long q_ss, const bf16_t* k
     return vz_launch_attention(a, s);
 }
 
+static int qf_visual_tokens(const vz_config& c) { return clip_tokens(c) - (c.clip_keep_cls ? 0 : 1); }      // per tile
+static bool qf_shape_ok(const vz_config& c, int T, int n_samples, int Lmax) {
+    return T >= 1 && T <= c.max_tiles && Lmax >= 0 && Lmax <= c.max_text && n_samples >= 1 && n_samples <= T;
+}
+// The cross-attention K|V projections of all blocks read the same pre-normed features.  When their weights (and biases) lie back
+// to back in memory (`contig` = qf_kv_contig) they run as ONE product over N = blocks * 2H: 256 column tiles per row tile = whole residency
+// rounds of the 256^2 kernel, no stream-K tail (8 x 217 us -> one launch).  The [T * P, blocks * 2H] result is capped at 2 GiB;
+// larger tile batches fill the chip per block anyway.
+static bool qf_kv_all(const vz_config& c, int T, bool contig) {
+    return contig && (size_t)T * qf_visual_tokens(c) * c.qf_blocks * 2 * c.hidden * sizeof(bf16_t) <= ((size_t)2 << 30) && g_qf_kv_all;
+}
+struct QfWs { bf16_t *fn, *ckv, *x0, *y0, *kv0, *q0, *a0, *xs, *x, *y, *qkv, *att, *ff; float* part; size_t part_floats; };
+static QfWs carve_qformer(Carver& m, const vz_config& c, int T, int n_samples, int Lmax, bool kv_all) {
+    const size_t H = c.hidden, NQ = c.qf_queries, P = qf_visual_tokens(c), N0 = NQ + Lmax, R = (size_t)T * NQ;
+    QfWs w;
+    w.fn = m.take<bf16_t>((size_t)T * P * c.qf_kv_dim);                               // pre_norm(features)
+    w.ckv = m.take<bf16_t>((size_t)T * P * (kv_all ? c.qf_blocks : 1) * 2 * H);        // cross-attention K|V of the current block (kv_all: of every block)
+    w.x0 = m.take<bf16_t>((size_t)n_samples * N0 * H);                                // [queries ; text] per sample
+    w.y0 = m.take<bf16_t>((size_t)n_samples * N0 * H);
+    w.kv0 = m.take<bf16_t>((size_t)n_samples * N0 * 2 * H);
+    w.q0 = m.take<bf16_t>(NQ * H);
+    w.a0 = m.take<bf16_t>((size_t)n_samples * NQ * H);
+    w.xs = m.take<bf16_t>((size_t)n_samples * NQ * H);
+    w.x = m.take<bf16_t>(R * H);                                                      // the query rows in flight after block 0's self-attention
+    w.y = m.take<bf16_t>(R * H);
+    w.qkv = m.take<bf16_t>(R * 3 * H);
+    w.att = m.take<bf16_t>(R * H);
+    w.ff = m.take<bf16_t>(R * 2 * H);
+    // key-split partials: what the launcher asks for the cross-attention over P keys and for block 0's self-attention over [queries ; text]
+    w.part_floats = std::max(vz_attn_split_floats(T, c.qf_heads, (int)NQ, (int)P), vz_attn_split_floats(n_samples, c.qf_heads, (int)NQ, (int)N0));
+    w.part = m.take<float>(w.part_floats);
+    return w;
+}
+
 extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* d_text, int n_samples, int Lmax,
                           const int* h_tile_sample, void* d_out, vz_stream stream) {
     NEED_READY();
@@ -662,47 +722,16 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_feats && d_out && T >= 1 && T <= c.max_tiles, "qformer: T=%d outside [1,%d]", T, c.max_tiles);
     VZ_CHECK_ARG(Lmax >= 0 && Lmax <= c.max_text, "qformer: Lmax=%d outside [0,%d]", Lmax, c.max_text);
-    VZ_CHECK_ARG(n_samples >= 1 && n_samples <= T && h_tile_sample && (Lmax == 0 || d_text), "qformer: bad sample map");
+    VZ_CHECK_ARG(qf_shape_ok(c, T, n_samples, Lmax) && h_tile_sample && (Lmax == 0 || d_text), "qformer: bad sample map");
     for (int t = 0; t < T; ++t) VZ_CHECK_ARG(h_tile_sample[t] >= 0 && h_tile_sample[t] < n_samples, "qformer: tile_sample[%d] out of range", t);
     const int H = c.hidden, NQ = c.qf_queries, KD = c.qf_kv_dim;
-    const int P = (c.clip_image / c.clip_patch) * (c.clip_image / c.clip_patch) + (c.clip_keep_cls ? 1 : 0);   // visual tokens per tile
-    const int N0 = NQ + Lmax, FF = 2 * H;
+    const int P = qf_visual_tokens(c), N0 = NQ + Lmax, FF = 2 * H;
     const size_t R = (size_t)T * NQ;  // query rows in flight after block 0's self-attention
-    // The cross-attention K|V projections of all blocks read the same pre-normed features.  When their weights (and biases) lie back
-    // to back in memory (qf_kv_contig) they run as ONE product over N = blocks * 2H: 256 column tiles per row tile = whole residency
-    // rounds of the 256^2 kernel, no stream-K tail (8 x 217 us -> one launch).  The [T * P, blocks * 2H] result is capped at 2 GiB;
-    // larger tile batches fill the chip per block anyway.
-    const int nb = c.qf_blocks;
-    const bool kv_all = e->qf_kv_contig && (size_t)T * P * nb * 2 * H * sizeof(bf16_t) <= ((size_t)2 << 30) && g_qf_kv_all;
-    const int kv_ld = kv_all ? nb * 2 * H : 2 * H;
-    size_t need;
-    {
-        Carver m(nullptr, ~(size_t)0);
-        m.take<bf16_t>((size_t)T * P * KD); m.take<bf16_t>((size_t)T * P * kv_ld);
-        m.take<bf16_t>((size_t)n_samples * N0 * H); m.take<bf16_t>((size_t)n_samples * N0 * H); m.take<bf16_t>((size_t)n_samples * N0 * 2 * H);
-        m.take<bf16_t>((size_t)NQ * H); m.take<bf16_t>((size_t)n_samples * NQ * H); m.take<bf16_t>((size_t)n_samples * NQ * H);
-        m.take<bf16_t>(R * H); m.take<bf16_t>(R * H); m.take<bf16_t>(R * 3 * H); m.take<bf16_t>(R * H); m.take<bf16_t>(R * FF);
-        m.take<float>(std::max((size_t)T * ((P + 95) / 96), (size_t)n_samples * ((N0 + 95) / 96)) * c.qf_heads * NQ * (512 + 4));
-        need = m.off + 256;
-    }
-    RC(ensure_arena(e, need));
-    Carver m(e->arena, e->arena_bytes);
-    bf16_t* fn = m.take<bf16_t>((size_t)T * P * KD);            // pre_norm(features)
-    bf16_t* ckv = m.take<bf16_t>((size_t)T * P * kv_ld);        // cross-attention K|V of the current block (kv_all: of every block)
-    bf16_t* x0 = m.take<bf16_t>((size_t)n_samples * N0 * H);    // [queries ; text] per sample
-    bf16_t* y0 = m.take<bf16_t>((size_t)n_samples * N0 * H);
-    bf16_t* kv0 = m.take<bf16_t>((size_t)n_samples * N0 * 2 * H);
-    bf16_t* q0 = m.take<bf16_t>((size_t)NQ * H);
-    bf16_t* a0 = m.take<bf16_t>((size_t)n_samples * NQ * H);
-    bf16_t* xs = m.take<bf16_t>((size_t)n_samples * NQ * H);
-    bf16_t* x = m.take<bf16_t>(R * H);
-    bf16_t* y = m.take<bf16_t>(R * H);
-    bf16_t* qkv = m.take<bf16_t>(R * 3 * H);
-    bf16_t* att = m.take<bf16_t>(R * H);
-    bf16_t* ff = m.take<bf16_t>(R * FF);
-    // key-split partials (96 keys per workgroup) of the cross-attention and of block 0's self-attention over [queries ; text]
-    const size_t part_floats = std::max((size_t)T * ((P + 95) / 96), (size_t)n_samples * ((N0 + 95) / 96)) * c.qf_heads * NQ * (512 + 4);
-    float* part = m.take<float>(part_floats);
+    const bool kv_all = qf_kv_all(c, T, e->qf_kv_contig);
+    const int kv_ld = kv_all ? c.qf_blocks * 2 * H : 2 * H;
+    QfWs w;
+    RC(carve_stage(e, "qformer", [&](Carver& m) { return carve_qformer(m, c, T, n_samples, Lmax, kv_all); }, &w));
+    bf16_t *fn = w.fn, *ckv = w.ckv, *x0 = w.x0, *y0 = w.y0, *kv0 = w.kv0, *q0 = w.q0, *a0 = w.a0, *xs = w.xs, *x = w.x, *y = w.y, *qkv = w.qkv, *att = w.att, *ff = w.ff;
     { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm((const bf16_t*)d_feats, KD, fn, KD, e->top.qf_pre_norm.w, e->top.qf_pre_norm.b, T * P, KD, c.qf_eps, s)); }
     const bf16_t* queries = e->top.qf_queries;
     // ---- block 0 self-attention, once per sample, query rows only ----
@@ -719,7 +748,7 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
         { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x0, H, y0, H, W.n1.w, W.n1.b, n_samples * N0, H, c.qf_eps, s)); }
         RC(linear(e, 0, y0, H, lin_rows(W.sa_in, H, H), H, kv0, 2 * H, n_samples * N0, 2 * H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
         RC(linear(e, 0, y0, H, W.sa_in, H, q0, H, NQ, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));  // rows 0..31 of sample 0 = LN1(queries)
-        RC(qf_attn(e, q0, 0, H, kv0, kv0 + H, (long)N0 * 2 * H, 2 * H, a0, n_samples, NQ, N0, s, part, part_floats));
+        RC(qf_attn(e, q0, 0, H, kv0, kv0 + H, (long)N0 * 2 * H, 2 * H, a0, n_samples, NQ, N0, s, w.part, w.part_floats));
         RC(linear(e, 0, a0, H, W.sa_out, H, xs, H, n_samples * NQ, H, H, xs, H, VZ_ACT_NONE, 0, s));
         ProfScope ps(e, K_OTHER, s);
         for (int t = 0; t < T; ++t) RC(vz_launch_copy_rows(xs + (size_t)h_tile_sample[t] * NQ * H, H, x + (size_t)t * NQ * H, H, NQ, H, s));
@@ -737,7 +766,7 @@ extern "C" int vz_qformer(vz_engine* e, const void* d_feats, int T, const void* 
         const bf16_t* ck = kv_all ? ckv + (size_t)i * 2 * H : ckv;
         { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, W.n2.w, W.n2.b, (int)R, H, c.qf_eps, s)); }
         RC(linear(e, 0, y, H, W.ca_q, H, qkv, H, (int)R, H, H, nullptr, 0, VZ_ACT_NONE, 0, s));
-        RC(qf_attn(e, qkv, (long)NQ * H, H, ck, ck + H, (long)P * kv_ld, kv_ld, att, T, NQ, P, s, part, part_floats));
+        RC(qf_attn(e, qkv, (long)NQ * H, H, ck, ck + H, (long)P * kv_ld, kv_ld, att, T, NQ, P, s, w.part, w.part_floats));
         RC(linear(e, 0, att, H, W.ca_out, H, x, H, (int)R, H, H, x, H, VZ_ACT_NONE, 0, s));
         // FFN
         { ProfScope ps(e, K_NORM, s); RC(vz_launch_layernorm(x, H, y, H, W.n3.w, W.n3.b, (int)R, H, c.qf_eps, s)); }
@@ -904,6 +933,24 @@ extern "C" int vz_tp_all_gather(vz_engine* e, const void* d_send, void* d_recv, 
 static bf16_t* kc_of(vz_engine* e, int layer) { return e->kv + (size_t)layer * e->kv_layer_elems; }
 static bf16_t* vc_of(vz_engine* e, int layer) { return kc_of(e, layer) + e->kv_layer_elems / 2; }
 
+static bool prefill_shape_ok(const vz_config& c, int row0, int B, int S) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && S >= 1 && S <= c.max_ctx; }
+struct PrefillWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; unsigned char* q8; float* qs; };
+static PrefillWs carve_prefill(Carver& m, const vz_config& c, const Shard& sh, int B, int S) {
+    const size_t rows = (size_t)B * S, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, QKV = (size_t)(sh.Hq + 2 * sh.Hkv) * c.head_dim, I = sh.I;
+    PrefillWs w;
+    w.x = m.take<bf16_t>(rows * H);
+    w.y = m.take<bf16_t>(rows * H);
+    w.qkv = m.take<bf16_t>(rows * QKV);
+    w.q = m.take<bf16_t>(rows * A);
+    w.att = m.take<bf16_t>(rows * A);
+    w.act = m.take<bf16_t>(rows * I);
+    w.ints = m.take<int>(rows + B + 16);                                      // slot[rows] | seqlens[B]
+    w.ylast = m.take<bf16_t>((size_t)B * H * 2);
+    w.q8 = m.take<unsigned char>(rows * std::max(std::max(H, A), I));         // e4m3 copy of a linear's input rows + their scales
+    w.qs = m.take<float>(rows);                                               // (fp8 MFMA prefill only)
+    return w;
+}
+
 extern "C" int vz_llm_prefill(vz_engine* e, const void* d_embeds, int B, int S, const int* h_seqlens, const int* d_pos,
                               float* d_logits_all, float* d_logits_last, vz_stream stream) {
     return vz_llm_prefill_rows(e, 0, d_embeds, B, S, h_seqlens, d_pos, d_logits_all, d_logits_last, stream);
@@ -916,7 +963,7 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
     NEED_READY();
     const vz_config& c = e->c;
     hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(d_embeds && h_seqlens && d_pos && B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && S >= 1 && S <= c.max_ctx,
+    VZ_CHECK_ARG(d_embeds && h_seqlens && d_pos && prefill_shape_ok(c, row0, B, S),
                  "prefill: rows %d..%d, S=%d outside capacity (max_batch %d, max_ctx %d)", row0, row0 + B - 1, S, c.max_batch, c.max_ctx);
     const size_t row_off = (size_t)row0 * e->Hkv_l * c.max_ctx * c.head_dim;      // cache rows are [kv head][max_ctx][128] blocks
     VZ_CHECK_ARG(e->cosT && e->rope_max >= c.max_ctx, "prefill: rotary tables not set or shorter than max_ctx");
@@ -924,26 +971,12 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
     const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
     const bool lead = e->rank == 0;   // the row-parallel partial sums carry the residual on one rank only
     const int rows = B * S;
-    size_t need;
-    {
-        Carver m(nullptr, ~(size_t)0);
-        m.take<bf16_t>((size_t)rows * H); m.take<bf16_t>((size_t)rows * H); m.take<bf16_t>((size_t)rows * QKV); m.take<bf16_t>((size_t)rows * A);
-        m.take<bf16_t>((size_t)rows * A); m.take<bf16_t>((size_t)rows * I); m.take<int>(rows + B + 16); m.take<bf16_t>((size_t)B * H * 2);
-        m.take<unsigned char>((size_t)rows * std::max(std::max(H, A), I)); m.take<float>(rows);
-        need = m.off + 256;
-    }
-    RC(ensure_arena(e, need));
-    Carver m(e->arena, e->arena_bytes);
-    bf16_t* x = m.take<bf16_t>((size_t)rows * H);
-    bf16_t* y = m.take<bf16_t>((size_t)rows * H);
-    bf16_t* qkv = m.take<bf16_t>((size_t)rows * QKV);
-    bf16_t* q = m.take<bf16_t>((size_t)rows * A);
-    bf16_t* att = m.take<bf16_t>((size_t)rows * A);
-    bf16_t* act = m.take<bf16_t>((size_t)rows * I);
-    int* d_ints = m.take<int>(rows + B + 16);   // slot[rows] | seqlens[B]
-    bf16_t* ylast = m.take<bf16_t>((size_t)B * H * 2);
-    unsigned char* q8 = m.take<unsigned char>((size_t)rows * std::max(std::max(H, A), I));     // e4m3 copy of a linear's input rows + their scales
-    float* qs = m.take<float>(rows);                                                           // (fp8 MFMA prefill only)
+    PrefillWs w;
+    RC(carve_stage(e, "prefill", [&](Carver& m) { return carve_prefill(m, c, Shard{Hq, Hkv, I}, B, S); }, &w));
+    bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
+    unsigned char* q8 = w.q8;
+    float* qs = w.qs;
+    int* d_ints = w.ints;
     int* d_slot = d_ints;
     int* d_len = d_ints + rows;
     {
@@ -1019,12 +1052,26 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
 // ------------------------------------------------------------------------------------------------
 // a13: greedy decode
 // ------------------------------------------------------------------------------------------------
+static bool decode_shape_ok(const vz_config& c, int B, bool spec) { return B >= 1 && B <= c.max_batch && B <= 64 && (!spec || (B >= 2 && B <= 8)); }
+struct DecodeWs { bf16_t *x, *qkv, *att, *act, *q_rot; };
+// spec: the speculative tail's verify steps keep the rotated queries of their R = B rows
+static DecodeWs carve_decode(Carver& m, const vz_config& c, const Shard& sh, int B, bool spec) {
+    const size_t A = (size_t)sh.Hq * c.head_dim;
+    DecodeWs w;
+    w.x = m.take<bf16_t>((size_t)B * c.hidden);
+    w.qkv = m.take<bf16_t>((size_t)B * (sh.Hq + 2 * sh.Hkv) * c.head_dim);
+    w.att = m.take<bf16_t>(B * A);
+    w.act = m.take<bf16_t>((size_t)B * sh.I);
+    w.q_rot = spec ? m.take<bf16_t>(B * A) : nullptr;
+    return w;
+}
+
 extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, const int* h_next_pos, const int* h_ctx_len,
                                    vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
     hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(B >= 1 && B <= c.max_batch && B <= 64 && d_first_ids && h_next_pos && h_ctx_len, "decode_begin: B=%d unsupported (1..min(64,max_batch))", B);
+    VZ_CHECK_ARG(decode_shape_ok(c, B, false) && d_first_ids && h_next_pos && h_ctx_len, "decode_begin: B=%d unsupported (1..min(64,max_batch))", B);
     const int mb = c.max_batch;
     std::vector<int> h(DecodeState::ints(mb), 0);       // host image of the state: everything behind `cur` goes up in one copy
     const DecodeState hs = decode_state(h.data(), mb), ds = decode_state(e->d_state, mb);
@@ -1102,8 +1149,9 @@ static int launch_spec_tail(vz_engine* e, const int* g, hipStream_t s) {
     return vz_launch_spec_tail(t, s);
 }
 
-// one decode step, all launches on `s`; every quantity that changes between steps lives in device memory
-static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, float* d_logits_dbg, hipStream_t s) {
+// one decode step, all launches on `s`; every quantity that changes between steps lives in device memory.  `w` = carve_decode over the
+// arena vz_llm_decode_steps sized with the same function (nothing may grow inside a capture)
+static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, int out_stride, float* d_logits_dbg, hipStream_t s) {
     const vz_config& c = e->c;
     const int B = e->dec_B;
     const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
@@ -1111,13 +1159,7 @@ static int decode_step_launch(vz_engine* e, int* d_out_ids, int out_stride, floa
     const DecodeState st = decode_state(e->d_state, c.max_batch);
     const TailKind tail = tail_kind(e);
     const bool spec = tail == TAIL_SPEC;
-    Carver m(e->arena, e->arena_bytes);
-    bf16_t* x = m.take<bf16_t>((size_t)B * H);
-    bf16_t* qkv = m.take<bf16_t>((size_t)B * QKV);
-    bf16_t* att = m.take<bf16_t>((size_t)B * A);
-    bf16_t* act = m.take<bf16_t>((size_t)B * I);
-    bf16_t* q_rot = spec ? m.take<bf16_t>((size_t)B * A) : nullptr;      // verify steps: the rotated queries of the R rows
-    if (!m.ok) { vz_set_error("decode: workspace too small"); return VZ_ERR_STATE; }
+    bf16_t *x = w.x, *qkv = w.qkv, *att = w.att, *act = w.act, *q_rot = w.q_rot;
     if (e->use_tok && e->tok) {
         // batch 1 on an MI355X: embedding row -> 32 layers -> logits as the phases of ONE resident grid (decode_persist.hip); same
         // arithmetic as the launches below, bit for bit
@@ -1476,8 +1518,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                  "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
                  "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
-    const size_t need = ((size_t)B * (3 * c.hidden + (c.n_heads + 2 * c.n_kv_heads) * c.head_dim + c.inter)) * 2 + 8192;   // upper bound (tp = 1 sizes)
-    RC(ensure_arena(e, need));
+    DecodeWs w;
+    RC(carve_stage(e, "decode", [&](Carver& m) { return carve_decode(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, spec); }, &w));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of
     // ~230 host launches); if RCCL refuses the capture the engine falls back to eager steps for good
     bool use_graph = !e->prof_on && !d_logits_dbg && getenv("VZ_NO_GRAPH") == nullptr &&
@@ -1555,7 +1597,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     }
     if (!use_graph) {
         for (int i = 0; i < n; ++i)
-            RC(decode_step_launch(e, d_out_ids, n, d_logits_dbg ? d_logits_dbg + (size_t)i * B * c.vocab : nullptr, s));
+            RC(decode_step_launch(e, w, d_out_ids, n, d_logits_dbg ? d_logits_dbg + (size_t)i * B * c.vocab : nullptr, s));
         return VZ_OK;
     }
     // the captured step is replayed while everything it froze is unchanged (seed, draw counter and the rows' state live in device memory)
@@ -1570,7 +1612,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             RC(vz_wide_reserve(e->cap_stream));
         }
         VZ_CHECK_HIP(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-        int r = decode_step_launch(e, d_out_ids, n, nullptr, e->cap_stream);
+        int r = decode_step_launch(e, w, d_out_ids, n, nullptr, e->cap_stream);
         graph = nullptr;
         hipError_t er = hipStreamEndCapture(e->cap_stream, &graph);
         if (r == VZ_OK && er == hipSuccess) er = hipGraphInstantiate(&e->dec_graph, graph, nullptr, nullptr, 0);
@@ -1580,7 +1622,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             if (tp_local(e)) { if (r) return r; VZ_CHECK_HIP(er); }
             (void)hipGetLastError();            // collectives would not capture: eager steps from now on
             e->comm_graph_ok = false;
-            for (int i = 0; i < n; ++i) RC(decode_step_launch(e, d_out_ids, n, nullptr, s));
+            for (int i = 0; i < n; ++i) RC(decode_step_launch(e, w, d_out_ids, n, nullptr, s));
             return VZ_OK;
         }
         e->dec_captures++;
@@ -1613,6 +1655,34 @@ extern "C" int vz_llm_decode_info(vz_engine* e, int* nsplit, int* captures) {
     VZ_CHECK_ARG(e && nsplit && captures, "decode_info: null argument");
     *nsplit = e->dec_nsplit; *captures = e->dec_captures;
     return VZ_OK;
+}
+
+// the arena's size and the mark the last stage call's carving reached in it (equal when that call sized the arena)
+extern "C" int vz_engine_ws_info(vz_engine* e, size_t* arena_bytes, size_t* peak_bytes) {
+    VZ_CHECK_ARG(e && arena_bytes && peak_bytes, "engine_ws_info: bad argument");
+    *arena_bytes = e->arena_bytes; *peak_bytes = e->arena_peak;
+    return VZ_OK;
+}
+
+// The bytes a stage's carving takes for a call of these dimensions on an engine of this config (this rank's shard sizes): the stage's own
+// carve function over a null arena.  -1 = a config or shape the stage would refuse.  Touches no device.
+extern "C" long vz_op_stage_ws_bytes(const vz_config* cfg, int stage, int n, int n2, int Lmax, unsigned flags) {
+    if (!cfg) return -1;
+    const vz_config& c = *cfg;
+    const std::string err = g_err;          // a query reports through its result: the checks it shares with vz_engine_create leave no message behind
+    const bool bad = check_config(c) != VZ_OK;
+    vz_set_error("%s", err.c_str());
+    if (bad) return -1;
+    const bool spec = (flags & VZ_WS_SPEC_TAIL) != 0;
+    Carver m(nullptr, ~(size_t)0);
+    switch (stage) {
+    case VZ_STAGE_CLIP: if (!clip_shape_ok(c, n)) return -1; carve_clip(m, c, n, !(flags & VZ_WS_CALLER_HIDDEN)); break;
+    case VZ_STAGE_QFORMER: if (!qf_shape_ok(c, n, n2, Lmax)) return -1; carve_qformer(m, c, n, n2, Lmax, qf_kv_all(c, n, (flags & VZ_WS_QF_KV_CONTIG) != 0)); break;
+    case VZ_STAGE_PREFILL: if (!prefill_shape_ok(c, 0, n, n2)) return -1; carve_prefill(m, c, shard_of(c), n, n2); break;
+    case VZ_STAGE_DECODE: if (!decode_shape_ok(c, n, spec)) return -1; carve_decode(m, c, shard_of(c), n, spec); break;
+    default: return -1;
+    }
+    return (long)m.off;
 }
 
 // Device-side waits of the one-launch attention half are bounded; one that expires raises a word the host reads here (blocking

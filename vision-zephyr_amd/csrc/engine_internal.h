@@ -98,8 +98,8 @@ struct vz_engine {
     bool finalized = false;
     // rope
     const float* cosT = nullptr; const float* sinT = nullptr; int rope_max = 0;
-    // workspace (one arena, carved per stage; stages never overlap in time on a stream)
-    char* arena = nullptr; size_t arena_bytes = 0;
+    // workspace (one arena, carved per stage; stages never overlap in time on a stream); arena_peak = the mark of the last stage's carving
+    char* arena = nullptr; size_t arena_bytes = 0, arena_peak = 0;
     // kv cache: [layer][2][B][Hkv][max_ctx][D]
     bf16_t* kv = nullptr; size_t kv_layer_elems = 0;
     // decode state (device)

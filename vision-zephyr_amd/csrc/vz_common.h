@@ -246,6 +246,7 @@ struct AttnArgs {
     const int* rope_pos = nullptr;
 };
 int vz_launch_attention(const AttnArgs& a, hipStream_t s);
+size_t vz_attn_split_floats(int B, int Hq, int Sq, int Sk);      // `part` floats a head_dim-512 key-split launch wants under knob 23; 0 = no split
 void vz_set_attn_version(int v);
 int vz_attn_version();
 void vz_set_attn_split(int v);
@@ -305,7 +306,7 @@ int vz_launch_flash_bwd(const AttnBwdArgs& a, void* scratch, size_t scratch_byte
 struct AttnDecodeFusedArgs {
     const bf16_t* qkv;     // [B, (Hq+2Hkv)*D]
     bf16_t *kc, *vc, *o;   // caches for this layer [B][Hkv][max_ctx][D]; o [B,Hq,D]
-    float* part;           // [B*Hkv*nsplit*(4*D+32)]
+    float* part;           // vz_attn_decode_part_floats
     unsigned* ticket;      // [B*Hkv], zeroed once
     const float *cosT, *sinT;
     const int *pos, *slot; // device int32 [B]
@@ -313,6 +314,7 @@ struct AttnDecodeFusedArgs {
     float scale;
 };
 int vz_launch_attn_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t s);
+size_t vz_attn_decode_part_floats(int B, int Hkv, int nsplit);   // [B][Hkv][nsplit] partial records of attn_decode_body.h
 // attn_o_fused.hip: the same attention + the O projection (x += att . o_w^T, batch 1) in one launch; `done` = a zeroed device word,
 // `step` = the decode call's device-side step counter
 int vz_launch_attn_o_fused(const AttnDecodeFusedArgs& a, const bf16_t* o_w, const unsigned char* o_w8, const float* o_scale, bf16_t* att_scratch,

@@ -73,6 +73,8 @@ SYMBOLS = {
     "vz_op_attention_decode_fused": (_I, [_P] * 10 + [_I] * 7 + [_F, _P]),
     "vz_engine_create": (_I, [C.POINTER(VzConfig), C.POINTER(_P)]),
     "vz_engine_destroy": (_I, [_P]),
+    "vz_engine_ws_info": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "vz_op_stage_ws_bytes": (_L, [C.POINTER(VzConfig), _I, _I, _I, _I, C.c_uint]),
     "vz_engine_set_weight": (_I, [_P, C.c_char_p, _P, _I, _L]),
     "vz_engine_finalize": (_I, [_P]),
     "vz_engine_set_rope": (_I, [_P, _P, _P, _I]),
@@ -352,6 +354,16 @@ def linear_route(M: int, N: int, K: int, lda: Optional[int] = None, ldw: Optiona
     r = lib().vz_op_linear_route(M, N, K, K if lda is None else lda, K if ldw is None else ldw, act, int(out_fp32), flags, entry,
                                  C.byref(pre), C.byref(sk))
     return (LIN_ROUTES[r] if 0 <= r < len(LIN_ROUTES) else "NONE"), bool(pre.value), sk.value
+
+
+STAGE_CLIP, STAGE_QFORMER, STAGE_PREFILL, STAGE_DECODE = range(4)
+WS_CALLER_HIDDEN, WS_QF_KV_CONTIG, WS_SPEC_TAIL = 1, 2, 4
+
+
+def stage_ws_bytes(cfg: VzConfig, stage: int, n: int, n2: int = 0, Lmax: int = 0, flags: int = 0) -> int:
+    """Bytes the stage's carving takes for a call of these dimensions on an engine of `cfg`, -1 where the config or the shape would be
+    refused; needs no GPU (vz_op_stage_ws_bytes)."""
+    return lib().vz_op_stage_ws_bytes(C.byref(cfg), stage, n, n2, Lmax, flags)
 
 
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor):

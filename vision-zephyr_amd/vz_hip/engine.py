@@ -62,6 +62,7 @@ class Engine:
             fusion_layers_per_group=cfg.fusion_layers_per_group, max_batch=max_batch, max_ctx=max_ctx,
             max_tiles=max_tiles, max_text=max_text, tp_size=tp_size, tp_rank=tp_rank,
             clip_keep_cls=int(cfg.clip_keep_cls), weight_fp8=int(weight_fp8))
+        self.c_cfg = c                         # what vz_op_stage_ws_bytes is asked with (stage_ws_bytes)
         self.weight_fp8 = bool(weight_fp8)
         if weight_fp8 and weight_nf4:
             raise ValueError("weight_fp8 and weight_nf4 are two quantisations of the same linears: pick one")
@@ -702,6 +703,19 @@ class Engine:
         ns, cap = C.c_int(0), C.c_int(0)
         B.check(self.lib.vz_llm_decode_info(self.h, C.byref(ns), C.byref(cap)))
         return ns.value, cap.value
+
+    def ws_info(self) -> Tuple[int, int]:
+        """(bytes of the stage arena, the mark the last stage call's carving reached in it)."""
+        arena, peak = C.c_size_t(0), C.c_size_t(0)
+        B.check(self.lib.vz_engine_ws_info(self.h, C.byref(arena), C.byref(peak)))
+        return arena.value, peak.value
+
+    def stage_ws_bytes(self, stage: int, n: int, n2: int = 0, Lmax: int = 0, flags: int = 0) -> int:
+        """What a stage call of these dimensions takes of the arena (binding.stage_ws_bytes on this engine's config; _dest lays the
+        Q-Former's ca_kv weights out back to back, so Q-Former queries carry WS_QF_KV_CONTIG)."""
+        if stage == B.STAGE_QFORMER:
+            flags |= B.WS_QF_KV_CONTIG
+        return B.stage_ws_bytes(self.c_cfg, stage, n, n2, Lmax, flags)
 
     # profiling hooks (bench.py roofline leg)
     def prof_enable(self, on: bool, klass: int = -1):
