@@ -30,7 +30,7 @@ P
 }
 mkdir -p $R/gpurun_out
 for C in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/pm1; VZ_NO_GRAPH=1 VZ_REPS=1 rocprofv3 --pmc $C --kernel-trace --kernel-include-regex "gemv_bf16_kernel|attn_decode_fused|attn_o_fused" -d /tmp/pm1 -o p --output-format csv -- python3 $R/tools/bench_decode.py "" > /tmp/pm1.log 2>&1
+  rm -rf /tmp/pm1; VZ_NO_GRAPH=1 VZ_REPS=1 rocprofv3 --pmc $C --kernel-trace --kernel-include-regex "gemv_bf16_kernel|gemv_bf16_noepi_kernel|attn_decode_fused|attn_o_fused" -d /tmp/pm1 -o p --output-format csv -- python3 $R/tools/bench_decode.py "" > /tmp/pm1.log 2>&1
   echo "== decode launch chain $C"; summ /tmp/pm1 $R/gpurun_out/pmc_decode_chain_$C.json "decode launch chain (GEMV + attention|O launch), configs[2], $C"
   [ "$PMC_ONLY" = chain ] && continue
   rm -rf /tmp/pm2; VZ_NO_GRAPH=1 VZ_REPS=1 rocprofv3 --pmc $C --kernel-trace --kernel-include-regex "decode_token_kernel" -d /tmp/pm2 -o p --output-format csv -- python3 $R/tools/bench_decode.py "28=1" > /tmp/pm2.log 2>&1

@@ -11,7 +11,7 @@ H, I, V, QKV = 4096, 14336, 32000, 6144
 alg = {"262144": 2 * I * H * 2, "131072": None, "196608": QKV * H * 2}          # by grid size (threads): gate|up, O / down / lm_head, QKV
 rows, by_grid, n_all, b_all = [], {}, 0, 0.0
 for k in d["kernels"]:
-    if not k["kernel"].startswith("gemv_bf16_kernel"):
+    if not k["kernel"].startswith(("gemv_bf16_kernel", "gemv_bf16_noepi_kernel")):      # both forms of the stream
         continue
     n, b = k["launches"], k["hbm_read_bytes_per_launch"]
     e = by_grid.setdefault(k["grid"], {"n": 0, "bytes": 0.0})

@@ -43,7 +43,7 @@ KNOB_DEFAULTS = {9: 1, 14: 29, 19: 1}
 KNOB_SETS = [{}] + [{9: v} for v in (0, 2, 3, 5, 7)] + [{19: 0}] + [{14: v} for v in (8, 17, 65)]
 
 # kernel name -> route name of csrc/linear_route.h (splitk_finalize_kernel belongs to the TILE128 launch before it)
-ROUTE_OF_KERNEL = [("gemv_bf16_kernel", "GEMV"), ("skinny_persist_kernel", "SKINNY_PERSIST"), ("skinny_wide_kernel", "SKINNY_WIDE"),
+ROUTE_OF_KERNEL = [("gemv_bf16_kernel", "GEMV"), ("gemv_bf16_noepi_kernel", "GEMV"), ("skinny_persist_kernel", "SKINNY_PERSIST"), ("skinny_wide_kernel", "SKINNY_WIDE"),
                    ("skinny_kernel", "SKINNY"), ("wide_tiled_fp8_kernel", "WIDE_E4M3"), ("wide_tiled_kernel", "WIDE_BF16"),
                    ("gemm256_bf16_kernel", "TILE256"), ("gemm_bf16_kernel", "TILE128")]
 

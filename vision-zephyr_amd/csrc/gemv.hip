@@ -15,7 +15,11 @@
 // their staging loops.  The stream itself is a ring of U slots per row: a slot is consumed under
 // a counted wait and at once requested again U chunks further on (gemv_step), also across the
 // boundary to the wave's next unit (limits: DESIGN.md 6b item 4); residual / bias / scale are
-// requested at the start of a unit, not after its reduction.  Accumulation: v_dot2c_f32_bf16 into fp32, wave
+// requested at the start of a unit, not after its reduction.  A launch that has neither bias
+// nor residual (bf16 weights, one or two rows: QKV, gate|up, lm_head of the decode step) runs
+// gemv_bf16_noepi_kernel, the same stream without that code: nothing is waited for between a
+// unit's reduction and its stores, so a looping wave's next unit stays in flight under them, and
+// it asks for that unit half a batch at a time (launch_noepi).  Accumulation: v_dot2c_f32_bf16 into fp32, wave
 // reduction, then the same epilogues as the tile GEMM (bias / act / SwiGLU pair / residual /
 // bf16|fp32 out).  The per-lane order of the sums is the one attn_o_fused.hip and
 // decode_persist.hip repeat: chunks ascending, the four fdot2 of dot8 in order.
@@ -33,6 +37,32 @@ namespace {
 
 int g_gemv_variant = 0;   // 0 = production choice; >0 = tuning variants (tools/bench_kernels.py)
 
+// The operand-free form of the stream (gemv_bf16_noepi_kernel): one kernel per K shape, chosen here as gemv_bf16_kernel chooses its body.
+template <int MB, int R, int U, bool NT, int NW, int MODE, int G>
+int launch_noepi_form(const GemvParams& p, int blocks, hipStream_t s, size_t lds) {
+    static VzDeviceOnce attr;
+    if (vz_device_first(attr)) {
+        VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_noepi_kernel<MB, R, U, NT, NW, MODE, G>, hipFuncAttributeMaxDynamicSharedMemorySize, NW == 4 ? 64 * 1024 : 160 * 1024));
+    }
+    vz_launch_timed(gemv_bf16_noepi_kernel<MB, R, U, NT, NW, MODE, G>, dim3(blocks), dim3(NW * 64), lds, s, p);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+template <int MB, int R, int U, bool NT, int NW>
+int launch_noepi(const GemvParams& p, int blocks, hipStream_t s, size_t lds) {
+    const int nchunk = p.K / 512;
+    if (nchunk == U) {
+        // looping (some wave walks more than one unit: gate|up, lm_head): the next unit is requested half a batch at a time, 8 loads behind
+        // every fourth slot (us per launch, best .. worst of 4 rounds: slot by slot 37.07 .. 37.18 / 39.58 .. 39.81, half batches
+        // 36.64 .. 36.72 / 39.64 .. 39.82, one burst of 16 behind the last slot 36.48 .. 36.81 / 39.88 .. 40.06)
+        if (p.units > blocks * NW) return launch_noepi_form<MB, R, U, NT, NW, GEMV_K_ONE, 4>(p, blocks, s, lds);
+        return launch_noepi_form<MB, R, U, NT, NW, GEMV_K_ONE, 1>(p, blocks, s, lds);
+    }
+    if (nchunk > U) return launch_noepi_form<MB, R, U, NT, NW, GEMV_K_MANY, 1>(p, blocks, s, lds);
+    return launch_noepi_form<MB, R, U, NT, NW, GEMV_K_SHORT, 1>(p, blocks, s, lds);
+}
+
 template <int MB, int R, int U, bool NT, bool FP8 = false, int NW = 4>
 int launch_variant(const GemvParams& p0, hipStream_t s, size_t lds) {
     GemvParams p = p0;
@@ -41,6 +71,10 @@ int launch_variant(const GemvParams& p0, hipStream_t s, size_t lds) {
     int cap = NW == 4 ? 2048 : 512;
     if (g_gemv_variant >= 7 && g_gemv_variant <= 10) cap = (g_gemv_variant & 1) ? 256 : 512;      // experiments: one / two workgroups per CU
     if (blocks > cap) blocks = cap;
+    // neither bias nor residual (QKV, gate|up, lm_head of the decode step): the form without the epilogue's operands; routed forms only
+    if constexpr (MB <= 2 && !FP8 && R == 2 && U == 8 && NT) {
+        if (!p.bias && !p.residual) return launch_noepi<MB, R, U, NT, NW>(p, blocks, s, lds);
+    }
     static VzDeviceOnce attr;
     if (vz_device_first(attr)) {
         VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_kernel<MB, R, U, NT, FP8, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, NW == 4 ? 64 * 1024 : 160 * 1024));
@@ -69,6 +103,13 @@ int launch_mb(const GemvParams& p, hipStream_t s, size_t lds) {
     //   gate|up  512 x 8 loop. 36.9 | 256 x 8 looping 37.2 | 2048 x 4 looping 36.8
     //   lm_head  512 x 8 loop. 40.2 | 256 x 8 looping 40.9 | 2048 x 4 looping 40.8
     // One looping workgroup per CU loses everywhere; the rule stays (gate|up's 0.1 us for 2048 x 4 is inside the spread of 0.4).
+    // This rule with the operand-free form where it applies, as the decode step launches them (fused norm; O and down with their residual;
+    // profiles/gemv_noepi_ab.txt; best .. worst of 4 rounds, the parent commit's library in the same session behind the bar):
+    //   QKV      768 x 4         9.61 ..  9.71 |  9.79 ..  9.98
+    //   O        256 x 8         7.29 ..  7.34 |  7.27 ..  7.51      (gemv_bf16_kernel in both)
+    //   down     256 x 8        19.19 .. 19.27 | 19.20 .. 19.31      (gemv_bf16_kernel in both)
+    //   gate|up  512 x 8 loop.  36.64 .. 36.72 | 37.23 .. 37.63
+    //   lm_head  512 x 8 loop.  39.64 .. 39.82 | 40.31 .. 40.53
     bool fat = false;
     if constexpr (MB <= 4) {
         const int units = p.act == VZ_ACT_SWIGLU ? p.N / 2 : (p.N + 1) / 2;
@@ -125,6 +166,13 @@ int vz_init_gemv_kernels() {
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_kernel<4, 2, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_kernel<8, 2, 8, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_kernel<8, 2, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+#define VZ_NOEPI_ATTR(MB, NW, MODE, G) \
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_bf16_noepi_kernel<MB, 2, 8, true, NW, MODE, G>, hipFuncAttributeMaxDynamicSharedMemorySize, NW == 4 ? 64 * 1024 : 160 * 1024))
+#define VZ_NOEPI_ATTRS(MB, NW) \
+    VZ_NOEPI_ATTR(MB, NW, GEMV_K_SHORT, 1); VZ_NOEPI_ATTR(MB, NW, GEMV_K_ONE, 1); VZ_NOEPI_ATTR(MB, NW, GEMV_K_ONE, 4); VZ_NOEPI_ATTR(MB, NW, GEMV_K_MANY, 1)
+    VZ_NOEPI_ATTRS(1, 4); VZ_NOEPI_ATTRS(1, 8); VZ_NOEPI_ATTRS(2, 4); VZ_NOEPI_ATTRS(2, 8);
+#undef VZ_NOEPI_ATTRS
+#undef VZ_NOEPI_ATTR
     return VZ_OK;
 }
 

@@ -1,5 +1,6 @@
-// gemv_bf16_kernel and what it is made of: included by gemv.hip (the launchers) and by gemv_audit.hip (the four batch-1 production
-// instantiations alone, for tests/test_gemv_isa_cpu.py).  The header of gemv.hip describes the kernel.
+// gemv_bf16_kernel, gemv_bf16_noepi_kernel and what they are made of: included by gemv.hip (the launchers) and by gemv_audit.hip (the
+// batch-1 production instantiations alone, for tests/test_gemv_isa_cpu.py and tests/test_gemv_noepi_isa_cpu.py).  The header of gemv.hip
+// describes the kernels.
 #pragma once
 #include "vz_common.h"
 
@@ -57,7 +58,8 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // straight-line code and the compiler waits vmcnt(in flight behind slot c) per chunk, so the wave keeps its loads in flight from the first
 // to the last.  NC = NR = -1 takes them at run time: every load then sits behind a branch of its own and the waits fall back to draining
 // (a conditional load may not have been issued, so nothing can be counted behind it) - used for the shapes without a compiled form.
-template <int MB, int R, int U, bool NT, bool FP8, int NC, int NR>
+// G: refill granularity.  Slots are requested again G at a time, behind the consumption of the last of the G (1: slot by slot).
+template <int MB, int R, int U, bool NT, bool FP8, int NC, int NR, int G = 1>
 __device__ __forceinline__ void gemv_step(u32x4 (&wreg)[R][U], float (&acc)[R][MB], const char* smem, int K, int lane, int xc0, int nc, int nr,
                                           const char* const (&rp)[R]) {
     constexpr int EPL = FP8 ? 16 : 8, CH = 64 * EPL, WBYTES = FP8 ? 1 : 2;
@@ -92,9 +94,13 @@ __device__ __forceinline__ void gemv_step(u32x4 (&wreg)[R][U], float (&acc)[R][M
         }
         // the refill of slot c stays behind its consumption and ahead of the next chunk's: hoisted, it would need a second set of registers
         __builtin_amdgcn_sched_barrier(0);
-        if (NR >= 0 ? c < NR : c < nr) {
+        if ((c + 1) % G == 0) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) wreg[r][c] = ldw<NT>(rp[r] + (size_t)c * CH * WBYTES);
+            for (int g = c + 1 - G; g <= c; ++g)
+                if (NR >= 0 ? g < NR : g < nr) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) wreg[r][g] = ldw<NT>(rp[r] + (size_t)g * CH * WBYTES);
+                }
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -107,8 +113,10 @@ __device__ __forceinline__ void gemv_step(u32x4 (&wreg)[R][U], float (&acc)[R][M
 //            and loads itself, the compiler drains the counter; here that happens once per wave, before the loop over units.
 //   K_MANY   more: a loop of compiled steps <U,U> (refill everything) and <U,0>, then a short last batch on the run-time step (K = 14336
 //            is 3.5 batches).  The drain ahead of the batch loop comes once per unit.
+// NOEPI: the launch has neither bias nor residual (bf16 weights, one or two rows): the early-operand code does not exist.
+// G: refill granularity of the K_ONE stream (gemv_step).
 enum { GEMV_K_SHORT = 0, GEMV_K_ONE = 1, GEMV_K_MANY = 2 };
-template <int MB, int R, int U, bool NT, bool FP8, int NW, int MODE>
+template <int MB, int R, int U, bool NT, bool FP8, int NW, int MODE, bool NOEPI = false, int G = 1>
 __device__ __forceinline__ void gemv_body(const GemvParams& p, char* smem) {
     constexpr bool WHOLE = MODE != GEMV_K_SHORT;      // K holds at least one whole batch: the first batch is U x R unconditional loads
     constexpr int NTHR = NW * 64;
@@ -356,11 +364,14 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, char* smem) {
         // One or two rows: the epilogue's operands are requested now, ahead of the unit's last weight loads, not after the reduction.
         // Every lane loads what lane 63 will use (one address per wave), and loads and uses are unconditional - an operand that does not
         // exist reads x[0] and is dropped by a select - so that the compiler can count these loads like the weights'.
+        // Without operands (NOEPI) nothing is requested: every wait between the reduction and the stores would be a wait for these
+        // registers, taken with the count of the step form without a refill - a drain of the next unit's loads, once per unit.
         constexpr bool EARLY = MB <= 2;
+        static_assert(!NOEPI || (EARLY && !FP8), "the operand-free form: bf16 weights, one or two rows");
         const bool use_bias = p.bias && !swiglu;
         float e_bias[R], e_scale[R];
         bf16_t e_res[R][MB];
-        if constexpr (EARLY) {
+        if constexpr (EARLY && !NOEPI) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int row = row_of(u, r);
@@ -374,8 +385,8 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, char* smem) {
 
         if constexpr (MODE == GEMV_K_ONE) {
             // the next unit's first batch rides under this unit's only one: the loads stay in flight across the unit boundary
-            if (has_next) gemv_step<MB, R, U, NT, FP8, U, U>(wreg, acc, smem, K, lane, 0, U, U, np);
-            else gemv_step<MB, R, U, NT, FP8, U, 0>(wreg, acc, smem, K, lane, 0, U, 0, np);
+            if (has_next) gemv_step<MB, R, U, NT, FP8, U, U, G>(wreg, acc, smem, K, lane, 0, U, U, np);
+            else gemv_step<MB, R, U, NT, FP8, U, 0, G>(wreg, acc, smem, K, lane, 0, U, 0, np);
         } else {
             int c0 = 0;
             if constexpr (WHOLE) {
@@ -414,8 +425,10 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, char* smem) {
                         float g = acc[2 * h][m], v = acc[2 * h + 1][m];
                         if constexpr (FP8) { g *= e_scale[2 * h]; v *= e_scale[2 * h + 1]; }
                         float t = act_silu(g) * v;
-                        const float tr = t + bf16_to_f32(e_res[2 * h][m]);
-                        t = p.residual ? tr : t;
+                        if constexpr (!NOEPI) {
+                            const float tr = t + bf16_to_f32(e_res[2 * h][m]);
+                            t = p.residual ? tr : t;
+                        }
                         if (last && m < p.M) {
                             if (p.out_fp32) ((float*)p.C)[(size_t)m * p.ldc + j] = t;
                             else ((bf16_t*)p.C)[(size_t)m * p.ldc + j] = f32_to_bf16(t);
@@ -427,10 +440,15 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, char* smem) {
                         const int n = u * R + r;
                         float t = acc[r][m];
                         if constexpr (FP8) t *= e_scale[r];
-                        const float tb = t + e_bias[r];
-                        t = apply_act(use_bias ? tb : t, p.act);
-                        const float tr = t + bf16_to_f32(e_res[r][m]);
-                        t = p.residual ? tr : t;
+                        if constexpr (!NOEPI) {
+                            const float tb = t + e_bias[r];
+                            t = use_bias ? tb : t;
+                        }
+                        t = apply_act(t, p.act);
+                        if constexpr (!NOEPI) {
+                            const float tr = t + bf16_to_f32(e_res[r][m]);
+                            t = p.residual ? tr : t;
+                        }
                         if (last && m < p.M && n < p.N) {
                             if (p.out_fp32) ((float*)p.C)[(size_t)m * p.ldc + n] = t;
                             else ((bf16_t*)p.C)[(size_t)m * p.ldc + n] = f32_to_bf16(t);
@@ -502,6 +520,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(gemv_mi
     if (MB <= 2 && nchunk == U) gemv_body<MB, R, U, NT, FP8, NW, GEMV_K_ONE>(p, smem);      // (4 and 8 rows: their sums need the registers)
     else if (nchunk >= U) gemv_body<MB, R, U, NT, FP8, NW, GEMV_K_MANY>(p, smem);
     else gemv_body<MB, R, U, NT, FP8, NW, GEMV_K_SHORT>(p, smem);
+}
+
+// The same stream for a launch without bias and residual (bf16 weights, one or two rows; in the decode step QKV, gate|up and lm_head):
+// gemv_body without its early-operand code.  Same sums, same order, same stores.  The launcher picks the K shape (MODE), so a kernel holds
+// one body: with the three bodies behind a branch in one kernel, as in gemv_bf16_kernel, hipcc compiles this form's stream with vmcnt(0) at
+// its second slot - one drain per unit again, only earlier (that kernel also holds flat loads, and a pending flat load turns every wait into
+// a drain; gemv_bf16_kernel's own drain per unit clears them).  One body per kernel: every slot under a counted wait, 86 registers.
+// G: gemv_step's refill granularity where K is one batch.
+template <int MB, int R, int U, bool NT, int NW, int MODE, int G = 1>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(gemv_min_waves(MB, R, U, false, NW)))) void gemv_bf16_noepi_kernel(GemvParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // xs[MB][K] bf16, then scratch
+    static_assert(G == 1 || MODE == GEMV_K_ONE, "the refill granularity belongs to the one-batch stream");
+    gemv_body<MB, R, U, NT, false, NW, MODE, true, G>(p, smem);
 }
 
 }  // namespace
