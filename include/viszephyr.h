@@ -392,6 +392,23 @@ int vz_llm_decode_sampling(vz_engine* e, int enable, float temperature, int top_
 int vz_llm_decode_ring(vz_engine* e, int* host_visible_ring, int ring_n, int ring_rows);
 int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, unsigned long long seed,
                  int counter, int* d_ids, vz_stream stream);
+/* Logits processors in the step (hf:generation/logits_process.py, in the order of `_get_logits_processor`: repetition penalty,
+ * no-repeat-n-gram, min-new-tokens, suppress-tokens, then the sampler's warpers): after vz_llm_decode_logits_proc(enable=1) every
+ * decode step whose tail is the argmax or the sampler first runs them on its fp32 logits, on the device and inside the per-token
+ * hipGraph (the parameters are part of what a captured step freezes: a change captures again).  They see the ids generated so
+ * far, never the prompt (the reference generates from inputs_embeds): a per-row history kept on the device, emptied here
+ * (stream-ordered) and extended at every step by the row's input token - so arm it before vz_llm_decode_begin, after the first
+ * token was chosen on logits that went through vz_op_logits_process with empty histories.  repetition_penalty > 0 (1 = off),
+ * 0 <= no_repeat_ngram <= 8 (0 = off), the <= 4 eos ids are -inf while fewer than min_new_tokens ids were generated, the <= 16
+ * suppressed ids always; vocabularies up to 65536.  vz_llm_decode_steps refuses the mode together with the beam or the
+ * speculative tail; tensor-parallel engines are VZ_ERR_UNSUPPORTED.  enable = 0: off (no launch is added to the step).
+ * vz_op_logits_process: the same kernel in place on fp32 logits [rows, cols] over the caller's histories d_hist [rows][hist_stride]
+ * (int32) of d_hist_len[row] ids each; ids outside [0, cols) are ignored.  Bit-identical to HF's processors on fp32. */
+int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
+                              const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream);
+int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
+                         int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
+                         vz_stream stream);
 /* how the last vz_llm_decode_steps ran: *graph = 1 when a captured hipGraph was replayed; *comm_in_graph = 1 when the RCCL
  * collectives of a tensor-parallel engine are part of that graph (0 = eager steps, e.g. after RCCL refused the capture) */
 int vz_llm_decode_mode(vz_engine* e, int* graph, int* comm_in_graph);

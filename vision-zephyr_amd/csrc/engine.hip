@@ -447,6 +447,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_ferr) hipFree(e->d_ferr);
     if (e->d_xnorm) hipFree(e->d_xnorm);
     if (e->beam.d) hipFree(e->beam.d);
+    if (e->proc.d) hipFree(e->proc.d);
     if (e->d_gather) (void)hipFree(e->d_gather);
     vz_decode_persist_destroy(e->tok);
     if (e->comm) (void)ncclCommDestroy(e->comm);
@@ -1137,6 +1138,21 @@ extern "C" int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const 
     return VZ_OK;
 }
 
+// the logits processors' buffer (vz_engine::proc.d): the rows' history lengths, then the histories [max_batch][max_ctx]
+static size_t proc_len_ints(const vz_config& c) { return align_up((size_t)c.max_batch, 64); }
+static int* proc_hist(const vz_engine* e) { return e->proc.d + proc_len_ints(e->c); }
+static int proc_args_of(float penalty, int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, ProcArgs* out) {
+    VZ_CHECK_ARG(penalty > 0.f && ngram >= 0 && ngram <= 8 && min_new >= 0, "logits_proc: repetition penalty %g > 0, 0 <= n-gram size %d <= 8, "
+                 "min_new_tokens %d >= 0 expected", (double)penalty, ngram, min_new);
+    VZ_CHECK_ARG(n_eos >= 0 && n_eos <= 4 && (n_eos == 0 || h_eos), "logits_proc: 0..4 eos ids expected, got %d", n_eos);
+    VZ_CHECK_ARG(n_suppress >= 0 && n_suppress <= 16 && (n_suppress == 0 || h_suppress), "logits_proc: 0..16 suppressed ids expected, got %d", n_suppress);
+    memset(out, 0, sizeof(*out));
+    out->penalty = penalty; out->ngram = ngram; out->min_new = min_new; out->eos.n = n_eos; out->n_suppress = n_suppress;
+    for (int i = 0; i < 4; ++i) out->eos.id[i] = i < n_eos ? h_eos[i] : -1;
+    for (int i = 0; i < 16; ++i) out->suppress[i] = i < n_suppress ? h_suppress[i] : -1;
+    return VZ_OK;
+}
+
 // the accept + draft launch of the armed speculative mode on the step's argmax ids g [R]; g = null: only the first draft (arming)
 static int launch_spec_tail(vz_engine* e, const int* g, hipStream_t s) {
     const SpecArgs& a = e->spec.a;
@@ -1220,6 +1236,10 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         ProfScope ps(e, K_OTHER, s);
         // per row: the token into d_out_ids (and the ring), position / slot / length one further
         const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
+        if (e->proc.on && (tail == TAIL_GREEDY || tail == TAIL_SAMPLE)) {
+            // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
+            RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, s));
+        }
         switch (tail) {
         case TAIL_SPEC: {
             // spec.hip: per-row argmax, then acceptance + state advance (its own, multi-row rule) + the next step's draft in one small launch
@@ -1289,6 +1309,37 @@ extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float tem
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 1), (int)(unsigned)seed, 1, s));
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 2), (int)(unsigned)(seed >> 32), 1, s));
     return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
+}
+
+// Logits processors in the step (hf:generation/logits_process.py; logits_proc.hip): after
+// vz_llm_decode_logits_proc(enable=1) every decode step whose tail is the argmax or the sampler first runs repetition penalty (1 = off),
+// no-repeat-n-gram (0 = off), min-new-tokens (the eos ids at -inf while fewer ids were generated) and suppress-tokens on its logits, over
+// the ids generated so far: each row's history lives on the device, restarts empty here (stream-ordered) and grows by the row's input
+// token at every step.  The mode is orthogonal to the tail; vz_llm_decode_steps refuses it together with the beam or the speculative tail.
+extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
+                                         const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->proc.on = 0; return VZ_OK; }
+    const vz_config& c = e->c;
+    if (e->tp > 1) { vz_set_error("decode_logits_proc: logits processors on a tensor-parallel engine are not built"); return VZ_ERR_UNSUPPORTED; }
+    ProcArgs a;
+    RC(proc_args_of(repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, &a));
+    VZ_CHECK_ARG(c.vocab <= 65536, "decode_logits_proc: vocabulary of %d, the kernel's bitmaps hold 65536", c.vocab);
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
+    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, proc_len_ints(c) * sizeof(int), s));
+    e->proc.on = 1; e->proc.a = a;
+    return VZ_OK;
+}
+
+// the same kernel on fp32 logits [rows, cols] in place, over the caller's histories d_hist [rows][hist_stride] of d_hist_len[row] ids
+// each; nothing is appended (the first token of a generation: the prefill logits and empty histories; tests)
+extern "C" int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
+                                    int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
+                                    vz_stream stream) {
+    ProcArgs a;
+    RC(proc_args_of(penalty, ngram, min_new, h_eos, n_eos, h_suppress, n_suppress, &a));
+    return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (hipStream_t)stream);
 }
 
 static int ensure_beam_state(vz_engine* e) {
@@ -1501,6 +1552,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_SAMPLE: k.samp = e->samp.a; break;
     case TAIL_GREEDY: break;
     }
+    if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; }
     return k;
 }
 
@@ -1518,6 +1570,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                  "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
                  "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
+    VZ_CHECK_ARG(!e->proc.on || tail == TAIL_GREEDY || tail == TAIL_SAMPLE, "decode_steps: the logits processors (vz_llm_decode_logits_proc) run in "
+                 "front of the argmax or the sampler only, not with the beam or the speculative tail");
     DecodeWs w;
     RC(carve_stage(e, "decode", [&](Carver& m) { return carve_decode(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, spec); }, &w));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of

@@ -1,0 +1,114 @@
+// HF's logits processors as one device-side filter between the lm_head and the step's tail:
+//   hf:generation/logits_process.py RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor ->
+//   MinNewTokensLengthLogitsProcessor(prompt_length_to_skip = 0) -> SuppressTokensLogitsProcessor, the order of
+//   hf:generation/utils.py `_get_logits_processor`; the warpers (sampling.hip) come after them.
+// The reference generates from inputs_embeds, so HF's processors see only the ids generated so far: the history h[0..n) of a row.
+//   penalty : every DISTINCT token of h: x < 0 ? x * p : x / p       (HF gathers, then scatters: once per token)
+//   n-gram g: ban h[i + g - 1] for every i with h[i .. i + g - 2] == h[n - g + 1 .. n); nothing while n < g; g = 1 bans all of h
+//   min-new : while n < min_new every eos id is -inf
+//   suppress: the listed ids are -inf
+// The last three only write -inf and -inf * p = -inf, so ONE pass applies all four: two bitmaps of `cols` bits in LDS, `seen` (tokens of
+// h) and `ban`; the history is marked with LDS atomics, then the bitmap WORDS are swept and only set bits touch a logit - penalty
+// first, then -inf; a logit has exactly one writer, the rest of the row is neither read nor written.  Plain fp32 * and / (correctly
+// rounded, no fast-math): bit-identical to torch on the CPU.
+// One 1024-thread workgroup per row, in place.  Inside a decode step the kernel first appends cur[row] - the token the previous tail
+// published - to the row's history (saturating at hist_stride), so no tail kernel has to know about the history.
+#include "vz_common.h"
+
+namespace {
+
+constexpr int PROC_MAX_COLS = 65536, PROC_WORDS = PROC_MAX_COLS / 32, PROC_G = 8;
+
+__device__ __forceinline__ void mark(unsigned* bm, int tok, int cols) {
+    if ((unsigned)tok < (unsigned)cols) atomicOr(&bm[tok >> 5], 1u << (tok & 31));
+}
+
+__global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict__ logits, int cols, int* __restrict__ hist, int hist_stride,
+                                                              int* __restrict__ hist_len, const int* __restrict__ cur, ProcArgs a) {
+    __shared__ unsigned seen[PROC_WORDS], ban[PROC_WORDS];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int W = (cols + 31) >> 5;
+    int* h = hist + (size_t)row * hist_stride;
+    float* lr = logits + (size_t)row * cols;
+
+    // every thread reads the length and the token to append BEFORE the barrier; thread 0 writes both behind it
+    const int n0 = min(max(hist_len[row], 0), hist_stride);
+    const bool app = cur != nullptr && n0 < hist_stride;
+    const int c = cur ? cur[row] : -1;
+    for (int w = tid; w < W; w += 1024) { seen[w] = 0; ban[w] = 0; }
+    __syncthreads();
+    if (app && tid == 0) { h[n0] = c; hist_len[row] = n0 + 1; }
+    const int n = app ? n0 + 1 : n0;                     // entries the processors see; h[n0] = c is taken from the register
+    const int g = a.ngram;
+
+    if (n > 0 && (a.penalty != 1.f || g > 0)) {
+        // the tail h[n - g + 1 .. n) the n-grams are compared with: g - 1 <= 7 tokens, once, in registers
+        const bool grams = g > 0 && n >= g;
+        int tail[PROC_G - 1];
+#pragma unroll
+        for (int j = 0; j < PROC_G - 1; ++j) {
+            const int k = min(max(n - g + 1 + j, 0), n - 1);
+            const int v = h[k];
+            tail[j] = (app && k == n0) ? c : v;
+        }
+        // position i: its token is seen; if an n-gram starts there (i + g - 1 < n) and its first g - 1 tokens equal the tail, its last
+        // token is banned.  The 8 loads of a position are independent (clamped addresses, no branch): one wait for the batch.
+        for (int i0 = 0; i0 < n; i0 += 1024) {
+            const int i = i0 + tid;
+            int w[PROC_G];
+#pragma unroll
+            for (int j = 0; j < PROC_G; ++j) {
+                const int k = min(i + (j < g ? j : 0), n - 1);
+                const int v = h[k];
+                w[j] = (app && k == n0) ? c : v;
+            }
+            if (i < n) {
+                if (a.penalty != 1.f) mark(seen, w[0], cols);
+                if (grams && i + g - 1 < n) {
+                    bool eq = true;
+                    int last = w[0];
+#pragma unroll
+                    for (int j = 0; j < PROC_G; ++j) {
+                        if (j < g - 1) eq = eq && w[j] == tail[j];
+                        if (j == g - 1) last = w[j];
+                    }
+                    if (eq) mark(ban, last, cols);
+                }
+            }
+        }
+    }
+    if (tid < 4 && tid < a.eos.n && n < a.min_new) mark(ban, a.eos.id[tid], cols);
+    if (tid >= 64 && tid < 64 + 16 && tid - 64 < a.n_suppress) mark(ban, a.suppress[tid - 64], cols);
+    __syncthreads();
+
+    const float p = a.penalty;
+    for (int w = tid; w < W; w += 1024) {
+        const unsigned b = ban[w];
+        unsigned m = seen[w] | b;
+        while (m) {
+            const int bit = __ffs(m) - 1;
+            m &= m - 1;
+            const int k = (w << 5) + bit;                // < cols: only ids inside [0, cols) set a bit
+            if ((b >> bit) & 1u) {
+                lr[k] = -INFINITY;
+            } else {
+                const float x = lr[k];
+                lr[k] = x < 0.f ? x * p : x / p;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
+                             const ProcArgs& a, hipStream_t s) {
+    VZ_CHECK_ARG(logits && hist && hist_len && rows > 0 && cols > 0 && hist_stride >= 1, "logits_process: bad argument");
+    VZ_CHECK_ARG(cols <= PROC_MAX_COLS, "logits_process: %d columns, the LDS bitmaps hold %d", cols, PROC_MAX_COLS);
+    VZ_CHECK_ARG(a.penalty > 0.f && a.ngram >= 0 && a.ngram <= PROC_G && a.min_new >= 0 && a.eos.n >= 0 && a.eos.n <= 4 && a.n_suppress >= 0 &&
+                 a.n_suppress <= 16, "logits_process: penalty %g > 0, 0 <= ngram %d <= 8, min_new %d >= 0, <= 4 eos ids (%d), <= 16 suppressed ids (%d) expected",
+                 (double)a.penalty, a.ngram, a.min_new, a.eos.n, a.n_suppress);
+    hipLaunchKernelGGL(logits_process_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, hist, hist_stride, hist_len, cur, a);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}

@@ -366,6 +366,15 @@ int vz_launch_step_advance(int* step, hipStream_t s);
 // beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
 struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);
+// HF's logits processors in front of the step's tail (logits_proc.hip): repetition penalty (1 = off), no-repeat-n-gram size (0 = off,
+// <= 8), eos ids at -inf while the history is shorter than min_new, ids at -inf always.  By value into the kernel and, as they are,
+// into the decode graph's key: no padding.
+struct ProcArgs { float penalty; int ngram, min_new; BeamEos eos; int n_suppress; int suppress[16]; };
+static_assert(sizeof(ProcArgs) == 4 * 4 + sizeof(BeamEos) + 16 * 4, "padding in ProcArgs");
+// in place on fp32 logits [rows, cols <= 65536]; the row's history hist[row * hist_stride + 0 .. hist_len[row]); cur != null: cur[row] is
+// appended first (saturating at hist_stride)
+int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
+                             const ProcArgs& a, hipStream_t s);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
                           int* next_parent, const RowEmit& emit, hipStream_t s);

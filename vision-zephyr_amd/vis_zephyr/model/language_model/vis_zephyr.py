@@ -351,16 +351,25 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               pad_token_id=None, streamer=None, stopping_criteria=None, use_cache: bool = True,
                               num_beams: int = 1, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
                               sync_every: int = 16, timing: Optional[dict] = None, prompt_lookup_num_tokens: Optional[int] = None,
-                              max_matching_ngram_size: Optional[int] = None, _spec_history=None, **unused):
+                              max_matching_ngram_size: Optional[int] = None, _spec_history=None,
+                              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                              min_new_tokens: Optional[int] = None, suppress_tokens=None, **unused):
+        from vz_hip import logits_proc
+        if eos_token_id is None:
+            eos_token_id = self.generation_config.eos_token_id
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id or []))
+        # HF's logits processors (csrc/logits_proc.hip): None = none of the four keywords is active, every path below is as it was
+        proc = logits_proc.parse(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, sorted(eos))
+        if proc is not None and num_beams != 1:
+            raise NotImplementedError("logits processors with num_beams > 1 are not built (HF applies them to log-softmax scores there)")
+        if proc is not None and self.engine.tp_size > 1:
+            raise NotImplementedError("logits processors on a tensor-parallel engine are not built")
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing, **unused)
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         if max_new_tokens is None:
             max_new_tokens = 20 if max_length is None else max(1, max_length - S)
-        if eos_token_id is None:
-            eos_token_id = self.generation_config.eos_token_id
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id or []))
         if pad_token_id is None:
             pad_token_id = self.generation_config.pad_token_id
         if pad_token_id is None:
@@ -375,7 +384,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                       device=generator.device if generator is not None else "cpu").item())
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
-        if prompt_lookup_num_tokens and _spec_history is not None:
+        if prompt_lookup_num_tokens and _spec_history is not None and proc is None:      # (with processors: the plain greedy path, same ids)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
@@ -390,13 +399,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                           _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
                 return torch.tensor([out], dtype=torch.long, device=self.device)
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
-            return self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing)
+            return self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc)
         outs = []
         for b in range(Bsz):               # per-token host callbacks / sampling: one sequence at a time
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
-                                           stopping_criteria, seed + b, sync_every, timing))
+                                           stopping_criteria, seed + b, sync_every, timing, proc))
         n = max(len(o) for o in outs)
         res = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
         for b, o in enumerate(outs):
@@ -422,17 +431,18 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             timing["spec"] = report
         return out
 
-    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None) -> torch.Tensor:
+    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step
         streams the weights once for all rows (the KV cache, positions and lengths are per slot).  Rows that hit eos keep
-        their slot but emit `pad_token_id` from then on, as HF does."""
+        their slot but emit `pad_token_id` from then on, as HF does.  `proc`: HF's logits processors (vz_hip.logits_proc) on the
+        prefill logits and, armed in the engine, on every step's."""
         eng = self.engine
         Bsz, S = embeds.shape[0], embeds.shape[1]
         cap = min(eng.max_batch, 64)
         if Bsz > cap:
             parts = [self._generate_batched(embeds[i:i + cap], seqlens[i:i + cap],
                                             None if position_ids is None else position_ids[i:i + cap], max_new, eos,
-                                            pad_token_id, sync_every) for i in range(0, Bsz, cap)]
+                                            pad_token_id, sync_every, None, proc) for i in range(0, Bsz, cap)]
             n = max(p.shape[1] for p in parts)
             out = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
             r = 0
@@ -444,6 +454,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         from vz_hip import binding as B
         _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
+        if proc is not None:
+            B.logits_process(last, proc)                 # the first step's processors see an empty history
         first = B.argmax(last)
         next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
         first_cpu = first.to(torch.long).cpu()
@@ -453,23 +465,29 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         cols = [first_cpu.view(Bsz, 1)]
         eos_t = torch.tensor(sorted(eos), dtype=torch.long)
         done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
-        eng.decode_begin(first, next_pos, list(seqlens))
-        remaining = max_new - 1
-        while remaining > 0 and not bool(done.all()):
-            n = min(sync_every, remaining) if eos else remaining
-            chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
-            remaining -= n
-            if eos:
-                hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
-                # a row is finished after its first eos (inclusive): later steps show the pad token
-                after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
-                chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
-                done_at = done.view(Bsz, 1) | (torch.cumsum(hit.to(torch.int32), dim=1) > 0)      # state after each step
-                all_done = done_at.all(dim=0)
-                if bool(all_done.any()):                                 # stop at the first step after which every row is done
-                    chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
-                done = done_at[:, chunk.shape[1] - 1]
-            cols.append(chunk)
+        if proc is not None:
+            eng.set_logits_proc(proc)
+        try:
+            eng.decode_begin(first, next_pos, list(seqlens))
+            remaining = max_new - 1
+            while remaining > 0 and not bool(done.all()):
+                n = min(sync_every, remaining) if eos else remaining
+                chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
+                remaining -= n
+                if eos:
+                    hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
+                    # a row is finished after its first eos (inclusive): later steps show the pad token
+                    after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
+                    chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
+                    done_at = done.view(Bsz, 1) | (torch.cumsum(hit.to(torch.int32), dim=1) > 0)      # state after each step
+                    all_done = done_at.all(dim=0)
+                    if bool(all_done.any()):                                 # stop at the first step after which every row is done
+                        chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
+                    done = done_at[:, chunk.shape[1] - 1]
+                cols.append(chunk)
+        finally:
+            if proc is not None:
+                eng.set_logits_proc(None)
         return torch.cat(cols, dim=1).to(self.device)
 
     # ---- beam search (hf:generation/utils.py `_beam_search`, do_sample=False; csrc/beam.hip + vz_hip/beam.py) ----------------
@@ -704,12 +722,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
         keeps ONE step in flight and reads token t from a host-visible ring when the event behind step t fires, so the callbacks
-        of token t run under step t+1 and no logits ever travel."""
+        of token t run under step t+1 and no logits ever travel.  `proc`: HF's logits processors (vz_hip.logits_proc) run on the
+        prefill logits before the first token is chosen and, armed in the engine, in front of every step's tail."""
         from vz_hip import binding as B
         eng = self.engine
         S = embeds.shape[1]
@@ -723,6 +742,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             # HF hands the (empty, since generation starts from embeddings) prompt ids to the streamer first;
             # TextStreamer(skip_prompt=True) swallows exactly one put() as "the prompt"
             streamer.put(torch.empty((1, 0), dtype=torch.long))
+        if proc is not None:
+            B.logits_process(last, proc)                 # the first step's processors see an empty history
         first = B.argmax(last) if greedy else B.sample(last, temperature, top_k, top_p, seed, 0)
         tok = int(first[0])          # int(): the host holds the first token here
         if timing is not None:
@@ -733,6 +754,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             return self._finish(out, streamer)
         eng.set_sampling(not greedy, temperature if not greedy else 1.0, top_k, top_p, seed, first_counter=1)
         try:
+            if proc is not None:
+                eng.set_logits_proc(proc)
             if per_token:
                 ring = self._token_ring()
                 R = ring.numel()
@@ -776,6 +799,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         finally:
             eng.set_sampling(False)
             eng.set_ring(None)
+            if proc is not None:
+                eng.set_logits_proc(None)
 
     def _emit(self, out, streamer, stopping_criteria, scores, eos) -> bool:
         """per-token host callbacks; returns True when generation must stop."""

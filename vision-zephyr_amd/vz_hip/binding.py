@@ -133,6 +133,8 @@ SYMBOLS = {
     "vz_op_lora_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _I, _I, C.c_ulonglong, _F, _F, _P]),
     "vz_op_vip_point": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, _P]),
     "vz_op_sample": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P, _P]),
+    "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
+    "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
@@ -624,6 +626,31 @@ def argmax(logits):
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
     check(lib().vz_op_argmax(ptr(logits), logits.shape[0], logits.shape[1], ptr(ids), stream_ptr(logits.device)))
     return ids
+
+
+def proc_lists(cfg):
+    """(eos array, n_eos, suppress array, n_suppress) of a vz_hip.logits_proc config for the C entry points."""
+    eos, sup = list(cfg.eos), list(cfg.suppress)
+    return (C.c_int * max(1, len(eos)))(*eos), len(eos), (C.c_int * max(1, len(sup)))(*sup), len(sup)
+
+
+def logits_process(logits, cfg, hist=None, hist_len=None):
+    """HF's logits processors (logits_proc.hip; cfg = vz_hip.logits_proc.parse(...)) IN PLACE on fp32 logits [rows, V] on the device,
+    over the histories hist int32 [rows, stride] of hist_len int32 [rows] ids each (None = empty: the first token of a generation).
+    Returns `logits`."""
+    _need_cuda(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    rows = logits.shape[0]
+    if hist is None:
+        hist = torch.zeros(rows, 1, dtype=torch.int32, device=logits.device)
+        hist_len = torch.zeros(rows, dtype=torch.int32, device=logits.device)
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.is_contiguous() and hist.shape[0] == rows and hist.shape[1] >= 1
+    assert hist_len.dtype == torch.int32 and hist_len.is_contiguous() and hist_len.numel() == rows
+    assert hist.device == logits.device and hist_len.device == logits.device
+    ea, ne, sa, ns = proc_lists(cfg)
+    check(lib().vz_op_logits_process(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), float(cfg.penalty),
+                                     int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns, stream_ptr(logits.device)))
+    return logits
 
 
 def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, counter: int = 0):

@@ -596,6 +596,16 @@ class Engine:
         B.check(self.lib.vz_llm_decode_sampling(self.h, int(on), float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_counter)))
 
+    def set_logits_proc(self, cfg=None):
+        """HF's logits processors in front of the argmax / the sampler of every decode step (logits_proc.hip; cfg =
+        vz_hip.logits_proc.parse(...), None = off).  Arming empties every row's history of generated ids: call it before
+        `decode_begin`, after the first token was chosen on logits that went through `binding.logits_process`."""
+        if cfg is None:
+            B.check(self.lib.vz_llm_decode_logits_proc(self.h, 0, 1.0, 0, 0, None, 0, None, 0, self._s()))
+            return
+        ea, ne, sa, ns = B.proc_lists(cfg)
+        B.check(self.lib.vz_llm_decode_logits_proc(self.h, 1, float(cfg.penalty), int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns, self._s()))
+
     def set_ring(self, ring: Optional[torch.Tensor]):
         """host-visible (pinned) int32 ring the step tails write their tokens to: [slots] for a one-row batch or [rows, slots]
         (slot = draw counter mod slots); None = off.  decode_steps refuses a batch with more rows than the ring has."""
