@@ -4,6 +4,18 @@
 // In the persistent kernel the workgroup has more waves than that: the extra waves pass `act = false` - they take part in every
 // workgroup barrier (the barrier count is uniform: it depends on the split's key range and on last_flag only) and touch no memory.
 // Arithmetic and summation orders are the stand-alone kernel's, so both paths give the same bits.
+//
+// The body is a chain of dependent memory round trips, so its loads go out in as few batches as the data dependences allow, each batch
+// free of branches (hipcc cannot count loads across a branch and drains the counter instead; tests/test_attn_decode_isa_cpu.py reads
+// the compiled waits):
+//   head   1. slot | pos together   2. ONE batch: cos, sin, the q pair, the new token's K or V pair, 8 K rows and 8 V rows of the first
+//          chunk (row indices clamped to the cache, nothing predicated) - the RoPE waits with the 16 rows in flight   [was 4 trips]
+//   merge  the last arriver of a KV head requests 2 statistics and all MAX_SPLITS partial pairs of its two outputs at once; the weights
+//          pass through LDS meanwhile   [was 1 + 2 x (8 + 8 + 1) trips at 17 splits]
+// Same values, same order of operations: tests/test_attn_decode_bits_gpu.py holds the outputs to the bits recorded before this form.
+// The persistent kernel (LEAN) keeps the predicated head; the next chunk's prefetch inside the chunk loop is predicated in every form,
+// which is why the chunk loop's first use of K still waits for K and V alike (the loop's back edge carries loads that may not have
+// been issued, and the compiler's count has to assume so).
 #pragma once
 #include "vz_common.h"
 
@@ -14,12 +26,16 @@ constexpr int G = 4;              // query heads per KV head (32 / 8)
 constexpr int CH = 128;           // keys per inner chunk
 constexpr int NR = CH / 16;       // K (and V) rows per lane per chunk
 constexpr int PW = G * D + 32;    // floats per partial record: o[4][128] | m[4] l[4] pad  (17 x 128-byte lines)
+constexpr int MAX_SPLITS = 32;    // context splits per (row, KV head): the merge holds one 8-byte partial per split in registers (every launcher checks nsplit)
 
 __device__ __forceinline__ void st_sc1(float* p, float v) {
     __hip_atomic_store((unsigned*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ float ld_sc1(const float* p) {
     return __uint_as_float(__hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ unsigned long long ld_sc1_x2(const float* p) {       // two neighbouring floats, 8-byte aligned
+    return __hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct FusedParams {
@@ -55,7 +71,11 @@ template <bool OUT_SC1, bool LEAN = false>
 __device__ __forceinline__ bool body(const FusedParams& p, const bf16_t* row, int split, int hk, int b, int tid, bool act, Shared& sm) {
     const int lane = tid & 63, wave = tid >> 6;
     const int sub = lane & 15, ks = (wave & 3) * 4 + (lane >> 4);     // 8-wide d chunk, key slot 0..15
-    const int slot = p.slot[b], len = slot + 1, position = p.pos[b];
+    // round trip 1 of the head: slot and position together (the empty asm uses both, so neither load sinks below the early return)
+    const int slot = p.slot[b], position = p.pos[b];
+    asm volatile("" ::"v"(slot), "v"(position));
+    __builtin_amdgcn_sched_barrier(0);
+    const int len = slot + 1;
     const int lo = p.window > 0 ? max(0, len - p.window) : 0;
     const int span = len - lo;
     // a split takes at least one chunk: a short context (a 16-row batch at ctx 100) is served by ONE workgroup per KV head
@@ -67,8 +87,9 @@ __device__ __forceinline__ bool body(const FusedParams& p, const bf16_t* row, in
     bf16_t* kb = p.kc + ((size_t)b * p.Hkv + hk) * (size_t)p.max_ctx * D;
     bf16_t* vb = p.vc + ((size_t)b * p.Hkv + hk) * (size_t)p.max_ctx * D;
 
-    // ---- the first chunk's K and V rows go in flight before anything else (the new token's row, index `slot`,
-    //      is not in the cache yet: it is patched in from LDS after the RoPE) ----
+    // ---- the first chunk's K and V rows go in flight together with the RoPE's operands (the new token's row, index `slot`,
+    //      is not in the cache yet: it is patched in from LDS after the RoPE).  issue_k / issue_v: the predicated form, used for
+    //      the NEXT chunk inside the chunk loop (and for the head of the persistent kernel) ----
     uint4 kreg[NR], vreg[NR];
     auto issue_k = [&](int c0, int n) {
 #pragma unroll
@@ -86,25 +107,49 @@ __device__ __forceinline__ bool body(const FusedParams& p, const bf16_t* row, in
             if (act && kk < n && kidx != slot) vreg[i] = *(const uint4*)(vb + (size_t)kidx * D + sub * 8);
         }
     };
-    if (k0 < k1) { issue_k(k0, min(CH, k1 - k0)); issue_v(k0, min(CH, k1 - k0)); }
+    // RoPE operands: cos, sin, the q pair (d, d + 64) of head hk*G + wave, and the new token's K pair (wave 0) or V pair (the other waves;
+    // wave 1 uses it)
+    const float* cosp = p.cosT + (size_t)position * (D / 2) + lane;
+    const float* sinp = p.sinT + (size_t)position * (D / 2) + lane;
+    const bf16_t* qh = row + (size_t)(hk * G + wave) * D;
+    const bf16_t* nh = row + (size_t)(wave == 0 ? p.Hq + hk : p.Hq + p.Hkv + hk) * D;
+    float c = 0.f, s = 0.f;
+    bf16_t qx = 0, qy = 0, nx = 0, ny = 0;
+    if constexpr (LEAN) {
+        // (persistent kernel: `row` is an LDS copy and `act` a run-time value - the loads stay behind their predicates)
+        issue_k(k0, min(CH, k1 - k0)); issue_v(k0, min(CH, k1 - k0));      // (split < n_active: k0 < k1)
+        if (act) {
+            c = *cosp; s = *sinp; qx = qh[lane]; qy = qh[lane + 64];
+            if (wave < 2) { nx = nh[lane]; ny = nh[lane + 64]; }
+        }
+    } else {
+        // round trip 2 of the head: ONE batch of 6 + 8 + 8 loads without a branch between them, so that the RoPE's wait is a counted one.
+        // K / V row indices are clamped to the cache's last row instead of predicated, and no select touches the loaded registers (a select
+        // makes the compiler wait for the row there): rows with kk >= n are never used (their scores are not stored, P V skips them), and row
+        // `slot` is overwritten from LDS before its use - reading it while split 0's workgroup appends it is harmless, the value is discarded.
+        c = *cosp; s = *sinp; qx = qh[lane]; qy = qh[lane + 64]; nx = nh[lane]; ny = nh[lane + 64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) kreg[i] = *(const uint4*)(kb + (size_t)min(k0 + ks + 16 * i, p.max_ctx - 1) * D + sub * 8);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) vreg[i] = *(const uint4*)(vb + (size_t)min(k0 + ks + 16 * i, p.max_ctx - 1) * D + sub * 8);
+        __builtin_amdgcn_sched_barrier(0);      // the RoPE below waits for its 6 operands with these 16 in flight (vmcnt(16))
+    }
 
     // ---- RoPE: thread (h = wave, pair = lane) rotates (d, d+64) of query head hk*G + h ----
     if (act) {
-        const float c = p.cosT[(size_t)position * (D / 2) + lane], s = p.sinT[(size_t)position * (D / 2) + lane];
-        const bf16_t* qh = row + (size_t)(hk * G + wave) * D;
-        const float x = bf16_to_f32(qh[lane]), y = bf16_to_f32(qh[lane + 64]);
+        const float x = bf16_to_f32(qx), y = bf16_to_f32(qy);
         // rounded to bf16 exactly like the stand-alone RoPE kernel before the attention consumes it
         sm.q_s[wave][lane] = bf16_to_f32(f32_to_bf16(x * c - y * s)) * p.scale;
         sm.q_s[wave][lane + 64] = bf16_to_f32(f32_to_bf16(y * c + x * s)) * p.scale;
         if (wave == 0) {
-            const bf16_t* kh = row + (size_t)(p.Hq + hk) * D;
-            const float kx = bf16_to_f32(kh[lane]), ky = bf16_to_f32(kh[lane + 64]);
+            const float kx = bf16_to_f32(nx), ky = bf16_to_f32(ny);
             sm.knew[lane] = f32_to_bf16(kx * c - ky * s);
             sm.knew[lane + 64] = f32_to_bf16(ky * c + kx * s);
         } else if (wave == 1) {
-            const bf16_t* vh = row + (size_t)(p.Hq + p.Hkv + hk) * D;
-            sm.vnew[lane] = vh[lane];
-            sm.vnew[lane + 64] = vh[lane + 64];
+            sm.vnew[lane] = nx;
+            sm.vnew[lane + 64] = ny;
         }
     }
     if (act && tid < G) { sm.stat[G + tid] = -INFINITY; sm.stat[2 * G + tid] = 0.f; }
@@ -267,10 +312,20 @@ __device__ __forceinline__ bool body(const FusedParams& p, const bf16_t* row, in
     if (!sm.last_flag) return false;
     const float* pp = p.part + ((size_t)b * p.Hkv + hk) * p.nsplit * PW;
     float* wgt = &sm.red[0][0][0];            // [G][64] weights, then [G] 1/l   (red is free again)
+    // The merge is ONE round trip: the statistics of every split and all of this thread's partial sums are requested before anything is
+    // waited for.  Thread t takes outputs 2t and 2t + 1 (both of head t >> 6): one 8-byte load per split over the compile-time bound
+    // MAX_SPLITS, the split index clamped to n_active - 1 instead of a branch around the load (a branch makes the compiler drain the
+    // counter per load: the loop this replaces cost 2 x (8 + 8 + 1) dependent trips at 17 splits).  The weights pass through LDS
+    // while the partials are in flight; splits >= n_active are left out of the sum by a select.
+    const int h = tid >> 6;
+    unsigned long long pr[MAX_SPLITS];
     if (act) {
-        const int h = tid >> 6, s2 = tid & 63;
-        float ms = -INFINITY, ls = 0.f;
-        if (s2 < n_active) { ms = ld_sc1(pp + (size_t)s2 * PW + G * D + h); ls = ld_sc1(pp + (size_t)s2 * PW + G * D + G + h); }
+        const int s2 = tid & 63, sc = min(s2, n_active - 1);
+        float ms = ld_sc1(pp + (size_t)sc * PW + G * D + h), ls = ld_sc1(pp + (size_t)sc * PW + G * D + G + h);
+#pragma unroll
+        for (int s3 = 0; s3 < MAX_SPLITS; ++s3) pr[s3] = ld_sc1_x2(pp + (size_t)min(s3, n_active - 1) * PW + 2 * tid);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s2 >= n_active) { ms = -INFINITY; ls = 0.f; }
         const float m = wave_max(ms);
         const float w = ms == -INFINITY ? 0.f : __expf(ms - m);
         const float l = wave_sum(w * ls);
@@ -279,20 +334,19 @@ __device__ __forceinline__ bool body(const FusedParams& p, const bf16_t* row, in
     }
     __syncthreads();
     if (act) {
-        for (int i = tid; i < G * D; i += 256) {
-            const int h = i >> 7;
-            float a = 0.f;
-#pragma unroll 8
-            for (int s2 = 0; s2 < n_active; ++s2) a += wgt[h * 64 + s2] * ld_sc1(pp + (size_t)s2 * PW + i);
-            const unsigned short ob = f32_to_bf16(a * wgt[G * 64 + h]);
-            bf16_t* dst = p.o + ((size_t)b * p.Hq + hk * G) * D + i;
-            if (OUT_SC1) {       // two neighbouring outputs per 4-byte write-through store (the even lane stores the pair)
-                const unsigned other = __shfl_xor((unsigned)ob, 1, 64);
-                if ((lane & 1) == 0) __hip_atomic_store((unsigned*)dst, (unsigned)ob | (other << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                *dst = ob;
-            }
+        float a0 = 0.f, a1 = 0.f;       // the same fmaf chain from 0.f in ascending split order as before
+#pragma unroll
+        for (int s3 = 0; s3 < MAX_SPLITS; ++s3) {
+            const float w = wgt[h * 64 + s3];
+            const float t0 = fmaf(w, __uint_as_float((unsigned)pr[s3]), a0), t1 = fmaf(w, __uint_as_float((unsigned)(pr[s3] >> 32)), a1);
+            a0 = s3 < n_active ? t0 : a0;
+            a1 = s3 < n_active ? t1 : a1;
         }
+        const float inv = wgt[G * 64 + h];
+        const unsigned pair = (unsigned)f32_to_bf16(a0 * inv) | ((unsigned)f32_to_bf16(a1 * inv) << 16);
+        unsigned* dst = (unsigned*)(p.o + ((size_t)b * p.Hq + hk * G) * D + 2 * tid);
+        if (OUT_SC1) __hip_atomic_store(dst, pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through, for the in-launch hand-off
+        else *dst = pair;
     }
     if (tid == 0) __hip_atomic_store(p.ticket + (size_t)b * p.Hkv + hk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;

@@ -20,6 +20,10 @@
 // (QKV role one block per CU, the cached K / V requested before QKV had finished, the O role waiting for QKV before it streams): bit-identical,
 // 30.3 us against 11.3 + 19.4 - the QKV role's slowest block finished at ~16 us (a CU's memory pipe accepts only ~25-60 GB/s and the role
 // shares it with the other roles' K / V loads and polls), which ate what the earlier K / V loads and the saved boundary gave.
+// Since then the attention body's own chain got shorter (attn_decode_body.h: slot | pos, then ONE batch of loads in the head; the merge's
+// statistics and partials in ONE round trip) and the O role's delay was scanned again against it (12 -> 8 units): 16.7 -> 15.65 us for the
+// two parts, 14.9 us with the delay, 365.4 -> 372.1 tok/s (profiles/attn_chain_ab.txt, attn_chain_kernel_stats.txt).  Not done in the
+// O role: requesting p.step[0] ahead of the weights - wave 0's first poll returns behind its own 16 weight loads in either order.
 // Hand-off form: cdna guide section 6 G16 / MI355X notes, measured row 1 (sc1 payload stores drained by every storing wave, workgroup
 // barrier, one agent-scope add; consumer: sc1 poll, workgroup barrier, sc1 loads).
 #include "attn_decode_body.h"
@@ -174,7 +178,7 @@ __global__ __launch_bounds__(256, 3) void attn_o_fused_kernel(AoParams p) {     
 
 }  // namespace
 
-int g_attn_o_delay = 12;      // vz_tune_set(31, n): the O role waits n x ~0.21 us before requesting its weights, so that the attention blocks' K / V loads reach the memory system first (scan at ctx 2048: 0 -> 344, 8 -> 346, 12 -> 357, 16 -> 352, 24 -> 348 tok/s)
+int g_attn_o_delay = 8;       // vz_tune_set(31, n): the O role waits n x ~0.21 us before requesting its weights, so that the attention blocks' K / V loads reach the memory system first (scan at ctx 2048 with the two-trip head, two runs each: 0 -> 372.5-372.7, 4 -> 375.4-377.4, 8 -> 376.5-377.0, 12 -> 373.0-373.6, 16 -> 368.8-370.0 tok/s; against the four-trip head it was 12: 0 -> 344, 8 -> 346, 12 -> 357, 16 -> 352, 24 -> 348)
 int vz_launch_attn_o_fused(const AttnDecodeFusedArgs& a, const bf16_t* o_w, const unsigned char* o_w8, const float* o_scale, bf16_t* att_scratch,
                            bf16_t* x, unsigned* done, const int* step, int layer, int n_layers, int* err, hipStream_t s) {
     VZ_CHECK_ARG((a.B == 1 || a.B == 2) && a.D == D && a.Hq == 32 && a.Hkv == 8 && a.nsplit >= 1 && a.B * a.nsplit <= 32,
