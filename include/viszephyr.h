@@ -460,6 +460,23 @@ int vz_engine_unset_weight(vz_engine* e, const char* name);
 int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds, int B, int S, const int* h_seqlens, const int* d_pos,
                         float* d_logits_all, float* d_logits_last, vz_stream stream);
 int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_pos, int ctx_len, vz_stream stream);
+/* Per-row tail (csrc/sampling.hip: sample_rows_kernel): every row of the decode batch chooses its next token by its own entry of a table
+ * in device memory - mode 0 = greedy (first maximal index), 1 = sample with the row's own temperature > 0, top_k >= 0, 0 < top_p <= 1,
+ * 64-bit seed and draw counter >= 0 (the kernel counts it up after every step).  A sampled row gets the bits vz_op_sample gives a ONE-row
+ * call with the same parameters: its Philox counter is (vocab index, 0, draw counter), so the draws of a request do not depend on the cache
+ * row it decodes in.  The captured step reads the table through a pointer: changing an entry changes no kernel argument and captures nothing.
+ * vz_llm_decode_sampling_rows(enable=1): arms the tail and keeps `rows` entries (0..max_batch; the rows behind them greedy) for the NEXT
+ * vz_llm_decode_begin to upload; enable = 0: the argmax / the sampler again.  vz_llm_decode_set_row_sampling: one row's entry of the running
+ * batch, stream-ordered - the counterpart of vz_llm_decode_set_row.  The logits processors may sit in front of the tail as in front of
+ * the sampler; vz_llm_decode_steps refuses it together with the beam or the speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.
+ * vz_op_sample_rows: the same kernel on fp32 logits [rows <= 64, cols] (the first token of each sequence from the prefill logits with
+ * counter 0; tests). */
+int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                const float* h_top_p, const unsigned long long* h_seed, const int* h_counter);
+int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, unsigned long long seed,
+                                   int counter, vz_stream stream);
+int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                      const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream);
 /* Batched admissions: prefill several requests together into spare cache rows (row0 >= the running batch), then move each one's
  * first h_len[i] cache positions from row h_src[i] to the freed row h_dst[i] (every layer, K and V; stream-ordered).  Rows of
  * one call must not overlap (no destination equal to another move's source or destination). */

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Batched greedy decode throughput: B text-only prompts of 64 ids, 64 new tokens each, Zephyr-7B shape.
-    python tools/bench_batched.py [layers]"""
+    python tools/bench_batched.py [layers] [fp8]
+    python tools/bench_batched.py [layers] --sample      the per-row sampling tail: step time at 16 and 64 rows with
+                                                         every row sampling (T 0.7, top_k 50, top_p 0.9) next to the greedy step at the same rows
+Under `rocprofv3 --kernel-trace --stats` the --sample leg's kernels of interest are sample_rows_kernel and argmax_kernel."""
 import os
 import sys
 import time
@@ -13,6 +16,8 @@ import torch  # noqa: E402
 from bench import build_model  # noqa: E402
 from vz_hip import synth  # noqa: E402
 
+SAMPLE = "--sample" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--sample"]
 layers = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 import bench  # noqa: E402
 
@@ -36,8 +41,44 @@ model = build(64)
 for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):       # experiments: "knob=value,..." for vz_tune_set
     from vz_hip import binding as _B
     _B.check(_B.lib().vz_tune_set(*(int(v) for v in kv.split("="))))
-ROWS = [int(v) for v in os.environ.get("VZ_ROWS", "1,2,4,8,16,32,48,64").split(",")]
+ROWS = [int(v) for v in os.environ.get("VZ_ROWS", "16,64" if SAMPLE else "1,2,4,8,16,32,48,64").split(",")]
 n_new = 64
+
+
+def step_ms(B, params, reps=5):
+    """ms per decode step of B rows behind 64-id prompts: n_new - 1 graph steps per window, ended by a device synchronise; (best, median) of
+    `reps` windows after a warm-up window.  params = the per-row table (vz_hip.sample_rows.RowParams per row), None = the greedy tail."""
+    from vz_hip import binding as Bd
+    eng = model.engine
+    ids = torch.stack([synth.synth_ids(64, 32000, image_pos=-1, seed=10 + b) for b in range(B)]).cuda()
+    _, last = eng.prefill(eng.embed_tokens(ids), [64] * B)
+    first = Bd.argmax(last)
+    out = torch.empty(B, n_new - 1, dtype=torch.int32, device="cuda:0")
+    ts = []
+    eng.set_sampling_rows(params)
+    try:
+        for _ in range(reps + 1):
+            eng.decode_begin(first, [64] * B, [64] * B)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.decode_steps(n_new - 1, out=out)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / (n_new - 1) * 1e3)
+    finally:
+        eng.set_sampling_rows(None)
+    ts = sorted(ts[1:])
+    return ts[0], ts[len(ts) // 2]
+
+
+if SAMPLE:
+    from vz_hip.sample_rows import RowParams
+    for B in ROWS:
+        g = step_ms(B, None)
+        sm = step_ms(B, [RowParams(True, 0.7, 50, 0.9, 1000 + r, 1) for r in range(B)])
+        g2 = step_ms(B, None)
+        print(f"rows {B}: greedy step {g[0]:.4f} ms (median {g[1]:.4f}; again {g2[0]:.4f} / {g2[1]:.4f}), per-row sampled step {sm[0]:.4f} ms "
+              f"(median {sm[1]:.4f}): {(sm[0] / min(g[0], g2[0]) - 1) * 100:+.2f} % on the best, {B / sm[0] * 1e3:.0f} sampled tokens/s", flush=True)
+    sys.exit(0)
 for B in ROWS:
     ids = torch.stack([synth.synth_ids(64, 32000, image_pos=-1, seed=10 + b) for b in range(B)]).cuda()
     model.generate(input_ids=ids, do_sample=False, max_new_tokens=n_new, eos_token_id=None, pad_token_id=2)

@@ -314,7 +314,10 @@ extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, v
 // ------------------------------------------------------------------------------------------------
 // engine
 // ------------------------------------------------------------------------------------------------
-static TailKind tail_kind(const vz_engine* e) { return e->spec.on ? TAIL_SPEC : e->beam.on ? TAIL_BEAM : e->samp.on ? TAIL_SAMPLE : TAIL_GREEDY; }
+static TailKind tail_kind(const vz_engine* e) {
+    return e->spec.on ? TAIL_SPEC : e->beam.on ? TAIL_BEAM : e->rows.on ? TAIL_ROWS : e->samp.on ? TAIL_SAMPLE : TAIL_GREEDY;
+}
+static bool tail_takes_proc(TailKind t) { return t == TAIL_GREEDY || t == TAIL_SAMPLE || t == TAIL_ROWS; }      // the logits processors may sit in front of it
 
 // One linear C = epi(A . W^T + W.b) of the engine: the route follows the row count, the caller (decode = the rows are the independent
 // sequences of a decode step) and what finalize attached to W - vz_plan_linear picks the copy the kernel reads.
@@ -1083,6 +1086,7 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
         hs.len[b] = h_ctx_len[b] + 1;      // keys visible to the next token
     }
     *hs.ctr = e->samp.ctr0; hs.seed[0] = e->samp.seed[0]; hs.seed[1] = e->samp.seed[1];      // (step = 0)
+    for (size_t r = 0; r < e->rows.tab.size(); ++r) hs.samp[r] = e->rows.tab[r];            // (never set: zeros = every row greedy)
     RC(upload_ints(e, hs.pos, h.size() - mb, ds.pos, s));
     VZ_CHECK_HIP(hipMemcpyAsync(ds.cur, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
     e->dec_B = B;
@@ -1236,7 +1240,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         ProfScope ps(e, K_OTHER, s);
         // per row: the token into d_out_ids (and the ring), position / slot / length one further
         const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
-        if (e->proc.on && (tail == TAIL_GREEDY || tail == TAIL_SAMPLE)) {
+        if (e->proc.on && tail_takes_proc(tail)) {
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
             RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, s));
         }
@@ -1259,6 +1263,9 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             RC(vz_launch_beam_advance(v.hidx, s));
             break;
         }
+        case TAIL_ROWS:
+            RC(vz_launch_sample_rows(e->d_logits, B, c.vocab, st.samp, st.cur, emit, s));
+            break;
         case TAIL_SAMPLE:
             RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, st.seed, st.ctr, 0, st.cur, emit, s));
             break;
@@ -1285,6 +1292,71 @@ extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperatur
     e->samp.on = 1; e->samp.a = SampleArgs{top_k, temperature, top_p};
     e->samp.seed[0] = (unsigned)seed; e->samp.seed[1] = (unsigned)(seed >> 32);
     return VZ_OK;
+}
+
+// The per-row tail: every row of the decode batch chooses its next token by its own entry of a table in device memory (sampling.hip:
+// sample_rows_kernel) - greedy, or sampled with its own temperature / top-k / top-p, 64-bit seed and draw counter.  Rows are independent
+// requests (continuous batching) or the n samples of one prompt.  An entry is checked as vz_llm_decode_sampling checks its arguments.
+static int row_sample_of(int mode, float temperature, int top_k, float top_p, unsigned long long seed, int counter, RowSample* out) {
+    VZ_CHECK_ARG((mode == VZ_ROW_GREEDY || mode == VZ_ROW_SAMPLE) && counter >= 0, "row sampling: mode %d (0 = greedy, 1 = sample), counter %d >= 0 expected", mode, counter);
+    VZ_CHECK_ARG(mode == VZ_ROW_GREEDY || (temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f),
+                 "row sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
+    *out = mode == VZ_ROW_GREEDY ? RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, counter, 0}
+                                 : RowSample{VZ_ROW_SAMPLE, temperature, top_k, top_p, {(unsigned)seed, (unsigned)(seed >> 32)}, counter, 0};
+    return VZ_OK;
+}
+static int row_samples_of(int rows, const int* h_mode, const float* h_temperature, const int* h_top_k, const float* h_top_p,
+                          const unsigned long long* h_seed, const int* h_counter, RowSample* out) {
+    VZ_CHECK_ARG(rows == 0 || (h_mode && h_temperature && h_top_k && h_top_p && h_seed && h_counter), "row sampling: null parameter array");
+    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_seed[r], h_counter[r], out + r));
+    return VZ_OK;
+}
+
+// enable = 1: the tail of every decode step is the per-row kernel, and the NEXT vz_llm_decode_begin uploads these `rows` entries (row r =
+// the r-th element of each array; the rows behind them greedy, rows = 0: every row greedy until vz_llm_decode_set_row_sampling arms it).
+// The table is device memory the captured step reads through a pointer: a changed entry needs no new graph.  enable = 0: off.
+extern "C" int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                           const float* h_top_p, const unsigned long long* h_seed, const int* h_counter) {
+    VZ_CHECK_ARG(e, "decode_sampling_rows: null engine");
+    if (!enable) { e->rows.on = 0; e->rows.tab.clear(); return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_sampling_rows: the per-row tail on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(rows >= 0 && rows <= e->c.max_batch, "decode_sampling_rows: %d rows outside [0, max_batch = %d]", rows, e->c.max_batch);
+    std::vector<RowSample> tab((size_t)e->c.max_batch, RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0});
+    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_seed, h_counter, tab.data()));
+    e->rows.tab.swap(tab);
+    e->rows.on = 1;
+    return VZ_OK;
+}
+
+// The sampling counterpart of vz_llm_decode_set_row: one row's entry of the running batch, stream-ordered, the other rows untouched.
+extern "C" int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, unsigned long long seed,
+                                              int counter, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row_sampling: row %d outside the running batch of %d", row, e->dec_B);
+    RowSample rs;
+    RC(row_sample_of(mode, temperature, top_k, top_p, seed, counter, &rs));
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(e->h_pinned && e->h_pinned_ints >= (size_t)DecodeState::SAMPLE_INTS, "decode_set_row_sampling: no staging buffer (vz_llm_decode_begin allocates it)");
+    VZ_CHECK_HIP(hipStreamSynchronize(s));                        // previous use of the staging buffer has drained
+    memcpy(e->h_pinned, &rs, sizeof(rs));
+    VZ_CHECK_HIP(hipMemcpyAsync(decode_state(e->d_state, e->c.max_batch).samp + row, e->h_pinned, sizeof(rs), hipMemcpyHostToDevice, s));
+    return VZ_OK;
+}
+
+// one token per row of fp32 logits [rows, cols] with the per-row kernel, rows <= 64 (the first tokens of sampled sequences, drawn from
+// the prefill logits with counter 0; tests).  The table goes through this (device, stream)'s own scratch.
+extern "C" int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                 const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_logits && d_ids && rows >= 1 && rows <= 64 && cols >= 1, "sample_rows: bad argument (1..64 rows)");
+    RowSample tab[64];
+    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_seed, h_counter, tab));
+    void* p = nullptr; size_t have = 0;
+    RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
+    VZ_CHECK_ARG(p && have >= sizeof(tab), "sample_rows: first use of a stream inside a capture (call it once before capturing)");
+    VZ_CHECK_HIP(hipMemcpyAsync(p, tab, (size_t)rows * sizeof(RowSample), hipMemcpyHostToDevice, s));
+    VZ_CHECK_HIP(hipStreamSynchronize(s));          // the table is on this frame: it has been read before the call returns
+    return vz_launch_sample_rows(d_logits, rows, cols, (RowSample*)p, d_ids, {}, s);
 }
 
 // Streamer / stopping-criteria path: besides d_out_ids every step's tail also writes its token to ring[row * ring_n + (draw
@@ -1550,7 +1622,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_SPEC: k.spec = e->spec.a; break;
     case TAIL_BEAM: k.beam = e->beam.a; break;
     case TAIL_SAMPLE: k.samp = e->samp.a; break;
-    case TAIL_GREEDY: break;
+    case TAIL_ROWS: case TAIL_GREEDY: break;
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; }
     return k;
@@ -1570,8 +1642,10 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                  "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
                  "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
-    VZ_CHECK_ARG(!e->proc.on || tail == TAIL_GREEDY || tail == TAIL_SAMPLE, "decode_steps: the logits processors (vz_llm_decode_logits_proc) run in "
+    VZ_CHECK_ARG(!e->proc.on || tail_takes_proc(tail), "decode_steps: the logits processors (vz_llm_decode_logits_proc) run in "
                  "front of the argmax or the sampler only, not with the beam or the speculative tail");
+    VZ_CHECK_ARG(!e->rows.on || (!e->beam.on && !e->spec.on && e->tp == 1), "decode_steps: the per-row tail (vz_llm_decode_sampling_rows) does not run "
+                 "together with the beam or the speculative tail, nor on a tensor-parallel engine");
     DecodeWs w;
     RC(carve_stage(e, "decode", [&](Carver& m) { return carve_decode(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, spec); }, &w));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of

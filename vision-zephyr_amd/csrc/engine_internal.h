@@ -36,21 +36,22 @@ static constexpr float ATTN_SCALE = 0.08838834764831845f;      // 128^-0.5 (vz_e
 
 // The device-side state of a decode batch of max_batch = mb rows: [cur | pos | slot | len], mb ints each (the row's input token, its
 // rotary position, the cache slot its keys are appended to, the keys it sees), then WORDS ints: the step index inside the running
-// vz_llm_decode_steps call, the draws since vz_llm_decode_begin, the sampler's seed (lo, hi).
+// vz_llm_decode_steps call, the draws since vz_llm_decode_begin, the sampler's seed (lo, hi); then the per-row tail's table, one
+// RowSample per row (16-byte aligned: 4 * (mb + 1) ints precede it).
 struct DecodeState {
-    static constexpr int ROW_ARRAYS = 4, WORDS = 4;
-    int *cur, *pos, *slot, *len, *step, *ctr; unsigned* seed;
-    static size_t ints(int mb) { return (size_t)ROW_ARRAYS * mb + WORDS; }
+    static constexpr int ROW_ARRAYS = 4, WORDS = 4, SAMPLE_INTS = sizeof(RowSample) / sizeof(int);
+    int *cur, *pos, *slot, *len, *step, *ctr; unsigned* seed; RowSample* samp;
+    static size_t ints(int mb) { return (size_t)(ROW_ARRAYS + SAMPLE_INTS) * mb + WORDS; }
 };
 static DecodeState decode_state(int* base, int mb) {
     int* w = base + DecodeState::ROW_ARRAYS * mb;
-    return {base, base + mb, base + 2 * mb, base + 3 * mb, w, w + 1, (unsigned*)(w + 2)};
+    return {base, base + mb, base + 2 * mb, base + 3 * mb, w, w + 1, (unsigned*)(w + 2), (RowSample*)(w + DecodeState::WORDS)};
 }
 
-// The tail of a decode step turns the logits into the next tokens: speculative verify > beam select > sampler > argmax, whichever
-// armed mode comes first (tail_kind).  The *Args of a mode are what its kernels take by value - a captured step freezes them, so
+// The tail of a decode step turns the logits into the next tokens: speculative verify > beam select > per-row table > sampler > argmax,
+// whichever armed mode comes first (tail_kind).  The *Args of a mode are what its kernels take by value - a captured step freezes them, so
 // they go into the graph key as they are; they are laid out without padding (the key is compared with memcmp).
-enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC };
+enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC, TAIL_ROWS };      // TAIL_ROWS takes nothing by value: its table is device memory
 struct SampleArgs { int top_k; float temp, top_p; };
 struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
 struct SpecArgs {
@@ -115,6 +116,8 @@ struct vz_engine {
     // the step's tail (tail_kind): each mode is armed on its own, so disarming one falls back to the next armed one
     // sampling (vz_llm_decode_sampling): ctr0 / seed = the draw counter and the key the next vz_llm_decode_begin uploads
     struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f}; } samp;
+    // per-row table (vz_llm_decode_sampling_rows): tab = the max_batch entries the next vz_llm_decode_begin uploads (all greedy until set)
+    struct { int on = 0; std::vector<RowSample> tab; } rows;
     // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)
     struct { int on = 0; BeamArgs a{}; int* d = nullptr; } beam;
     // prompt-lookup speculation (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0; base_len / base_pos = keys visible

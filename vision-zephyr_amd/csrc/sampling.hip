@@ -63,14 +63,13 @@ __device__ __forceinline__ float block_max(float v, SampleShared& sh) {
         for (int k = tid; k < cols; k += 1024) { const float x = lr[k] / temperature; BODY }                         \
     }
 
+// One row's draw, steps 1..4 above, up to each thread's own best (value, index) of the race; `stream_row` = the Philox counter's
+// row word.  Shared by the two kernels below, so a row gets the same bits from either.
 template <bool REG>
-__global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ logits, int cols, float temperature, int top_k,
-                                                      float top_p, const unsigned* __restrict__ seed, const int* __restrict__ ctr,
-                                                      int ctr_add, int* __restrict__ ids, RowEmit emit) {
-    __shared__ SampleShared sh;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* lr = logits + (size_t)row * cols;
-
+__device__ __forceinline__ void sample_row_race(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
+                                                unsigned k0, unsigned k1, unsigned stream_row, unsigned c2, SampleShared& sh,
+                                                float& bv, int& bi) {
+    const int tid = threadIdx.x;
     extern __shared__ float lx[];          // REG: cols floats
     if (REG) {
         float t[32];
@@ -155,18 +154,21 @@ __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ 
     const unsigned keep = kth > pth ? kth : pth;
 
     // ---- 4. Gumbel race over the kept tokens ----
-    const unsigned k0 = seed[0], k1 = seed[1];
-    const unsigned c2 = (unsigned)(ctr[0] + ctr_add);
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    bv = -INFINITY;
+    bi = 0x7fffffff;
     VZ_FOR_LOGITS({
         if (fkey(x) >= keep) {
-            const unsigned w = philox_word0((unsigned)k, (unsigned)row, c2, 0x565au, k0, k1);
+            const unsigned w = philox_word0((unsigned)k, stream_row, c2, 0x565au, k0, k1);
             const float u = ((float)(w >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23; exact in fp32, inside (0, 1)
             const float v = x - logf(-logf(u));
             if (v > bv || (v == bv && k < bi)) { bv = v; bi = k; }
         }
     })
+}
+
+// the workgroup's best of the threads' (value, index): larger value, ties to the smaller index; the result is thread 0's
+__device__ __forceinline__ int block_first_best(float bv, int bi, SampleShared& sh) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o, 64);
@@ -179,8 +181,64 @@ __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ 
         for (int w = 1; w < 16; ++w)
             if (sh.redf[w] > bv || (sh.redf[w] == bv && sh.redi[w] < bi)) { bv = sh.redf[w]; bi = sh.redi[w]; }
         if (bi == 0x7fffffff) bi = 0;     // all-NaN row
+    }
+    return bi;
+}
+
+template <bool REG>
+__global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ logits, int cols, float temperature, int top_k,
+                                                      float top_p, const unsigned* __restrict__ seed, const int* __restrict__ ctr,
+                                                      int ctr_add, int* __restrict__ ids, RowEmit emit) {
+    __shared__ SampleShared sh;
+    const int row = blockIdx.x;
+    const unsigned c2 = (unsigned)(ctr[0] + ctr_add);
+    float bv;
+    int bi;
+    sample_row_race<REG>(logits + (size_t)row * cols, cols, temperature, top_k, top_p, seed[0], seed[1], (unsigned)row, c2, sh, bv, bi);
+    bi = block_first_best(bv, bi, sh);
+    if (threadIdx.x == 0) {
         ids[row] = bi;
         vz_emit_advance(emit, row, bi, c2);          // ring slot = draw counter
+    }
+}
+
+// The per-row tail (continuous batching, n samples of one prompt): every row takes its parameters from its own entry of a table in
+// device memory, so re-arming a row changes no kernel argument and a captured step stays valid.  A sampled row draws as sample_kernel
+// does when called on that row alone - Philox counter (vocab index, 0, the row's draw counter, 0x565a) under the row's own seed: its
+// draws do not depend on the cache row it sits in.  A greedy row takes the first maximal index, as argmax_kernel does.  Then the row's
+// draw counter moves on by one (parked rows of a continuous batch step for ever: theirs just counts).
+template <bool REG>
+__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ logits, int cols, RowSample* tab, int* __restrict__ ids,
+                                                           RowEmit emit) {
+    __shared__ SampleShared sh;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lr = logits + (size_t)row * cols;
+    // the entry is the same for every lane: one 32-byte read at the top, held in scalar registers from then on
+    const int4 e0 = ((const int4*)(tab + row))[0], e1 = ((const int4*)(tab + row))[1];
+    const int mode = __builtin_amdgcn_readfirstlane(e0.x), top_k = __builtin_amdgcn_readfirstlane(e0.z);
+    const float temperature = __int_as_float(__builtin_amdgcn_readfirstlane(e0.y)), top_p = __int_as_float(__builtin_amdgcn_readfirstlane(e0.w));
+    const unsigned k0 = (unsigned)__builtin_amdgcn_readfirstlane(e1.x), k1 = (unsigned)__builtin_amdgcn_readfirstlane(e1.y);
+    const int ctr = __builtin_amdgcn_readfirstlane(e1.z);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    if (mode == VZ_ROW_GREEDY) {
+        if (REG) {          // the row as one batch of loads, as the sampled rows stage it
+            float t[32];
+#pragma unroll
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; t[i] = k < cols ? lr[k] : -INFINITY; }
+#pragma unroll
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; if (k < cols && (t[i] > bv || (t[i] == bv && k < bi))) { bv = t[i]; bi = k; } }
+        } else {
+            for (int k = tid; k < cols; k += 1024) { const float v = lr[k]; if (v > bv || (v == bv && k < bi)) { bv = v; bi = k; } }
+        }
+    } else {
+        sample_row_race<REG>(lr, cols, temperature, top_k, top_p, k0, k1, 0u, (unsigned)ctr, sh, bv, bi);
+    }
+    bi = block_first_best(bv, bi, sh);
+    if (tid == 0) {
+        ids[row] = bi;
+        vz_emit_advance(emit, row, bi, emit.ring ? (unsigned)emit.step[1] : 0u);      // ring slot = the draws since decode_begin, as the argmax tail
+        tab[row].ctr = ctr + 1;
     }
 }
 
@@ -192,6 +250,7 @@ int vz_init_sampling_kernels() {
     static VzDeviceOnce once;
     if (!vz_device_first(once)) return VZ_OK;
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     g_sample_lds_ok = true;
     return VZ_OK;
 }
@@ -205,6 +264,18 @@ int vz_launch_sample(const float* logits, int rows, int cols, float temperature,
         hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
     else
         hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+// tab: one RowSample per row, in device memory (the host entries were checked by whoever wrote them: row_sample_of, engine.hip)
+int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* tab, int* ids, const RowEmit& emit, hipStream_t s) {
+    VZ_CHECK_ARG(logits && ids && tab && rows > 0 && cols > 0 && (!emit.ring || emit.ring_n > 0), "sample_rows: bad argument");
+    { int r = vz_init_sampling_kernels(); if (r) return r; }
+    if (cols <= 32768 && g_sample_lds_ok)
+        hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, tab, ids, emit);
+    else
+        hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, tab, ids, emit);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -349,7 +349,13 @@ __device__ __forceinline__ void vz_emit_advance(const RowEmit& t, int row, int t
     if (t.pos && t.pos[row] + 1 < t.rope_max) t.pos[row] += 1;
     if (t.len && t.len[row] < t.max_ctx) { t.len[row] += 1; if (t.slot) t.slot[row] += 1; }
 }
+// One decode row's entry of the per-row tail's table (sampling.hip: sample_rows_kernel), 32 bytes in device memory: how the row's next
+// token is chosen, and the row's own Philox key and draw counter (the kernel counts it up).
+enum { VZ_ROW_GREEDY = 0, VZ_ROW_SAMPLE = 1 };
+struct RowSample { int mode; float temp; int top_k; float top_p; unsigned seed[2]; int ctr; int pad; };
+static_assert(sizeof(RowSample) == 32, "RowSample is read as two 16-byte words");
 int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const RowEmit& emit, hipStream_t s);
+int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* tab, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const unsigned* seed,
                      const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s);
 // set dynamic-LDS limits of every kernel up front (never inside a stream capture)

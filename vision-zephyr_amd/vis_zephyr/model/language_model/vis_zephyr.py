@@ -103,6 +103,32 @@ class PastKeyValues:
         return max(self.lengths) if self.lengths else 0
 
 
+def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every) -> torch.Tensor:
+    """the steps of a batch `decode_begin` has armed with the rows' first tokens `first_cpu` (host): [rows, <= max_new] new tokens,
+    `sync_every` steps per host sync (host tensor), a row showing `pad_token_id` behind its eos, until every row is done."""
+    Bsz = first_cpu.numel()
+    cols = [first_cpu.view(Bsz, 1)]
+    eos_t = torch.tensor(sorted(eos), dtype=torch.long)
+    done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
+    remaining = max_new - 1
+    while remaining > 0 and not bool(done.all()):
+        n = min(sync_every, remaining) if eos else remaining
+        chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
+        remaining -= n
+        if eos:
+            hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
+            # a row is finished after its first eos (inclusive): later steps show the pad token
+            after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
+            chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
+            done_at = done.view(Bsz, 1) | (torch.cumsum(hit.to(torch.int32), dim=1) > 0)      # state after each step
+            all_done = done_at.all(dim=0)
+            if bool(all_done.any()):                                 # stop at the first step after which every row is done
+                chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
+            done = done_at[:, chunk.shape[1] - 1]
+        cols.append(chunk)
+    return torch.cat(cols, dim=1)
+
+
 class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     config_class = VisZephyrConfig
 
@@ -353,8 +379,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               sync_every: int = 16, timing: Optional[dict] = None, prompt_lookup_num_tokens: Optional[int] = None,
                               max_matching_ngram_size: Optional[int] = None, _spec_history=None,
                               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                              min_new_tokens: Optional[int] = None, suppress_tokens=None, **unused):
-        from vz_hip import logits_proc
+                              min_new_tokens: Optional[int] = None, suppress_tokens=None, num_return_sequences: int = 1, **unused):
+        from vz_hip import logits_proc, sample_rows
         if eos_token_id is None:
             eos_token_id = self.generation_config.eos_token_id
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id or []))
@@ -366,7 +392,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             raise NotImplementedError("logits processors on a tensor-parallel engine are not built")
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
-                                       eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing, **unused)
+                                       eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing,
+                                       num_return_sequences=num_return_sequences, **unused)
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         if max_new_tokens is None:
             max_new_tokens = 20 if max_length is None else max(1, max_length - S)
@@ -375,6 +402,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if pad_token_id is None:
             pad_token_id = min(eos) if eos else 0
         greedy = (not do_sample) or temperature is None or temperature <= 0
+        nrs = sample_rows.check_return_sequences(num_return_sequences, greedy, self.engine.max_batch, streamer, stopping_criteria)
         if top_k == -1:                      # not passed: HF's generation-config default (50); None / 0 = no top-k filter
             top_k = self.generation_config.top_k
         if top_p is None:
@@ -384,6 +412,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                       device=generator.device if generator is not None else "cpu").item())
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
+        if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
+            return self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
+                                          pad_token_id, sync_every, timing, proc)
         if prompt_lookup_num_tokens and _spec_history is not None and proc is None:      # (with processors: the plain greedy path, same ids)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
@@ -462,33 +493,72 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if timing is not None:
             import time
             timing["t_first_token"] = time.perf_counter()        # the host holds every row's first token here
-        cols = [first_cpu.view(Bsz, 1)]
-        eos_t = torch.tensor(sorted(eos), dtype=torch.long)
-        done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
         if proc is not None:
             eng.set_logits_proc(proc)
         try:
             eng.decode_begin(first, next_pos, list(seqlens))
-            remaining = max_new - 1
-            while remaining > 0 and not bool(done.all()):
-                n = min(sync_every, remaining) if eos else remaining
-                chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
-                remaining -= n
-                if eos:
-                    hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
-                    # a row is finished after its first eos (inclusive): later steps show the pad token
-                    after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
-                    chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
-                    done_at = done.view(Bsz, 1) | (torch.cumsum(hit.to(torch.int32), dim=1) > 0)      # state after each step
-                    all_done = done_at.all(dim=0)
-                    if bool(all_done.any()):                                 # stop at the first step after which every row is done
-                        chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
-                    done = done_at[:, chunk.shape[1] - 1]
-                cols.append(chunk)
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every).to(self.device)
         finally:
             if proc is not None:
                 eng.set_logits_proc(None)
-        return torch.cat(cols, dim=1).to(self.device)
+
+    # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
+    def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
+                          timing=None, proc=None, prompt0: int = 0) -> torch.Tensor:
+        """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
+        prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
+        row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
+        `seed + b * n + j` (vz_hip.sample_rows.row_seed) with its own counter, so it gets the tokens that seed gives it alone."""
+        from vz_hip import binding as B
+        from vz_hip import sample_rows as SR
+        eng = self.engine
+        if eng.tp_size > 1:
+            raise NotImplementedError("num_return_sequences > 1 on a tensor-parallel engine (tp_size > 1) is not built")
+        Bsz = embeds.shape[0]
+        G = SR.prompts_per_chunk(n, eng.max_batch)
+        if Bsz > G:
+            parts = [self._generate_samples(embeds[i:i + G], seqlens[i:i + G], None if position_ids is None else position_ids[i:i + G], n, max_new,
+                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i)
+                     for i in range(0, Bsz, G)]
+            out = torch.full((Bsz * n, max(p.shape[1] for p in parts)), pad_token_id, dtype=torch.long, device=self.device)
+            r = 0
+            for p in parts:
+                out[r:r + p.shape[0], :p.shape[1]] = p
+                r += p.shape[0]
+            return out
+        if max(seqlens) + max_new > eng.max_ctx:
+            raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
+        R = Bsz * n
+        # every row parked (the cache moves below may only touch parked rows), then one prefill per prompt into its first row
+        eng.decode_begin(torch.zeros(R, dtype=torch.int32), [0] * R, [0] * R)
+        last = []
+        for g in range(Bsz):
+            Sg = int(seqlens[g])
+            last.append(eng.prefill_rows(g * n, embeds[g:g + 1, :Sg], [Sg], None if position_ids is None else position_ids[g:g + 1, :Sg]))
+        last = torch.cat(last, 0).contiguous()
+        if proc is not None:
+            B.logits_process(last, proc)                 # the first step's processors see an empty history
+        params = [SR.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
+                               SR.row_seed(seed, prompt0 + r // n, n, r % n), 0) for r in range(R)]
+        first = B.sample_rows(last.repeat_interleave(n, dim=0).contiguous(), params)      # a prompt's one logits row, once per sample
+        first_cpu = first.to(torch.long).cpu()
+        if timing is not None:
+            import time
+            timing["t_first_token"] = time.perf_counter()        # the host holds every row's first token here
+        src = [g * n for g in range(Bsz) for _ in range(1, n)]
+        dst = [g * n + j for g in range(Bsz) for j in range(1, n)]
+        eng.kv_move_rows(src, dst, [seqlens[d // n] for d in dst])          # the prompt KV of each prompt into its samples' rows
+        next_pos = [int(seqlens[r // n]) if position_ids is None else int(position_ids[r // n, seqlens[r // n] - 1]) + 1 for r in range(R)]
+        try:
+            if proc is not None:
+                eng.set_logits_proc(proc)
+            eng.set_sampling_rows([p.at(1) for p in params])
+            eng.decode_begin(first, next_pos, [int(seqlens[r // n]) for r in range(R)])
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every).to(self.device)
+        finally:
+            eng.set_sampling_rows(None)
+            if proc is not None:
+                eng.set_logits_proc(None)
 
     # ---- beam search (hf:generation/utils.py `_beam_search`, do_sample=False; csrc/beam.hip + vz_hip/beam.py) ----------------
     def _generate_beam(self, inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
@@ -609,8 +679,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     @torch.no_grad()
     def generate_stream(self, requests, max_new_tokens: int = 128, eos_token_id=None, rows: Optional[int] = None, sync_every: int = 16,
                         admit: Optional[int] = None):
-        """Greedy generation over an iterable of requests - dicts with `input_ids` [1, L] (IMAGE_TOKEN_INDEX sentinels allowed),
-        optional `images` ([N,3,336,336]) / `images_size`, optional `max_new_tokens` - with CONTINUOUS batching: up to `rows`
+        """Generation over an iterable of requests - dicts with `input_ids` [1, L] (IMAGE_TOKEN_INDEX sentinels allowed),
+        optional `images` ([N,3,336,336]) / `images_size`, optional `max_new_tokens`, optional sampling parameters `do_sample`,
+        `temperature`, `top_p`, `top_k`, `seed` (read as `generate` reads them; greedy without them) - with CONTINUOUS batching: up to `rows`
         KV-cache rows decode together; a row whose sequence ends (eos or its token budget) is re-armed with the next request at
         the next host sync (every `sync_every` steps), the other rows keep decoding.  Yields `(index, LongTensor[n_new])` in
         completion order.  Rows are independent sequences: every sequence gets the tokens `generate` gives it alone UP TO kernel-route
@@ -620,17 +691,28 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         pinned (vz_tune_set(26, 0)) the ids are bit-identical (tests/test_stages_gpu.py::test_continuous_batching_matches_static_batches);
         at the default knobs they agree up to the first near-tie (::test_continuous_batching_default_knobs_near_tie).
 
+        Greedy and sampled requests share a batch.  A sampled request (do_sample=True, temperature > 0; top_k defaults to the generation
+        config's 50, top_p to 1.0, a missing seed is drawn from torch's global generator) gets, up to the same kernel-route
+        re-association, the tokens `generate(input_ids, do_sample=True, seed=s, ...)` gives it alone: its first token is drawn from
+        its prefill logits with draw counter 0 and its row then steps with the per-row tail (csrc/sampling.hip: sample_rows_kernel)
+        under the request's own seed and counter, whichever cache row it lands in.  The per-row tail is armed when the first sampled
+        request is admitted; a call in which no request samples runs as it always did.  `repetition_penalty`, `no_repeat_ngram_size`,
+        `min_new_tokens` and `suppress_tokens` in a request raise NotImplementedError.
+
         Admissions are BATCHED when the engine has cache rows to spare (`max_batch > rows`): all requests entering at one sync
         share one Zephyr prefill (right-padded, up to `admit` = min(max_batch - rows, 16) sequences) into the spare rows, one
         argmax readback, and their KV is then moved to the freed rows (`vz_llm_kv_move_rows`).  The vision stage stays per request:
         the Q-Former's text conditioning makes a request's visual tokens depend on the padded length of its batch."""
         from vz_hip import binding as B
+        from vz_hip import sample_rows as SR
         self._kv_epoch += 1
         self._ensure_ready()
         eng = self.engine
         if eos_token_id is None:
             eos_token_id = self.generation_config.eos_token_id
         eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(t) for t in eos_token_id})
+        draw_seed = lambda: int(torch.randint(0, 2 ** 62, (1,)).item())      # noqa: E731  (as generate draws its seed)
+        armed = False                           # the per-row tail: from the first sampled request on
         n_rows = min(eng.max_batch, 64) if rows is None else int(rows)
         if not 1 <= n_rows <= min(eng.max_batch, 64):
             raise ValueError(f"rows must be in [1, {min(eng.max_batch, 64)}]")
@@ -657,63 +739,78 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             S = emb.shape[1]
             if S + budget > eng.max_ctx:
                 raise ValueError(f"request {idx}: prompt ({S}) + max_new_tokens ({budget}) exceeds the engine's max_ctx ({eng.max_ctx})")
-            return emb, S, budget
+            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed)
 
-        while True:
-            while not exhausted:                # admit requests into free rows
-                free = [r for r in range(n_rows) if slots[r] is None]
-                if not free:
-                    break
-                group = []
-                while len(group) < (min(len(free), width) if width >= 2 else 1):
-                    try:
-                        idx, req = next(it)
-                    except StopIteration:
-                        exhausted = True
+        def first_tokens(logits, params):       # one launch and one readback for the group: argmax, or each row by its own parameters
+            if not any(p.sample for p in params):
+                return B.argmax(logits).tolist()
+            return B.sample_rows(logits, params).tolist()
+
+        try:
+            while True:
+                while not exhausted:                # admit requests into free rows
+                    free = [r for r in range(n_rows) if slots[r] is None]
+                    if not free:
                         break
-                    group.append((idx,) + embed(idx, req))
-                if not group:
-                    break
-                if len(group) == 1:             # straight into the free row
-                    idx, emb, S, budget = group[0]
-                    firsts = [int(B.argmax(eng.prefill_rows(free[0], emb, [S]))[0])]
-                else:                           # one prefill for the group in the spare rows, one readback
-                    Smax = max(g[2] for g in group)
-                    pad = torch.zeros(len(group), Smax, group[0][1].shape[-1], dtype=torch.bfloat16, device=self.device)
-                    for j, g in enumerate(group):
-                        pad[j, :g[2]] = g[1][0]
-                    firsts = B.argmax(eng.prefill_rows(n_rows, pad, [g[2] for g in group])).tolist()
-                moves = []
-                for j, (idx, emb, S, budget) in enumerate(group):
-                    first = int(firsts[j])
-                    if first in eos or budget <= 1:
-                        yield idx, torch.tensor([first], dtype=torch.long)
+                    group = []
+                    while len(group) < (min(len(free), width) if width >= 2 else 1):
+                        try:
+                            idx, req = next(it)
+                        except StopIteration:
+                            exhausted = True
+                            break
+                        group.append((idx,) + embed(idx, req))
+                    if not group:
+                        break
+                    if len(group) == 1:             # straight into the free row
+                        idx, emb, S, budget, par = group[0]
+                        firsts = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par])
+                    else:                           # one prefill for the group in the spare rows, one readback
+                        Smax = max(g[2] for g in group)
+                        pad = torch.zeros(len(group), Smax, group[0][1].shape[-1], dtype=torch.bfloat16, device=self.device)
+                        for j, g in enumerate(group):
+                            pad[j, :g[2]] = g[1][0]
+                        firsts = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group])
+                    moves = []
+                    if not armed and any(g[4].sample for g in group):
+                        # the table the running batch uploaded holds every row greedy: rows keep their ids when the tail changes under them
+                        eng.set_sampling_rows([])
+                        armed = True
+                    for j, (idx, emb, S, budget, par) in enumerate(group):
+                        first = int(firsts[j])
+                        if first in eos or budget <= 1:
+                            yield idx, torch.tensor([first], dtype=torch.long)
+                            continue
+                        r = free.pop(0)
+                        if len(group) > 1:
+                            moves.append((n_rows + j, r, S))
+                        slots[r] = [idx, [first], budget]
+                        group[j] = (idx, None, S, budget, par, r, first)
+                    if moves:
+                        eng.kv_move_rows([m[0] for m in moves], [m[1] for m in moves], [m[2] for m in moves])
+                    for g in group:
+                        if len(g) == 7:
+                            eng.decode_set_row(g[5], g[6], g[2], g[2])
+                            if armed:                   # the row's second token is draw 1 of the request's own stream
+                                eng.decode_set_row_sampling(g[5], g[4].at(1))
+                if all(s is None for s in slots):
+                    return
+                n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
+                chunk = eng.decode_steps(n).cpu()                           # [rows, n]; the only host sync of the chunk
+                for r, st in enumerate(slots):
+                    if st is None:
                         continue
-                    r = free.pop(0)
-                    if len(group) > 1:
-                        moves.append((n_rows + j, r, S))
-                    slots[r] = [idx, [first], budget]
-                    group[j] = (idx, None, S, budget, r, first)
-                if moves:
-                    eng.kv_move_rows([m[0] for m in moves], [m[1] for m in moves], [m[2] for m in moves])
-                for g in group:
-                    if len(g) == 6:
-                        eng.decode_set_row(g[4], g[5], g[2], g[2])
-            if all(s is None for s in slots):
-                return
-            n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
-            chunk = eng.decode_steps(n).cpu()                           # [rows, n]; the only host sync of the chunk
-            for r, st in enumerate(slots):
-                if st is None:
-                    continue
-                for t in chunk[r].tolist():
-                    st[1].append(int(t))
-                    if int(t) in eos or len(st[1]) >= st[2]:
-                        break
-                if st[1][-1] in eos or len(st[1]) >= st[2]:
-                    yield st[0], torch.tensor(st[1], dtype=torch.long)
-                    eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
-                    slots[r] = None
+                    for t in chunk[r].tolist():
+                        st[1].append(int(t))
+                        if int(t) in eos or len(st[1]) >= st[2]:
+                            break
+                    if st[1][-1] in eos or len(st[1]) >= st[2]:
+                        yield st[0], torch.tensor(st[1], dtype=torch.long)
+                        eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
+                        slots[r] = None
+        finally:
+            if armed:
+                eng.set_sampling_rows(None)
 
     def _token_ring(self, n: int = 8) -> torch.Tensor:
         """pinned host buffer the step tails write their tokens to (device-visible: hipHostMalloc memory is mapped)."""

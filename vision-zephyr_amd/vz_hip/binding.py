@@ -133,6 +133,9 @@ SYMBOLS = {
     "vz_op_lora_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _I, _I, C.c_ulonglong, _F, _F, _P]),
     "vz_op_vip_point": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, _P]),
     "vz_op_sample": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P, _P]),
+    "vz_llm_decode_sampling_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_set_row_sampling": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P]),
+    "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -661,6 +664,24 @@ def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed:
     check(lib().vz_op_sample(ptr(logits), logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0),
                              float(1.0 if top_p is None else top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter), ptr(ids),
                              stream_ptr(logits.device)))
+    return ids
+
+
+def row_sample_arrays(params):
+    """the six parameter arrays of the per-row entry points from a list of vz_hip.sample_rows.RowParams"""
+    n = max(1, len(params))
+    return ((C.c_int * n)(*[int(p.sample) for p in params]), (C.c_float * n)(*[float(p.temperature) for p in params]),
+            (C.c_int * n)(*[int(p.top_k) for p in params]), (C.c_float * n)(*[float(p.top_p) for p in params]),
+            (C.c_ulonglong * n)(*[int(p.seed) & 0xFFFFFFFFFFFFFFFF for p in params]), (C.c_int * n)(*[int(p.counter) for p in params]))
+
+
+def sample_rows(logits, params):
+    """one token per row of fp32 logits [rows <= 64, V] by that row's own parameters (params[r]: vz_hip.sample_rows.RowParams - greedy, or
+    sampled with its own temperature / top-k / top-p / seed / draw counter; sampling.hip's per-row kernel): int32 [rows]."""
+    _need_cuda(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(params) == logits.shape[0]
+    ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
+    check(lib().vz_op_sample_rows(ptr(logits), logits.shape[0], logits.shape[1], *row_sample_arrays(params), ptr(ids), stream_ptr(logits.device)))
     return ids
 
 

@@ -596,6 +596,19 @@ class Engine:
         B.check(self.lib.vz_llm_decode_sampling(self.h, int(on), float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_counter)))
 
+    def set_sampling_rows(self, params=None):
+        """the per-row tail (sampling.hip: sample_rows_kernel): params = a list of vz_hip.sample_rows.RowParams, one per row of the NEXT
+        decode_begin (rows behind the list, or an empty list: greedy until `decode_set_row_sampling` arms them); None = off."""
+        if params is None:
+            B.check(self.lib.vz_llm_decode_sampling_rows(self.h, 0, 0, None, None, None, None, None, None))
+            return
+        B.check(self.lib.vz_llm_decode_sampling_rows(self.h, 1, len(params), *B.row_sample_arrays(params)))
+
+    def decode_set_row_sampling(self, row: int, p):
+        """one row's entry of the running batch's per-row table (p: vz_hip.sample_rows.RowParams), stream-ordered like `decode_set_row`."""
+        B.check(self.lib.vz_llm_decode_set_row_sampling(self.h, int(row), int(p.sample), float(p.temperature), int(p.top_k), float(p.top_p),
+                                                        int(p.seed) & 0xFFFFFFFFFFFFFFFF, int(p.counter), self._s()))
+
     def set_logits_proc(self, cfg=None):
         """HF's logits processors in front of the argmax / the sampler of every decode step (logits_proc.hip; cfg =
         vz_hip.logits_proc.parse(...), None = off).  Arming empties every row's history of generated ids: call it before

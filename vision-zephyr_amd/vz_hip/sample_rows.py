@@ -1,0 +1,82 @@
+"""Per-row sampling of a decode batch (csrc/sampling.hip: sample_rows_kernel): what a `generate_stream` request
+and `generate(do_sample=True, num_return_sequences=n)` ask for, checked and turned into one table entry per decode row.  Needs no GPU."""
+from dataclasses import dataclass, replace
+from typing import Callable, Mapping, Optional
+
+ROW_CAP = 64                     # rows one decode batch holds at the most
+UNBUILT_REQUEST_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
+
+
+@dataclass(frozen=True)
+class RowParams:
+    """one row's entry of the per-row table; `counter` = the draw counter of the row's next token"""
+    sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0               # 0 = no top-k filter
+    top_p: float = 1.0           # 1 = no top-p filter
+    seed: int = 0
+    counter: int = 0
+
+    def at(self, counter: int) -> "RowParams":
+        return replace(self, counter=int(counter))
+
+
+GREEDY = RowParams()
+
+
+def row_params(do_sample, temperature, top_k, top_p, seed: Optional[int], gen, draw_seed: Callable[[], int]) -> RowParams:
+    """`generate`'s reading of its sampling keywords: greedy unless do_sample with a temperature > 0; top_k = -1 (not named) takes the
+    generation config's (`gen.top_k`), None / 0 = no filter; top_p None takes `gen.top_p`; a sampled row without a seed draws one.
+    A greedy row reads neither `gen` nor a seed."""
+    if (not do_sample) or temperature is None or temperature <= 0:
+        return GREEDY
+    if top_k == -1:
+        top_k = gen.top_k
+    top_k = int(top_k or 0)
+    if top_p is None:
+        top_p = gen.top_p
+    top_p = float(1.0 if top_p is None else top_p)
+    if top_k < 0:
+        raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+    return RowParams(True, float(temperature), top_k, top_p, int(draw_seed() if seed is None else seed), 0)
+
+
+def parse_request(req: Mapping, gen, draw_seed: Callable[[], int]) -> RowParams:
+    """the sampling parameters of one `generate_stream` request (keys do_sample, temperature, top_p, top_k, seed; defaults as `generate`'s,
+    `gen` = the model's generation config).
+    Logits processors per request are not built: a row's processor history would have to restart at admission."""
+    for k in UNBUILT_REQUEST_KEYS:
+        if req.get(k) is not None:
+            raise NotImplementedError(f"generate_stream: `{k}` in a request is not built (logits processors run over a whole batch: generate())")
+    return row_params(req.get("do_sample", False), req.get("temperature", 1.0), req.get("top_k", -1), req.get("top_p"), req.get("seed"),
+                      gen, draw_seed)
+
+
+def row_seed(seed: int, prompt: int, n: int, j: int) -> int:
+    """seed of sample j of prompt `prompt` when every prompt returns n sequences (n = 1: seed + prompt, the sequential batch's rule)"""
+    return int(seed) + int(prompt) * int(n) + int(j)
+
+
+def check_return_sequences(n, greedy: bool, row_capacity: int, streamer=None, stopping_criteria=None) -> int:
+    """`num_return_sequences` of a generate() call without beams: the checked n.  n = 1 is every existing path, untouched."""
+    if n is None:
+        return 1
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+        raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n}")
+    if n == 1:
+        return 1
+    if greedy:
+        raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
+    if streamer is not None or stopping_criteria is not None:
+        raise NotImplementedError("a streamer or stopping_criteria with num_return_sequences > 1 is not built")
+    cap = min(int(row_capacity), ROW_CAP)
+    if n > cap:
+        raise ValueError(f"num_return_sequences = {n} exceeds the {cap} rows that decode together (min(max_batch, {ROW_CAP})): every sample needs a KV-cache row")
+    return n
+
+
+def prompts_per_chunk(n: int, row_capacity: int) -> int:
+    """prompts that decode together when each takes n rows: chunk * n <= min(max_batch, 64)"""
+    return max(1, min(int(row_capacity), ROW_CAP) // int(n))
