@@ -477,6 +477,30 @@ int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temper
                                    int counter, vz_stream stream);
 int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
                       const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream);
+/* Step recorder (csrc/sampling.hip: token_scores_kernel): per-token scores and log-probs of a generation, recorded
+ * on the device.  After vz_llm_decode_scores(what != 0) every decode step writes, behind its tail (argmax, sampler or per-row tail) and
+ * inside the per-token hipGraph, one record of four 32-bit words per row about the token the tail chose:
+ *   x_tok    = logits[row, tok] after the logits processors, before temperature (NaN for a token outside the vocabulary)
+ *   lse      = log sum_i exp(x_i) over the whole row (fp32, natural log): log-prob at temperature 1 = x_tok - lse
+ *   lse_kept = log sum_{i kept} exp(x_i / T) over the tokens the row's sampler keeps for its (T, top_k, top_p) - the sampler's own set;
+ *              a greedy row: lse.  x_tok / T - lse_kept = HF's compute_transition_scores(normalize_logits=True) on its warped scores
+ *   n_kept   = size of that set (int32; its finite entries); a greedy row: cols
+ * what = VZ_SCORE_REC, optionally | VZ_SCORE_WARPED (also the row HF calls scores[t]: x for a greedy row, x / T where kept and -inf
+ * elsewhere for a sampled one) | VZ_SCORE_RAW (also logits[t]: the row as the lm_head left it, copied in front of the processors).
+ * The buffers are rings of cap_steps steps in device memory: d_rec [slot][B][4], d_warped / d_raw [slot][B][vocab] (null when not asked
+ * for); slot = the steps launched since vz_llm_decode_begin (or since this call, whichever is later) modulo cap_steps, counted on the
+ * device; vz_llm_decode_set_row leaves it alone.  The pointers, `what` and cap_steps are frozen by a captured step: a change captures
+ * again, and with the recorder off no launch is added.  vz_llm_decode_steps refuses n > cap_steps and the recorder together with the beam
+ * or the speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.  what = 0: off.
+ * vz_op_token_scores: the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by h_mode[r] (0 =
+ * greedy, 1 = sampled) and its temperature / top_k / top_p as vz_op_sample_rows takes them: d_rec [rows][4], d_warped [rows][cols] or
+ * null (the first token of a generation, chosen from the prefill logits; tests). */
+#define VZ_SCORE_REC    1u   /* the 16-byte records            */
+#define VZ_SCORE_WARPED 2u   /* + processed, warped score rows */
+#define VZ_SCORE_RAW    4u   /* + raw logits rows              */
+int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, float* d_warped, float* d_raw, int cap_steps, vz_stream stream);
+int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
+                       const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream);
 /* Batched admissions: prefill several requests together into spare cache rows (row0 >= the running batch), then move each one's
  * first h_len[i] cache positions from row h_src[i] to the freed row h_dst[i] (every layer, K and V; stream-ordered).  Rows of
  * one call must not overlap (no destination equal to another move's source or destination). */

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
 
 // step[0] = index of the step inside this vz_llm_decode_steps call; step[1] = tokens drawn since vz_llm_decode_begin (the
 // Philox counter of the sampling tail)
-__global__ void step_advance_kernel(int* step) { step[0] += 1; step[1] += 1; }
+__global__ void step_advance_kernel(int* step, int* also) { step[0] += 1; step[1] += 1; if (also) also[0] += 1; }
 
 // vocab-parallel logits after the all-gather: gathered[r][row][j] (j < Vp, zero-padded shards) -> out[row][r*Vp + j]
 __global__ __launch_bounds__(256) void repack_logits_kernel(const float* __restrict__ g, float* __restrict__ out, int rows, int Vp, int V, int tp) {
@@ -504,8 +504,8 @@ int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const Ro
     return VZ_OK;
 }
 
-int vz_launch_step_advance(int* step, hipStream_t s) {
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step);
+int vz_launch_step_advance(int* step, int* also, hipStream_t s) {
+    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step, also);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

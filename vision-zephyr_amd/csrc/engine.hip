@@ -451,6 +451,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_xnorm) hipFree(e->d_xnorm);
     if (e->beam.d) hipFree(e->beam.d);
     if (e->proc.d) hipFree(e->proc.d);
+    if (e->score.d_slot) hipFree(e->score.d_slot);
     if (e->d_gather) (void)hipFree(e->d_gather);
     vz_decode_persist_destroy(e->tok);
     if (e->comm) (void)ncclCommDestroy(e->comm);
@@ -1089,6 +1090,7 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     for (size_t r = 0; r < e->rows.tab.size(); ++r) hs.samp[r] = e->rows.tab[r];            // (never set: zeros = every row greedy)
     RC(upload_ints(e, hs.pos, h.size() - mb, ds.pos, s));
     VZ_CHECK_HIP(hipMemcpyAsync(ds.cur, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (e->score.d_slot) VZ_CHECK_HIP(hipMemsetAsync(e->score.d_slot, 0, sizeof(int), s));      // the step recorder's ring restarts with the batch
     e->dec_B = B;
     e->spec.on = 0;          // a new batch starts with the plain tail: vz_llm_decode_spec is armed AFTER this call
     e->h_len.assign(B, 0); e->h_pos.assign(B, 0); e->h_parked.assign(B, 0);
@@ -1240,6 +1242,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         ProfScope ps(e, K_OTHER, s);
         // per row: the token into d_out_ids (and the ring), position / slot / length one further
         const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
+        if (e->score.what & VZ_SCORE_RAW) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, e->score.raw, e->score.d_slot, e->score.cap, s));
         if (e->proc.on && tail_takes_proc(tail)) {
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
             RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, s));
@@ -1273,9 +1276,56 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             RC(vz_launch_argmax(e->d_logits, B, c.vocab, st.cur, emit, s));
             break;
         }
-        RC(vz_launch_step_advance(st.step, s));
+        if (e->score.what) {
+            // sampling.hip: the record of the token the tail just left in st.cur, by the parameters the tail took it with
+            const RowSample one = tail == TAIL_SAMPLE ? RowSample{VZ_ROW_SAMPLE, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, {0u, 0u}, 0, 0}
+                                                      : RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0};
+            RC(vz_launch_token_scores(e->d_logits, B, c.vocab, tail == TAIL_ROWS ? st.samp : nullptr, one, st.cur, e->score.rec,
+                                      (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
+        }
+        RC(vz_launch_step_advance(st.step, e->score.what ? e->score.d_slot : nullptr, s));
     }
     return VZ_OK;
+}
+
+static int row_sample_of(int mode, float temperature, int top_k, float top_p, unsigned long long seed, int counter, RowSample* out);
+
+// The step recorder (sampling.hip: token_scores_kernel): armed, every decode step whose tail is the argmax, the
+// sampler or the per-row tail writes, behind that tail and inside the per-token hipGraph, one record {x_tok, lse, lse_kept, n_kept} per
+// row about the token it chose, and on request the warped score rows and the raw logits rows (copied in front of the processors), into
+// rings of cap_steps steps in the caller's device memory.  The slot is a device-side count of the steps launched since
+// vz_llm_decode_begin (restarted here too, stream-ordered), so a replayed graph takes no per-step argument.  what = 0: off.
+extern "C" int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, float* d_warped, float* d_raw, int cap_steps, vz_stream stream) {
+    NEED_READY();
+    if (!what) { e->score.what = 0; e->score.rec = e->score.warped = e->score.raw = nullptr; e->score.cap = 0; return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_scores: the step recorder on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG((what & VZ_SCORE_REC) && !(what & ~(VZ_SCORE_REC | VZ_SCORE_WARPED | VZ_SCORE_RAW)) && d_rec && cap_steps >= 1,
+                 "decode_scores: what = %u needs VZ_SCORE_REC, a record ring and cap_steps %d >= 1", what, cap_steps);
+    VZ_CHECK_ARG((!(what & VZ_SCORE_WARPED) || d_warped) && (!(what & VZ_SCORE_RAW) || d_raw), "decode_scores: a requested row output has no ring");
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->score.d_slot) VZ_CHECK_HIP(hipMalloc((void**)&e->score.d_slot, 64));
+    VZ_CHECK_HIP(hipMemsetAsync(e->score.d_slot, 0, sizeof(int), s));
+    e->score.what = what; e->score.rec = d_rec; e->score.cap = cap_steps;
+    e->score.warped = (what & VZ_SCORE_WARPED) ? d_warped : nullptr; e->score.raw = (what & VZ_SCORE_RAW) ? d_raw : nullptr;
+    return VZ_OK;
+}
+
+// the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by (h_mode[r] 0 = greedy / 1 = sampled,
+// temperature, top_k, top_p) as vz_op_sample_rows takes them: d_rec [rows][4], d_warped [rows][cols] or null (the first token's record,
+// taken from the prefill logits; tests)
+extern "C" int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
+                                  const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_logits && d_ids && d_rec && rows >= 1 && rows <= 64 && cols >= 1, "token_scores: bad argument (1..64 rows)");
+    VZ_CHECK_ARG(h_mode && h_temperature && h_top_k && h_top_p, "token_scores: null parameter array");
+    RowSample tab[64];
+    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], 0ull, 0, tab + r));
+    void* p = nullptr; size_t have = 0;
+    RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
+    VZ_CHECK_ARG(p && have >= sizeof(tab), "token_scores: first use of a stream inside a capture (call it once before capturing)");
+    VZ_CHECK_HIP(hipMemcpyAsync(p, tab, (size_t)rows * sizeof(RowSample), hipMemcpyHostToDevice, s));
+    VZ_CHECK_HIP(hipStreamSynchronize(s));          // the table is on this frame: it has been read before the call returns
+    return vz_launch_token_scores(d_logits, rows, cols, (const RowSample*)p, tab[0], d_ids, d_rec, d_warped, nullptr, 0, s);
 }
 
 // Sampling instead of argmax as the tail of every decode step (hf:generation/utils.py `_sample`, do_sample=True; see
@@ -1625,6 +1675,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; }
+    if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
 }
 
@@ -1646,6 +1697,9 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                  "front of the argmax or the sampler only, not with the beam or the speculative tail");
     VZ_CHECK_ARG(!e->rows.on || (!e->beam.on && !e->spec.on && e->tp == 1), "decode_steps: the per-row tail (vz_llm_decode_sampling_rows) does not run "
                  "together with the beam or the speculative tail, nor on a tensor-parallel engine");
+    VZ_CHECK_ARG(!e->score.what || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the step recorder (vz_llm_decode_scores) runs behind the "
+                 "argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
+    VZ_CHECK_ARG(!e->score.what || n <= e->score.cap, "decode_steps: %d steps, the step recorder's rings hold cap_steps = %d", n, e->score.cap);
     DecodeWs w;
     RC(carve_stage(e, "decode", [&](Carver& m) { return carve_decode(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, spec); }, &w));
     // tensor-parallel steps: the RCCL all-reduces / all-gather are captured with the kernels (one graph launch per token instead of

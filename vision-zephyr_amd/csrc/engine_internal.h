@@ -67,8 +67,9 @@ struct DecodeGraphKey {
     int* out; char* arena; int* ring; int ring_n;
     SampleArgs samp; BeamArgs beam; SpecArgs spec;
     int* proc_hist; ProcArgs proc; int proc_on;      // the logits processors in front of the tail and their history buffer (zero when off)
+    float *sc_rec, *sc_warped, *sc_raw; unsigned sc_what; int sc_cap;      // the step recorder behind the tail and its rings (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 8 + sizeof(ProcArgs) + 4 &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
 
 // The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
@@ -126,6 +127,9 @@ struct vz_engine {
     // logits processors (vz_llm_decode_logits_proc; logits_proc.hip): orthogonal to the tail - armed, they run on the step's logits in front
     // of the argmax / the sampler.  d = [hist_len: max_batch ints, padded to 64 | hist: max_batch x max_ctx ints], its own allocation
     struct { int on = 0; ProcArgs a{}; int* d = nullptr; } proc;
+    // step recorder (vz_llm_decode_scores; sampling.hip: token_scores_kernel): behind the tail, a record per row and step into the caller's
+    // rings of `cap` steps; d_slot = the steps launched since vz_llm_decode_begin (one word of its own, counted by the step-advance launch)
+    struct { unsigned what = 0; float *rec = nullptr, *warped = nullptr, *raw = nullptr; int cap = 0; int* d_slot = nullptr; } score;
     struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)

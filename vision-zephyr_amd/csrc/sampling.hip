@@ -18,6 +18,8 @@
 // restatement oracle/sampling_oracle.py (same Philox stream).
 // The same kernel is the step's tail inside the per-token hipGraph: it publishes the token for the next step, appends it
 // to the output ids and advances the per-row position / cache slot / length kept on the device (as argmax_kernel does).
+#include <algorithm>
+
 #include "vz_common.h"
 
 namespace {
@@ -63,20 +65,26 @@ __device__ __forceinline__ float block_max(float v, SampleShared& sh) {
         for (int k = tid; k < cols; k += 1024) { const float x = lr[k] / temperature; BODY }                         \
     }
 
-// One row's draw, steps 1..4 above, up to each thread's own best (value, index) of the race; `stream_row` = the Philox counter's
-// row word.  Shared by the two kernels below, so a row gets the same bits from either.
+// One row's kept set, steps 1..3 above: stages the tempered row (REG), returns the threshold key - a token is kept iff fkey(x) >= it -
+// and the maximum m of the tempered row.  Shared by the draw (sample_row_race) and the step recorder (token_scores_kernel), so the set
+// a record describes is the set the token was drawn from.
 template <bool REG>
-__device__ __forceinline__ void sample_row_race(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
-                                                unsigned k0, unsigned k1, unsigned stream_row, unsigned c2, SampleShared& sh,
-                                                float& bv, int& bi) {
+__device__ __forceinline__ unsigned sample_row_keep(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
+                                                    SampleShared& sh, float& m_out, const float* have = nullptr) {
+    // have (REG only): the caller's registers already hold the row's batch of loads, have[i] = lr[tid + i * 1024] - staged from there
     const int tid = threadIdx.x;
     extern __shared__ float lx[];          // REG: cols floats
     if (REG) {
-        float t[32];
+        if (have) {
 #pragma unroll
-        for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; t[i] = k < cols ? lr[k] : 0.f; }
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; if (k < cols) lx[k] = have[i] / temperature; }
+        } else {
+            float t[32];
 #pragma unroll
-        for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; if (k < cols) lx[k] = t[i] / temperature; }
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; t[i] = k < cols ? lr[k] : 0.f; }
+#pragma unroll
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; if (k < cols) lx[k] = t[i] / temperature; }
+        }
         __syncthreads();
     }
 
@@ -151,7 +159,20 @@ __device__ __forceinline__ void sample_row_race(const float* __restrict__ lr, in
         }
         pth = prefix;
     }
-    const unsigned keep = kth > pth ? kth : pth;
+    m_out = m;
+    return kth > pth ? kth : pth;
+}
+
+// One row's draw, steps 1..4 above, up to each thread's own best (value, index) of the race; `stream_row` = the Philox counter's
+// row word.  Shared by the two kernels below, so a row gets the same bits from either.
+template <bool REG>
+__device__ __forceinline__ void sample_row_race(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
+                                                unsigned k0, unsigned k1, unsigned stream_row, unsigned c2, SampleShared& sh,
+                                                float& bv, int& bi) {
+    const int tid = threadIdx.x;
+    extern __shared__ float lx[];          // REG: cols floats, staged by sample_row_keep
+    float m;
+    const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, sh, m);
 
     // ---- 4. Gumbel race over the kept tokens ----
     bv = -INFINITY;
@@ -242,6 +263,137 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     }
 }
 
+// ---- the step recorder -------------------------------------------------------------------------------------------
+// Behind the tail: one 16-byte record per row about the token the tail chose, ids[row]:
+//   x_tok    = logits[row, tok] as it stands (in a step: after the logits processors, before temperature); NaN if tok is outside [0, cols)
+//   lse      = m + log(sum_i exp(x_i - m)) over the whole row, natural log: the log-partition at temperature 1
+//   lse_kept = mT + log(sum_{i kept} exp(x_i / T - mT)) over the set the sampler keeps for the row's (T, top_k, top_p) - sample_row_keep,
+//              the sampler's own; a greedy row: lse
+//   n_kept   = size of that set (int32), -inf entries not counted; a greedy row: cols
+// and, if asked for, the row HF calls scores[t]: x for a greedy row, x / T where kept and -inf elsewhere for a sampled one.
+// Fixed reduction shape - each thread sums its stride-1024 elements in index order, the wave's 64 partials go through wave_sum's fixed
+// butterfly, the 16 wave partials are added in index order: a replayed graph, an eager step and a second run give the same bits.  The
+// maximum is subtracted first; a row of -inf gives lse = -inf without evaluating (-inf) - (-inf).
+__device__ __forceinline__ float block_sum(float v, SampleShared& sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh.redf[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = sh.redf[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) r += sh.redf[w];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ int block_sum_int(int v, SampleShared& sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh.redi[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) r += sh.redi[w];
+    __syncthreads();
+    return r;
+}
+
+// the recording's place in the rings: slot = (*slot_word) mod cap_steps (null: slot 0, the standalone op), rows = gridDim.x
+struct ScoreOut { float* rec; float* warped; const int* slot_word; int cap_steps; };
+
+template <bool REG>
+__global__ __launch_bounds__(1024) void token_scores_kernel(const float* __restrict__ logits, int cols, const RowSample* __restrict__ tab,
+                                                            RowSample one, const int* __restrict__ ids, ScoreOut out) {
+    __shared__ SampleShared sh;
+    extern __shared__ float lx[];          // REG: cols floats, staged by sample_row_keep
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lr = logits + (size_t)row * cols;
+    int mode = one.mode, top_k = one.top_k;
+    float temperature = one.temp, top_p = one.top_p;
+    if (tab) {          // the per-row table, read as sample_rows_kernel reads it
+        const int4 e0 = ((const int4*)(tab + row))[0];
+        mode = __builtin_amdgcn_readfirstlane(e0.x); top_k = __builtin_amdgcn_readfirstlane(e0.z);
+        temperature = __int_as_float(__builtin_amdgcn_readfirstlane(e0.y)); top_p = __int_as_float(__builtin_amdgcn_readfirstlane(e0.w));
+    }
+    const int slot = out.slot_word ? (int)((unsigned)out.slot_word[0] % (unsigned)out.cap_steps) : 0;
+    const size_t orow = (size_t)slot * gridDim.x + row;
+    float* wr = out.warped ? out.warped + orow * cols : nullptr;
+    const int tok = ids[row];
+    const bool greedy = mode == VZ_ROW_GREEDY;
+
+    // ---- the whole row at temperature 1: max, then the sum of exp(x - max) ----
+    float m = -INFINITY, sum = 0.f;
+    float t[32];        // REG: the row's one batch of 32 loads per thread, held across the two reductions and staged by sample_row_keep
+    if (REG) {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; t[i] = k < cols ? lr[k] : -INFINITY; }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) m = fmaxf(m, t[i]);
+        m = block_max(m, sh);
+        if (m > -INFINITY) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) sum += expf(t[i] - m);          // (a lane behind the row: exp(-inf) = 0)
+        }
+        if (wr && greedy) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) { const int k = tid + i * 1024; if (k < cols) wr[k] = t[i]; }
+        }
+    } else {            // batches of 8 loads per thread
+        for (int k0 = tid; k0 < cols; k0 += 8 * 1024) {
+            float u[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { const int k = k0 + i * 1024; u[i] = k < cols ? lr[k] : -INFINITY; }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) m = fmaxf(m, u[i]);
+        }
+        m = block_max(m, sh);
+        for (int k0 = tid; k0 < cols; k0 += 8 * 1024) {
+            float u[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { const int k = k0 + i * 1024; u[i] = k < cols ? lr[k] : -INFINITY; }
+            if (m > -INFINITY) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) sum += expf(u[i] - m);
+            }
+            if (wr && greedy) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { const int k = k0 + i * 1024; if (k < cols) wr[k] = u[i]; }
+            }
+        }
+    }
+    sum = block_sum(sum, sh);
+    const float lse = m > -INFINITY ? m + logf(sum) : -INFINITY;
+
+    // ---- the kept set of a sampled row: the sampler's threshold, then the same sum over the kept tempered values ----
+    float lse_kept = lse;
+    int n_kept = cols;
+    if (!greedy) {
+        float mT;
+        const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, sh, mT, REG ? t : nullptr);
+        float sk = 0.f;
+        int nk = 0;
+        VZ_FOR_LOGITS({
+            const bool in = fkey(x) >= keep;
+            if (in && x > -INFINITY) { nk += 1; sk += expf(x - mT); }          // (a -inf entry above the threshold has no mass: not counted)
+            if (wr) wr[k] = in ? x : -INFINITY;
+        })
+        sk = block_sum(sk, sh);
+        n_kept = block_sum_int(nk, sh);
+        lse_kept = mT > -INFINITY ? mT + logf(sk) : -INFINITY;
+    }
+    if (tid == 0) {
+        float4 r;
+        r.x = (tok >= 0 && tok < cols) ? lr[tok] : __int_as_float(0x7fc00000);
+        r.y = lse; r.z = lse_kept; r.w = __int_as_float(n_kept);
+        ((float4*)out.rec)[orow] = r;
+    }
+}
+
+// a step's logits rows as they leave the lm_head, into the slot the step's record goes to (what HF calls logits[t])
+__global__ __launch_bounds__(256) void score_raw_rows_kernel(const float* __restrict__ logits, long n, float* __restrict__ raw,
+                                                             const int* __restrict__ slot_word, int cap_steps) {
+    float* dst = raw + (size_t)((unsigned)slot_word[0] % (unsigned)cap_steps) * n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = logits[i];
+}
+
 }  // namespace
 
 static bool g_sample_lds_ok = false;
@@ -251,6 +403,7 @@ int vz_init_sampling_kernels() {
     if (!vz_device_first(once)) return VZ_OK;
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)token_scores_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     g_sample_lds_ok = true;
     return VZ_OK;
 }
@@ -276,6 +429,30 @@ int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* ta
         hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, tab, ids, emit);
     else
         hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, tab, ids, emit);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+// The step recorder on `rows` rows of fp32 logits about the tokens ids[row]: tab = the rows' entries in device memory (the per-row tail's
+// table) or null = every row by `one`.  slot_word / cap_steps: the ring slot (null: slot 0); rec [slots][rows][4], warped [slots][rows][cols] or null.
+int vz_launch_token_scores(const float* logits, int rows, int cols, const RowSample* tab, const RowSample& one, const int* ids, float* rec,
+                           float* warped, const int* slot_word, int cap_steps, hipStream_t s) {
+    VZ_CHECK_ARG(logits && ids && rec && rows > 0 && cols > 0 && (!slot_word || cap_steps > 0), "token_scores: bad argument");
+    VZ_CHECK_ARG(tab || one.mode == VZ_ROW_GREEDY || (one.temp > 0.f && one.top_p > 0.f), "token_scores: temperature %g and top_p %g must be positive", (double)one.temp, (double)one.top_p);
+    { int r = vz_init_sampling_kernels(); if (r) return r; }
+    const ScoreOut out{rec, warped, slot_word, cap_steps};
+    if (cols <= 32768 && g_sample_lds_ok)
+        hipLaunchKernelGGL(token_scores_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, tab, one, ids, out);
+    else
+        hipLaunchKernelGGL(token_scores_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, tab, one, ids, out);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+int vz_launch_score_raw_rows(const float* logits, int rows, int cols, float* raw, const int* slot_word, int cap_steps, hipStream_t s) {
+    VZ_CHECK_ARG(logits && raw && slot_word && rows > 0 && cols > 0 && cap_steps > 0, "score_raw_rows: bad argument");
+    const long n = (long)rows * cols;
+    hipLaunchKernelGGL(score_raw_rows_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 2048)), dim3(256), 0, s, logits, n, raw, slot_word, cap_steps);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -368,7 +368,11 @@ int vz_launch_copy_rows(const bf16_t* src, long src_stride, bf16_t* dst, long ds
 struct KvMoves { int n; int src[16], dst[16], len[16]; };
 int vz_launch_kv_move_rows(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, const KvMoves& mv,
                            hipStream_t s);
-int vz_launch_step_advance(int* step, hipStream_t s);
+int vz_launch_step_advance(int* step, int* also, hipStream_t s);      // also: one more word that counts the steps (the recorder's slot), or null
+// the step recorder (sampling.hip): a 16-byte record per row about the token the tail chose, optionally the warped score row
+int vz_launch_token_scores(const float* logits, int rows, int cols, const RowSample* tab, const RowSample& one, const int* ids, float* rec,
+                           float* warped, const int* slot_word, int cap_steps, hipStream_t s);
+int vz_launch_score_raw_rows(const float* logits, int rows, int cols, float* raw, const int* slot_word, int cap_steps, hipStream_t s);
 // beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
 struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);

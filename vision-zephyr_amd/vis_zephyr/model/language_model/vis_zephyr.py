@@ -103,17 +103,20 @@ class PastKeyValues:
         return max(self.lengths) if self.lengths else 0
 
 
-def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every) -> torch.Tensor:
+def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=None) -> torch.Tensor:
     """the steps of a batch `decode_begin` has armed with the rows' first tokens `first_cpu` (host): [rows, <= max_new] new tokens,
-    `sync_every` steps per host sync (host tensor), a row showing `pad_token_id` behind its eos, until every row is done."""
+    `sync_every` steps per host sync (host tensor), a row showing `pad_token_id` behind its eos, until every row is done.
+    blk (vz_hip.scores block; the engine's step recorder is armed for `sync_every` steps): every chunk's records are added to it."""
     Bsz = first_cpu.numel()
     cols = [first_cpu.view(Bsz, 1)]
     eos_t = torch.tensor(sorted(eos), dtype=torch.long)
     done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
     remaining = max_new - 1
     while remaining > 0 and not bool(done.all()):
-        n = min(sync_every, remaining) if eos else remaining
+        n = min(sync_every, remaining) if (eos or blk is not None) else remaining
         chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
+        if blk is not None:
+            blk.add(*eng.scores_steps(n))
         remaining -= n
         if eos:
             hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
@@ -379,8 +382,26 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               sync_every: int = 16, timing: Optional[dict] = None, prompt_lookup_num_tokens: Optional[int] = None,
                               max_matching_ngram_size: Optional[int] = None, _spec_history=None,
                               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                              min_new_tokens: Optional[int] = None, suppress_tokens=None, num_return_sequences: int = 1, **unused):
+                              min_new_tokens: Optional[int] = None, suppress_tokens=None, num_return_sequences: int = 1,
+                              return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
+                              output_logprobs: bool = False, **unused):
+        """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
+        generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
+        `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
+        `output_logprobs` (ours: only `token_logprobs` = log-prob of each token under the model's distribution after the processors at
+        temperature 1, and `token_logprobs_warped` = under the distribution it was drawn from, both [rows, T], no [T, rows, V] tensors)
+        every step also runs the step recorder behind its tail, inside the per-token graph (csrc/sampling.hip: token_scores_kernel;
+        vz_hip/scores.py); without `return_dict_in_generate` they are ignored, as in HF.  Positions behind a row's eos are 0.0 in both
+        log-prob tensors; their `scores` / `logits` rows are whatever the parked row produced.  With any of the three,
+        `prompt_lookup_num_tokens` takes the plain greedy path (the ids are the same by construction).  With a streamer or stopping
+        criteria the records wait in a device ring of `max_new_tokens` slots that is allocated up front: 16 bytes per slot, and with
+        `output_scores` / `output_logits` another V fp32 per slot and output (260 MB each at V = 32000, max_new_tokens = 2048), even if
+        a criterion stops the call after a few tokens - HF's [T, rows, V] outputs cost that; `output_logprobs` does not.  With `num_beams > 1` the three
+        raise NotImplementedError; `return_dict_in_generate` alone gives `sequences` and `sequences_scores`."""
         from vz_hip import logits_proc, sample_rows
+        from vz_hip import scores as SC
+        what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams)
+        sink = SC.Sink(what) if what else None
         if eos_token_id is None:
             eos_token_id = self.generation_config.eos_token_id
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id or []))
@@ -393,7 +414,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing,
-                                       num_return_sequences=num_return_sequences, **unused)
+                                       num_return_sequences=num_return_sequences, return_dict_in_generate=return_dict_in_generate, **unused)
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         if max_new_tokens is None:
             max_new_tokens = 20 if max_length is None else max(1, max_length - S)
@@ -412,10 +433,11 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                       device=generator.device if generator is not None else "cpu").item())
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
+        done = lambda seqs: self._generate_output(seqs, sink, eos, return_dict_in_generate)      # noqa: E731  (the plain tensor unless asked)
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
-            return self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
-                                          pad_token_id, sync_every, timing, proc)
-        if prompt_lookup_num_tokens and _spec_history is not None and proc is None:      # (with processors: the plain greedy path, same ids)
+            return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
+                                               pad_token_id, sync_every, timing, proc, sink=sink))
+        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None:      # (with processors or scores: the plain greedy path, same ids)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
@@ -428,20 +450,48 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 assert len(_spec_history) == seqlens[0], f"history of {len(_spec_history)} ids for a prompt of {seqlens[0]} positions"
                 out = self._generate_spec(inputs_embeds[0:1, :seqlens[0]], None if position_ids is None else position_ids[0:1, :seqlens[0]],
                                           _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
-                return torch.tensor([out], dtype=torch.long, device=self.device)
+                return done(torch.tensor([out], dtype=torch.long, device=self.device))
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
-            return self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc)
+            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink))
         outs = []
         for b in range(Bsz):               # per-token host callbacks / sampling: one sequence at a time
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
-                                           stopping_criteria, seed + b, sync_every, timing, proc))
+                                           stopping_criteria, seed + b, sync_every, timing, proc, sink))
         n = max(len(o) for o in outs)
         res = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
         for b, o in enumerate(outs):
             res[b, :len(o)] = torch.tensor(o, dtype=torch.long, device=self.device)
-        return res
+        return done(res)
+
+    def _generate_output(self, seqs, sink, eos, return_dict_in_generate):
+        """what generate() returns for the new tokens `seqs` [rows, T]: the tensor, or HF's output object with what `sink` recorded"""
+        if not return_dict_in_generate:
+            return seqs
+        from vz_hip import scores as SC
+        Scored, _ = SC.output_classes()
+        if sink is None:
+            return Scored(sequences=seqs)
+        f = sink.finish(seqs, eos)
+        return Scored(sequences=seqs, scores=f["scores"], logits=f["logits"], token_logprobs=f["token_logprobs"],
+                      token_logprobs_warped=f["token_logprobs_warped"])
+
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits: bool = False):
+        """HF's `GenerationMixin.compute_transition_scores` for the outputs of `generate(return_dict_in_generate=True, output_scores=True)`
+        (no beams: `beam_indices` raises NotImplementedError)."""
+        from vz_hip import scores as SC
+        return SC.transition_scores(sequences, scores, beam_indices, normalize_logits)
+
+    def _score_first(self, sink, rows, temperature, last, raw, first, params):
+        """the block of `rows` rows that are about to decode together, holding the record of their first tokens `first` (device), chosen
+        on the processed prefill logits `last` [rows, V] by `params`; raw = those logits before the processors"""
+        from vz_hip import binding as B
+        blk = sink.block(rows, temperature)
+        r = B.token_scores(last, first, params, warped=sink.warped)
+        rec, w = r if sink.warped else (r, None)
+        blk.add(rec.unsqueeze(0), None if w is None else w.unsqueeze(0), raw.unsqueeze(0) if sink.raw else None)
+        return blk
 
     def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None) -> List[int]:
         """One greedy sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
@@ -462,7 +512,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             timing["spec"] = report
         return out
 
-    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None) -> torch.Tensor:
+    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None, sink=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step
         streams the weights once for all rows (the KV cache, positions and lengths are per slot).  Rows that hit eos keep
         their slot but emit `pad_token_id` from then on, as HF does.  `proc`: HF's logits processors (vz_hip.logits_proc) on the
@@ -473,7 +523,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if Bsz > cap:
             parts = [self._generate_batched(embeds[i:i + cap], seqlens[i:i + cap],
                                             None if position_ids is None else position_ids[i:i + cap], max_new, eos,
-                                            pad_token_id, sync_every, None, proc) for i in range(0, Bsz, cap)]
+                                            pad_token_id, sync_every, None, proc, sink) for i in range(0, Bsz, cap)]
             n = max(p.shape[1] for p in parts)
             out = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
             r = 0
@@ -484,10 +534,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if S + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         from vz_hip import binding as B
+        from vz_hip.sample_rows import GREEDY
         _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
+        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
         if proc is not None:
             B.logits_process(last, proc)                 # the first step's processors see an empty history
         first = B.argmax(last)
+        blk = None if sink is None else self._score_first(sink, Bsz, 1.0, last, raw, first, [GREEDY] * Bsz)
         next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
         first_cpu = first.to(torch.long).cpu()
         if timing is not None:
@@ -496,15 +549,19 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if proc is not None:
             eng.set_logits_proc(proc)
         try:
+            if blk is not None:
+                eng.set_scores(max(1, min(sync_every, max_new - 1)), Bsz, sink.warped, sink.raw)
             eng.decode_begin(first, next_pos, list(seqlens))
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every).to(self.device)
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk).to(self.device)
         finally:
+            if blk is not None:
+                eng.set_scores(None)
             if proc is not None:
                 eng.set_logits_proc(None)
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
-                          timing=None, proc=None, prompt0: int = 0) -> torch.Tensor:
+                          timing=None, proc=None, prompt0: int = 0, sink=None) -> torch.Tensor:
         """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
@@ -518,7 +575,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         G = SR.prompts_per_chunk(n, eng.max_batch)
         if Bsz > G:
             parts = [self._generate_samples(embeds[i:i + G], seqlens[i:i + G], None if position_ids is None else position_ids[i:i + G], n, max_new,
-                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i)
+                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i, sink)
                      for i in range(0, Bsz, G)]
             out = torch.full((Bsz * n, max(p.shape[1] for p in parts)), pad_token_id, dtype=torch.long, device=self.device)
             r = 0
@@ -536,11 +593,15 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             Sg = int(seqlens[g])
             last.append(eng.prefill_rows(g * n, embeds[g:g + 1, :Sg], [Sg], None if position_ids is None else position_ids[g:g + 1, :Sg]))
         last = torch.cat(last, 0).contiguous()
+        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
         if proc is not None:
             B.logits_process(last, proc)                 # the first step's processors see an empty history
         params = [SR.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
                                SR.row_seed(seed, prompt0 + r // n, n, r % n), 0) for r in range(R)]
-        first = B.sample_rows(last.repeat_interleave(n, dim=0).contiguous(), params)      # a prompt's one logits row, once per sample
+        last_rows = last.repeat_interleave(n, dim=0).contiguous()                          # a prompt's one logits row, once per sample
+        first = B.sample_rows(last_rows, params)
+        blk = None if sink is None else self._score_first(sink, R, float(temperature), last_rows, raw.repeat_interleave(n, dim=0) if sink.raw else None,
+                                                          first, params)
         first_cpu = first.to(torch.long).cpu()
         if timing is not None:
             import time
@@ -553,9 +614,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             if proc is not None:
                 eng.set_logits_proc(proc)
             eng.set_sampling_rows([p.at(1) for p in params])
+            if blk is not None:
+                eng.set_scores(max(1, min(sync_every, max_new - 1)), R, sink.warped, sink.raw)
             eng.decode_begin(first, next_pos, [int(seqlens[r // n]) for r in range(R)])
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every).to(self.device)
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk).to(self.device)
         finally:
+            if blk is not None:
+                eng.set_scores(None)
             eng.set_sampling_rows(None)
             if proc is not None:
                 eng.set_logits_proc(None)
@@ -623,8 +688,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 scores[b * nrs + r] = sc
         seqs = seqs.to(self.device)
         if return_dict_in_generate:
-            return SimpleNamespace(sequences=seqs, sequences_scores=scores.to(self.device), scores=None, logits=None,
-                                   beam_indices=None, attentions=None, hidden_states=None, past_key_values=None)
+            from vz_hip import scores as SC
+            return SC.output_classes()[1](sequences=seqs, sequences_scores=scores.to(self.device))      # HF's GenerateBeamDecoderOnlyOutput
         return seqs
 
     def _beam_chunk(self, embeds, seqlens, position_ids, nb, max_new, eos, length_penalty, early_stopping, nrs, sync_every, timing=None):
@@ -702,9 +767,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         Admissions are BATCHED when the engine has cache rows to spare (`max_batch > rows`): all requests entering at one sync
         share one Zephyr prefill (right-padded, up to `admit` = min(max_batch - rows, 16) sequences) into the spare rows, one
         argmax readback, and their KV is then moved to the freed rows (`vz_llm_kv_move_rows`).  The vision stage stays per request:
-        the Q-Former's text conditioning makes a request's visual tokens depend on the padded length of its batch."""
+        the Q-Former's text conditioning makes a request's visual tokens depend on the padded length of its batch.
+
+        A request may carry `logprobs=True`: that request, and only that one, is yielded as `(index, ids, logprobs)` with `logprobs` fp32
+        [n_new] = the log-prob of each of its tokens under the model's own distribution at temperature 1 (`generate`'s `token_logprobs`).
+        The step recorder (csrc/sampling.hip: token_scores_kernel) is armed when the first such request is admitted - the step's graph is
+        captured once more, no id changes - and one more device-to-host copy of [n, rows, 4] words rides with each chunk's ids; a call
+        in which no request asks runs as it always did."""
         from vz_hip import binding as B
         from vz_hip import sample_rows as SR
+        from vz_hip import scores as SC
         self._kv_epoch += 1
         self._ensure_ready()
         eng = self.engine
@@ -713,6 +785,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(t) for t in eos_token_id})
         draw_seed = lambda: int(torch.randint(0, 2 ** 62, (1,)).item())      # noqa: E731  (as generate draws its seed)
         armed = False                           # the per-row tail: from the first sampled request on
+        scored = False                          # the step recorder: from the first request with logprobs=True on
         n_rows = min(eng.max_batch, 64) if rows is None else int(rows)
         if not 1 <= n_rows <= min(eng.max_batch, 64):
             raise ValueError(f"rows must be in [1, {min(eng.max_batch, 64)}]")
@@ -739,12 +812,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             S = emb.shape[1]
             if S + budget > eng.max_ctx:
                 raise ValueError(f"request {idx}: prompt ({S}) + max_new_tokens ({budget}) exceeds the engine's max_ctx ({eng.max_ctx})")
-            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed)
+            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed), SC.wants_logprobs(req)
 
-        def first_tokens(logits, params):       # one launch and one readback for the group: argmax, or each row by its own parameters
-            if not any(p.sample for p in params):
-                return B.argmax(logits).tolist()
-            return B.sample_rows(logits, params).tolist()
+        def first_tokens(logits, params, want):     # one launch and one readback for the group: argmax, or each row by its own parameters
+            ids = B.argmax(logits) if not any(p.sample for p in params) else B.sample_rows(logits, params)
+            if not any(want):
+                return ids.tolist(), None
+            x, lse, _, _ = SC.unpack(B.token_scores(logits, ids, params))
+            return ids.tolist(), (x - lse).tolist()
 
         try:
             while True:
@@ -762,29 +837,36 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                         group.append((idx,) + embed(idx, req))
                     if not group:
                         break
+                    want = [g[5] for g in group]
                     if len(group) == 1:             # straight into the free row
-                        idx, emb, S, budget, par = group[0]
-                        firsts = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par])
+                        idx, emb, S, budget, par, _ = group[0]
+                        firsts, lp0 = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par], want)
                     else:                           # one prefill for the group in the spare rows, one readback
                         Smax = max(g[2] for g in group)
                         pad = torch.zeros(len(group), Smax, group[0][1].shape[-1], dtype=torch.bfloat16, device=self.device)
                         for j, g in enumerate(group):
                             pad[j, :g[2]] = g[1][0]
-                        firsts = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group])
+                        firsts, lp0 = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group], want)
                     moves = []
+                    if not scored and any(want):
+                        eng.set_scores(max(1, int(sync_every)), n_rows)      # records only; restarts the ring between two chunks
+                        scored = True
                     if not armed and any(g[4].sample for g in group):
                         # the table the running batch uploaded holds every row greedy: rows keep their ids when the tail changes under them
                         eng.set_sampling_rows([])
                         armed = True
-                    for j, (idx, emb, S, budget, par) in enumerate(group):
+                    for j, (idx, emb, S, budget, par, wants) in enumerate(group):
                         first = int(firsts[j])
                         if first in eos or budget <= 1:
-                            yield idx, torch.tensor([first], dtype=torch.long)
+                            if wants:
+                                yield idx, torch.tensor([first], dtype=torch.long), torch.tensor([lp0[j]], dtype=torch.float32)
+                            else:
+                                yield idx, torch.tensor([first], dtype=torch.long)
                             continue
                         r = free.pop(0)
                         if len(group) > 1:
                             moves.append((n_rows + j, r, S))
-                        slots[r] = [idx, [first], budget]
+                        slots[r] = [idx, [first], budget, [lp0[j]] if wants else None]
                         group[j] = (idx, None, S, budget, par, r, first)
                     if moves:
                         eng.kv_move_rows([m[0] for m in moves], [m[1] for m in moves], [m[2] for m in moves])
@@ -797,18 +879,29 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     return
                 n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
                 chunk = eng.decode_steps(n).cpu()                           # [rows, n]; the only host sync of the chunk
+                lps = None
+                if scored:
+                    x, lse, _, _ = SC.unpack(eng.scores_steps(n)[0].cpu())  # [n, rows]
+                    lps = (x - lse).transpose(0, 1).tolist()
                 for r, st in enumerate(slots):
                     if st is None:
                         continue
-                    for t in chunk[r].tolist():
+                    for i, t in enumerate(chunk[r].tolist()):
                         st[1].append(int(t))
+                        if st[3] is not None:
+                            st[3].append(lps[r][i])
                         if int(t) in eos or len(st[1]) >= st[2]:
                             break
                     if st[1][-1] in eos or len(st[1]) >= st[2]:
-                        yield st[0], torch.tensor(st[1], dtype=torch.long)
+                        if st[3] is not None:
+                            yield st[0], torch.tensor(st[1], dtype=torch.long), torch.tensor(st[3], dtype=torch.float32)
+                        else:
+                            yield st[0], torch.tensor(st[1], dtype=torch.long)
                         eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
                         slots[r] = None
         finally:
+            if scored:
+                eng.set_scores(None)
             if armed:
                 eng.set_sampling_rows(None)
 
@@ -819,7 +912,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None, proc=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
@@ -839,9 +932,15 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             # HF hands the (empty, since generation starts from embeddings) prompt ids to the streamer first;
             # TextStreamer(skip_prompt=True) swallows exactly one put() as "the prompt"
             streamer.put(torch.empty((1, 0), dtype=torch.long))
+        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
         if proc is not None:
             B.logits_process(last, proc)                 # the first step's processors see an empty history
         first = B.argmax(last) if greedy else B.sample(last, temperature, top_k, top_p, seed, 0)
+        blk = None
+        if sink is not None:
+            from vz_hip.sample_rows import GREEDY, RowParams
+            par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0)
+            blk = self._score_first(sink, 1, 1.0 if greedy else float(temperature), last, raw, first, [par])
         tok = int(first[0])          # int(): the host holds the first token here
         if timing is not None:
             import time
@@ -857,6 +956,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 ring = self._token_ring()
                 R = ring.numel()
                 eng.set_ring(ring)
+                if blk is not None:          # a device ring of max_new slots, read once at the end: no step waits for its record
+                    eng.set_scores(max_new, 1, sink.warped, sink.raw)
                 eng.decode_begin(first, [next_pos], [S])
                 dev_out = torch.empty(1, 1, dtype=torch.int32, device=self.device)
                 events = {}
@@ -879,14 +980,20 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     t += 1
                 torch.cuda.current_stream(self.device).synchronize()      # a speculative step may still be running
                 eng.check_async()
+                if blk is not None:
+                    blk.add(*eng.scores_steps(len(out) - 1, first=0))     # (a speculative step's record behind them is not read)
                 return self._finish(out, streamer)
             # no host callbacks: steps are enqueued back to back, the host looks at the ids every `sync_every` tokens only to honour eos
+            if blk is not None:
+                eng.set_scores(max(1, min(sync_every, max_new - 1)), 1, sink.warped, sink.raw)
             eng.decode_begin(first, [next_pos], [S])
             remaining = max_new - 1
             while remaining > 0:
-                n = min(sync_every, remaining) if eos else remaining
+                n = min(sync_every, remaining) if (eos or blk is not None) else remaining
                 ids = eng.decode_steps(n)[0].tolist()
                 eng.check_async()                 # a bounded device-side wait that expired = invalid ids: fail loudly
+                if blk is not None:
+                    blk.add(*eng.scores_steps(n))
                 remaining -= n
                 for t in ids:
                     out.append(int(t))
@@ -896,6 +1003,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         finally:
             eng.set_sampling(False)
             eng.set_ring(None)
+            if blk is not None:
+                eng.set_scores(None)
             if proc is not None:
                 eng.set_logits_proc(None)
 

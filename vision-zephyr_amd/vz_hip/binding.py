@@ -21,6 +21,7 @@ VZ_ASYNC_PERSIST = 3
 VZ_ASYNC_ONESHOT = 4
 VZ_ASYNC_ATTN_O = 5
 ABI_VERSION = 10
+SCORE_REC, SCORE_WARPED, SCORE_RAW = 1, 2, 4          # vz_llm_decode_scores `what`
 SPEC_CTL_WRITE, SPEC_CTL_HIST, SPEC_CTL_DONE, SPEC_CTL_DRAFTED, SPEC_CTL_STEPS, SPEC_CTL_IDS, SPEC_CTL_WORDS = 0, 1, 2, 3, 4, 8, 16
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF, ACT_SWIGLU = 0, 1, 2, 3
 K_GEMM, K_GEMV, K_ATTN, K_ATTN_DEC, K_NORM, K_OTHER, K_FUSED, K_COMM = range(8)
@@ -136,6 +137,8 @@ SYMBOLS = {
     "vz_llm_decode_sampling_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_set_row_sampling": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P]),
     "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_scores": (_I, [_P, C.c_uint, _P, _P, _P, _I, _P]),
+    "vz_op_token_scores": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -683,6 +686,25 @@ def sample_rows(logits, params):
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
     check(lib().vz_op_sample_rows(ptr(logits), logits.shape[0], logits.shape[1], *row_sample_arrays(params), ptr(ids), stream_ptr(logits.device)))
     return ids
+
+
+def token_scores(logits, ids, params, warped=False):
+    """the step recorder (sampling.hip: token_scores_kernel) on fp32 logits [rows, V] about the tokens ids [rows]: row r by params[r]
+    (vz_hip.sample_rows.RowParams: greedy, or temperature / top-k / top-p; seed and counter are not read).  Returns the records fp32
+    [rows, 4] = (x_tok, lse, lse_kept, n_kept as int32 bits) (vz_hip.scores.unpack), with warped=True also the score rows fp32 [rows, V]."""
+    _need_cuda(logits, ids)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(params) == logits.shape[0]
+    rows, V = logits.shape
+    ids = ids.to(torch.int32).contiguous().view(-1)
+    assert ids.numel() == rows and ids.device == logits.device
+    rec = torch.empty(rows, 4, dtype=torch.float32, device=logits.device)
+    w = torch.empty(rows, V, dtype=torch.float32, device=logits.device) if warped else None
+    for r0 in range(0, rows, 64):          # the op takes up to 64 rows
+        r1 = min(rows, r0 + 64)
+        mode, temp, top_k, top_p, _, _ = row_sample_arrays(params[r0:r1])
+        check(lib().vz_op_token_scores(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), mode, temp, top_k, top_p, ptr(rec[r0:r1]),
+                                       ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
+    return (rec, w) if warped else rec
 
 
 def beam_k(nb: int, n_eos: int) -> int:

@@ -78,6 +78,7 @@ class Engine:
         self._cos, self._sin = cos.to(self.device), sin.to(self.device)
         B.check(self.lib.vz_engine_set_rope(self.h, B.ptr(self._cos), B.ptr(self._sin), max_ctx))
         self.ready = False
+        self._score = None                     # the step recorder's rings and step count while armed (set_scores)
 
     def set_prefill_fp8(self, on: bool = True):
         """weight_fp8 engines: run the Zephyr prefill linears on the fp8 MFMA (activations quantised to e4m3 per row on the device,
@@ -568,6 +569,8 @@ class Engine:
         self._spec = None                  # a new batch starts with the plain tail (the library clears the mode too)
         B.check(self.lib.vz_llm_decode_begin(self.h, Bn, B.ptr(ids), np_, cl, self._s()))
         self._dec_B = Bn
+        if self._score is not None:
+            self._score["count"] = 0       # the recorder's ring restarts with the batch
 
     def decode_steps(self, n: int, out: Optional[torch.Tensor] = None, return_logits: bool = False):
         """enqueue n greedy steps; returns int32 [B,n] (device; no host sync) (+ fp32 logits [n,B,V]).  With the speculative tail
@@ -588,8 +591,39 @@ class Engine:
         if out is None:
             out = torch.empty(Bn, n, dtype=torch.int32, device=self.device)
         lg = torch.empty(n, Bn, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logits else None
+        sc = self._score
+        if sc is not None and sc["rows"] != Bn:          # the rings are [cap_steps][rows]: the recorder writes one record per row of the batch
+            raise ValueError(f"decode_steps: the step recorder was armed for {sc['rows']} rows (set_scores), the decode batch has {Bn}")
         B.check(self.lib.vz_llm_decode_steps(self.h, n, B.ptr(out), B.ptr(lg), self._s()))
+        if sc is not None:
+            sc["count"] += n
         return (out, lg) if return_logits else out
+
+    def set_scores(self, cap_steps: Optional[int] = None, rows: int = 1, warped: bool = False, raw: bool = False):
+        """the step recorder (sampling.hip: token_scores_kernel): every step of a `rows`-row decode batch records (x_tok, lse, lse_kept,
+        n_kept) per row about the token its tail chose - with `warped` also the score rows HF calls scores[t], with `raw` the logits rows
+        as the lm_head left them - into device rings of `cap_steps` steps, read with `scores_steps`.  None = off.  Arming restarts the
+        ring, as `decode_begin` does; `decode_steps` refuses more than `cap_steps` steps per call."""
+        if cap_steps is None:
+            self._score = None
+            B.check(self.lib.vz_llm_decode_scores(self.h, 0, None, None, None, 0, self._s()))
+            return
+        cap, rows, V = int(cap_steps), int(rows), self.cfg.vocab
+        sc = {"cap": cap, "rows": rows, "count": 0, "rec": torch.zeros(cap, rows, 4, dtype=torch.float32, device=self.device),
+              "warped": torch.empty(cap, rows, V, dtype=torch.float32, device=self.device) if warped else None,
+              "raw": torch.empty(cap, rows, V, dtype=torch.float32, device=self.device) if raw else None}
+        what = B.SCORE_REC | (B.SCORE_WARPED if warped else 0) | (B.SCORE_RAW if raw else 0)
+        B.check(self.lib.vz_llm_decode_scores(self.h, what, B.ptr(sc["rec"]), B.ptr(sc["warped"]), B.ptr(sc["raw"]), cap, self._s()))
+        self._score = sc
+
+    def scores_steps(self, n: int, first: Optional[int] = None):
+        """what the recorder holds of `n` steps, from step `first` counted from the last `decode_begin` / `set_scores` (default: the last
+        n): (records fp32 [n, rows, 4], warped rows [n, rows, V] or None, raw rows or None), device tensors in step order."""
+        from . import scores as SC
+        sc = self._score
+        assert sc is not None, "scores_steps: the recorder is off (set_scores)"
+        pick = lambda ring: None if ring is None else SC.ring_order(ring, sc["count"], n, first)      # noqa: E731
+        return pick(sc["rec"]), pick(sc["warped"]), pick(sc["raw"])
 
     def set_sampling(self, on: bool, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, first_counter: int = 1):
         """tail of every decode step: greedy argmax (off) or the device-side sampler (sampling.hip); applies from the next decode_begin."""
