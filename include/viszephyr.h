@@ -501,6 +501,39 @@ int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mo
 int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, float* d_warped, float* d_raw, int cap_steps, vz_stream stream);
 int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
                        const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream);
+/* Stop matcher (csrc/stop.hip: stop_match_kernel): stop strings and keyword stops decided on the device.  After
+ * vz_llm_decode_stop(enable = 1) every decode step runs, behind its tail (argmax, sampler or per-row tail; behind the step recorder if
+ * that is armed) and inside the per-token hipGraph, one 64-lane wave per row over the row's state: n = generated tokens seen, at = -1
+ * or the 0-based index of the token at which a stop condition first held (sticky), and a ring of the last VZ_STOP_W ids.  Two rules:
+ *   stop strings: HF's StopStringCriteria.__call__ over the tables HF's constructor builds - h_emb = embedding_vec, int32 [emb_rows =
+ *     V + 2][vec = n_str * (max_pos + max_end) + 1], max_pos = max_valid_positions, max_end = max_valid_end_lens, window =
+ *     maximum_token_len, h_target = target_lens [n_str];
+ *   id sequences (KeywordsStoppingCriteria of mm_utils): h_seq int32 [n_seq][VZ_STOP_SEQ_STRIDE] = [len, start, the ids NEWEST FIRST];
+ *     sequence k matches when n >= start + len and the last len generated ids equal it.
+ * Limits: VZ_STOP_MAX_STR strings, window <= VZ_STOP_W, max_pos <= VZ_STOP_MAX_POS, max_end <= VZ_STOP_MAX_END, VZ_STOP_MAX_SEQ sequences
+ * of <= VZ_STOP_MAX_SEQ_LEN ids.  The call copies the tables into engine-owned device memory (never inside a capture); the matcher writes
+ * only its own state, never a word the step reads, so arming it changes no id.  Frozen by a captured step: a change captures again, and
+ * with the matcher off no launch is added.  Refused with the beam or the speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.
+ * vz_llm_decode_stop_rows: rows [row0, row0 + rows) start clean and their first tokens d_first_ids [rows] (int32, device; chosen from the
+ * prefill logits, outside the step) go through the same kernel - call it where vz_llm_decode_begin / vz_llm_decode_set_row are called.
+ * Every arming starts with no row watched: a row is matched from this call on, never from what an earlier arming left in its state.  vz_llm_decode_stop_read: at[row0 .. row0 + rows) into d_at (int32, device), stream-ordered.
+ * vz_op_stop_match: the kernel on caller-owned state d_state [rows][VZ_STOP_ROW] and device tables, one new id per row d_ids [rows]
+ * (reset != 0: the rows start clean first); state word 0 = n, word 1 = at, words 2.. = the ring. */
+#define VZ_STOP_W 64
+#define VZ_STOP_ROW (2 + VZ_STOP_W)
+#define VZ_STOP_MAX_STR 8
+#define VZ_STOP_MAX_POS 16
+#define VZ_STOP_MAX_END 8
+#define VZ_STOP_MAX_SEQ 16
+#define VZ_STOP_MAX_SEQ_LEN 32
+#define VZ_STOP_SEQ_STRIDE (2 + VZ_STOP_MAX_SEQ_LEN)
+#define VZ_STOP_UNARMED (-2)
+int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, int emb_rows, int vec, int n_str, int max_pos, int max_end, int window,
+                       const int* h_target, const int* h_seq, int n_seq, vz_stream stream);
+int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const int* d_first_ids, vz_stream stream);
+int vz_llm_decode_stop_read(vz_engine* e, int row0, int rows, int* d_at, vz_stream stream);
+int vz_op_stop_match(int* d_state, int rows, const int* d_ids, int reset, const int* d_emb, int emb_rows, int vec, int n_str, int max_pos,
+                     int max_end, int window, const int* d_target, const int* d_seq, int n_seq, vz_stream stream);
 /* Batched admissions: prefill several requests together into spare cache rows (row0 >= the running batch), then move each one's
  * first h_len[i] cache positions from row h_src[i] to the freed row h_dst[i] (every layer, K and V; stream-ordered).  Rows of
  * one call must not overlap (no destination equal to another move's source or destination). */

@@ -452,6 +452,8 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->beam.d) hipFree(e->beam.d);
     if (e->proc.d) hipFree(e->proc.d);
     if (e->score.d_slot) hipFree(e->score.d_slot);
+    if (e->stop.d_state) hipFree(e->stop.d_state);
+    if (e->stop.d_tab) hipFree(e->stop.d_tab);
     if (e->d_gather) (void)hipFree(e->d_gather);
     vz_decode_persist_destroy(e->tok);
     if (e->comm) (void)ncclCommDestroy(e->comm);
@@ -1283,12 +1285,99 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             RC(vz_launch_token_scores(e->d_logits, B, c.vocab, tail == TAIL_ROWS ? st.samp : nullptr, one, st.cur, e->score.rec,
                                       (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
         }
+        // stop.hip: the token the tail just left in st.cur through the rows' stop conditions (writes its own state only)
+        if (e->stop.on) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s)); }      // (its own profiling scope: one more counted launch)
         RC(vz_launch_step_advance(st.step, e->score.what ? e->score.d_slot : nullptr, s));
     }
     return VZ_OK;
 }
 
 static int row_sample_of(int mode, float temperature, int top_k, float top_p, unsigned long long seed, int counter, RowSample* out);
+
+// The stop matcher (stop.hip: stop_match_kernel): armed, every decode step whose tail is the argmax, the sampler or the
+// per-row tail passes, behind that tail (and the recorder) and inside the per-token hipGraph, the token each row just chose through the
+// row's stop conditions and records the index of the token at which one first held.  The tables are copied into the engine's own device
+// memory here, outside any capture; a row is watched from vz_llm_decode_stop_rows on.  enable = 0: off.
+extern "C" int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, int emb_rows, int vec, int n_str, int max_pos, int max_end, int window,
+                                  const int* h_target, const int* h_seq, int n_seq, vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->stop.on = 0; memset(&e->stop.a, 0, sizeof(e->stop.a)); return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_stop: the stop matcher on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(n_str >= 0 && n_str <= VZ_STOP_MAX_STR && n_seq >= 0 && n_seq <= VZ_STOP_MAX_SEQ && n_str + n_seq >= 1,
+                 "decode_stop: %d stop strings (0..%d), %d id sequences (0..%d), at least one of either", n_str, VZ_STOP_MAX_STR, n_seq, VZ_STOP_MAX_SEQ);
+    VZ_CHECK_ARG(n_str == 0 || (h_emb && h_target && emb_rows >= 1 && emb_rows <= (1 << 22) && vec == n_str * (max_pos + max_end) + 1 && max_pos >= 1 &&
+                                max_pos <= VZ_STOP_MAX_POS && max_end >= 1 && max_end <= VZ_STOP_MAX_END && window >= 1 && window <= VZ_STOP_W),
+                 "decode_stop: stop-string tables outside the matcher's limits (rows %d, vec %d, max_valid_positions %d <= %d, max_valid_end_lens %d <= %d, "
+                 "maximum_token_len %d <= %d)", emb_rows, vec, max_pos, VZ_STOP_MAX_POS, max_end, VZ_STOP_MAX_END, window, VZ_STOP_W);
+    VZ_CHECK_ARG(n_seq == 0 || h_seq, "decode_stop: id sequences without their table");
+    for (int k = 0; k < n_seq; ++k)
+        VZ_CHECK_ARG(h_seq[k * VZ_STOP_SEQ_STRIDE] >= 1 && h_seq[k * VZ_STOP_SEQ_STRIDE] <= VZ_STOP_MAX_SEQ_LEN && h_seq[k * VZ_STOP_SEQ_STRIDE + 1] >= 0,
+                     "decode_stop: id sequence %d of %d ids from %d (1..%d ids, start >= 0)", k, h_seq[k * VZ_STOP_SEQ_STRIDE], h_seq[k * VZ_STOP_SEQ_STRIDE + 1], VZ_STOP_MAX_SEQ_LEN);
+    hipStream_t s = (hipStream_t)stream;
+    const int mb = e->c.max_batch;
+    if (!e->stop.d_state) {
+        e->stop.h_init.assign((size_t)mb * VZ_STOP_ROW, 0);
+        for (int r = 0; r < mb; ++r) e->stop.h_init[(size_t)r * VZ_STOP_ROW + 1] = VZ_STOP_UNARMED;
+        VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_state, e->stop.h_init.size() * sizeof(int)));
+    }
+    // every arming starts with no row watched (stream-ordered behind the steps of an earlier arming): a row is matched from its
+    // vz_llm_decode_stop_rows on, never from what an earlier call left in its state
+    VZ_CHECK_HIP(hipMemcpyAsync(e->stop.d_state, e->stop.h_init.data(), e->stop.h_init.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    const size_t emb_ints = n_str ? (size_t)emb_rows * vec : 0, tgt_ints = VZ_STOP_MAX_STR, seq_ints = (size_t)VZ_STOP_MAX_SEQ * VZ_STOP_SEQ_STRIDE;
+    const size_t need = emb_ints + tgt_ints + seq_ints;
+    std::vector<int> tab(need, 0);                  // [emb | target | seq], as the device holds it
+    if (emb_ints) memcpy(tab.data(), h_emb, emb_ints * sizeof(int));
+    for (int i = 0; i < n_str; ++i) tab[emb_ints + i] = h_target[i];
+    if (n_seq) memcpy(tab.data() + emb_ints + tgt_ints, h_seq, (size_t)n_seq * VZ_STOP_SEQ_STRIDE * sizeof(int));
+    // the stop set of the previous arming again (a serving loop that calls generate() per request): the device holds these tables already -
+    // no synchronise, no upload
+    if (!(e->stop.d_tab && tab == e->stop.h_tab)) {
+        VZ_CHECK_HIP(hipStreamSynchronize(s));      // steps still in flight read the tables of the previous stop set
+        if (need > e->stop.tab_ints) {
+            if (e->stop.d_tab) { VZ_CHECK_HIP(hipFree(e->stop.d_tab)); e->stop.d_tab = nullptr; e->stop.tab_ints = 0; e->stop.h_tab.clear(); }
+            VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_tab, need * sizeof(int)));
+            e->stop.tab_ints = need;
+        }
+        VZ_CHECK_HIP(hipMemcpy(e->stop.d_tab, tab.data(), need * sizeof(int), hipMemcpyHostToDevice));
+        e->stop.h_tab.swap(tab);
+    }
+    StopArgs a;
+    memset(&a, 0, sizeof(a));
+    a.emb = n_str ? e->stop.d_tab : nullptr; a.target = e->stop.d_tab + emb_ints; a.seq = e->stop.d_tab + emb_ints + tgt_ints;
+    a.n_str = n_str; a.n_seq = n_seq;
+    if (n_str) { a.emb_rows = emb_rows; a.vec = vec; a.max_pos = max_pos; a.max_end = max_end; a.window = window; }
+    e->stop.a = a; e->stop.on = 1;
+    return VZ_OK;
+}
+
+// rows [row0, row0 + rows) start clean and their first tokens (chosen from the prefill logits, outside the step) go through the step's own
+// kernel: one implementation, no host mirror
+extern "C" int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const int* d_first_ids, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->stop.on, "decode_stop_rows: the stop matcher is off (vz_llm_decode_stop)");
+    VZ_CHECK_ARG(row0 >= 0 && rows >= 1 && row0 + rows <= e->c.max_batch && d_first_ids, "decode_stop_rows: rows [%d, %d) outside max_batch = %d", row0, row0 + rows, e->c.max_batch);
+    return vz_launch_stop_match(e->stop.a, e->stop.d_state + (size_t)row0 * VZ_STOP_ROW, rows, d_first_ids, 1, (hipStream_t)stream);
+}
+
+// at[row0 .. row0 + rows) -> d_at (device), stream-ordered behind the steps: rides with the chunk's ids at the host's sync
+extern "C" int vz_llm_decode_stop_read(vz_engine* e, int row0, int rows, int* d_at, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->stop.d_state, "decode_stop_read: the stop matcher was never armed (vz_llm_decode_stop)");
+    VZ_CHECK_ARG(row0 >= 0 && rows >= 1 && row0 + rows <= e->c.max_batch && d_at, "decode_stop_read: rows [%d, %d) outside max_batch = %d", row0, row0 + rows, e->c.max_batch);
+    VZ_CHECK_HIP(hipMemcpy2DAsync(d_at, sizeof(int), e->stop.d_state + (size_t)row0 * VZ_STOP_ROW + 1, VZ_STOP_ROW * sizeof(int), sizeof(int), rows,
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return VZ_OK;
+}
+
+// the kernel on caller-owned state and device tables, one new id per row (tests)
+extern "C" int vz_op_stop_match(int* d_state, int rows, const int* d_ids, int reset, const int* d_emb, int emb_rows, int vec, int n_str, int max_pos,
+                                int max_end, int window, const int* d_target, const int* d_seq, int n_seq, vz_stream stream) {
+    StopArgs a;
+    memset(&a, 0, sizeof(a));
+    a.emb = d_emb; a.target = d_target; a.seq = d_seq; a.emb_rows = emb_rows; a.vec = vec; a.n_str = n_str; a.max_pos = max_pos; a.max_end = max_end;
+    a.window = window; a.n_seq = n_seq;
+    return vz_launch_stop_match(a, d_state, rows, d_ids, reset, (hipStream_t)stream);
+}
 
 // The step recorder (sampling.hip: token_scores_kernel): armed, every decode step whose tail is the argmax, the
 // sampler or the per-row tail writes, behind that tail and inside the per-token hipGraph, one record {x_tok, lse, lse_kept, n_kept} per
@@ -1675,6 +1764,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; }
+    if (e->stop.on) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
 }
@@ -1698,6 +1788,8 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(!e->rows.on || (!e->beam.on && !e->spec.on && e->tp == 1), "decode_steps: the per-row tail (vz_llm_decode_sampling_rows) does not run "
                  "together with the beam or the speculative tail, nor on a tensor-parallel engine");
     VZ_CHECK_ARG(!e->score.what || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the step recorder (vz_llm_decode_scores) runs behind the "
+                 "argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
+    VZ_CHECK_ARG(!e->stop.on || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the stop matcher (vz_llm_decode_stop) runs behind the "
                  "argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
     VZ_CHECK_ARG(!e->score.what || n <= e->score.cap, "decode_steps: %d steps, the step recorder's rings hold cap_steps = %d", n, e->score.cap);
     DecodeWs w;

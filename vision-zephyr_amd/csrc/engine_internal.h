@@ -68,8 +68,9 @@ struct DecodeGraphKey {
     SampleArgs samp; BeamArgs beam; SpecArgs spec;
     int* proc_hist; ProcArgs proc; int proc_on;      // the logits processors in front of the tail and their history buffer (zero when off)
     float *sc_rec, *sc_warped, *sc_raw; unsigned sc_what; int sc_cap;      // the step recorder behind the tail and its rings (zero when off)
+    int* stop_state; StopArgs stop;      // the stop matcher behind the tail: its state, tables and dims (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
 
 // The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
@@ -130,6 +131,10 @@ struct vz_engine {
     // step recorder (vz_llm_decode_scores; sampling.hip: token_scores_kernel): behind the tail, a record per row and step into the caller's
     // rings of `cap` steps; d_slot = the steps launched since vz_llm_decode_begin (one word of its own, counted by the step-advance launch)
     struct { unsigned what = 0; float *rec = nullptr, *warped = nullptr, *raw = nullptr; int cap = 0; int* d_slot = nullptr; } score;
+    // stop matcher (vz_llm_decode_stop; stop.hip: stop_match_kernel): behind the tail and the recorder.  d_state = max_batch rows of VZ_STOP_ROW
+    // ints [n | at | ring]; d_tab = the tables of the armed stop set [emb | target | seq] (a.emb / a.target / a.seq point into it)
+    // h_tab = the host image of d_tab (an arming with the same stop set uploads nothing); h_init = the state with no row watched
+    struct { int on = 0; StopArgs a{}; int* d_state = nullptr; int* d_tab = nullptr; size_t tab_ints = 0; std::vector<int> h_tab, h_init; } stop;
     struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)

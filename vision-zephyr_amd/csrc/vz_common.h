@@ -373,6 +373,13 @@ int vz_launch_step_advance(int* step, int* also, hipStream_t s);      // also: o
 int vz_launch_token_scores(const float* logits, int rows, int cols, const RowSample* tab, const RowSample& one, const int* ids, float* rec,
                            float* warped, const int* slot_word, int cap_steps, hipStream_t s);
 int vz_launch_score_raw_rows(const float* logits, int rows, int cols, float* raw, const int* slot_word, int cap_steps, hipStream_t s);
+// the stop matcher (stop.hip): per row a state of VZ_STOP_ROW ints [n | at | ring of the last VZ_STOP_W ids]; the tables are
+// HF's StopStringCriteria attributes (emb = embedding_vec [emb_rows = V + 2][vec], target = target_lens [n_str]) and the id sequences
+// seq [n_seq][VZ_STOP_SEQ_STRIDE] = [len, start, ids newest first], all in device memory
+struct StopArgs { const int* emb; const int* target; const int* seq; int emb_rows, vec, n_str, max_pos, max_end, window, n_seq, pad; };
+static_assert(sizeof(StopArgs) == 3 * 8 + 8 * 4, "padding in StopArgs");
+// one new id per row (ids[row]) through the matcher; reset != 0: the rows start clean (n = 0, at = -1) and are armed
+int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s);
 // beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
 struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);

@@ -103,23 +103,33 @@ class PastKeyValues:
         return max(self.lengths) if self.lengths else 0
 
 
-def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=None) -> torch.Tensor:
+def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=None, stop: bool = False) -> torch.Tensor:
     """the steps of a batch `decode_begin` has armed with the rows' first tokens `first_cpu` (host): [rows, <= max_new] new tokens,
     `sync_every` steps per host sync (host tensor), a row showing `pad_token_id` behind its eos, until every row is done.
-    blk (vz_hip.scores block; the engine's step recorder is armed for `sync_every` steps): every chunk's records are added to it."""
+    blk (vz_hip.scores block; the engine's step recorder is armed for `sync_every` steps): every chunk's records are added to it.
+    stop: the engine's stop matcher watches the rows (`Engine.set_stop`, `stop_rows`): the token at which a row's stop condition first
+    held ends the row as an eos does - the indices ride with each chunk's ids."""
     Bsz = first_cpu.numel()
     cols = [first_cpu.view(Bsz, 1)]
     eos_t = torch.tensor(sorted(eos), dtype=torch.long)
     done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
+    if stop:
+        done = done | (eng.stop_at(0, Bsz).cpu() == 0)
     remaining = max_new - 1
+    seen = 1                                                         # generated tokens per row in front of the next chunk
     while remaining > 0 and not bool(done.all()):
-        n = min(sync_every, remaining) if (eos or blk is not None) else remaining
-        chunk = eng.decode_steps(n).to(torch.long).cpu()             # [B, n]: the only host sync of the chunk
+        n = min(sync_every, remaining) if (eos or stop or blk is not None) else remaining
+        chunk = eng.decode_steps(n)
+        at = eng.stop_at(0, Bsz) if stop else None
+        chunk = chunk.to(torch.long).cpu()                           # [B, n]: the only host sync of the chunk
         if blk is not None:
             blk.add(*eng.scores_steps(n))
         remaining -= n
-        if eos:
-            hit = torch.isin(chunk, eos_t)                           # eos emitted at (row, step)
+        if eos or stop:
+            hit = torch.isin(chunk, eos_t) if eos else torch.zeros_like(chunk, dtype=torch.bool)      # eos emitted at (row, step)
+            if stop:                                                 # ... or the row's stop condition first held at that token
+                hit = hit | (at.cpu().to(torch.long).view(Bsz, 1) == seen + torch.arange(n, dtype=torch.long).view(1, n))
+            seen += n
             # a row is finished after its first eos (inclusive): later steps show the pad token
             after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
             chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
@@ -129,7 +139,11 @@ def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=Non
                 chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
             done = done_at[:, chunk.shape[1] - 1]
         cols.append(chunk)
-    return torch.cat(cols, dim=1)
+    out = torch.cat(cols, dim=1)
+    if stop and blk is not None:
+        at = eng.stop_at(0, Bsz).cpu().to(torch.long)
+        blk.ends = torch.where((at >= 0) & (at < out.shape[1]), at + 1, torch.full_like(at, out.shape[1]))
+    return out
 
 
 class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
@@ -384,7 +398,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                               min_new_tokens: Optional[int] = None, suppress_tokens=None, num_return_sequences: int = 1,
                               return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
-                              output_logprobs: bool = False, **unused):
+                              output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True, **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -397,9 +411,22 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         criteria the records wait in a device ring of `max_new_tokens` slots that is allocated up front: 16 bytes per slot, and with
         `output_scores` / `output_logits` another V fp32 per slot and output (260 MB each at V = 32000, max_new_tokens = 2048), even if
         a criterion stops the call after a few tokens - HF's [T, rows, V] outputs cost that; `output_logprobs` does not.  With `num_beams > 1` the three
-        raise NotImplementedError; `return_dict_in_generate` alone gives `sequences` and `sequences_scores`."""
+        raise NotImplementedError; `return_dict_in_generate` alone gives `sequences` and `sequences_scores`.
+
+        Stops (vz_hip/stop.py; csrc/stop.hip: stop_match_kernel): HF's `stop_strings=` (+ `tokenizer=`; default
+        `generation_config.stop_strings`), and `stopping_criteria` made only of HF's `StopStringCriteria` and this package's
+        `KeywordsStoppingCriteria`, are decided on the device, behind every step's tail inside the per-token graph: the call keeps its
+        batched route (`Bsz > 1` greedy rows decode together, `num_return_sequences > 1` works), the host reads where each row stopped at
+        the syncs it already has, and a stopped row keeps its stopping token and shows `pad_token_id` behind it, as behind eos.  With a
+        streamer, `num_beams > 1`, a tensor-parallel engine, any other criterion in the list, a stop set beyond the matcher's limits or
+        `device_stop=False` every criterion stays on the host (one sequence at a time, one callback per token), and stop strings given
+        by keyword join them as a `StopStringCriteria`."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
+        from vz_hip import stop as ST
+        # what the device takes of the call's stop conditions (all or nothing); every check below sees the host's remainder only
+        stop, stopping_criteria = ST.parse(stop_strings, tokenizer, stopping_criteria, self.generation_config,
+                                           device_stop and streamer is None and num_beams == 1 and self.engine.tp_size == 1)
         what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams)
         sink = SC.Sink(what) if what else None
         if eos_token_id is None:
@@ -436,8 +463,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         done = lambda seqs: self._generate_output(seqs, sink, eos, return_dict_in_generate)      # noqa: E731  (the plain tensor unless asked)
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
-                                               pad_token_id, sync_every, timing, proc, sink=sink))
-        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None:      # (with processors or scores: the plain greedy path, same ids)
+                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop))
+        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None:      # (with processors, scores or device stops: the plain greedy path, same ids)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
@@ -452,13 +479,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                           _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
                 return done(torch.tensor([out], dtype=torch.long, device=self.device))
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
-            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink))
+            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop))
         outs = []
         for b in range(Bsz):               # per-token host callbacks / sampling: one sequence at a time
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
-                                           stopping_criteria, seed + b, sync_every, timing, proc, sink))
+                                           stopping_criteria, seed + b, sync_every, timing, proc, sink, stop))
         n = max(len(o) for o in outs)
         res = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
         for b, o in enumerate(outs):
@@ -512,18 +539,20 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             timing["spec"] = report
         return out
 
-    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None, sink=None) -> torch.Tensor:
+    def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None, sink=None,
+                          stop=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step
         streams the weights once for all rows (the KV cache, positions and lengths are per slot).  Rows that hit eos keep
         their slot but emit `pad_token_id` from then on, as HF does.  `proc`: HF's logits processors (vz_hip.logits_proc) on the
-        prefill logits and, armed in the engine, on every step's."""
+        prefill logits and, armed in the engine, on every step's.  `stop`: the stop conditions the engine's matcher decides per row
+        (vz_hip.stop.Plan): a row that stops is treated as a row that emitted eos."""
         eng = self.engine
         Bsz, S = embeds.shape[0], embeds.shape[1]
         cap = min(eng.max_batch, 64)
         if Bsz > cap:
             parts = [self._generate_batched(embeds[i:i + cap], seqlens[i:i + cap],
                                             None if position_ids is None else position_ids[i:i + cap], max_new, eos,
-                                            pad_token_id, sync_every, None, proc, sink) for i in range(0, Bsz, cap)]
+                                            pad_token_id, sync_every, None, proc, sink, stop) for i in range(0, Bsz, cap)]
             n = max(p.shape[1] for p in parts)
             out = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
             r = 0
@@ -552,8 +581,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             if blk is not None:
                 eng.set_scores(max(1, min(sync_every, max_new - 1)), Bsz, sink.warped, sink.raw)
             eng.decode_begin(first, next_pos, list(seqlens))
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk).to(self.device)
+            if stop is not None:
+                eng.set_stop(stop)
+                eng.stop_rows(0, first)
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
         finally:
+            if stop is not None:
+                eng.set_stop(None)
             if blk is not None:
                 eng.set_scores(None)
             if proc is not None:
@@ -561,7 +595,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
-                          timing=None, proc=None, prompt0: int = 0, sink=None) -> torch.Tensor:
+                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None) -> torch.Tensor:
         """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
@@ -575,7 +609,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         G = SR.prompts_per_chunk(n, eng.max_batch)
         if Bsz > G:
             parts = [self._generate_samples(embeds[i:i + G], seqlens[i:i + G], None if position_ids is None else position_ids[i:i + G], n, max_new,
-                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i, sink)
+                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i, sink, stop)
                      for i in range(0, Bsz, G)]
             out = torch.full((Bsz * n, max(p.shape[1] for p in parts)), pad_token_id, dtype=torch.long, device=self.device)
             r = 0
@@ -617,8 +651,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             if blk is not None:
                 eng.set_scores(max(1, min(sync_every, max_new - 1)), R, sink.warped, sink.raw)
             eng.decode_begin(first, next_pos, [int(seqlens[r // n]) for r in range(R)])
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk).to(self.device)
+            if stop is not None:
+                eng.set_stop(stop)
+                eng.stop_rows(0, first)
+            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
         finally:
+            if stop is not None:
+                eng.set_stop(None)
             if blk is not None:
                 eng.set_scores(None)
             eng.set_sampling_rows(None)
@@ -743,7 +782,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     # ---- continuous batching: the 23 K-item eval loop without waiting for a batch's longest answer ----
     @torch.no_grad()
     def generate_stream(self, requests, max_new_tokens: int = 128, eos_token_id=None, rows: Optional[int] = None, sync_every: int = 16,
-                        admit: Optional[int] = None):
+                        admit: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_sequences=None):
         """Generation over an iterable of requests - dicts with `input_ids` [1, L] (IMAGE_TOKEN_INDEX sentinels allowed),
         optional `images` ([N,3,336,336]) / `images_size`, optional `max_new_tokens`, optional sampling parameters `do_sample`,
         `temperature`, `top_p`, `top_k`, `seed` (read as `generate` reads them; greedy without them) - with CONTINUOUS batching: up to `rows`
@@ -773,10 +812,21 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         [n_new] = the log-prob of each of its tokens under the model's own distribution at temperature 1 (`generate`'s `token_logprobs`).
         The step recorder (csrc/sampling.hip: token_scores_kernel) is armed when the first such request is admitted - the step's graph is
         captured once more, no id changes - and one more device-to-host copy of [n, rows, 4] words rides with each chunk's ids; a call
-        in which no request asks runs as it always did."""
+        in which no request asks runs as it always did.
+
+        `stop_strings` (+ `tokenizer`, HF's keywords) and `stop_token_sequences` (lists of ids) are call-level stop conditions that
+        apply to every request: the stop matcher (csrc/stop.hip: stop_match_kernel; vz_hip/stop.py) is armed once, before the first
+        admission, and decides them on the device behind every step's tail; where each row stopped rides with the chunk's ids.  A
+        stopped request is yielded inclusive of its stopping token and its row parked at that sync.  A stop set beyond the matcher's
+        limits raises (NotImplementedError for stop strings, ValueError for more than 16 or malformed `stop_token_sequences`) before
+        anything runs: this loop has no per-token host path, and a stop condition is never dropped.  Per-request stop sets are not built."""
         from vz_hip import binding as B
         from vz_hip import sample_rows as SR
         from vz_hip import scores as SC
+        from vz_hip import stop as ST
+        stop, host_stop = ST.parse(stop_strings, tokenizer, None, self.generation_config, True, stop_token_sequences)
+        if host_stop is not None or (stop is not None and self.engine.tp_size > 1):
+            raise NotImplementedError("generate_stream: these stop strings are beyond what the device matcher takes (vz_hip.stop.parse)")
         self._kv_epoch += 1
         self._ensure_ready()
         eng = self.engine
@@ -796,6 +846,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         it = iter(enumerate(requests))
         slots = [None] * n_rows                 # per row: [request index, tokens so far, budget]
         eng.decode_begin(torch.zeros(n_rows, dtype=torch.int32), [0] * n_rows, [0] * n_rows)       # every row parked
+        if stop is not None:
+            eng.set_stop(stop)                  # no row is watched until a request lands in it (stop_rows)
         exhausted = False
 
         def embed(idx, req):
@@ -873,12 +925,17 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     for g in group:
                         if len(g) == 7:
                             eng.decode_set_row(g[5], g[6], g[2], g[2])
+                            if stop is not None:        # the row starts clean and its first token goes through the matcher
+                                eng.stop_rows(g[5], torch.tensor([g[6]], dtype=torch.int32))
                             if armed:                   # the row's second token is draw 1 of the request's own stream
                                 eng.decode_set_row_sampling(g[5], g[4].at(1))
                 if all(s is None for s in slots):
                     return
                 n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
-                chunk = eng.decode_steps(n).cpu()                           # [rows, n]; the only host sync of the chunk
+                chunk = eng.decode_steps(n)
+                at = eng.stop_at(0, n_rows) if stop is not None else None
+                chunk = chunk.cpu()                                         # [rows, n]; the only host sync of the chunk
+                at = None if at is None else at.tolist()
                 lps = None
                 if scored:
                     x, lse, _, _ = SC.unpack(eng.scores_steps(n)[0].cpu())  # [n, rows]
@@ -886,13 +943,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 for r, st in enumerate(slots):
                     if st is None:
                         continue
+                    cut = at[r] + 1 if at is not None and at[r] >= 0 else st[2]      # tokens the row keeps if its stop condition held
                     for i, t in enumerate(chunk[r].tolist()):
+                        if len(st[1]) >= cut:
+                            break
                         st[1].append(int(t))
                         if st[3] is not None:
                             st[3].append(lps[r][i])
                         if int(t) in eos or len(st[1]) >= st[2]:
                             break
-                    if st[1][-1] in eos or len(st[1]) >= st[2]:
+                    if st[1][-1] in eos or len(st[1]) >= min(st[2], cut):
                         if st[3] is not None:
                             yield st[0], torch.tensor(st[1], dtype=torch.long), torch.tensor(st[3], dtype=torch.float32)
                         else:
@@ -900,6 +960,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                         eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
                         slots[r] = None
         finally:
+            if stop is not None:
+                eng.set_stop(None)
             if scored:
                 eng.set_scores(None)
             if armed:
@@ -912,7 +974,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
@@ -987,20 +1049,34 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             if blk is not None:
                 eng.set_scores(max(1, min(sync_every, max_new - 1)), 1, sink.warped, sink.raw)
             eng.decode_begin(first, [next_pos], [S])
+            at = -1
+            if stop is not None:                  # the device decides the stop conditions (vz_hip.stop): no callback, the loop below as it is
+                eng.set_stop(stop)
+                eng.stop_rows(0, first)
+                at = int(eng.stop_at(0, 1)[0])
             remaining = max_new - 1
-            while remaining > 0:
-                n = min(sync_every, remaining) if (eos or blk is not None) else remaining
-                ids = eng.decode_steps(n)[0].tolist()
+            while remaining > 0 and at < 0:
+                n = min(sync_every, remaining) if (eos or stop is not None or blk is not None) else remaining
+                ids = eng.decode_steps(n)
+                if stop is not None:
+                    at = int(eng.stop_at(0, 1)[0])
+                ids = ids[0].tolist()
                 eng.check_async()                 # a bounded device-side wait that expired = invalid ids: fail loudly
                 if blk is not None:
                     blk.add(*eng.scores_steps(n))
                 remaining -= n
                 for t in ids:
                     out.append(int(t))
-                    if int(t) in eos:
+                    if int(t) in eos or len(out) - 1 == at:
+                        if blk is not None and stop is not None:
+                            blk.ends = torch.tensor([len(out)], dtype=torch.long)
                         return out
+            if blk is not None and stop is not None:
+                blk.ends = torch.tensor([len(out)], dtype=torch.long)
             return out
         finally:
+            if stop is not None:
+                eng.set_stop(None)
             eng.set_sampling(False)
             eng.set_ring(None)
             if blk is not None:

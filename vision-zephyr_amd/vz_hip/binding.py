@@ -139,6 +139,10 @@ SYMBOLS = {
     "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_scores": (_I, [_P, C.c_uint, _P, _P, _P, _I, _P]),
     "vz_op_token_scores": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_stop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "vz_llm_decode_stop_rows": (_I, [_P, _I, _I, _P, _P]),
+    "vz_llm_decode_stop_read": (_I, [_P, _I, _I, _P, _P]),
+    "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -705,6 +709,38 @@ def token_scores(logits, ids, params, warped=False):
         check(lib().vz_op_token_scores(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), mode, temp, top_k, top_p, ptr(rec[r0:r1]),
                                        ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
     return (rec, w) if warped else rec
+
+
+class StopTables:
+    """the tables of a vz_hip.stop.Plan in device memory, for `stop_match` (the engine keeps its own copy: Engine.set_stop)"""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        self.emb = None if plan.emb is None else plan.emb.to(device)
+        self.target = None if plan.target is None else plan.target.to(device)
+        self.seq = plan.seq_table().to(device) if plan.seqs else None
+
+
+def stop_state(rows: int, device) -> torch.Tensor:
+    """caller-owned matcher state for `rows` rows, int32 [rows, 2 + 64] = [n | at | ring]; `stop_match(..., reset=True)` starts it"""
+    from . import stop as ST
+    st = torch.zeros(rows, ST.ROW, dtype=torch.int32, device=device)
+    st[:, 1] = ST.UNARMED
+    return st
+
+
+def stop_match(state, ids, tabs: StopTables, reset: bool = False):
+    """the stop matcher (stop.hip: stop_match_kernel) on caller-owned state int32 [rows, 2 + 64]: one new id per row (ids [rows]); reset:
+    the rows start clean first.  state[:, 0] = tokens seen, state[:, 1] = -1 or the index of the token at which a stop first held."""
+    from . import stop as ST
+    _need_cuda(state, ids)
+    assert state.dtype == torch.int32 and state.dim() == 2 and state.shape[1] == ST.ROW and state.stride(1) == 1 and state.stride(0) == ST.ROW
+    ids = ids.to(torch.int32).contiguous().view(-1)
+    assert ids.numel() == state.shape[0] and ids.device == state.device
+    p = tabs.plan
+    check(lib().vz_op_stop_match(ptr(state), state.shape[0], ptr(ids), int(bool(reset)), ptr(tabs.emb), 0 if tabs.emb is None else tabs.emb.shape[0],
+                                 p.vec, p.n_str, p.max_pos, p.max_end, p.window, ptr(tabs.target), ptr(tabs.seq), len(p.seqs), stream_ptr(state.device)))
+    return state
 
 
 def beam_k(nb: int, n_eos: int) -> int:

@@ -625,6 +625,32 @@ class Engine:
         pick = lambda ring: None if ring is None else SC.ring_order(ring, sc["count"], n, first)      # noqa: E731
         return pick(sc["rec"]), pick(sc["warped"]), pick(sc["raw"])
 
+    def set_stop(self, plan=None):
+        """the stop matcher (stop.hip: stop_match_kernel): every decode step passes the token each row's tail chose through the stop
+        conditions of `plan` (vz_hip.stop.Plan) and records the index of the token at which one first held (`stop_at`); None = off.  A
+        row is watched from `stop_rows` on.  The tables are copied into the engine's own device memory; the step's graph is captured
+        once more when the matcher comes or goes."""
+        if plan is None:
+            B.check(self.lib.vz_llm_decode_stop(self.h, 0, None, 0, 0, 0, 0, 0, 0, None, None, 0, self._s()))
+            return
+        seq = plan.seq_table().contiguous() if plan.seqs else None
+        emb = None if plan.emb is None else plan.emb.to("cpu", torch.int32).contiguous()
+        tgt = None if plan.target is None else plan.target.to("cpu", torch.int32).contiguous()
+        B.check(self.lib.vz_llm_decode_stop(self.h, 1, B.ptr(emb), 0 if emb is None else emb.shape[0], plan.vec, plan.n_str, plan.max_pos, plan.max_end,
+                                            plan.window, B.ptr(tgt), B.ptr(seq), len(plan.seqs), self._s()))
+
+    def stop_rows(self, row0: int, first_ids: torch.Tensor):
+        """rows row0.. of the matcher start clean and take their first tokens (chosen from the prefill logits) through the step's own
+        kernel: call it where `decode_begin` / `decode_set_row` arm those rows"""
+        ids = first_ids.to(self.device, torch.int32).contiguous().view(-1)
+        B.check(self.lib.vz_llm_decode_stop_rows(self.h, int(row0), ids.numel(), B.ptr(ids), self._s()))
+
+    def stop_at(self, row0: int, rows: int) -> torch.Tensor:
+        """int32 [rows] (device): per row -1, or the 0-based index of the generated token at which a stop condition first held"""
+        at = torch.empty(int(rows), dtype=torch.int32, device=self.device)
+        B.check(self.lib.vz_llm_decode_stop_read(self.h, int(row0), int(rows), B.ptr(at), self._s()))
+        return at
+
     def set_sampling(self, on: bool, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, first_counter: int = 1):
         """tail of every decode step: greedy argmax (off) or the device-side sampler (sampling.hip); applies from the next decode_begin."""
         B.check(self.lib.vz_llm_decode_sampling(self.h, int(on), float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),

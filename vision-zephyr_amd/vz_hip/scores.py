@@ -108,6 +108,7 @@ class _Block:
     def __init__(self, rows: int, temperature):
         self.rows, self.temperature = rows, temperature
         self.rec, self.warped, self.raw = [], [], []
+        self.ends = None         # LongTensor [rows]: tokens a row kept when a device-side stop ended it (vz_hip.stop), else None
 
     def add(self, rec, warped=None, raw=None):
         """steps [n, rows, 4] (+ [n, rows, V] rows), on any device"""
@@ -149,6 +150,9 @@ class Sink:
         temps = torch.cat([torch.as_tensor(b.temperature, dtype=torch.float32).reshape(-1).expand(b.rows) for b in self.blocks]).to(dev)
         steps = torch.cat([torch.full((b.rows,), sum(c.shape[0] for c in b.rec), dtype=torch.long) for b in self.blocks]).to(dev)
         mask = behind_eos(ids, eos) | (torch.arange(T, device=dev).view(1, T) >= steps.view(-1, 1))
+        if any(b.ends is not None for b in self.blocks):          # positions behind a stop string / keyword stop: as behind eos
+            ends = torch.cat([torch.full((b.rows,), T, dtype=torch.long) if b.ends is None else b.ends.to(torch.long).cpu() for b in self.blocks]).to(dev)
+            mask = mask | (torch.arange(T, device=dev).view(1, T) >= ends.view(-1, 1))
         lp, lpw = logprobs(rec, temps, mask)
         out = {"token_logprobs": lp, "token_logprobs_warped": lpw, "scores": None, "logits": None}
         for key, on, pick in (("scores", self.warped, lambda b: b.warped), ("logits", self.raw, lambda b: b.raw)):
