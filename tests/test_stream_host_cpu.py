@@ -82,6 +82,9 @@ class ToyEngine:
                 out[r, s_] = self.cur[r]
         return out
 
+    def check_async(self):
+        pass
+
 
 @pytest.fixture()
 def stream(monkeypatch):

@@ -15,11 +15,13 @@ This one owns a `vz_hip.Engine` (weights + KV cache in HBM, hand-written HIP ker
 """
 from __future__ import annotations
 
+import time
 from types import SimpleNamespace
 from typing import List, Optional, Sequence, Union
 
 import torch
 
+from vz_hip import decode_loop as DL
 from vz_hip.engine import Engine
 from vz_hip.synth import ArchConfig
 
@@ -101,49 +103,6 @@ class PastKeyValues:
 
     def get_seq_length(self, layer_idx: int = 0):
         return max(self.lengths) if self.lengths else 0
-
-
-def _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=None, stop: bool = False) -> torch.Tensor:
-    """the steps of a batch `decode_begin` has armed with the rows' first tokens `first_cpu` (host): [rows, <= max_new] new tokens,
-    `sync_every` steps per host sync (host tensor), a row showing `pad_token_id` behind its eos, until every row is done.
-    blk (vz_hip.scores block; the engine's step recorder is armed for `sync_every` steps): every chunk's records are added to it.
-    stop: the engine's stop matcher watches the rows (`Engine.set_stop`, `stop_rows`): the token at which a row's stop condition first
-    held ends the row as an eos does - the indices ride with each chunk's ids."""
-    Bsz = first_cpu.numel()
-    cols = [first_cpu.view(Bsz, 1)]
-    eos_t = torch.tensor(sorted(eos), dtype=torch.long)
-    done = torch.isin(first_cpu, eos_t) if eos else torch.zeros(Bsz, dtype=torch.bool)
-    if stop:
-        done = done | (eng.stop_at(0, Bsz).cpu() == 0)
-    remaining = max_new - 1
-    seen = 1                                                         # generated tokens per row in front of the next chunk
-    while remaining > 0 and not bool(done.all()):
-        n = min(sync_every, remaining) if (eos or stop or blk is not None) else remaining
-        chunk = eng.decode_steps(n)
-        at = eng.stop_at(0, Bsz) if stop else None
-        chunk = chunk.to(torch.long).cpu()                           # [B, n]: the only host sync of the chunk
-        if blk is not None:
-            blk.add(*eng.scores_steps(n))
-        remaining -= n
-        if eos or stop:
-            hit = torch.isin(chunk, eos_t) if eos else torch.zeros_like(chunk, dtype=torch.bool)      # eos emitted at (row, step)
-            if stop:                                                 # ... or the row's stop condition first held at that token
-                hit = hit | (at.cpu().to(torch.long).view(Bsz, 1) == seen + torch.arange(n, dtype=torch.long).view(1, n))
-            seen += n
-            # a row is finished after its first eos (inclusive): later steps show the pad token
-            after = (torch.cumsum(hit.to(torch.int32), dim=1) - hit.to(torch.int32)) > 0
-            chunk = torch.where(done.view(Bsz, 1) | after, torch.full_like(chunk, pad_token_id), chunk)
-            done_at = done.view(Bsz, 1) | (torch.cumsum(hit.to(torch.int32), dim=1) > 0)      # state after each step
-            all_done = done_at.all(dim=0)
-            if bool(all_done.any()):                                 # stop at the first step after which every row is done
-                chunk = chunk[:, : int(torch.nonzero(all_done)[0]) + 1]
-            done = done_at[:, chunk.shape[1] - 1]
-        cols.append(chunk)
-    out = torch.cat(cols, dim=1)
-    if stop and blk is not None:
-        at = eng.stop_at(0, Bsz).cpu().to(torch.long)
-        blk.ends = torch.where((at >= 0) & (at < out.shape[1]), at + 1, torch.full_like(at, out.shape[1]))
-    return out
 
 
 class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
@@ -429,9 +388,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                            device_stop and streamer is None and num_beams == 1 and self.engine.tp_size == 1)
         what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams)
         sink = SC.Sink(what) if what else None
-        if eos_token_id is None:
-            eos_token_id = self.generation_config.eos_token_id
-        eos = set([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id or []))
+        Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length, S, pad_token_id)
+        eos = d.eos
         # HF's logits processors (csrc/logits_proc.hip): None = none of the four keywords is active, every path below is as it was
         proc = logits_proc.parse(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, sorted(eos))
         if proc is not None and num_beams != 1:
@@ -442,13 +401,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing,
                                        num_return_sequences=num_return_sequences, return_dict_in_generate=return_dict_in_generate, **unused)
-        Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        if max_new_tokens is None:
-            max_new_tokens = 20 if max_length is None else max(1, max_length - S)
-        if pad_token_id is None:
-            pad_token_id = self.generation_config.pad_token_id
-        if pad_token_id is None:
-            pad_token_id = min(eos) if eos else 0
+        max_new_tokens, pad_token_id = d.max_new, d.fill
         greedy = (not do_sample) or temperature is None or temperature <= 0
         nrs = sample_rows.check_return_sequences(num_return_sequences, greedy, self.engine.max_batch, streamer, stopping_criteria)
         if top_k == -1:                      # not passed: HF's generation-config default (50); None / 0 = no top-k filter
@@ -486,11 +439,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
                                            stopping_criteria, seed + b, sync_every, timing, proc, sink, stop))
-        n = max(len(o) for o in outs)
-        res = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
-        for b, o in enumerate(outs):
-            res[b, :len(o)] = torch.tensor(o, dtype=torch.long, device=self.device)
-        return done(res)
+        return done(DL.pad_parts([torch.tensor([o], dtype=torch.long, device=self.device) for o in outs], pad_token_id, self.device))
 
     def _generate_output(self, seqs, sink, eos, return_dict_in_generate):
         """what generate() returns for the new tokens `seqs` [rows, T]: the tensor, or HF's output object with what `sink` recorded"""
@@ -510,16 +459,6 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         from vz_hip import scores as SC
         return SC.transition_scores(sequences, scores, beam_indices, normalize_logits)
 
-    def _score_first(self, sink, rows, temperature, last, raw, first, params):
-        """the block of `rows` rows that are about to decode together, holding the record of their first tokens `first` (device), chosen
-        on the processed prefill logits `last` [rows, V] by `params`; raw = those logits before the processors"""
-        from vz_hip import binding as B
-        blk = sink.block(rows, temperature)
-        r = B.token_scores(last, first, params, warped=sink.warped)
-        rec, w = r if sink.warped else (r, None)
-        blk.add(rec.unsqueeze(0), None if w is None else w.unsqueeze(0), raw.unsqueeze(0) if sink.raw else None)
-        return blk
-
     def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None) -> List[int]:
         """One greedy sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
         (csrc/spec.hip), `sync_every` per host sync."""
@@ -531,7 +470,6 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         next_pos = S if position_ids is None else int(position_ids[0, -1]) + 1
         tok = int(B.argmax(last)[0])          # int(): the host holds the first token here
         if timing is not None:
-            import time
             timing["t_first_token"] = time.perf_counter()
         report = {}
         out = spec.decode(eng, tok, next_pos, S, history, D, max_new, eos, max_ngram, max(1, int(sync_every)), report=report)
@@ -550,48 +488,18 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         Bsz, S = embeds.shape[0], embeds.shape[1]
         cap = min(eng.max_batch, 64)
         if Bsz > cap:
-            parts = [self._generate_batched(embeds[i:i + cap], seqlens[i:i + cap],
-                                            None if position_ids is None else position_ids[i:i + cap], max_new, eos,
-                                            pad_token_id, sync_every, None, proc, sink, stop) for i in range(0, Bsz, cap)]
-            n = max(p.shape[1] for p in parts)
-            out = torch.full((Bsz, n), pad_token_id, dtype=torch.long, device=self.device)
-            r = 0
-            for p in parts:
-                out[r:r + p.shape[0], :p.shape[1]] = p
-                r += p.shape[0]
-            return out
+            part = lambda lo, hi, tm: self._generate_batched(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi],      # noqa: E731
+                                                             max_new, eos, pad_token_id, sync_every, tm, proc, sink, stop)
+            return DL.run_parts(part, Bsz, cap, pad_token_id, self.device, timing)
         if S + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
-        from vz_hip import binding as B
         from vz_hip.sample_rows import GREEDY
         _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
-        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
-        if proc is not None:
-            B.logits_process(last, proc)                 # the first step's processors see an empty history
-        first = B.argmax(last)
-        blk = None if sink is None else self._score_first(sink, Bsz, 1.0, last, raw, first, [GREEDY] * Bsz)
         next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
-        first_cpu = first.to(torch.long).cpu()
-        if timing is not None:
-            import time
-            timing["t_first_token"] = time.perf_counter()        # the host holds every row's first token here
-        if proc is not None:
-            eng.set_logits_proc(proc)
-        try:
-            if blk is not None:
-                eng.set_scores(max(1, min(sync_every, max_new - 1)), Bsz, sink.warped, sink.raw)
-            eng.decode_begin(first, next_pos, list(seqlens))
-            if stop is not None:
-                eng.set_stop(stop)
-                eng.stop_rows(0, first)
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
-        finally:
-            if stop is not None:
-                eng.set_stop(None)
-            if blk is not None:
-                eng.set_scores(None)
-            if proc is not None:
-                eng.set_logits_proc(None)
+        first, first_cpu, blk = DL.first_tokens(last, [GREEDY] * Bsz, proc, sink, timing)
+        with DL.armed(eng, proc=proc, scores=DL.chunk_recorder(sink, Bsz, sync_every, max_new), stop=stop) as begin:
+            begin(first, next_pos, list(seqlens))
+            return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
@@ -600,7 +508,6 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
         `seed + b * n + j` (vz_hip.sample_rows.row_seed) with its own counter, so it gets the tokens that seed gives it alone."""
-        from vz_hip import binding as B
         from vz_hip import sample_rows as SR
         eng = self.engine
         if eng.tp_size > 1:
@@ -608,61 +515,22 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         Bsz = embeds.shape[0]
         G = SR.prompts_per_chunk(n, eng.max_batch)
         if Bsz > G:
-            parts = [self._generate_samples(embeds[i:i + G], seqlens[i:i + G], None if position_ids is None else position_ids[i:i + G], n, max_new,
-                                            temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, None, proc, prompt0 + i, sink, stop)
-                     for i in range(0, Bsz, G)]
-            out = torch.full((Bsz * n, max(p.shape[1] for p in parts)), pad_token_id, dtype=torch.long, device=self.device)
-            r = 0
-            for p in parts:
-                out[r:r + p.shape[0], :p.shape[1]] = p
-                r += p.shape[0]
-            return out
+            part = lambda lo, hi, tm: self._generate_samples(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi], n,      # noqa: E731
+                                                             max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, tm, proc,
+                                                             prompt0 + lo, sink, stop)
+            return DL.run_parts(part, Bsz, G, pad_token_id, self.device, timing)
         if max(seqlens) + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         R = Bsz * n
-        # every row parked (the cache moves below may only touch parked rows), then one prefill per prompt into its first row
-        eng.decode_begin(torch.zeros(R, dtype=torch.int32), [0] * R, [0] * R)
-        last = []
-        for g in range(Bsz):
-            Sg = int(seqlens[g])
-            last.append(eng.prefill_rows(g * n, embeds[g:g + 1, :Sg], [Sg], None if position_ids is None else position_ids[g:g + 1, :Sg]))
-        last = torch.cat(last, 0).contiguous()
-        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
-        if proc is not None:
-            B.logits_process(last, proc)                 # the first step's processors see an empty history
+        last = DL.fan_prefill(eng, embeds, seqlens, position_ids, n)
         params = [SR.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
                                SR.row_seed(seed, prompt0 + r // n, n, r % n), 0) for r in range(R)]
-        last_rows = last.repeat_interleave(n, dim=0).contiguous()                          # a prompt's one logits row, once per sample
-        first = B.sample_rows(last_rows, params)
-        blk = None if sink is None else self._score_first(sink, R, float(temperature), last_rows, raw.repeat_interleave(n, dim=0) if sink.raw else None,
-                                                          first, params)
-        first_cpu = first.to(torch.long).cpu()
-        if timing is not None:
-            import time
-            timing["t_first_token"] = time.perf_counter()        # the host holds every row's first token here
-        src = [g * n for g in range(Bsz) for _ in range(1, n)]
-        dst = [g * n + j for g in range(Bsz) for j in range(1, n)]
-        eng.kv_move_rows(src, dst, [seqlens[d // n] for d in dst])          # the prompt KV of each prompt into its samples' rows
-        next_pos = [int(seqlens[r // n]) if position_ids is None else int(position_ids[r // n, seqlens[r // n] - 1]) + 1 for r in range(R)]
-        try:
-            if proc is not None:
-                eng.set_logits_proc(proc)
-            eng.set_sampling_rows([p.at(1) for p in params])
-            if blk is not None:
-                eng.set_scores(max(1, min(sync_every, max_new - 1)), R, sink.warped, sink.raw)
-            eng.decode_begin(first, next_pos, [int(seqlens[r // n]) for r in range(R)])
-            if stop is not None:
-                eng.set_stop(stop)
-                eng.stop_rows(0, first)
-            return _decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
-        finally:
-            if stop is not None:
-                eng.set_stop(None)
-            if blk is not None:
-                eng.set_scores(None)
-            eng.set_sampling_rows(None)
-            if proc is not None:
-                eng.set_logits_proc(None)
+        first, first_cpu, blk = DL.first_tokens(last, params, proc, sink, timing)
+        next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, n)
+        with DL.armed(eng, proc=proc, sampling_rows=[p.at(1) for p in params], scores=DL.chunk_recorder(sink, R, sync_every, max_new),
+                      stop=stop) as begin:
+            begin(first, next_pos, ctx_len)
+            return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
 
     # ---- beam search (hf:generation/utils.py `_beam_search`, do_sample=False; csrc/beam.hip + vz_hip/beam.py) ----------------
     def _generate_beam(self, inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
@@ -676,7 +544,6 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         `sync_every` steps per host sync, whose history records the host replays (vz_hip.beam.BeamReplay) to keep HF's finished
         hypotheses and to stop where HF stops."""
         from vz_hip import beam as BM
-        from vz_hip import binding as B
         eng = self.engine
         nb = int(num_beams)
         if do_sample:
@@ -697,17 +564,11 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if early_stopping not in (False, True, "never"):
             raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}.")
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        if max_new_tokens is None:
-            max_new_tokens = 20 if max_length is None else max(1, max_length - S)
-        max_new = int(max_new_tokens)
-        if eos_token_id is None:
-            eos_token_id = self.generation_config.eos_token_id
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
+        d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length, S, pad_token_id)
+        max_new, eos = d.max_new, d.eos_list          # the ids in the caller's order, as the device and `fill_value` take them
         if len(eos) > 4:
             raise NotImplementedError(f"{len(eos)} eos ids: the beam tail takes up to 4")
-        if pad_token_id is None:
-            pad_token_id = self.generation_config.pad_token_id
-        fill = BM.fill_value(pad_token_id, eos)
+        fill = BM.fill_value(d.pad, eos)
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
         if max(seqlens) + max_new > eng.max_ctx:
@@ -718,17 +579,11 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             hyps += self._beam_chunk(inputs_embeds[b0:b0 + G], seqlens[b0:b0 + G],
                                      None if position_ids is None else position_ids[b0:b0 + G], nb, max_new, eos,
                                      float(length_penalty), early_stopping, nrs, max(1, int(sync_every)), timing)
-        n = max(len(t) for h in hyps for t, _ in h)
-        seqs = torch.full((Bsz * nrs, n), fill, dtype=torch.long)
-        scores = torch.empty(Bsz * nrs, dtype=torch.float32)
-        for b, h in enumerate(hyps):
-            for r, (t, sc) in enumerate(h):
-                seqs[b * nrs + r, :len(t)] = torch.tensor(t, dtype=torch.long)
-                scores[b * nrs + r] = sc
-        seqs = seqs.to(self.device)
+        seqs = DL.pad_parts([torch.tensor([t], dtype=torch.long) for h in hyps for t, _ in h], fill, "cpu").to(self.device)
         if return_dict_in_generate:
             from vz_hip import scores as SC
-            return SC.output_classes()[1](sequences=seqs, sequences_scores=scores.to(self.device))      # HF's GenerateBeamDecoderOnlyOutput
+            scores = torch.tensor([sc for h in hyps for _, sc in h], dtype=torch.float32, device=self.device)
+            return SC.output_classes()[1](sequences=seqs, sequences_scores=scores)      # HF's GenerateBeamDecoderOnlyOutput
         return seqs
 
     def _beam_chunk(self, embeds, seqlens, position_ids, nb, max_new, eos, length_penalty, early_stopping, nrs, sync_every, timing=None):
@@ -736,34 +591,19 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         from vz_hip import binding as B
         eng = self.engine
         G = embeds.shape[0]
-        R = G * nb
-        # every row parked (the cache moves below may only touch parked rows), then one prefill per prompt into its first beam row
-        eng.decode_begin(torch.zeros(R, dtype=torch.int32), [0] * R, [0] * R)
-        last = []
-        for g in range(G):
-            Sg = int(seqlens[g])
-            last.append(eng.prefill_rows(g * nb, embeds[g:g + 1, :Sg], [Sg],
-                                         None if position_ids is None else position_ids[g:g + 1, :Sg]))
-        last = torch.cat(last, 0).contiguous()
+        last = DL.fan_prefill(eng, embeds, seqlens, position_ids, nb)          # one prefill per prompt into its first beam row
         rec, tok, sc, _ = B.beam_select(last, None, 1, nb, eos)
         replays = [BM.BeamReplay(nb, eos, max_new, length_penalty, early_stopping) for _ in range(G)]
         s0, t0, p0 = BM.decode_records(rec)
         if timing is not None:
-            import time
             timing["t_first_token"] = time.perf_counter()        # the host holds every prompt's first step here
         for g in range(G):
             replays[g].step(s0[g], t0[g], p0[g])
         if not all(r.done for r in replays):
-            src = [g * nb for g in range(G) for _ in range(1, nb)]
-            dst = [g * nb + j for g in range(G) for j in range(1, nb)]
-            eng.kv_move_rows(src, dst, [seqlens[d // nb] for d in dst])          # the prompt KV of each prompt into its beam rows
-            next_pos = [int(seqlens[r // nb]) if position_ids is None else int(position_ids[r // nb, seqlens[r // nb] - 1]) + 1
-                        for r in range(R)]
-            eng.decode_begin(tok, next_pos, [int(seqlens[r // nb]) for r in range(R)])
-            K = BM.beam_k(nb, len(eos))
-            hist = torch.empty(max(1, max_new - 1), G, K, 3, dtype=torch.int32, device=self.device)
-            eng.set_beam(True, nb, G, eos, [int(v) for v in seqlens], sc, hist)
-            try:
+            next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, nb)          # the prompt KV of each prompt into its beam rows
+            hist = torch.empty(max(1, max_new - 1), G, BM.beam_k(nb, len(eos)), 3, dtype=torch.int32, device=self.device)
+            with DL.armed(eng, beam=(True, nb, G, eos, [int(v) for v in seqlens], sc, hist)) as begin:
+                begin(tok, next_pos, ctx_len)
                 done_steps, remaining = 0, max_new - 1
                 while remaining > 0 and not all(r.done for r in replays):
                     n = min(sync_every, remaining)
@@ -775,8 +615,6 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                         for g in range(G):
                             if not replays[g].done:
                                 replays[g].step(s[i, g], t[i, g], p[i, g])
-            finally:
-                eng.set_beam(False)
         return [r.best(nrs) for r in replays]
 
     # ---- continuous batching: the 23 K-item eval loop without waiting for a batch's longest answer ----
@@ -830,9 +668,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         self._kv_epoch += 1
         self._ensure_ready()
         eng = self.engine
-        if eos_token_id is None:
-            eos_token_id = self.generation_config.eos_token_id
-        eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(t) for t in eos_token_id})
+        eos = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens).eos
         draw_seed = lambda: int(torch.randint(0, 2 ** 62, (1,)).item())      # noqa: E731  (as generate draws its seed)
         armed = False                           # the per-row tail: from the first sampled request on
         scored = False                          # the step recorder: from the first request with logprobs=True on
@@ -981,7 +817,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         keeps ONE step in flight and reads token t from a host-visible ring when the event behind step t fires, so the callbacks
         of token t run under step t+1 and no logits ever travel.  `proc`: HF's logits processors (vz_hip.logits_proc) run on the
         prefill logits before the first token is chosen and, armed in the engine, in front of every step's tail."""
-        from vz_hip import binding as B
+        from vz_hip.sample_rows import GREEDY, RowParams
         eng = self.engine
         S = embeds.shape[1]
         if S + max_new > eng.max_ctx:
@@ -989,100 +825,52 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
         next_pos = S if position_ids is None else int(position_ids[0, -1]) + 1
         per_token = streamer is not None or stopping_criteria is not None
-        out: List[int] = []
         if streamer is not None:
             # HF hands the (empty, since generation starts from embeddings) prompt ids to the streamer first;
             # TextStreamer(skip_prompt=True) swallows exactly one put() as "the prompt"
             streamer.put(torch.empty((1, 0), dtype=torch.long))
-        raw = last.clone() if sink is not None and sink.raw and proc is not None else last
-        if proc is not None:
-            B.logits_process(last, proc)                 # the first step's processors see an empty history
-        first = B.argmax(last) if greedy else B.sample(last, temperature, top_k, top_p, seed, 0)
-        blk = None
-        if sink is not None:
-            from vz_hip.sample_rows import GREEDY, RowParams
-            par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0)
-            blk = self._score_first(sink, 1, 1.0 if greedy else float(temperature), last, raw, first, [par])
-        tok = int(first[0])          # int(): the host holds the first token here
-        if timing is not None:
-            import time
-            timing["t_first_token"] = time.perf_counter()
-        out.append(tok)
+        par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0)
+        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed))
+        out: List[int] = [int(first_cpu[0])]
         if self._emit(out, streamer, stopping_criteria, None, eos) or max_new <= 1:
             return self._finish(out, streamer)
-        eng.set_sampling(not greedy, temperature if not greedy else 1.0, top_k, top_p, seed, first_counter=1)
-        try:
-            if proc is not None:
-                eng.set_logits_proc(proc)
-            if per_token:
-                ring = self._token_ring()
-                R = ring.numel()
-                eng.set_ring(ring)
-                if blk is not None:          # a device ring of max_new slots, read once at the end: no step waits for its record
-                    eng.set_scores(max_new, 1, sink.warped, sink.raw)
-                eng.decode_begin(first, [next_pos], [S])
-                dev_out = torch.empty(1, 1, dtype=torch.int32, device=self.device)
-                events = {}
-
-                def launch(t):               # step producing generated token index t (draw counter t)
-                    eng.decode_steps(1, out=dev_out)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(self.device))
-                    events[t] = ev
-
-                launch(1)
-                t = 1
-                while True:
-                    if t + 1 < max_new:
-                        launch(t + 1)        # speculative: its cache slot / ring slot are simply ignored if token t stops the sequence
-                    events.pop(t).synchronize()
-                    out.append(int(ring[t % R]))
-                    if self._emit(out, streamer, stopping_criteria, None, eos) or len(out) >= max_new:
-                        break
-                    t += 1
-                torch.cuda.current_stream(self.device).synchronize()      # a speculative step may still be running
-                eng.check_async()
-                if blk is not None:
-                    blk.add(*eng.scores_steps(len(out) - 1, first=0))     # (a speculative step's record behind them is not read)
-                return self._finish(out, streamer)
+        # the step's tail: a greedy call names it only with the ring, whose slot is the draw counter that `set_sampling` starts at 1
+        tail = None if greedy and not per_token else (not greedy, 1.0 if greedy else temperature, top_k, top_p, seed, 1)
+        if not per_token:
             # no host callbacks: steps are enqueued back to back, the host looks at the ids every `sync_every` tokens only to honour eos
+            # and the stop conditions the device decides (vz_hip.stop)
+            with DL.armed(eng, proc=proc, sampling=tail, scores=DL.chunk_recorder(sink, 1, sync_every, max_new), stop=stop) as begin:
+                begin(first, [next_pos], [S])
+                return DL.decode_rows(eng, first_cpu, max_new, eos, 0, sync_every, blk, stop is not None)[0].tolist()
+        ring = self._token_ring()
+        R = ring.numel()
+        # with a sink: a device ring of max_new slots, read once at the end - no step waits for its record
+        with DL.armed(eng, proc=proc, sampling=tail, ring=ring, scores=None if blk is None else (max_new, 1, sink.warped, sink.raw)) as begin:
+            begin(first, [next_pos], [S])
+            dev_out = torch.empty(1, 1, dtype=torch.int32, device=self.device)
+            events = {}
+
+            def launch(t):               # step producing generated token index t (draw counter t)
+                eng.decode_steps(1, out=dev_out)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                events[t] = ev
+
+            launch(1)
+            t = 1
+            while True:
+                if t + 1 < max_new:
+                    launch(t + 1)        # speculative: its cache slot / ring slot are simply ignored if token t stops the sequence
+                events.pop(t).synchronize()
+                out.append(int(ring[t % R]))
+                if self._emit(out, streamer, stopping_criteria, None, eos) or len(out) >= max_new:
+                    break
+                t += 1
+            torch.cuda.current_stream(self.device).synchronize()      # a speculative step may still be running
+            eng.check_async()
             if blk is not None:
-                eng.set_scores(max(1, min(sync_every, max_new - 1)), 1, sink.warped, sink.raw)
-            eng.decode_begin(first, [next_pos], [S])
-            at = -1
-            if stop is not None:                  # the device decides the stop conditions (vz_hip.stop): no callback, the loop below as it is
-                eng.set_stop(stop)
-                eng.stop_rows(0, first)
-                at = int(eng.stop_at(0, 1)[0])
-            remaining = max_new - 1
-            while remaining > 0 and at < 0:
-                n = min(sync_every, remaining) if (eos or stop is not None or blk is not None) else remaining
-                ids = eng.decode_steps(n)
-                if stop is not None:
-                    at = int(eng.stop_at(0, 1)[0])
-                ids = ids[0].tolist()
-                eng.check_async()                 # a bounded device-side wait that expired = invalid ids: fail loudly
-                if blk is not None:
-                    blk.add(*eng.scores_steps(n))
-                remaining -= n
-                for t in ids:
-                    out.append(int(t))
-                    if int(t) in eos or len(out) - 1 == at:
-                        if blk is not None and stop is not None:
-                            blk.ends = torch.tensor([len(out)], dtype=torch.long)
-                        return out
-            if blk is not None and stop is not None:
-                blk.ends = torch.tensor([len(out)], dtype=torch.long)
-            return out
-        finally:
-            if stop is not None:
-                eng.set_stop(None)
-            eng.set_sampling(False)
-            eng.set_ring(None)
-            if blk is not None:
-                eng.set_scores(None)
-            if proc is not None:
-                eng.set_logits_proc(None)
+                blk.add(*eng.scores_steps(len(out) - 1, first=0))     # (a speculative step's record behind them is not read)
+            return self._finish(out, streamer)
 
     def _emit(self, out, streamer, stopping_criteria, scores, eos) -> bool:
         """per-token host callbacks; returns True when generation must stop."""
