@@ -720,6 +720,49 @@ int vz_prof_gemm_stamps(long long* host_out, int max_wgs, int* n_wgs);
  * of per-workgroup schedule: start, end (s_memrealtime, 100 MHz), XCC id << 32 | HW_ID, query block << 32 | tiles.  host buffer: 16 + 8192 int64 */
 int vz_prof_attn_stamps(long long* host16);
 
+/* ---- HF's warpers behind top-k / top-p (csrc/sampling.hip step 3b) ----
+ * The sampling entry points above with one more column: the warpers hf:generation/utils.py `_get_logits_processor` puts behind
+ * TopPLogitsWarper, in its order - h_warp [4] (one sequence) or [rows][4] (per row) = (min_p, typical_p, epsilon_cutoff, eta_cutoff):
+ *   min_p           drop p_i < min_p * p_max                              0 <= min_p <= 1; 0 = off
+ *   typical_p       ascending in |-log p_i - H| keep the shortest prefix whose mass reaches typical_p (it may leave out the most
+ *                   likely token)                                           0 or >= 1 = off
+ *   epsilon_cutoff  drop p_i < epsilon                                    0 or >= 1 = off
+ *   eta_cutoff      drop p_i < min(eta, sqrt(eta) * exp(-H))              0 or >= 1 = off
+ * each over the set the one before it left (p = softmax over that set, H its entropy) and each keeping at least the largest score
+ * of that set.  The kept set is a key interval of x; the draw and the step recorder (lse_kept, n_kept, warped rows) take the same
+ * one.  A greedy row ignores the column.  h_warp = NULL: all off - then every call below is the entry point it extends, which keep
+ * their signatures and meaning.  A negative or NaN entry, or min_p > 1: VZ_ERR_ARG. */
+int vz_llm_decode_sampling_warp(vz_engine* e, int enable, float temperature, int top_k, float top_p, const float* h_warp,
+                                unsigned long long seed, int first_counter);
+int vz_op_sample_warp(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, const float* h_warp,
+                      unsigned long long seed, int counter, int* d_ids, vz_stream stream);
+int vz_llm_decode_sampling_rows_warp(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                     const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter);
+int vz_llm_decode_set_row_sampling_warp(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, const float* h_warp,
+                                        unsigned long long seed, int counter, vz_stream stream);
+int vz_op_sample_rows_warp(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                           const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter, int* d_ids,
+                           vz_stream stream);
+int vz_op_token_scores_warp(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
+                            const int* h_top_k, const float* h_top_p, const float* h_warp, float* d_rec, float* d_warped, vz_stream stream);
+
+/* ---- sequence_bias and bad_words_ids in the processor filter (csrc/logits_proc.hip) ----
+ * vz_llm_decode_logits_proc / vz_op_logits_process with one more table: the id sequences of hf:SequenceBiasLogitsProcessor (first in
+ * HF's chain, in front of the repetition penalty) and hf:NoBadWordsLogitsProcessor (behind the n-gram ban), h_seq [n_seq][12] ints =
+ *   [len 1..8 | kind: 0 = bias, 1 = bad word | bias, fp32 bits | 0 | ids[8]],  n_seq <= 64
+ * with the one-id sequences first and each group in the caller's order - the order HF adds the biases in.  A one-id sequence acts at
+ * every step; a longer one acts on its last id when the ids generated so far end in its first len - 1 ids and (HF's length check) at
+ * least len ids were generated.  Biases that land on one id add up in fp32 in table order, then the penalty acts on the biased score,
+ * then the bans write -inf; a bad word bans without arithmetic.  Ids outside [0, cols) are ignored.  The engine keeps the table in its
+ * own device memory: an arming with the table of the previous arming uploads nothing, a new table is uploaded outside any capture and
+ * the next vz_llm_decode_steps captures again.  n_seq = 0: the entry points they extend, which keep their signatures and meaning. */
+int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
+                                  const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, const int* h_seq, int n_seq,
+                                  vz_stream stream);
+int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
+                             int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
+                             const int* h_seq, int n_seq, vz_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -451,6 +451,7 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_xnorm) hipFree(e->d_xnorm);
     if (e->beam.d) hipFree(e->beam.d);
     if (e->proc.d) hipFree(e->proc.d);
+    if (e->proc.d_seq) hipFree(e->proc.d_seq);
     if (e->score.d_slot) hipFree(e->score.d_slot);
     if (e->stop.d_state) hipFree(e->stop.d_state);
     if (e->stop.d_tab) hipFree(e->stop.d_tab);
@@ -1160,6 +1161,17 @@ static int proc_args_of(float penalty, int ngram, int min_new, const int* h_eos,
     for (int i = 0; i < 16; ++i) out->suppress[i] = i < n_suppress ? h_suppress[i] : -1;
     return VZ_OK;
 }
+// the id-sequence table of sequence_bias / bad_words_ids as the entry points take it (vz_common.h: ProcArgs)
+static int proc_seq_check(const int* h_seq, int n_seq) {
+    VZ_CHECK_ARG(n_seq >= 0 && n_seq <= VZ_PROC_MAX_SEQ && (n_seq == 0 || h_seq), "logits_proc: 0..%d id sequences expected, got %d", VZ_PROC_MAX_SEQ, n_seq);
+    for (int k = 0; k < n_seq; ++k) {
+        const int* q = h_seq + (size_t)k * VZ_PROC_SEQ_STRIDE;
+        VZ_CHECK_ARG(q[0] >= 1 && q[0] <= VZ_PROC_SEQ_IDS && (q[1] == 0 || q[1] == 1), "logits_proc: id sequence %d of %d ids (1..%d), kind %d (0 = bias, 1 = bad word)",
+                     k, q[0], VZ_PROC_SEQ_IDS, q[1]);
+        for (int j = 0; j < q[0]; ++j) VZ_CHECK_ARG(q[4 + j] >= 0, "logits_proc: id sequence %d holds the negative id %d", k, q[4 + j]);
+    }
+    return VZ_OK;
+}
 
 // the accept + draft launch of the armed speculative mode on the step's argmax ids g [R]; g = null: only the first draft (arming)
 static int launch_spec_tail(vz_engine* e, const int* g, hipStream_t s) {
@@ -1247,7 +1259,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         if (e->score.what & VZ_SCORE_RAW) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, e->score.raw, e->score.d_slot, e->score.cap, s));
         if (e->proc.on && tail_takes_proc(tail)) {
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
-            RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, s));
+            RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, e->proc.a.n_seq ? e->proc.d_seq : nullptr, s));
         }
         switch (tail) {
         case TAIL_SPEC: {
@@ -1272,7 +1284,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             RC(vz_launch_sample_rows(e->d_logits, B, c.vocab, st.samp, st.cur, emit, s));
             break;
         case TAIL_SAMPLE:
-            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, st.seed, st.ctr, 0, st.cur, emit, s));
+            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, e->samp.a.warp, st.seed, st.ctr, 0, st.cur, emit, s));
             break;
         case TAIL_GREEDY:
             RC(vz_launch_argmax(e->d_logits, B, c.vocab, st.cur, emit, s));
@@ -1280,7 +1292,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         }
         if (e->score.what) {
             // sampling.hip: the record of the token the tail just left in st.cur, by the parameters the tail took it with
-            const RowSample one = tail == TAIL_SAMPLE ? RowSample{VZ_ROW_SAMPLE, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, {0u, 0u}, 0, 0}
+            const RowSample one = tail == TAIL_SAMPLE ? RowSample{VZ_ROW_SAMPLE, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, {0u, 0u}, 0, 0, e->samp.a.warp}
                                                       : RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0};
             RC(vz_launch_token_scores(e->d_logits, B, c.vocab, tail == TAIL_ROWS ? st.samp : nullptr, one, st.cur, e->score.rec,
                                       (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
@@ -1292,7 +1304,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
     return VZ_OK;
 }
 
-static int row_sample_of(int mode, float temperature, int top_k, float top_p, unsigned long long seed, int counter, RowSample* out);
+static int row_sample_of(int mode, float temperature, int top_k, float top_p, const float* warp, unsigned long long seed, int counter, RowSample* out);
 
 // The stop matcher (stop.hip: stop_match_kernel): armed, every decode step whose tail is the argmax, the sampler or the
 // per-row tail passes, behind that tail (and the recorder) and inside the per-token hipGraph, the token each row just chose through the
@@ -1404,11 +1416,16 @@ extern "C" int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, f
 // taken from the prefill logits; tests)
 extern "C" int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
                                   const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream) {
+    return vz_op_token_scores_warp(d_logits, rows, cols, d_ids, h_mode, h_temperature, h_top_k, h_top_p, nullptr, d_rec, d_warped, stream);
+}
+// ... with the rows' further warpers h_warp [rows][4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff), 0 = off; null: all off
+extern "C" int vz_op_token_scores_warp(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
+                                       const int* h_top_k, const float* h_top_p, const float* h_warp, float* d_rec, float* d_warped, vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_ids && d_rec && rows >= 1 && rows <= 64 && cols >= 1, "token_scores: bad argument (1..64 rows)");
     VZ_CHECK_ARG(h_mode && h_temperature && h_top_k && h_top_p, "token_scores: null parameter array");
     RowSample tab[64];
-    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], 0ull, 0, tab + r));
+    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_warp ? h_warp + 4 * r : nullptr, 0ull, 0, tab + r));
     void* p = nullptr; size_t have = 0;
     RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
     VZ_CHECK_ARG(p && have >= sizeof(tab), "token_scores: first use of a stream inside a capture (call it once before capturing)");
@@ -1421,14 +1438,33 @@ extern "C" int vz_op_token_scores(const float* d_logits, int rows, int cols, con
 // sampling.hip): temperature > 0, top_k (0 = off; HF's default 50 is the caller's business), top_p (1 = off), a 64-bit seed and
 // the draw counter the NEXT vz_llm_decode_begin starts from (the caller drew token 0 from the prefill logits with vz_op_sample
 // and counter 0, so it passes 1).  enable = 0: greedy.
+static int sample_warp_of(const float* w, SampleWarp* out) {
+    *out = SampleWarp{0.f, 0.f, 0.f, 0.f};
+    if (!w) return VZ_OK;
+    // (written so that a NaN fails)
+    VZ_CHECK_ARG(w[0] >= 0.f && w[0] <= 1.f && w[1] >= 0.f && w[2] >= 0.f && w[3] >= 0.f,
+                 "sampling warpers: 0 <= min_p %g <= 1, typical_p %g >= 0, epsilon_cutoff %g >= 0, eta_cutoff %g >= 0 expected", (double)w[0], (double)w[1],
+                 (double)w[2], (double)w[3]);
+    // HF's off values arm nothing: typical_p >= 1, a cutoff outside (0, 1)
+    *out = SampleWarp{w[0], w[1] < 1.f ? w[1] : 0.f, w[2] < 1.f ? w[2] : 0.f, w[3] < 1.f ? w[3] : 0.f};
+    return VZ_OK;
+}
+
 extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperature, int top_k, float top_p, unsigned long long seed,
                                       int first_counter) {
+    return vz_llm_decode_sampling_warp(e, enable, temperature, top_k, top_p, nullptr, seed, first_counter);
+}
+// ... with HF's further warpers h_warp [4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff) behind top-p, 0 = off; null: all off
+extern "C" int vz_llm_decode_sampling_warp(vz_engine* e, int enable, float temperature, int top_k, float top_p, const float* h_warp,
+                                           unsigned long long seed, int first_counter) {
     VZ_CHECK_ARG(e && first_counter >= 0, "decode_sampling: null engine / negative counter");
     e->samp.ctr0 = first_counter;        // the draw counter also indexes the host-visible token ring of a greedy streamer loop
     if (!enable) { e->samp.on = 0; return VZ_OK; }
     VZ_CHECK_ARG(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f && first_counter >= 0,
                  "decode_sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
-    e->samp.on = 1; e->samp.a = SampleArgs{top_k, temperature, top_p};
+    SampleWarp wp;
+    RC(sample_warp_of(h_warp, &wp));
+    e->samp.on = 1; e->samp.a = SampleArgs{top_k, temperature, top_p, wp};
     e->samp.seed[0] = (unsigned)seed; e->samp.seed[1] = (unsigned)(seed >> 32);
     return VZ_OK;
 }
@@ -1436,18 +1472,21 @@ extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperatur
 // The per-row tail: every row of the decode batch chooses its next token by its own entry of a table in device memory (sampling.hip:
 // sample_rows_kernel) - greedy, or sampled with its own temperature / top-k / top-p, 64-bit seed and draw counter.  Rows are independent
 // requests (continuous batching) or the n samples of one prompt.  An entry is checked as vz_llm_decode_sampling checks its arguments.
-static int row_sample_of(int mode, float temperature, int top_k, float top_p, unsigned long long seed, int counter, RowSample* out) {
+static int row_sample_of(int mode, float temperature, int top_k, float top_p, const float* warp, unsigned long long seed, int counter, RowSample* out) {
     VZ_CHECK_ARG((mode == VZ_ROW_GREEDY || mode == VZ_ROW_SAMPLE) && counter >= 0, "row sampling: mode %d (0 = greedy, 1 = sample), counter %d >= 0 expected", mode, counter);
     VZ_CHECK_ARG(mode == VZ_ROW_GREEDY || (temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f),
                  "row sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
-    *out = mode == VZ_ROW_GREEDY ? RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, counter, 0}
-                                 : RowSample{VZ_ROW_SAMPLE, temperature, top_k, top_p, {(unsigned)seed, (unsigned)(seed >> 32)}, counter, 0};
+    SampleWarp wp;
+    RC(sample_warp_of(mode == VZ_ROW_GREEDY ? nullptr : warp, &wp));
+    *out = mode == VZ_ROW_GREEDY ? RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, counter, 0, wp}
+                                 : RowSample{VZ_ROW_SAMPLE, temperature, top_k, top_p, {(unsigned)seed, (unsigned)(seed >> 32)}, counter, 0, wp};
     return VZ_OK;
 }
-static int row_samples_of(int rows, const int* h_mode, const float* h_temperature, const int* h_top_k, const float* h_top_p,
+static int row_samples_of(int rows, const int* h_mode, const float* h_temperature, const int* h_top_k, const float* h_top_p, const float* h_warp,
                           const unsigned long long* h_seed, const int* h_counter, RowSample* out) {
     VZ_CHECK_ARG(rows == 0 || (h_mode && h_temperature && h_top_k && h_top_p && h_seed && h_counter), "row sampling: null parameter array");
-    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_seed[r], h_counter[r], out + r));
+    for (int r = 0; r < rows; ++r)
+        RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_warp ? h_warp + 4 * r : nullptr, h_seed[r], h_counter[r], out + r));
     return VZ_OK;
 }
 
@@ -1456,12 +1495,17 @@ static int row_samples_of(int rows, const int* h_mode, const float* h_temperatur
 // The table is device memory the captured step reads through a pointer: a changed entry needs no new graph.  enable = 0: off.
 extern "C" int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
                                            const float* h_top_p, const unsigned long long* h_seed, const int* h_counter) {
+    return vz_llm_decode_sampling_rows_warp(e, enable, rows, h_mode, h_temperature, h_top_k, h_top_p, nullptr, h_seed, h_counter);
+}
+// ... with the rows' further warpers h_warp [rows][4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff), 0 = off; null: all off
+extern "C" int vz_llm_decode_sampling_rows_warp(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                                const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter) {
     VZ_CHECK_ARG(e, "decode_sampling_rows: null engine");
     if (!enable) { e->rows.on = 0; e->rows.tab.clear(); return VZ_OK; }
     if (e->tp > 1) { vz_set_error("decode_sampling_rows: the per-row tail on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(rows >= 0 && rows <= e->c.max_batch, "decode_sampling_rows: %d rows outside [0, max_batch = %d]", rows, e->c.max_batch);
     std::vector<RowSample> tab((size_t)e->c.max_batch, RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0});
-    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_seed, h_counter, tab.data()));
+    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_warp, h_seed, h_counter, tab.data()));
     e->rows.tab.swap(tab);
     e->rows.on = 1;
     return VZ_OK;
@@ -1470,10 +1514,14 @@ extern "C" int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, c
 // The sampling counterpart of vz_llm_decode_set_row: one row's entry of the running batch, stream-ordered, the other rows untouched.
 extern "C" int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, unsigned long long seed,
                                               int counter, vz_stream stream) {
+    return vz_llm_decode_set_row_sampling_warp(e, row, mode, temperature, top_k, top_p, nullptr, seed, counter, stream);
+}
+extern "C" int vz_llm_decode_set_row_sampling_warp(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, const float* h_warp,
+                                                   unsigned long long seed, int counter, vz_stream stream) {
     NEED_READY();
     VZ_CHECK_ARG(e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row_sampling: row %d outside the running batch of %d", row, e->dec_B);
     RowSample rs;
-    RC(row_sample_of(mode, temperature, top_k, top_p, seed, counter, &rs));
+    RC(row_sample_of(mode, temperature, top_k, top_p, h_warp, seed, counter, &rs));
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(e->h_pinned && e->h_pinned_ints >= (size_t)DecodeState::SAMPLE_INTS, "decode_set_row_sampling: no staging buffer (vz_llm_decode_begin allocates it)");
     VZ_CHECK_HIP(hipStreamSynchronize(s));                        // previous use of the staging buffer has drained
@@ -1486,10 +1534,15 @@ extern "C" int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, f
 // the prefill logits with counter 0; tests).  The table goes through this (device, stream)'s own scratch.
 extern "C" int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
                                  const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream) {
+    return vz_op_sample_rows_warp(d_logits, rows, cols, h_mode, h_temperature, h_top_k, h_top_p, nullptr, h_seed, h_counter, d_ids, stream);
+}
+extern "C" int vz_op_sample_rows_warp(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
+                                      const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter, int* d_ids,
+                                      vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_ids && rows >= 1 && rows <= 64 && cols >= 1, "sample_rows: bad argument (1..64 rows)");
     RowSample tab[64];
-    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_seed, h_counter, tab));
+    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_warp, h_seed, h_counter, tab));
     void* p = nullptr; size_t have = 0;
     RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
     VZ_CHECK_ARG(p && have >= sizeof(tab), "sample_rows: first use of a stream inside a capture (call it once before capturing)");
@@ -1510,16 +1563,22 @@ extern "C" int vz_llm_decode_ring(vz_engine* e, int* ring, int ring_n, int ring_
 // one draw per row of fp32 logits [rows, cols] with the same kernel (the first token of a sampled generation; tests)
 extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p,
                             unsigned long long seed, int counter, int* d_ids, vz_stream stream) {
+    return vz_op_sample_warp(d_logits, rows, cols, temperature, top_k, top_p, nullptr, seed, counter, d_ids, stream);
+}
+extern "C" int vz_op_sample_warp(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, const float* h_warp,
+                                 unsigned long long seed, int counter, int* d_ids, vz_stream stream) {
     // [counter, seed lo, seed hi, -] in this (device, stream)'s own scratch words: launches on other streams or devices have theirs
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_ids && rows >= 1 && cols >= 1, "sample: bad argument");
+    SampleWarp wp;
+    RC(sample_warp_of(h_warp, &wp));
     int* d_scratch = nullptr;
     { void* p = nullptr; size_t have = 0; int r = vz_stream_ws(4, s, 64, true, &p, &have); if (r) return r;
       VZ_CHECK_ARG(p && have >= 16, "sample: first use of a stream inside a capture (call it once before capturing)"); d_scratch = (int*)p; }
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)d_scratch, counter, 1, s));
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 1), (int)(unsigned)seed, 1, s));
     VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 2), (int)(unsigned)(seed >> 32), 1, s));
-    return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
+    return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, wp, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
 }
 
 // Logits processors in the step (hf:generation/logits_process.py; logits_proc.hip): after
@@ -1529,6 +1588,13 @@ extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float tem
 // token at every step.  The mode is orthogonal to the tail; vz_llm_decode_steps refuses it together with the beam or the speculative tail.
 extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
                                          const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream) {
+    return vz_llm_decode_logits_proc_seq(e, enable, repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, nullptr, 0, stream);
+}
+// ... with the id sequences of HF's sequence_bias / bad_words_ids, h_seq [n_seq][VZ_PROC_SEQ_STRIDE] (include/viszephyr.h).  The table is
+// copied into the engine's own device memory here, outside any capture; the table of the previous arming again: nothing is uploaded.
+extern "C" int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
+                                             const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, const int* h_seq, int n_seq,
+                                             vz_stream stream) {
     NEED_READY();
     if (!enable) { e->proc.on = 0; return VZ_OK; }
     const vz_config& c = e->c;
@@ -1539,6 +1605,18 @@ extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetit
     hipStream_t s = (hipStream_t)stream;
     if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
     VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, proc_len_ints(c) * sizeof(int), s));
+    RC(proc_seq_check(h_seq, n_seq));
+    if (n_seq) {
+        std::vector<int> tab(h_seq, h_seq + (size_t)n_seq * VZ_PROC_SEQ_STRIDE);
+        if (!(e->proc.d_seq && tab == e->proc.h_seq)) {
+            VZ_CHECK_HIP(hipStreamSynchronize(s));      // steps still in flight read the table of the previous arming
+            if (!e->proc.d_seq) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d_seq, (size_t)VZ_PROC_MAX_SEQ * VZ_PROC_SEQ_STRIDE * sizeof(int)));
+            VZ_CHECK_HIP(hipMemcpy(e->proc.d_seq, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            e->proc.h_seq.swap(tab);
+            e->proc.seq_epoch += 1;
+        }
+        a.n_seq = n_seq; a.seq_epoch = e->proc.seq_epoch;
+    }
     e->proc.on = 1; e->proc.a = a;
     return VZ_OK;
 }
@@ -1548,9 +1626,28 @@ extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetit
 extern "C" int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
                                     int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
                                     vz_stream stream) {
+    return vz_op_logits_process_seq(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, penalty, ngram, min_new, h_eos, n_eos, h_suppress, n_suppress,
+                                    nullptr, 0, stream);
+}
+// ... with the id sequences h_seq [n_seq][VZ_PROC_SEQ_STRIDE]; the table goes through this (device, stream)'s own scratch
+extern "C" int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
+                                        int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
+                                        const int* h_seq, int n_seq, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
     ProcArgs a;
     RC(proc_args_of(penalty, ngram, min_new, h_eos, n_eos, h_suppress, n_suppress, &a));
-    return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (hipStream_t)stream);
+    RC(proc_seq_check(h_seq, n_seq));
+    void* p = nullptr;
+    if (n_seq) {
+        size_t have = 0;
+        const size_t need = (size_t)VZ_PROC_MAX_SEQ * VZ_PROC_SEQ_STRIDE * sizeof(int);
+        RC(vz_stream_ws(7, s, need, false, &p, &have));
+        VZ_CHECK_ARG(p && have >= need, "logits_process: first use of a stream inside a capture (call it once before capturing)");
+        VZ_CHECK_HIP(hipStreamSynchronize(s));          // an earlier call's kernel has read its table
+        VZ_CHECK_HIP(hipMemcpy(p, h_seq, (size_t)n_seq * VZ_PROC_SEQ_STRIDE * sizeof(int), hipMemcpyHostToDevice));
+        a.n_seq = n_seq;
+    }
+    return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (const int*)p, s);
 }
 
 static int ensure_beam_state(vz_engine* e) {
@@ -1763,7 +1860,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_SAMPLE: k.samp = e->samp.a; break;
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
-    if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; }
+    if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; k.proc_seq = e->proc.a.n_seq ? e->proc.d_seq : nullptr; }
     if (e->stop.on) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;

@@ -52,7 +52,7 @@ static DecodeState decode_state(int* base, int mb) {
 // whichever armed mode comes first (tail_kind).  The *Args of a mode are what its kernels take by value - a captured step freezes them, so
 // they go into the graph key as they are; they are laid out without padding (the key is compared with memcmp).
 enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC, TAIL_ROWS };      // TAIL_ROWS takes nothing by value: its table is device memory
-struct SampleArgs { int top_k; float temp, top_p; };
+struct SampleArgs { int top_k; float temp, top_p; SampleWarp warp; };
 struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
 struct SpecArgs {
     int *hist, *out, *ctl, *stats; const int* stream;
@@ -66,11 +66,11 @@ struct DecodeGraphKey {
     int B, n, nsplit, use_tok, kind; unsigned tune_epoch;
     int* out; char* arena; int* ring; int ring_n;
     SampleArgs samp; BeamArgs beam; SpecArgs spec;
-    int* proc_hist; ProcArgs proc; int proc_on;      // the logits processors in front of the tail and their history buffer (zero when off)
+    int* proc_hist; const int* proc_seq; ProcArgs proc; int proc_on;      // the logits processors in front of the tail, their history buffer and sequence table (zero when off)
     float *sc_rec, *sc_warped, *sc_raw; unsigned sc_what; int sc_cap;      // the step recorder behind the tail and its rings (zero when off)
     int* stop_state; StopArgs stop;      // the stop matcher behind the tail: its state, tables and dims (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
 
 // The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
@@ -117,7 +117,7 @@ struct vz_engine {
     std::vector<int> h_len, h_pos; std::vector<char> h_parked;
     // the step's tail (tail_kind): each mode is armed on its own, so disarming one falls back to the next armed one
     // sampling (vz_llm_decode_sampling): ctr0 / seed = the draw counter and the key the next vz_llm_decode_begin uploads
-    struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f}; } samp;
+    struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f, {0.f, 0.f, 0.f, 0.f}}; } samp;
     // per-row table (vz_llm_decode_sampling_rows): tab = the max_batch entries the next vz_llm_decode_begin uploads (all greedy until set)
     struct { int on = 0; std::vector<RowSample> tab; } rows;
     // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)
@@ -127,7 +127,9 @@ struct vz_engine {
     struct { int on = 0, R = 0, base_len = 0, base_pos = 0; SpecArgs a{}; } spec;
     // logits processors (vz_llm_decode_logits_proc; logits_proc.hip): orthogonal to the tail - armed, they run on the step's logits in front
     // of the argmax / the sampler.  d = [hist_len: max_batch ints, padded to 64 | hist: max_batch x max_ctx ints], its own allocation
-    struct { int on = 0; ProcArgs a{}; int* d = nullptr; } proc;
+    // d_seq / h_seq = the id-sequence table of sequence_bias / bad_words_ids (VZ_PROC_MAX_SEQ entries) and its host image: an arming
+    // with an equal table uploads nothing; seq_epoch counts the uploads
+    struct { int on = 0; ProcArgs a{}; int* d = nullptr; int* d_seq = nullptr; std::vector<int> h_seq; int seq_epoch = 0; } proc;
     // step recorder (vz_llm_decode_scores; sampling.hip: token_scores_kernel): behind the tail, a record per row and step into the caller's
     // rings of `cap` steps; d_slot = the steps launched since vz_llm_decode_begin (one word of its own, counted by the step-advance launch)
     struct { unsigned what = 0; float *rec = nullptr, *warped = nullptr, *raw = nullptr; int cap = 0; int* d_slot = nullptr; } score;

@@ -11,6 +11,12 @@
 // h) and `ban`; the history is marked with LDS atomics, then the bitmap WORDS are swept and only set bits touch a logit - penalty
 // first, then -inf; a logit has exactly one writer, the rest of the row is neither read nor written.  Plain fp32 * and / (correctly
 // rounded, no fast-math): bit-identical to torch on the CPU.
+// In front of them, opt-in: HF's SequenceBiasLogitsProcessor (first in HF's chain) and NoBadWordsLogitsProcessor
+// (behind the n-gram ban) from one table of id sequences in device memory, seq[k] = [len 1..8 | bad | bias (fp32 bits) | - | ids[8]]:
+//   a one-id sequence acts at every step; a longer one acts on its last id when h ends in its first len - 1 ids - and, as HF's length
+//   check has it, only once len <= n.  bad = 1 (a bad word): the id is banned, no arithmetic.  Else the id is marked in a third bitmap,
+//   `biased`, and the sweep adds, in fp32 and in table order, the biases of the acting sequences that end in it: x + (((0 + b1) + b2) ...),
+//   HF's zero-initialised bias row - then the penalty, which acts on the biased score, then -inf.  Still one writer per logit.
 // One 1024-thread workgroup per row, in place.  Inside a decode step the kernel first appends cur[row] - the token the previous tail
 // published - to the row's history (saturating at hist_stride), so no tail kernel has to know about the history.
 #include "vz_common.h"
@@ -24,8 +30,11 @@ __device__ __forceinline__ void mark(unsigned* bm, int tok, int cols) {
 }
 
 __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict__ logits, int cols, int* __restrict__ hist, int hist_stride,
-                                                              int* __restrict__ hist_len, const int* __restrict__ cur, ProcArgs a) {
-    __shared__ unsigned seen[PROC_WORDS], ban[PROC_WORDS];
+                                                              int* __restrict__ hist_len, const int* __restrict__ cur, ProcArgs a,
+                                                              const int* __restrict__ seqtab) {
+    __shared__ unsigned seen[PROC_WORDS], ban[PROC_WORDS], biased[PROC_WORDS];
+    __shared__ int s_tok[VZ_PROC_MAX_SEQ];          // the id sequence k biases in this row, -1: none (it does not act, or it bans)
+    __shared__ float s_bias[VZ_PROC_MAX_SEQ];
     const int row = blockIdx.x, tid = threadIdx.x;
     const int W = (cols + 31) >> 5;
     int* h = hist + (size_t)row * hist_stride;
@@ -35,7 +44,8 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
     const int n0 = min(max(hist_len[row], 0), hist_stride);
     const bool app = cur != nullptr && n0 < hist_stride;
     const int c = cur ? cur[row] : -1;
-    for (int w = tid; w < W; w += 1024) { seen[w] = 0; ban[w] = 0; }
+    const int n_seq = seqtab ? a.n_seq : 0;
+    for (int w = tid; w < W; w += 1024) { seen[w] = 0; ban[w] = 0; if (n_seq) biased[w] = 0; }
     __syncthreads();
     if (app && tid == 0) { h[n0] = c; hist_len[row] = n0 + 1; }
     const int n = app ? n0 + 1 : n0;                     // entries the processors see; h[n0] = c is taken from the register
@@ -79,12 +89,30 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
     }
     if (tid < 4 && tid < a.eos.n && n < a.min_new) mark(ban, a.eos.id[tid], cols);
     if (tid >= 64 && tid < 64 + 16 && tid - 64 < a.n_suppress) mark(ban, a.suppress[tid - 64], cols);
+    if (tid >= 128 && tid - 128 < n_seq) {          // one thread per sequence of the table
+        const int* q = seqtab + (tid - 128) * VZ_PROC_SEQ_STRIDE;
+        const int L = min(max(q[0], 1), VZ_PROC_SEQ_IDS);
+        bool hit = L == 1 || n >= L;                     // HF skips a sequence while len(sequence) > ids generated (not len - 1)
+        for (int j = 0; j + 1 < L && hit; ++j) {
+            const int k = n - (L - 1) + j;               // >= 1 here
+            const int v = h[k];
+            hit = ((app && k == n0) ? c : v) == q[4 + j];
+        }
+        const int last = q[4 + L - 1];
+        int act = -1;
+        if (hit && (unsigned)last < (unsigned)cols) {
+            if (q[1]) mark(ban, last, cols);
+            else { mark(biased, last, cols); act = last; }
+        }
+        s_tok[tid - 128] = act;
+        s_bias[tid - 128] = __int_as_float(q[2]);
+    }
     __syncthreads();
 
     const float p = a.penalty;
     for (int w = tid; w < W; w += 1024) {
-        const unsigned b = ban[w];
-        unsigned m = seen[w] | b;
+        const unsigned b = ban[w], sn = seen[w], bs = n_seq ? biased[w] : 0u;
+        unsigned m = sn | b | bs;
         while (m) {
             const int bit = __ffs(m) - 1;
             m &= m - 1;
@@ -92,8 +120,14 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
             if ((b >> bit) & 1u) {
                 lr[k] = -INFINITY;
             } else {
-                const float x = lr[k];
-                lr[k] = x < 0.f ? x * p : x / p;
+                float x = lr[k];
+                if ((bs >> bit) & 1u) {
+                    float s = 0.f;
+                    for (int i = 0; i < n_seq; ++i) if (s_tok[i] == k) s += s_bias[i];
+                    x = x + s;
+                }
+                if ((sn >> bit) & 1u) x = x < 0.f ? x * p : x / p;
+                lr[k] = x;
             }
         }
     }
@@ -102,13 +136,14 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
 }  // namespace
 
 int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
-                             const ProcArgs& a, hipStream_t s) {
+                             const ProcArgs& a, const int* seqtab, hipStream_t s) {
     VZ_CHECK_ARG(logits && hist && hist_len && rows > 0 && cols > 0 && hist_stride >= 1, "logits_process: bad argument");
     VZ_CHECK_ARG(cols <= PROC_MAX_COLS, "logits_process: %d columns, the LDS bitmaps hold %d", cols, PROC_MAX_COLS);
     VZ_CHECK_ARG(a.penalty > 0.f && a.ngram >= 0 && a.ngram <= PROC_G && a.min_new >= 0 && a.eos.n >= 0 && a.eos.n <= 4 && a.n_suppress >= 0 &&
                  a.n_suppress <= 16, "logits_process: penalty %g > 0, 0 <= ngram %d <= 8, min_new %d >= 0, <= 4 eos ids (%d), <= 16 suppressed ids (%d) expected",
                  (double)a.penalty, a.ngram, a.min_new, a.eos.n, a.n_suppress);
-    hipLaunchKernelGGL(logits_process_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, hist, hist_stride, hist_len, cur, a);
+    VZ_CHECK_ARG(a.n_seq >= 0 && a.n_seq <= VZ_PROC_MAX_SEQ && (a.n_seq == 0 || seqtab), "logits_process: %d id sequences, 0..%d with their table expected", a.n_seq, VZ_PROC_MAX_SEQ);
+    hipLaunchKernelGGL(logits_process_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, hist, hist_stride, hist_len, cur, a, seqtab);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

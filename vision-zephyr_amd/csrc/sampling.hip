@@ -10,6 +10,10 @@
 //   3. top-p: Z = sum of w_i = floor(exp(x_i - max) * 2^40) over the kept tokens (integer mass: order-independent, so a
 //      replayed graph, an eager step and a second run give the same bits), then a 4-pass radix select ASCENDING on the
 //      same key with the histogram weighted by w: smallest key t with mass{key <= t} > (1 - top_p) * Z; keep key >= t
+//   3b. (opt-in) HF's further warpers in HF's order, each over the set kept so far: min_p, typical_p,
+//      epsilon_cutoff, eta_cutoff.  min_p / epsilon / eta raise the lower threshold on x; typical_p keeps a band of log p that may
+//      leave out the most likely token, so the kept set is a key interval [lo, hi].  typical_p's cut is the same mass-weighted
+//      radix select as top-p's, keyed by |-log p - H|; the float sums (Z, entropy) have a fixed reduction shape.
 //   4. draw: token = argmax_i (x_i + G_i) over the kept tokens, G_i = -log(-log(u_i)) (Gumbel race: P[argmax = i] =
 //      softmax(x)_i, the distribution torch.multinomial draws from), u_i = Philox4x32-10(key = seed, counter =
 //      (i, row, token counter, 0x565a)) word 0 -> ((w >> 9) + 0.5) * 2^-23; ties -> smallest index.
@@ -54,6 +58,18 @@ __device__ __forceinline__ float block_max(float v, SampleShared& sh) {
     return r;
 }
 
+// fixed reduction shape (see the step recorder below): the same bits eager, replayed and on a second run
+__device__ __forceinline__ float block_sum(float v, SampleShared& sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh.redf[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = sh.redf[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) r += sh.redf[w];
+    __syncthreads();
+    return r;
+}
+
 // REG (cols <= 32768): the tempered row is staged ONCE in LDS (one batch of 32 global loads per thread) and all passes (maximum, the two
 // radix selects, the Gumbel race: up to 11 sweeps) read it from there; the loop form re-reads the row from L2 in every sweep, one
 // dependent 4-byte load at a time (the streamer path paid ~80 us per token for it).  Same values, same order-independent sums.
@@ -65,12 +81,125 @@ __device__ __forceinline__ float block_max(float v, SampleShared& sh) {
         for (int k = tid; k < cols; k += 1024) { const float x = lr[k] / temperature; BODY }                         \
     }
 
-// One row's kept set, steps 1..3 above: stages the tempered row (REG), returns the threshold key - a token is kept iff fkey(x) >= it -
-// and the maximum m of the tempered row.  Shared by the draw (sample_row_race) and the step recorder (token_scores_kernel), so the set
-// a record describes is the set the token was drawn from.
+// the sweeps of the opt-in step 3b: not unrolled, so that the calls that leave the step out keep the registers they had
+#define VZ_FOR_LOGITS_1(BODY)                                                                                        \
+    if (REG) {                                                                                                       \
+        _Pragma("unroll 1") for (int k = tid; k < cols; k += 1024) { const float x = lx[k]; BODY }                    \
+    } else {                                                                                                         \
+        _Pragma("unroll 1") for (int k = tid; k < cols; k += 1024) { const float x = lr[k] / temperature; BODY }     \
+    }
+
+__device__ __forceinline__ float unfkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// Z = sum e_i and S = sum e_i * (x_i - m), e_i = exp(x_i - m), over the tokens whose key lies in [lo, hi]: softmax and entropy
+// H = log Z - S / Z of the set kept so far (-inf entries have no mass: skipped, as HF's nansum skips them)
+template <bool REG>
+__device__ __forceinline__ void kept_sums(const float* __restrict__ lr, int cols, float temperature, float m, unsigned lo, unsigned hi,
+                                          SampleShared& sh, float& Z, float& S) {
+    const int tid = threadIdx.x;
+    extern __shared__ float lx[];
+    float z = 0.f, sm = 0.f;
+    VZ_FOR_LOGITS_1({
+        const unsigned key = fkey(x);
+        if (key >= lo && key <= hi && x > -INFINITY) { const float d = x - m; const float e = expf(d); z += e; sm += e * d; }
+    })
+    Z = block_sum(z, sh);
+    S = block_sum(sm, sh);
+}
+
+// Step 3b: the kept interval [lo, hi] after min_p, typical_p, epsilon_cutoff and eta_cutoff (HF's order; each sees what the one before
+// left; each keeps at least the largest score of its input set).  On entry [lo, hi] = [top-k / top-p threshold, all ones]: the row's
+// maximum m is inside.
+template <bool REG>
+__device__ __forceinline__ void sample_row_warp(const float* __restrict__ lr, int cols, float temperature, const SampleWarp& wp, float m,
+                                                SampleShared& sh, unsigned& lo, unsigned& hi) {
+    const int tid = threadIdx.x;
+    extern __shared__ float lx[];
+    float top = m;                                   // the largest kept score
+    // ---- min_p: drop p_i < min_p * p_max, p_max = exp(0) / Z ----
+    if (wp.min_p > 0.f) lo = max(lo, fkey(m + logf(wp.min_p)));
+    // ---- typical_p: ascending in s_i = |-log p_i - H|, the shortest prefix with mass >= typical_p ----
+    if (wp.typical_p > 0.f && wp.typical_p < 1.f) {
+        float Z, S;
+        kept_sums<REG>(lr, cols, temperature, m, lo, hi, sh, Z, S);
+        const float logZ = logf(Z), H = logZ - S / Z;
+        unsigned long long zi = 0;
+        VZ_FOR_LOGITS_1({
+            const unsigned key = fkey(x);
+            if (key >= lo && key <= hi) zi += (unsigned long long)(expf(x - m) * 1099511627776.0f);
+        })
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) zi += __shfl_xor(zi, o, 64);
+        if ((tid & 63) == 0) sh.redm[tid >> 6] = zi;
+        __syncthreads();
+        zi = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) zi += sh.redm[w];
+        __syncthreads();
+        unsigned long long want = (unsigned long long)((double)wp.typical_p * (double)zi);
+        if (want < 1) want = 1;
+        // smallest s-key t with mass{s <= t} >= want (s >= 0: its bits ascend with it)
+        unsigned prefix = 0, pmask = 0;
+        unsigned long long below = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) sh.mass[tid] = 0;
+            __syncthreads();
+            VZ_FOR_LOGITS_1({
+                const unsigned key = fkey(x);
+                if (key >= lo && key <= hi && x > -INFINITY) {
+                    const unsigned sk = __float_as_uint(fabsf((logZ - (x - m)) - H));
+                    if ((sk & pmask) == prefix) atomicAdd(&sh.mass[(sk >> shift) & 255], (unsigned long long)(expf(x - m) * 1099511627776.0f));
+                }
+            })
+            __syncthreads();
+            if (tid == 0) {
+                unsigned long long cum = below;
+                int b = 0;
+                for (; b < 255; ++b) { if (cum + sh.mass[b] >= want) break; cum += sh.mass[b]; }
+                sh.sel = (unsigned)b; sh.carry = cum;
+            }
+            __syncthreads();
+            prefix |= sh.sel << shift; pmask |= 255u << shift; below = sh.carry;
+            __syncthreads();
+        }
+        // s is monotone in |x - c| step by step in fp32, so {s <= t} is an interval of x: its two ends
+        unsigned nlo = 0xffffffffu, nhi = 0u;
+        VZ_FOR_LOGITS_1({
+            const unsigned key = fkey(x);
+            if (key >= lo && key <= hi && x > -INFINITY && __float_as_uint(fabsf((logZ - (x - m)) - H)) <= prefix) { nlo = min(nlo, key); nhi = max(nhi, key); }
+        })
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { nlo = min(nlo, (unsigned)__shfl_xor((int)nlo, o, 64)); nhi = max(nhi, (unsigned)__shfl_xor((int)nhi, o, 64)); }
+        if ((tid & 63) == 0) { sh.redi[tid >> 6] = (int)nlo; sh.hist[tid >> 6] = nhi; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 16; ++w) { nlo = min(nlo, (unsigned)sh.redi[w]); nhi = max(nhi, sh.hist[w]); }
+        __syncthreads();
+        if (nlo <= nhi) { lo = nlo; hi = nhi; top = unfkey(hi); }
+    }
+    // ---- epsilon_cutoff: drop p_i < epsilon ----
+    if (wp.epsilon > 0.f && wp.epsilon < 1.f) {
+        float Z, S;
+        kept_sums<REG>(lr, cols, temperature, m, lo, hi, sh, Z, S);
+        lo = max(lo, min(fkey(m + logf(wp.epsilon * Z)), fkey(top)));
+    }
+    // ---- eta_cutoff: drop p_i < min(eta, sqrt(eta) * exp(-H)) ----
+    if (wp.eta > 0.f && wp.eta < 1.f) {
+        float Z, S;
+        kept_sums<REG>(lr, cols, temperature, m, lo, hi, sh, Z, S);
+        const float H = logf(Z) - S / Z;
+        const float eta = fminf(wp.eta, sqrtf(wp.eta) * expf(-H));
+        lo = max(lo, min(fkey(m + logf(eta * Z)), fkey(top)));
+    }
+}
+
+// One row's kept set, steps 1..3b above: stages the tempered row (REG), returns the interval's lower key and sets its upper key hi_out -
+// a token is kept iff lo <= fkey(x) <= hi - and the maximum m of the tempered row.  Shared by the draw (sample_row_race) and the step
+// recorder (token_scores_kernel), so the set a record describes is the set the token was drawn from.
 template <bool REG>
 __device__ __forceinline__ unsigned sample_row_keep(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
-                                                    SampleShared& sh, float& m_out, const float* have = nullptr) {
+                                                    const SampleWarp& wp, SampleShared& sh, float& m_out, unsigned& hi_out,
+                                                    const float* have = nullptr) {
     // have (REG only): the caller's registers already hold the row's batch of loads, have[i] = lr[tid + i * 1024] - staged from there
     const int tid = threadIdx.x;
     extern __shared__ float lx[];          // REG: cols floats
@@ -160,25 +289,31 @@ __device__ __forceinline__ unsigned sample_row_keep(const float* __restrict__ lr
         pth = prefix;
     }
     m_out = m;
-    return kth > pth ? kth : pth;
+    unsigned lo = kth > pth ? kth : pth, hi = 0xffffffffu;
+    if ((wp.min_p > 0.f || wp.typical_p > 0.f || wp.epsilon > 0.f || wp.eta > 0.f) && m > -INFINITY)
+        sample_row_warp<REG>(lr, cols, temperature, wp, m, sh, lo, hi);
+    hi_out = hi;
+    return lo;
 }
 
 // One row's draw, steps 1..4 above, up to each thread's own best (value, index) of the race; `stream_row` = the Philox counter's
 // row word.  Shared by the two kernels below, so a row gets the same bits from either.
 template <bool REG>
 __device__ __forceinline__ void sample_row_race(const float* __restrict__ lr, int cols, float temperature, int top_k, float top_p,
-                                                unsigned k0, unsigned k1, unsigned stream_row, unsigned c2, SampleShared& sh,
+                                                const SampleWarp& wp, unsigned k0, unsigned k1, unsigned stream_row, unsigned c2, SampleShared& sh,
                                                 float& bv, int& bi) {
     const int tid = threadIdx.x;
     extern __shared__ float lx[];          // REG: cols floats, staged by sample_row_keep
     float m;
-    const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, sh, m);
+    unsigned keep_hi;
+    const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, wp, sh, m, keep_hi);
 
     // ---- 4. Gumbel race over the kept tokens ----
     bv = -INFINITY;
     bi = 0x7fffffff;
     VZ_FOR_LOGITS({
-        if (fkey(x) >= keep) {
+        const unsigned key = fkey(x);
+        if (key >= keep && key <= keep_hi) {
             const unsigned w = philox_word0((unsigned)k, stream_row, c2, 0x565au, k0, k1);
             const float u = ((float)(w >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23; exact in fp32, inside (0, 1)
             const float v = x - logf(-logf(u));
@@ -208,14 +343,14 @@ __device__ __forceinline__ int block_first_best(float bv, int bi, SampleShared& 
 
 template <bool REG>
 __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ logits, int cols, float temperature, int top_k,
-                                                      float top_p, const unsigned* __restrict__ seed, const int* __restrict__ ctr,
-                                                      int ctr_add, int* __restrict__ ids, RowEmit emit) {
+                                                      float top_p, SampleWarp wp, const unsigned* __restrict__ seed,
+                                                      const int* __restrict__ ctr, int ctr_add, int* __restrict__ ids, RowEmit emit) {
     __shared__ SampleShared sh;
     const int row = blockIdx.x;
     const unsigned c2 = (unsigned)(ctr[0] + ctr_add);
     float bv;
     int bi;
-    sample_row_race<REG>(logits + (size_t)row * cols, cols, temperature, top_k, top_p, seed[0], seed[1], (unsigned)row, c2, sh, bv, bi);
+    sample_row_race<REG>(logits + (size_t)row * cols, cols, temperature, top_k, top_p, wp, seed[0], seed[1], (unsigned)row, c2, sh, bv, bi);
     bi = block_first_best(bv, bi, sh);
     if (threadIdx.x == 0) {
         ids[row] = bi;
@@ -234,12 +369,14 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     __shared__ SampleShared sh;
     const int row = blockIdx.x, tid = threadIdx.x;
     const float* lr = logits + (size_t)row * cols;
-    // the entry is the same for every lane: one 32-byte read at the top, held in scalar registers from then on
-    const int4 e0 = ((const int4*)(tab + row))[0], e1 = ((const int4*)(tab + row))[1];
+    // the entry is the same for every lane: one 48-byte read at the top, held in scalar registers from then on
+    const int4 e0 = ((const int4*)(tab + row))[0], e1 = ((const int4*)(tab + row))[1], e2 = ((const int4*)(tab + row))[2];
     const int mode = __builtin_amdgcn_readfirstlane(e0.x), top_k = __builtin_amdgcn_readfirstlane(e0.z);
     const float temperature = __int_as_float(__builtin_amdgcn_readfirstlane(e0.y)), top_p = __int_as_float(__builtin_amdgcn_readfirstlane(e0.w));
     const unsigned k0 = (unsigned)__builtin_amdgcn_readfirstlane(e1.x), k1 = (unsigned)__builtin_amdgcn_readfirstlane(e1.y);
     const int ctr = __builtin_amdgcn_readfirstlane(e1.z);
+    const SampleWarp wp{__int_as_float(__builtin_amdgcn_readfirstlane(e2.x)), __int_as_float(__builtin_amdgcn_readfirstlane(e2.y)),
+                        __int_as_float(__builtin_amdgcn_readfirstlane(e2.z)), __int_as_float(__builtin_amdgcn_readfirstlane(e2.w))};
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     if (mode == VZ_ROW_GREEDY) {
@@ -253,7 +390,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
             for (int k = tid; k < cols; k += 1024) { const float v = lr[k]; if (v > bv || (v == bv && k < bi)) { bv = v; bi = k; } }
         }
     } else {
-        sample_row_race<REG>(lr, cols, temperature, top_k, top_p, k0, k1, 0u, (unsigned)ctr, sh, bv, bi);
+        sample_row_race<REG>(lr, cols, temperature, top_k, top_p, wp, k0, k1, 0u, (unsigned)ctr, sh, bv, bi);
     }
     bi = block_first_best(bv, bi, sh);
     if (tid == 0) {
@@ -267,23 +404,13 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
 // Behind the tail: one 16-byte record per row about the token the tail chose, ids[row]:
 //   x_tok    = logits[row, tok] as it stands (in a step: after the logits processors, before temperature); NaN if tok is outside [0, cols)
 //   lse      = m + log(sum_i exp(x_i - m)) over the whole row, natural log: the log-partition at temperature 1
-//   lse_kept = mT + log(sum_{i kept} exp(x_i / T - mT)) over the set the sampler keeps for the row's (T, top_k, top_p) - sample_row_keep,
+//   lse_kept = mT + log(sum_{i kept} exp(x_i / T - mT)) over the set the sampler keeps for the row's (T, top_k, top_p, warpers) - sample_row_keep,
 //              the sampler's own; a greedy row: lse
 //   n_kept   = size of that set (int32), -inf entries not counted; a greedy row: cols
 // and, if asked for, the row HF calls scores[t]: x for a greedy row, x / T where kept and -inf elsewhere for a sampled one.
 // Fixed reduction shape - each thread sums its stride-1024 elements in index order, the wave's 64 partials go through wave_sum's fixed
 // butterfly, the 16 wave partials are added in index order: a replayed graph, an eager step and a second run give the same bits.  The
 // maximum is subtracted first; a row of -inf gives lse = -inf without evaluating (-inf) - (-inf).
-__device__ __forceinline__ float block_sum(float v, SampleShared& sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh.redf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sh.redf[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) r += sh.redf[w];
-    __syncthreads();
-    return r;
-}
 __device__ __forceinline__ int block_sum_int(int v, SampleShared& sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -308,8 +435,11 @@ __global__ __launch_bounds__(1024) void token_scores_kernel(const float* __restr
     const float* lr = logits + (size_t)row * cols;
     int mode = one.mode, top_k = one.top_k;
     float temperature = one.temp, top_p = one.top_p;
+    SampleWarp wp = one.warp;
     if (tab) {          // the per-row table, read as sample_rows_kernel reads it
-        const int4 e0 = ((const int4*)(tab + row))[0];
+        const int4 e0 = ((const int4*)(tab + row))[0], e2 = ((const int4*)(tab + row))[2];
+        wp = SampleWarp{__int_as_float(__builtin_amdgcn_readfirstlane(e2.x)), __int_as_float(__builtin_amdgcn_readfirstlane(e2.y)),
+                        __int_as_float(__builtin_amdgcn_readfirstlane(e2.z)), __int_as_float(__builtin_amdgcn_readfirstlane(e2.w))};
         mode = __builtin_amdgcn_readfirstlane(e0.x); top_k = __builtin_amdgcn_readfirstlane(e0.z);
         temperature = __int_as_float(__builtin_amdgcn_readfirstlane(e0.y)); top_p = __int_as_float(__builtin_amdgcn_readfirstlane(e0.w));
     }
@@ -367,11 +497,13 @@ __global__ __launch_bounds__(1024) void token_scores_kernel(const float* __restr
     int n_kept = cols;
     if (!greedy) {
         float mT;
-        const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, sh, mT, REG ? t : nullptr);
+        unsigned keep_hi;
+        const unsigned keep = sample_row_keep<REG>(lr, cols, temperature, top_k, top_p, wp, sh, mT, keep_hi, REG ? t : nullptr);
         float sk = 0.f;
         int nk = 0;
         VZ_FOR_LOGITS({
-            const bool in = fkey(x) >= keep;
+            const unsigned key = fkey(x);
+            const bool in = key >= keep && key <= keep_hi;
             if (in && x > -INFINITY) { nk += 1; sk += expf(x - mT); }          // (a -inf entry above the threshold has no mass: not counted)
             if (wr) wr[k] = in ? x : -INFINITY;
         })
@@ -408,15 +540,15 @@ int vz_init_sampling_kernels() {
     return VZ_OK;
 }
 
-int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const unsigned* seed,
-                     const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s) {
+int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const SampleWarp& warp,
+                     const unsigned* seed, const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s) {
     VZ_CHECK_ARG(logits && ids && seed && ctr && rows > 0 && cols > 0 && (!emit.ring || emit.ring_n > 0), "sample: bad argument");
     VZ_CHECK_ARG(temperature > 0.f && top_p > 0.f, "sample: temperature %g and top_p %g must be positive (temperature 0 = greedy: use argmax)", (double)temperature, (double)top_p);
     { int r = vz_init_sampling_kernels(); if (r) return r; }
     if (cols <= 32768 && g_sample_lds_ok)
-        hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, temperature, top_k, top_p, warp, seed, ctr, ctr_add, ids, emit);
     else
-        hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, temperature, top_k, top_p, seed, ctr, ctr_add, ids, emit);
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, temperature, top_k, top_p, warp, seed, ctr, ctr_add, ids, emit);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -349,14 +349,17 @@ __device__ __forceinline__ void vz_emit_advance(const RowEmit& t, int row, int t
     if (t.pos && t.pos[row] + 1 < t.rope_max) t.pos[row] += 1;
     if (t.len && t.len[row] < t.max_ctx) { t.len[row] += 1; if (t.slot) t.slot[row] += 1; }
 }
-// One decode row's entry of the per-row tail's table (sampling.hip: sample_rows_kernel), 32 bytes in device memory: how the row's next
+// The warpers behind top-k / top-p (sampling.hip), each 0 = off: min_p in (0, 1], typical_p in (0, 1),
+// epsilon_cutoff in (0, 1), eta_cutoff in (0, 1).
+struct SampleWarp { float min_p, typical_p, epsilon, eta; };
+// One decode row's entry of the per-row tail's table (sampling.hip: sample_rows_kernel), 48 bytes in device memory: how the row's next
 // token is chosen, and the row's own Philox key and draw counter (the kernel counts it up).
 enum { VZ_ROW_GREEDY = 0, VZ_ROW_SAMPLE = 1 };
-struct RowSample { int mode; float temp; int top_k; float top_p; unsigned seed[2]; int ctr; int pad; };
-static_assert(sizeof(RowSample) == 32, "RowSample is read as two 16-byte words");
+struct RowSample { int mode; float temp; int top_k; float top_p; unsigned seed[2]; int ctr; int pad; SampleWarp warp; };
+static_assert(sizeof(RowSample) == 48, "RowSample is read as three 16-byte words");
 int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* tab, int* ids, const RowEmit& emit, hipStream_t s);
-int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const unsigned* seed,
+int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const SampleWarp& warp, const unsigned* seed,
                      const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s);
 // set dynamic-LDS limits of every kernel up front (never inside a stream capture)
 int vz_init_gemm_kernels();
@@ -386,12 +389,17 @@ int vz_beam_k(int nb, int n_eos);
 // HF's logits processors in front of the step's tail (logits_proc.hip): repetition penalty (1 = off), no-repeat-n-gram size (0 = off,
 // <= 8), eos ids at -inf while the history is shorter than min_new, ids at -inf always.  By value into the kernel and, as they are,
 // into the decode graph's key: no padding.
-struct ProcArgs { float penalty; int ngram, min_new; BeamEos eos; int n_suppress; int suppress[16]; };
-static_assert(sizeof(ProcArgs) == 4 * 4 + sizeof(BeamEos) + 16 * 4, "padding in ProcArgs");
+// n_seq: the id sequences of sequence_bias / bad_words_ids, a table in device memory handed over beside the
+// struct: [n_seq][VZ_PROC_SEQ_STRIDE] = [len 1..VZ_PROC_SEQ_IDS | 1 = bad word (ban), 0 = bias | bias, fp32 bits | - | ids]; one-id
+// sequences first, each group in the caller's order (the order HF adds the biases in).  seq_epoch counts the tables the owner of that
+// memory has uploaded: a captured step froze one of them.
+enum { VZ_PROC_MAX_SEQ = 64, VZ_PROC_SEQ_IDS = 8, VZ_PROC_SEQ_STRIDE = 12 };
+struct ProcArgs { float penalty; int ngram, min_new; BeamEos eos; int n_suppress; int suppress[16]; int n_seq, seq_epoch; };
+static_assert(sizeof(ProcArgs) == 6 * 4 + sizeof(BeamEos) + 16 * 4, "padding in ProcArgs");
 // in place on fp32 logits [rows, cols <= 65536]; the row's history hist[row * hist_stride + 0 .. hist_len[row]); cur != null: cur[row] is
 // appended first (saturating at hist_stride)
 int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
-                             const ProcArgs& a, hipStream_t s);
+                             const ProcArgs& a, const int* seqtab, hipStream_t s);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
                           int* next_parent, const RowEmit& emit, hipStream_t s);

@@ -357,7 +357,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                               min_new_tokens: Optional[int] = None, suppress_tokens=None, num_return_sequences: int = 1,
                               return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
-                              output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True, **unused):
+                              output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True,
+                              min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                              eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -379,7 +381,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         the syncs it already has, and a stopped row keeps its stopping token and shows `pad_token_id` behind it, as behind eos.  With a
         streamer, `num_beams > 1`, a tensor-parallel engine, any other criterion in the list, a stop set beyond the matcher's limits or
         `device_stop=False` every criterion stays on the host (one sequence at a time, one callback per token), and stop strings given
-        by keyword join them as a `StopStringCriteria`."""
+        by keyword join them as a `StopStringCriteria`.
+
+        Warpers: HF's `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` (default: the generation config's)
+        act behind temperature / top-k / top-p in HF's order, inside the device-side sampler (csrc/sampling.hip), on every sampled
+        route; a greedy call ignores them, as HF does.  HF's `sequence_bias` and `bad_words_ids` (default: the generation config's) join
+        the logits processors (csrc/logits_proc.hip), over the generated ids only, in HF's positions: the bias in front of the
+        repetition penalty, the bad words behind the n-gram ban; up to 64 sequences of up to 8 ids, NotImplementedError beyond."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
         from vz_hip import stop as ST
@@ -392,7 +400,10 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length, S, pad_token_id)
         eos = d.eos
         # HF's logits processors (csrc/logits_proc.hip): None = none of the four keywords is active, every path below is as it was
-        proc = logits_proc.parse(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, sorted(eos))
+        gcf = self.generation_config
+        proc = logits_proc.parse(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, sorted(eos),
+                                 getattr(gcf, "sequence_bias", None) if sequence_bias is None else sequence_bias,
+                                 getattr(gcf, "bad_words_ids", None) if bad_words_ids is None else bad_words_ids, self.config.vocab_size)
         if proc is not None and num_beams != 1:
             raise NotImplementedError("logits processors with num_beams > 1 are not built (HF applies them to log-softmax scores there)")
         if proc is not None and self.engine.tp_size > 1:
@@ -408,6 +419,12 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             top_k = self.generation_config.top_k
         if top_p is None:
             top_p = self.generation_config.top_p
+        # HF's further warpers as RowParams fields: {} = none is active (a greedy call, None, HF's off values), every path below is as it was
+        gc = self.generation_config
+        warp = {} if greedy else sample_rows.parse_warpers(
+            getattr(gc, "min_p", None) if min_p is None else min_p, getattr(gc, "typical_p", None) if typical_p is None else typical_p,
+            getattr(gc, "epsilon_cutoff", None) if epsilon_cutoff is None else epsilon_cutoff,
+            getattr(gc, "eta_cutoff", None) if eta_cutoff is None else eta_cutoff)
         if seed is None:                     # one 64-bit seed per generate call: from the caller's generator, else from torch's global one
             seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,), generator=generator,
                                                       device=generator.device if generator is not None else "cpu").item())
@@ -416,7 +433,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         done = lambda seqs: self._generate_output(seqs, sink, eos, return_dict_in_generate)      # noqa: E731  (the plain tensor unless asked)
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
-                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop))
+                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp))
         if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None:      # (with processors, scores or device stops: the plain greedy path, same ids)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
@@ -438,7 +455,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
-                                           stopping_criteria, seed + b, sync_every, timing, proc, sink, stop))
+                                           stopping_criteria, seed + b, sync_every, timing, proc, sink, stop, warp))
         return done(DL.pad_parts([torch.tensor([o], dtype=torch.long, device=self.device) for o in outs], pad_token_id, self.device))
 
     def _generate_output(self, seqs, sink, eos, return_dict_in_generate):
@@ -503,7 +520,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
-                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None) -> torch.Tensor:
+                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None, warp=None) -> torch.Tensor:
         """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
@@ -517,14 +534,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if Bsz > G:
             part = lambda lo, hi, tm: self._generate_samples(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi], n,      # noqa: E731
                                                              max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, tm, proc,
-                                                             prompt0 + lo, sink, stop)
+                                                             prompt0 + lo, sink, stop, warp)
             return DL.run_parts(part, Bsz, G, pad_token_id, self.device, timing)
         if max(seqlens) + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         R = Bsz * n
         last = DL.fan_prefill(eng, embeds, seqlens, position_ids, n)
         params = [SR.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
-                               SR.row_seed(seed, prompt0 + r // n, n, r % n), 0) for r in range(R)]
+                               SR.row_seed(seed, prompt0 + r // n, n, r % n), 0, **(warp or {})) for r in range(R)]
         first, first_cpu, blk = DL.first_tokens(last, params, proc, sink, timing)
         next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, n)
         with DL.armed(eng, proc=proc, sampling_rows=[p.at(1) for p in params], scores=DL.chunk_recorder(sink, R, sync_every, max_new),
@@ -810,7 +827,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None, warp=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
@@ -829,13 +846,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             # HF hands the (empty, since generation starts from embeddings) prompt ids to the streamer first;
             # TextStreamer(skip_prompt=True) swallows exactly one put() as "the prompt"
             streamer.put(torch.empty((1, 0), dtype=torch.long))
-        par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0)
-        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed))
+        par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0, **(warp or {}))
+        more = () if par.warp is None else (par.warp,)      # the further warpers' column, named only when one is active
+        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed) + more)
         out: List[int] = [int(first_cpu[0])]
         if self._emit(out, streamer, stopping_criteria, None, eos) or max_new <= 1:
             return self._finish(out, streamer)
         # the step's tail: a greedy call names it only with the ring, whose slot is the draw counter that `set_sampling` starts at 1
-        tail = None if greedy and not per_token else (not greedy, 1.0 if greedy else temperature, top_k, top_p, seed, 1)
+        tail = None if greedy and not per_token else (not greedy, 1.0 if greedy else temperature, top_k, top_p, seed, 1) + more
         if not per_token:
             # no host callbacks: steps are enqueued back to back, the host looks at the ids every `sync_every` tokens only to honour eos
             # and the stop conditions the device decides (vz_hip.stop)

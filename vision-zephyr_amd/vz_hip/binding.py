@@ -139,12 +139,20 @@ SYMBOLS = {
     "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_scores": (_I, [_P, C.c_uint, _P, _P, _P, _I, _P]),
     "vz_op_token_scores": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_sampling_warp": (_I, [_P, _I, _F, _I, _F, _P, C.c_ulonglong, _I]),
+    "vz_op_sample_warp": (_I, [_P, _I, _I, _F, _I, _F, _P, C.c_ulonglong, _I, _P, _P]),
+    "vz_llm_decode_sampling_rows_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_set_row_sampling_warp": (_I, [_P, _I, _I, _F, _I, _F, _P, C.c_ulonglong, _I, _P]),
+    "vz_op_sample_rows_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_op_token_scores_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_stop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_stop_rows": (_I, [_P, _I, _I, _P, _P]),
     "vz_llm_decode_stop_read": (_I, [_P, _I, _I, _P, _P]),
     "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
+    "vz_llm_decode_logits_proc_seq": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
+    "vz_op_logits_process_seq": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
@@ -644,6 +652,15 @@ def proc_lists(cfg):
     return (C.c_int * max(1, len(eos)))(*eos), len(eos), (C.c_int * max(1, len(sup)))(*sup), len(sup)
 
 
+def proc_seq(cfg):
+    """(table, n_seq) of a config's sequence_bias / bad_words_ids sequences for the *_seq entry points; (NULL, 0) without any"""
+    seq = getattr(cfg, "seq", ())
+    if not seq:
+        return None, 0
+    tab = cfg.seq_table()
+    return (C.c_int * len(tab))(*tab), len(seq)
+
+
 def logits_process(logits, cfg, hist=None, hist_len=None):
     """HF's logits processors (logits_proc.hip; cfg = vz_hip.logits_proc.parse(...)) IN PLACE on fp32 logits [rows, V] on the device,
     over the histories hist int32 [rows, stride] of hist_len int32 [rows] ids each (None = empty: the first token of a generation).
@@ -658,19 +675,29 @@ def logits_process(logits, cfg, hist=None, hist_len=None):
     assert hist_len.dtype == torch.int32 and hist_len.is_contiguous() and hist_len.numel() == rows
     assert hist.device == logits.device and hist_len.device == logits.device
     ea, ne, sa, ns = proc_lists(cfg)
-    check(lib().vz_op_logits_process(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), float(cfg.penalty),
-                                     int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns, stream_ptr(logits.device)))
+    check(lib().vz_op_logits_process_seq(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), float(cfg.penalty),
+                                         int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns, *proc_seq(cfg), stream_ptr(logits.device)))
     return logits
 
 
-def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, counter: int = 0):
-    """one draw per row of fp32 logits [rows, V] on the device (sampling.hip): int32 [rows]."""
+def warp_array(warps):
+    """the `h_warp` column of the *_warp entry points: warps = one (min_p, typical_p, epsilon_cutoff, eta_cutoff) per row, 0 = off
+    (vz_hip.sample_rows.RowParams.warp), or None for a row without any; NULL when no row has one"""
+    if all(w is None for w in warps):
+        return None
+    flat = [float(v) for w in warps for v in (w or (0.0, 0.0, 0.0, 0.0))]
+    return (C.c_float * len(flat))(*flat)
+
+
+def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, counter: int = 0, warp=None):
+    """one draw per row of fp32 logits [rows, V] on the device (sampling.hip): int32 [rows].  warp: None, or (min_p, typical_p,
+    epsilon_cutoff, eta_cutoff) behind top-p, 0 = off."""
     _need_cuda(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    check(lib().vz_op_sample(ptr(logits), logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0),
-                             float(1.0 if top_p is None else top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter), ptr(ids),
-                             stream_ptr(logits.device)))
+    check(lib().vz_op_sample_warp(ptr(logits), logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0),
+                                  float(1.0 if top_p is None else top_p), warp_array([warp]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter),
+                                  ptr(ids), stream_ptr(logits.device)))
     return ids
 
 
@@ -682,19 +709,26 @@ def row_sample_arrays(params):
             (C.c_ulonglong * n)(*[int(p.seed) & 0xFFFFFFFFFFFFFFFF for p in params]), (C.c_int * n)(*[int(p.counter) for p in params]))
 
 
+def row_sample_columns(params):
+    """the seven columns of the per-row *_warp entry points: `row_sample_arrays` with the warpers' column behind top_p"""
+    a = row_sample_arrays(params)
+    return a[:4] + (warp_array([getattr(p, "warp", None) for p in params]),) + a[4:]
+
+
 def sample_rows(logits, params):
     """one token per row of fp32 logits [rows <= 64, V] by that row's own parameters (params[r]: vz_hip.sample_rows.RowParams - greedy, or
     sampled with its own temperature / top-k / top-p / seed / draw counter; sampling.hip's per-row kernel): int32 [rows]."""
     _need_cuda(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(params) == logits.shape[0]
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    check(lib().vz_op_sample_rows(ptr(logits), logits.shape[0], logits.shape[1], *row_sample_arrays(params), ptr(ids), stream_ptr(logits.device)))
+    check(lib().vz_op_sample_rows_warp(ptr(logits), logits.shape[0], logits.shape[1], *row_sample_columns(params), ptr(ids),
+                                       stream_ptr(logits.device)))
     return ids
 
 
 def token_scores(logits, ids, params, warped=False):
     """the step recorder (sampling.hip: token_scores_kernel) on fp32 logits [rows, V] about the tokens ids [rows]: row r by params[r]
-    (vz_hip.sample_rows.RowParams: greedy, or temperature / top-k / top-p; seed and counter are not read).  Returns the records fp32
+    (vz_hip.sample_rows.RowParams: greedy, or temperature / top-k / top-p / the further warpers; seed and counter are not read).  Returns the records fp32
     [rows, 4] = (x_tok, lse, lse_kept, n_kept as int32 bits) (vz_hip.scores.unpack), with warped=True also the score rows fp32 [rows, V]."""
     _need_cuda(logits, ids)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(params) == logits.shape[0]
@@ -705,9 +739,9 @@ def token_scores(logits, ids, params, warped=False):
     w = torch.empty(rows, V, dtype=torch.float32, device=logits.device) if warped else None
     for r0 in range(0, rows, 64):          # the op takes up to 64 rows
         r1 = min(rows, r0 + 64)
-        mode, temp, top_k, top_p, _, _ = row_sample_arrays(params[r0:r1])
-        check(lib().vz_op_token_scores(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), mode, temp, top_k, top_p, ptr(rec[r0:r1]),
-                                       ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
+        mode, temp, top_k, top_p, warp, _, _ = row_sample_columns(params[r0:r1])
+        check(lib().vz_op_token_scores_warp(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), mode, temp, top_k, top_p, warp, ptr(rec[r0:r1]),
+                                            ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
     return (rec, w) if warped else rec
 
 

@@ -38,8 +38,8 @@ def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None):
     """The first token of every row, chosen on the prefill logits `last` [prompts, V] (processed in place by `proc`, whose first step
     sees an empty history): (first - device, first - host, the sink's block of these rows or None).  params: one
     vz_hip.sample_rows.RowParams per row; with n times as many rows as prompts each prompt's logits row serves its n adjacent rows.
-    The choice is B.argmax when no row samples, else B.sample_rows; draw = (temperature, top_k, top_p, seed): the serial sampled
-    sequence's B.sample(..., seed, 0) instead (`params` then only describes the row to the sink).  timing: stamped once the host
+    The choice is B.argmax when no row samples, else B.sample_rows; draw = (temperature, top_k, top_p, seed[, warp]): the serial sampled
+    sequence's B.sample(..., seed, 0[, warp]) instead (`params` then only describes the row to the sink).  timing: stamped once the host
     holds the tokens."""
     keep_raw = sink is not None and sink.raw
     raw = last.clone() if keep_raw and proc is not None else last
@@ -49,7 +49,7 @@ def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None):
     if n > 1:                                                    # a prompt's one logits row, once per sample
         last, raw = last.repeat_interleave(n, dim=0).contiguous(), raw.repeat_interleave(n, dim=0) if keep_raw else None
     if draw is not None:
-        first = B.sample(last, *draw, 0)
+        first = B.sample(last, *draw[:4], 0, *draw[4:])
     else:
         first = B.sample_rows(last, params) if any(p.sample for p in params) else B.argmax(last)
     blk = None

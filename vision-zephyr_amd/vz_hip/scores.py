@@ -171,7 +171,7 @@ def output_classes():
         class GenerateScoredDecoderOnlyOutput(GenerateDecoderOnlyOutput):
             """`token_logprobs` [rows, T]: log-prob of each generated token under the model's own distribution (after the logits
             processors, temperature 1); `token_logprobs_warped` [rows, T]: under the distribution it was drawn from (temperature, top-k,
-            top-p applied) = compute_transition_scores(sequences, scores, normalize_logits=True).  Both 0.0 behind a row's eos."""
+            top-p, min_p, typical_p and the epsilon / eta cutoffs applied) = compute_transition_scores(sequences, scores, normalize_logits=True).  Both 0.0 behind a row's eos."""
             token_logprobs: Optional[torch.FloatTensor] = None
             token_logprobs_warped: Optional[torch.FloatTensor] = None
         _SCORED = GenerateScoredDecoderOnlyOutput
