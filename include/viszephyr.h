@@ -400,8 +400,9 @@ int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, i
  * (stream-ordered) and extended at every step by the row's input token - so arm it before vz_llm_decode_begin, after the first
  * token was chosen on logits that went through vz_op_logits_process with empty histories.  repetition_penalty > 0 (1 = off),
  * 0 <= no_repeat_ngram <= 8 (0 = off), the <= 4 eos ids are -inf while fewer than min_new_tokens ids were generated, the <= 16
- * suppressed ids always; vocabularies up to 65536.  vz_llm_decode_steps refuses the mode together with the beam or the
- * speculative tail; tensor-parallel engines are VZ_ERR_UNSUPPORTED.  enable = 0: off (no launch is added to the step).
+ * suppressed ids always; vocabularies up to 65536.  vz_llm_decode_steps refuses the mode together with the speculative tail
+ * (with the beam tail: see "beam search: processors and rows" below); tensor-parallel engines are VZ_ERR_UNSUPPORTED.  enable = 0:
+ * off (no launch is added to the step).
  * vz_op_logits_process: the same kernel in place on fp32 logits [rows, cols] over the caller's histories d_hist [rows][hist_stride]
  * (int32) of d_hist_len[row] ids each; ids outside [0, cols) are ignored.  Bit-identical to HF's processors on fp32. */
 int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
@@ -762,6 +763,30 @@ int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float repetition_pen
 int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
                              int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
                              const int* h_seq, int n_seq, vz_stream stream);
+
+/* ---- beam search: processors and rows (csrc/beam.hip, csrc/logits_proc.hip) ----
+ * vz_llm_decode_logits_proc[_seq] may be armed together with vz_llm_decode_beam.  HF's `_beam_search` hands the processors the
+ * log-softmax row of every running beam and that beam's own ids, so a beam step then runs: log-prob rows in place (the reductions
+ * and the fp32 association of the fused select), the processor kernel on them, the select on the rows as they are (s_i = row_i +
+ * score[row]), the KV reorder, the reorder of the id histories (a row whose parent is another row takes its parent's history,
+ * length included; the processor kernel appends the row's own token at the next step), the history index.  Without processors and
+ * without recorded score rows the step is the fused select on the logits, launch for launch.  Log-prob rows followed by the select on
+ * rows give the records and next beams of the fused select bit for bit.  The first step runs at op level on the prefill logits:
+ * vz_op_beam_logprob_rows, vz_op_logits_process_seq with empty histories, vz_op_beam_select_rows with nb_in = 1.
+ * vz_op_beam_logprob_rows: d_lp [rows][cols] = (x - max) - log(sum exp(x - max)) of fp32 logits; d_lp may be d_logits.
+ * vz_op_beam_select_rows: vz_op_beam_select on rows that hold scores already (no normalisation).
+ * vz_op_hist_beam_reorder: groups x nb (<= 16) histories d_hist [groups * nb][hist_stride] of d_hist_len[row] ids follow d_parent
+ *   [groups * nb] (local beam indices), in place; cycles and parents with several children are safe.
+ * vz_llm_decode_beam_rows: the beam step also copies its processed log-prob rows (HF's scores[t]) into d_scores and / or its raw logits
+ *   rows into d_raw, rings fp32 [cap_steps][groups * nb][vocab] written at (history index of vz_llm_decode_beam) mod cap_steps, inside
+ *   the per-token hipGraph (the rings are part of what a captured step freezes); vz_llm_decode_steps refuses n > cap_steps.  Both
+ *   NULL: off, nothing is added to the step.  Tensor-parallel engines: VZ_ERR_UNSUPPORTED. */
+int vz_op_beam_logprob_rows(const float* d_logits, int rows, int cols, float* d_lp, vz_stream stream);
+int vz_op_beam_select_rows(const float* d_rows, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                           const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
+                           vz_stream stream);
+int vz_op_hist_beam_reorder(int* d_hist_len, int* d_hist, int hist_stride, int nb, int groups, const int* d_parent, vz_stream stream);
+int vz_llm_decode_beam_rows(vz_engine* e, float* d_scores, float* d_raw, int cap_steps);
 
 #ifdef __cplusplus
 }

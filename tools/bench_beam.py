@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Beam-search decode step against the greedy step at the same row count: 32-layer synthetic Zephyr-7B, one text prompt of
 S = 2048 ids (configs[2]-shaped), 128 new tokens, eos disabled (every step runs).  ms per step = (end - first step on the host) / 127.
-    python tools/bench_beam.py [--nb 1,2,4,8] [--layers 32] [--reps 2]"""
+    python tools/bench_beam.py [--nb 1,2,4,8] [--layers 32] [--reps 2] [--legs proc,rows] [--no-greedy]
+--legs adds beam legs beside the plain one: `proc` = logits processors armed (repetition_penalty 1.2 +
+no_repeat_ngram_size 3: log-prob rows, the processor kernel, the select on rows, the history reorder), `rows` = the processed rows
+recorded (output_scores: log-prob rows, one copy of [nb, V] per step into the ring, the select on rows; the host drains the ring at
+every sync, which is part of the figure)."""
 import argparse
 import json
 import os
@@ -22,6 +26,8 @@ ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--S", type=int, default=2048)
 ap.add_argument("--new", type=int, default=128)
 ap.add_argument("--out", default="")
+ap.add_argument("--legs", default="")
+ap.add_argument("--no-greedy", action="store_true")
 a = ap.parse_args()
 
 from vis_zephyr.model import VisZephyrConfig, VisZephyrForCausalLM  # noqa: E402
@@ -46,14 +52,23 @@ def per_step(**kw):
     return best * 1e3, out
 
 
+LEGS = {"proc": dict(repetition_penalty=1.2, no_repeat_ngram_size=3, beam_extended=True),
+        "rows": dict(return_dict_in_generate=True, output_scores=True, beam_extended=True)}
 rows = []
 for nb in NBS:
-    greedy, _ = per_step(input_ids=ids.expand(nb, -1).contiguous(), do_sample=False)
-    r = dict(nb=nb, greedy_ms_per_step=round(greedy, 4))
+    r = dict(nb=nb)
+    if not a.no_greedy:
+        greedy, _ = per_step(input_ids=ids.expand(nb, -1).contiguous(), do_sample=False)
+        r.update(greedy_ms_per_step=round(greedy, 4))
     if nb > 1:
         beam, out = per_step(input_ids=ids, num_beams=nb)
         assert out.shape == (1, a.new)
-        r.update(beam_ms_per_step=round(beam, 4), beam_over_greedy=round(beam / greedy, 4))
+        r.update(beam_ms_per_step=round(beam, 4))
+        if not a.no_greedy:
+            r.update(beam_over_greedy=round(beam / greedy, 4))
+        for leg in [v for v in a.legs.split(",") if v]:
+            ms, _ = per_step(input_ids=ids, num_beams=nb, **LEGS[leg])
+            r.update({f"beam_{leg}_ms_per_step": round(ms, 4), f"beam_{leg}_added_us": round((ms - beam) * 1e3, 1)})
     rows.append(r)
     print(json.dumps(r), flush=True)
 if a.out:

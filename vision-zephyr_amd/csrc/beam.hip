@@ -46,10 +46,15 @@ struct RowShared {
         for (int k = tid; k < cols; k += 1024) { const float x = lr[k]; BODY }                                        \
     }
 
-template <bool REG>
-__global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __restrict__ logits, int cols, int K,
+// MODE: BEAM_FUSED = select on logits (the parent's step); BEAM_ON_ROWS = select on rows that are log-probs already (s_i = lp_i +
+// score[row], no reduction); BEAM_LOGPROB = write the log-prob rows lp_i = (x_i - max) - log(sum) to lp_out (may be `logits`: every
+// element is read and written by the same thread, behind the reductions) and select nothing.
+enum { BEAM_FUSED = 0, BEAM_ON_ROWS = 1, BEAM_LOGPROB = 2 };
+
+template <bool REG, int MODE>
+__global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* logits, int cols, int K,
                                                              const float* __restrict__ scores_in, float* __restrict__ cand_s,
-                                                             int* __restrict__ cand_t) {
+                                                             int* __restrict__ cand_t, float* lp_out) {
     __shared__ RowShared sh;
     extern __shared__ float lx[];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -61,25 +66,33 @@ __global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __rest
     const float bs = scores_in ? scores_in[row] : 0.f;
 
     // ---- max and sum of exp, fixed reduction order ----
-    float m = -INFINITY;
-    BEAM_FOR_ROW({ m = fmaxf(m, x); })
-    m = wave_max(m);
-    if (lane == 0) sh.redf[wv] = m;
-    __syncthreads();
-    m = sh.redf[0];
-    for (int w = 1; w < 16; ++w) m = fmaxf(m, sh.redf[w]);
-    __syncthreads();
-    float z = 0.f;
-    BEAM_FOR_ROW({ z += expf(x - m); })
+    float m = 0.f, lse = 0.f;
+    if (MODE != BEAM_ON_ROWS) {
+        m = -INFINITY;
+        BEAM_FOR_ROW({ m = fmaxf(m, x); })
+        m = wave_max(m);
+        if (lane == 0) sh.redf[wv] = m;
+        __syncthreads();
+        m = sh.redf[0];
+        for (int w = 1; w < 16; ++w) m = fmaxf(m, sh.redf[w]);
+        __syncthreads();
+        float z = 0.f;
+        BEAM_FOR_ROW({ z += expf(x - m); })
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
-    if (lane == 0) sh.redf[wv] = z;
-    __syncthreads();
-    z = 0.f;
-    for (int w = 0; w < 16; ++w) z += sh.redf[w];
-    const float lse = logf(z);
-    __syncthreads();
-#define BEAM_S(x) (((x) - m) - lse + bs)
+        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+        if (lane == 0) sh.redf[wv] = z;
+        __syncthreads();
+        z = 0.f;
+        for (int w = 0; w < 16; ++w) z += sh.redf[w];
+        lse = logf(z);
+        __syncthreads();
+    }
+    if (MODE == BEAM_LOGPROB) {
+        float* out = lp_out + (size_t)row * cols;
+        BEAM_FOR_ROW({ out[k] = (x - m) - lse; })
+        return;
+    }
+#define BEAM_S(x) (MODE == BEAM_ON_ROWS ? (x) + bs : ((x) - m) - lse + bs)
 
     // ---- key of the K-th largest s: 4-pass radix select ----
     unsigned prefix = 0, pmask = 0, want = (unsigned)K;
@@ -195,6 +208,51 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
 
 __global__ void beam_advance_kernel(int* hidx) { hidx[0] += 1; }
 
+// The processors' id histories (logits_proc.hip: lens[row], ids[row][stride]) follow the beams: the history of every row whose parent
+// is another row becomes its parent's, length included.  One workgroup per group; like the KV reorder it stages the piece of every
+// row that is some changed row's parent in LDS before it writes the changed rows, HIST_CH ids at a time, so cycles and parents with
+// several children are safe; the lengths are read before anything is written and written last.
+constexpr int HIST_CH = 512;            // 16 rows x 512 ids x 4 B = 32 KiB of LDS
+
+__global__ __launch_bounds__(1024) void hist_beam_reorder_kernel(int* __restrict__ lens, int* __restrict__ ids, int stride, int nb,
+                                                                 const int* __restrict__ parent) {
+    __shared__ int stage[16 * HIST_CH];
+    __shared__ int par[16], slot_of[16], srcs[16], dsts[16], len0[16];
+    __shared__ int n_src, n_dst, n_max;
+    const int tid = threadIdx.x, r0 = blockIdx.x * nb;
+    if (tid == 0) {
+        int ns = 0, nd = 0, mx = 0;
+        for (int j = 0; j < nb; ++j) {
+            const int p = parent[r0 + j];
+            par[j] = (p >= 0 && p < nb) ? p : j; slot_of[j] = -1; len0[j] = min(max(lens[r0 + j], 0), stride);
+        }
+        for (int j = 0; j < nb; ++j)
+            if (par[j] != j) {
+                dsts[nd++] = j;
+                if (slot_of[par[j]] < 0) { slot_of[par[j]] = ns; srcs[ns++] = par[j]; mx = max(mx, len0[par[j]]); }
+            }
+        n_src = ns; n_dst = nd; n_max = mx;
+    }
+    __syncthreads();
+    const int ns = n_src, nd = n_dst, nm = n_max;
+    if (nd == 0) return;
+    for (int p0 = 0; p0 < nm; p0 += HIST_CH) {
+        const int np = min(HIST_CH, nm - p0);
+        for (int i = tid; i < ns * np; i += 1024) {
+            const int q = i / np, v = i % np;
+            stage[q * HIST_CH + v] = ids[(size_t)(r0 + srcs[q]) * stride + p0 + v];
+        }
+        __syncthreads();
+        for (int i = tid; i < nd * np; i += 1024) {
+            const int d = i / np, v = i % np;
+            const int j = dsts[d];
+            if (p0 + v < len0[par[j]]) ids[(size_t)(r0 + j) * stride + p0 + v] = stage[slot_of[par[j]] * HIST_CH + v];
+        }
+        __syncthreads();
+    }
+    if (tid < nd) lens[r0 + dsts[tid]] = len0[par[dsts[tid]]];
+}
+
 __global__ __launch_bounds__(256) void kv_beam_reorder_kernel(bf16_t* __restrict__ kv, size_t layer_elems, int n_layers, int max_batch,
                                                               int Hkv, int max_ctx, int D, int nb, int groups, const int* __restrict__ parent,
                                                               const int* __restrict__ base, int base_stride, const int* __restrict__ end,
@@ -257,7 +315,9 @@ static bool g_beam_lds_ok = false;
 static int init_beam_kernels() {
     static VzDeviceOnce once;
     if (!vz_device_first(once)) return VZ_OK;
-    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)beam_row_topk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)beam_row_topk_kernel<true, BEAM_FUSED>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)beam_row_topk_kernel<true, BEAM_ON_ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)beam_row_topk_kernel<true, BEAM_LOGPROB>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     g_beam_lds_ok = true;
     return VZ_OK;
 }
@@ -266,20 +326,46 @@ int vz_beam_k(int nb, int n_eos) { return (n_eos + 1 > 2 ? n_eos + 1 : 2) * nb; 
 
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
-                          int* next_parent, const RowEmit& emit, hipStream_t s) {
+                          int* next_parent, const RowEmit& emit, bool on_rows, hipStream_t s) {
     const int K = vz_beam_k(nb_out, eos.n);
     VZ_CHECK_ARG(logits && cand_s && cand_t && next_tok && rows >= 1 && cols >= 1 && nb_in >= 1 && nb_in <= 16 && nb_out >= 1 &&
                  nb_out <= 16 && rows % nb_in == 0 && eos.n >= 0 && eos.n <= 4 && K <= BEAM_KMAX && !emit.ring,
                  "beam_select: bad argument (rows %d, nb_in %d, nb_out %d, %d eos ids)", rows, nb_in, nb_out, eos.n);
     VZ_CHECK_ARG(cols >= K, "beam_select: %d candidates per row exceed the vocabulary of %d", K, cols);
     { int r = init_beam_kernels(); if (r) return r; }
-    if (cols <= 32768 && g_beam_lds_ok)
-        hipLaunchKernelGGL(beam_row_topk_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, K, scores_in, cand_s, cand_t);
-    else
-        hipLaunchKernelGGL(beam_row_topk_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, K, scores_in, cand_s, cand_t);
+    const bool reg = cols <= 32768 && g_beam_lds_ok;
+    const size_t lds = reg ? (size_t)cols * sizeof(float) : 0;
+    float* const none = nullptr;
+    if (on_rows) {          // the rows are log-probs already (vz_launch_beam_logprob_rows, then maybe the processors)
+        if (reg) hipLaunchKernelGGL((beam_row_topk_kernel<true, BEAM_ON_ROWS>), dim3(rows), dim3(1024), lds, s, logits, cols, K, scores_in, cand_s, cand_t, none);
+        else hipLaunchKernelGGL((beam_row_topk_kernel<false, BEAM_ON_ROWS>), dim3(rows), dim3(1024), lds, s, logits, cols, K, scores_in, cand_s, cand_t, none);
+    } else {
+        if (reg) hipLaunchKernelGGL((beam_row_topk_kernel<true, BEAM_FUSED>), dim3(rows), dim3(1024), lds, s, logits, cols, K, scores_in, cand_s, cand_t, none);
+        else hipLaunchKernelGGL((beam_row_topk_kernel<false, BEAM_FUSED>), dim3(rows), dim3(1024), lds, s, logits, cols, K, scores_in, cand_s, cand_t, none);
+    }
     VZ_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_merge_kernel, dim3(rows / nb_in), dim3(256), 0, s, cand_s, cand_t, cols, nb_in, nb_out, K, eos, rows / nb_in,
                        hist, hidx, hist_cap, next_tok, next_score, next_parent, emit);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+// lp[row][i] = (x_i - max) - log(sum_j exp(x_j - max)) with the reductions and the association of the fused select; lp may be `logits`
+int vz_launch_beam_logprob_rows(const float* logits, int rows, int cols, float* lp, hipStream_t s) {
+    VZ_CHECK_ARG(logits && lp && rows >= 1 && cols >= 1, "beam_logprob_rows: bad argument (rows %d, cols %d)", rows, cols);
+    { int r = init_beam_kernels(); if (r) return r; }
+    float* const nof = nullptr; int* const noi = nullptr;
+    if (cols <= 32768 && g_beam_lds_ok)
+        hipLaunchKernelGGL((beam_row_topk_kernel<true, BEAM_LOGPROB>), dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, 0, nof, nof, noi, lp);
+    else
+        hipLaunchKernelGGL((beam_row_topk_kernel<false, BEAM_LOGPROB>), dim3(rows), dim3(1024), 0, s, logits, cols, 0, nof, nof, noi, lp);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+int vz_launch_hist_beam_reorder(int* lens, int* ids, int stride, int nb, int groups, const int* parent, hipStream_t s) {
+    VZ_CHECK_ARG(lens && ids && parent && stride >= 1 && nb >= 1 && nb <= 16 && groups >= 1, "hist_beam_reorder: bad argument (nb %d, groups %d)", nb, groups);
+    hipLaunchKernelGGL(hist_beam_reorder_kernel, dim3(groups), dim3(1024), 0, s, lens, ids, stride, nb, parent);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -317,7 +317,7 @@ extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, v
 static TailKind tail_kind(const vz_engine* e) {
     return e->spec.on ? TAIL_SPEC : e->beam.on ? TAIL_BEAM : e->rows.on ? TAIL_ROWS : e->samp.on ? TAIL_SAMPLE : TAIL_GREEDY;
 }
-static bool tail_takes_proc(TailKind t) { return t == TAIL_GREEDY || t == TAIL_SAMPLE || t == TAIL_ROWS; }      // the logits processors may sit in front of it
+static bool tail_takes_proc(TailKind t) { return t != TAIL_SPEC; }      // the logits processors may sit in front of it
 
 // One linear C = epi(A . W^T + W.b) of the engine: the route follows the row count, the caller (decode = the rows are the independent
 // sequences of a decode step) and what finalize attached to W - vz_plan_linear picks the copy the kernel reads.
@@ -1257,10 +1257,17 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         // per row: the token into d_out_ids (and the ring), position / slot / length one further
         const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
         if (e->score.what & VZ_SCORE_RAW) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, e->score.raw, e->score.d_slot, e->score.cap, s));
+        // the beam tail with processors or with its processed rows recorded: the logits become log-prob rows in place first, as HF
+        // hands log_softmax rows to the processors there; otherwise the fused select takes the logits as they are
+        const BeamRowsArgs& br = e->beam.rows;
+        const bool beam_lp = tail == TAIL_BEAM && (e->proc.on || br.scores);
+        if (tail == TAIL_BEAM && br.raw) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, br.raw, beam_view(e->beam.d).hidx, br.cap, s));
+        if (beam_lp) RC(vz_launch_beam_logprob_rows(e->d_logits, B, c.vocab, e->d_logits, s));
         if (e->proc.on && tail_takes_proc(tail)) {
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
             RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, e->proc.a.n_seq ? e->proc.d_seq : nullptr, s));
         }
+        if (beam_lp && br.scores) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, br.scores, beam_view(e->beam.d).hidx, br.cap, s));
         switch (tail) {
         case TAIL_SPEC: {
             // spec.hip: per-row argmax, then acceptance + state advance (its own, multi-row rule) + the next step's draft in one small launch
@@ -1270,13 +1277,15 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             break;
         }
         case TAIL_BEAM: {
-            // beam.hip: select, then the KV of rows whose parent is another row follows the parent, then the history index
+            // beam.hip: select, then the KV of rows whose parent is another row follows the parent (and, with processors, the row's id
+            // history does: the processor kernel appends the row's own token to it at the next step), then the history index
             const BeamArgs& a = e->beam.a;
             const BeamView v = beam_view(e->beam.d);
             RC(vz_launch_beam_select(e->d_logits, a.nb * a.groups, c.vocab, a.nb, a.nb, a.eos, v.score, v.cand_s, v.cand_t, a.hist, v.hidx, a.hist_cap,
-                                     st.cur, v.score, v.parent, emit, s));
+                                     st.cur, v.score, v.parent, emit, beam_lp, s));
             RC(vz_launch_kv_beam_reorder(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, a.nb, a.groups,
                                          v.parent, v.base, a.nb, st.slot, a.nb, s));
+            if (e->proc.on) RC(vz_launch_hist_beam_reorder(e->proc.d, proc_hist(e), c.max_ctx, a.nb, a.groups, v.parent, s));
             RC(vz_launch_beam_advance(v.hidx, s));
             break;
         }
@@ -1585,7 +1594,8 @@ extern "C" int vz_op_sample_warp(const float* d_logits, int rows, int cols, floa
 // vz_llm_decode_logits_proc(enable=1) every decode step whose tail is the argmax or the sampler first runs repetition penalty (1 = off),
 // no-repeat-n-gram (0 = off), min-new-tokens (the eos ids at -inf while fewer ids were generated) and suppress-tokens on its logits, over
 // the ids generated so far: each row's history lives on the device, restarts empty here (stream-ordered) and grows by the row's input
-// token at every step.  The mode is orthogonal to the tail; vz_llm_decode_steps refuses it together with the beam or the speculative tail.
+// token at every step.  The mode is orthogonal to the tail; vz_llm_decode_steps refuses it together with the speculative tail.  With the
+// beam tail the kernel runs on the log-prob rows, as HF's processors do there.
 extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
                                          const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream) {
     return vz_llm_decode_logits_proc_seq(e, enable, repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, nullptr, 0, stream);
@@ -1697,9 +1707,9 @@ extern "C" int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, 
 // The beam tail's selection on given fp32 logits [rows, cols] (rows = groups * nb_in beam rows, running scores d_scores_in [rows] or
 // NULL = 0): the group's top K candidates -> d_records [groups][K][3] ({score bits, token, parent beam}), the first nb_out non-eos
 // ones -> d_next_tok / d_next_score / d_next_parent [groups * nb_out].  The first step of a beam search: nb_in = 1 on the prefill logits.
-extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
-                                 const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
-                                 vz_stream stream) {
+static int beam_select_op(const float* d_logits, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                          const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
+                          bool on_rows, vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_records && d_next_tok && rows >= 1 && cols >= 1 && nb_in >= 1 && nb_in <= 16 && nb_out >= 1 && nb_out <= 16 &&
                  rows % nb_in == 0, "beam_select: bad argument");
@@ -1711,7 +1721,43 @@ extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int 
     VZ_CHECK_ARG(p && have >= (size_t)rows * K * 2 * sizeof(int), "beam_select: first use of a stream inside a capture (call it once before capturing)");
     float* cand_s = (float*)p; int* cand_t = (int*)p + (size_t)rows * K;
     return vz_launch_beam_select(d_logits, rows, cols, nb_in, nb_out, eos, d_scores_in, cand_s, cand_t, d_records, nullptr, 1, d_next_tok,
-                                 d_next_score, d_next_parent, {}, s);
+                                 d_next_score, d_next_parent, {}, on_rows, s);
+}
+extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                                 const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
+                                 vz_stream stream) {
+    return beam_select_op(d_logits, rows, cols, nb_in, nb_out, h_eos, n_eos, d_scores_in, d_records, d_next_tok, d_next_score, d_next_parent, false, stream);
+}
+// ... on rows that hold scores already (vz_op_beam_logprob_rows, then maybe vz_op_logits_process_seq): s_i = row_i + d_scores_in[row],
+// no normalisation.  On log-prob rows as they are it gives the records and next beams of vz_op_beam_select on the logits, bit for bit.
+extern "C" int vz_op_beam_select_rows(const float* d_rows, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
+                                      const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
+                                      vz_stream stream) {
+    return beam_select_op(d_rows, rows, cols, nb_in, nb_out, h_eos, n_eos, d_scores_in, d_records, d_next_tok, d_next_score, d_next_parent, true, stream);
+}
+
+// HF's log_softmax rows of fp32 logits [rows, cols] with the beam select's own reductions: d_lp[row][i] = (x_i - max) - log(sum_j
+// exp(x_j - max)); d_lp may be d_logits.
+extern "C" int vz_op_beam_logprob_rows(const float* d_logits, int rows, int cols, float* d_lp, vz_stream stream) {
+    return vz_launch_beam_logprob_rows(d_logits, rows, cols, d_lp, (hipStream_t)stream);
+}
+
+// The beam tail's history reorder on its own: d_hist_len [groups * nb] and d_hist [groups * nb][hist_stride] (the processors' id
+// histories) - row g * nb + j takes the history and the length of row g * nb + d_parent[g * nb + j], in place.
+extern "C" int vz_op_hist_beam_reorder(int* d_hist_len, int* d_hist, int hist_stride, int nb, int groups, const int* d_parent, vz_stream stream) {
+    return vz_launch_hist_beam_reorder(d_hist_len, d_hist, hist_stride, nb, groups, d_parent, (hipStream_t)stream);
+}
+
+// The beam tail's row recorder: after vz_llm_decode_beam_rows every beam step copies, inside the step, its processed log-prob rows (HF's
+// scores[t]) into d_scores and / or its raw logits rows into d_raw, rings [cap_steps][groups * nb][vocab] fp32 written at the history
+// index of vz_llm_decode_beam mod cap_steps.  Both NULL: off, and nothing is added to the step.
+extern "C" int vz_llm_decode_beam_rows(vz_engine* e, float* d_scores, float* d_raw, int cap_steps) {
+    NEED_READY();
+    if (!d_scores && !d_raw) { e->beam.rows = BeamRowsArgs{}; return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_beam_rows: beam search on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(cap_steps >= 1, "decode_beam_rows: cap_steps = %d, at least one step expected", cap_steps);
+    e->beam.rows = BeamRowsArgs{d_scores, d_raw, cap_steps, 0};
+    return VZ_OK;
 }
 
 // The beam tail's KV reorder on its own: for every group g of `nb` rows (row g * nb + j), cache positions [h_base[g], h_end[g]) of row j
@@ -1856,7 +1902,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     k.out = d_out_ids; k.arena = e->arena; k.ring = e->ring.p; k.ring_n = e->ring.n;
     switch (k.kind) {
     case TAIL_SPEC: k.spec = e->spec.a; break;
-    case TAIL_BEAM: k.beam = e->beam.a; break;
+    case TAIL_BEAM: k.beam = e->beam.a; k.beam_rows = e->beam.rows; break;
     case TAIL_SAMPLE: k.samp = e->samp.a; break;
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
@@ -1881,7 +1927,9 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
                  "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
     VZ_CHECK_ARG(!e->proc.on || tail_takes_proc(tail), "decode_steps: the logits processors (vz_llm_decode_logits_proc) run in "
-                 "front of the argmax or the sampler only, not with the beam or the speculative tail");
+                 "front of the argmax, the sampler or the beam tail, not with the speculative tail");
+    VZ_CHECK_ARG(tail != TAIL_BEAM || !(e->beam.rows.scores || e->beam.rows.raw) || n <= e->beam.rows.cap, "decode_steps: %d steps, the beam row "
+                 "recorder's rings hold cap_steps = %d", n, e->beam.rows.cap);
     VZ_CHECK_ARG(!e->rows.on || (!e->beam.on && !e->spec.on && e->tp == 1), "decode_steps: the per-row tail (vz_llm_decode_sampling_rows) does not run "
                  "together with the beam or the speculative tail, nor on a tensor-parallel engine");
     VZ_CHECK_ARG(!e->score.what || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the step recorder (vz_llm_decode_scores) runs behind the "

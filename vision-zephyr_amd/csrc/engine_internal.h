@@ -54,6 +54,9 @@ static DecodeState decode_state(int* base, int mb) {
 enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC, TAIL_ROWS };      // TAIL_ROWS takes nothing by value: its table is device memory
 struct SampleArgs { int top_k; float temp, top_p; SampleWarp warp; };
 struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
+// the beam tail's row recorder (vz_llm_decode_beam_rows): rings of `cap` steps x (groups * nb) rows x vocab fp32, written at the beam
+// tail's history index mod cap - scores = the processed log-prob rows (HF's scores[t]), raw = the logits rows; null = not recorded
+struct BeamRowsArgs { float *scores, *raw; int cap, pad; };
 struct SpecArgs {
     int *hist, *out, *ctl, *stats; const int* stream;
     int ngram, source, budget, hist_cap, stats_cap, stream_len;
@@ -69,8 +72,10 @@ struct DecodeGraphKey {
     int* proc_hist; const int* proc_seq; ProcArgs proc; int proc_on;      // the logits processors in front of the tail, their history buffer and sequence table (zero when off)
     float *sc_rec, *sc_warped, *sc_raw; unsigned sc_what; int sc_cap;      // the step recorder behind the tail and its rings (zero when off)
     int* stop_state; StopArgs stop;      // the stop matcher behind the tail: its state, tables and dims (zero when off)
+    BeamRowsArgs beam_rows;              // the beam tail's row recorder: its rings (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) &&
+              sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
 
 // The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
@@ -121,7 +126,8 @@ struct vz_engine {
     // per-row table (vz_llm_decode_sampling_rows): tab = the max_batch entries the next vz_llm_decode_begin uploads (all greedy until set)
     struct { int on = 0; std::vector<RowSample> tab; } rows;
     // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)
-    struct { int on = 0; BeamArgs a{}; int* d = nullptr; } beam;
+    // rows = the row recorder of the beam tail (zero: off)
+    struct { int on = 0; BeamArgs a{}; int* d = nullptr; BeamRowsArgs rows{}; } beam;
     // prompt-lookup speculation (vz_llm_decode_spec; spec.hip): R = D + 1 rows of one sequence in cache row 0; base_len / base_pos = keys visible
     // to row 0 and its position when the mode was armed
     struct { int on = 0, R = 0, base_len = 0, base_pos = 0; SpecArgs a{}; } spec;

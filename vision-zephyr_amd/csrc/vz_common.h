@@ -402,7 +402,9 @@ int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int h
                              const ProcArgs& a, const int* seqtab, hipStream_t s);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
-                          int* next_parent, const RowEmit& emit, hipStream_t s);
+                          int* next_parent, const RowEmit& emit, bool on_rows, hipStream_t s);      // on_rows: `logits` are log-prob rows already
+int vz_launch_beam_logprob_rows(const float* logits, int rows, int cols, float* lp, hipStream_t s);
+int vz_launch_hist_beam_reorder(int* lens, int* ids, int stride, int nb, int groups, const int* parent, hipStream_t s);
 int vz_launch_beam_advance(int* hidx, hipStream_t s);
 int vz_launch_kv_beam_reorder(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, int nb, int groups,
                               const int* parent, const int* base, int base_stride, const int* end, int end_stride, hipStream_t s);

@@ -359,7 +359,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
                               output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True,
                               min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
-                              eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, **unused):
+                              eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, beam_extended: bool = False,
+                              **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -371,8 +372,20 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         `prompt_lookup_num_tokens` takes the plain greedy path (the ids are the same by construction).  With a streamer or stopping
         criteria the records wait in a device ring of `max_new_tokens` slots that is allocated up front: 16 bytes per slot, and with
         `output_scores` / `output_logits` another V fp32 per slot and output (260 MB each at V = 32000, max_new_tokens = 2048), even if
-        a criterion stops the call after a few tokens - HF's [T, rows, V] outputs cost that; `output_logprobs` does not.  With `num_beams > 1` the three
-        raise NotImplementedError; `return_dict_in_generate` alone gives `sequences` and `sequences_scores`.
+        a criterion stops the call after a few tokens - HF's [T, rows, V] outputs cost that; `output_logprobs` does not.
+
+        Beam search (`num_beams` 2..16; `_generate_beam`): `return_dict_in_generate` gives HF's `GenerateBeamDecoderOnlyOutput` with
+        `sequences`, `sequences_scores` and `beam_indices`.  The rest of HF's surface there is opt-in, `beam_extended=True`: calls written
+        against the earlier versions rely on `NotImplementedError` for the logits-processor and `output_*` keywords with beams, and
+        without the flag they still get it.  With it: `output_scores` / `output_logits` give `scores` / `logits`, tuples of
+        [Bsz * num_beams, V] fp32 per step (rows prompt-major, beam-minor) - the log-softmax rows after the logits processors / the
+        raw logits, as `_beam_search` fills them; `compute_transition_scores(sequences, scores, beam_indices)` gathers through them.
+        The logits-processor keywords then work with beams: they act on every beam's log-softmax row over that beam's own ids, as in HF.
+        Two deviations, both documented in INTEGRATION.md: at step 0 HF runs `num_beams` identical rows per prompt, this engine
+        prefills one and replicates its row; and when `Bsz * num_beams` exceeds the cache rows the prompts run in chunks that may
+        take different numbers of steps - `len(scores)` is the largest step count any prompt's search took, and the rows of a
+        prompt behind the step at which its own search ended are zeros.  `output_logprobs`, sampling, `stopping_criteria` and
+        `stop_strings` with beams raise NotImplementedError.
 
         Stops (vz_hip/stop.py; csrc/stop.hip: stop_match_kernel): HF's `stop_strings=` (+ `tokenizer=`; default
         `generation_config.stop_strings`), and `stopping_criteria` made only of HF's `StopStringCriteria` and this package's
@@ -394,7 +407,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         # what the device takes of the call's stop conditions (all or nothing); every check below sees the host's remainder only
         stop, stopping_criteria = ST.parse(stop_strings, tokenizer, stopping_criteria, self.generation_config,
                                            device_stop and streamer is None and num_beams == 1 and self.engine.tp_size == 1)
-        what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams)
+        what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams, bool(beam_extended))
         sink = SC.Sink(what) if what else None
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length, S, pad_token_id)
@@ -404,14 +417,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         proc = logits_proc.parse(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, sorted(eos),
                                  getattr(gcf, "sequence_bias", None) if sequence_bias is None else sequence_bias,
                                  getattr(gcf, "bad_words_ids", None) if bad_words_ids is None else bad_words_ids, self.config.vocab_size)
-        if proc is not None and num_beams != 1:
-            raise NotImplementedError("logits processors with num_beams > 1 are not built (HF applies them to log-softmax scores there)")
+        if proc is not None and num_beams != 1 and not beam_extended:
+            raise NotImplementedError("logits processors with num_beams > 1 need `beam_extended=True` (HF applies them to every beam's "
+                                      "log-softmax scores there, and so does the beam step then)")
         if proc is not None and self.engine.tp_size > 1:
             raise NotImplementedError("logits processors on a tensor-parallel engine are not built")
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing,
-                                       num_return_sequences=num_return_sequences, return_dict_in_generate=return_dict_in_generate, **unused)
+                                       num_return_sequences=num_return_sequences, return_dict_in_generate=return_dict_in_generate,
+                                       proc=proc, what=what, **unused)
         max_new_tokens, pad_token_id = d.max_new, d.fill
         greedy = (not do_sample) or temperature is None or temperature <= 0
         nrs = sample_rows.check_return_sequences(num_return_sequences, greedy, self.engine.max_batch, streamer, stopping_criteria)
@@ -471,10 +486,12 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                       token_logprobs_warped=f["token_logprobs_warped"])
 
     def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits: bool = False):
-        """HF's `GenerationMixin.compute_transition_scores` for the outputs of `generate(return_dict_in_generate=True, output_scores=True)`
-        (no beams: `beam_indices` raises NotImplementedError)."""
+        """HF's `GenerationMixin.compute_transition_scores` for the outputs of `generate(return_dict_in_generate=True, output_scores=True)`;
+        with beam search pass the output's `beam_indices`."""
         from vz_hip import scores as SC
-        return SC.transition_scores(sequences, scores, beam_indices, normalize_logits)
+        if beam_indices is None:
+            return SC.transition_scores(sequences, scores, None, normalize_logits)
+        return SC.beam_transition_scores(sequences, scores, beam_indices, normalize_logits, self.config.vocab_size)
 
     def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None) -> List[int]:
         """One greedy sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
@@ -553,14 +570,19 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     def _generate_beam(self, inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, length_penalty: float = 1.0,
                        early_stopping=False, num_return_sequences: int = 1, return_dict_in_generate: bool = False,
-                       timing: Optional[dict] = None, **unused):
+                       timing: Optional[dict] = None, proc=None, what: int = 0, **unused):
         """Beam search over the prompts of a batch: `Bsz * num_return_sequences` rows of new tokens, HF's `sequences` of a
         decoder-only model generating from inputs_embeds (shorter hypotheses filled as HF fills them, vz_hip.beam.fill_value).
         Each prompt is prefilled once; its first step is chosen on the prefill logits (vz_op_beam_select), its prompt KV copied
         into its num_beams cache rows, and then the decode steps run with the beam tail (selection + KV reorder on the device),
         `sync_every` steps per host sync, whose history records the host replays (vz_hip.beam.BeamReplay) to keep HF's finished
-        hypotheses and to stop where HF stops."""
+        hypotheses and to stop where HF stops.
+        proc (vz_hip.logits_proc config): HF's logits processors on every beam's log-prob row over that beam's own ids, on the
+        device.  what (vz_hip.scores flags): the steps' processed rows / raw logits rows are recorded on the
+        device and returned as HF's `scores` / `logits`; step 0 replicates each prompt's one prefill row over its beams, and a
+        prompt's rows behind the step at which its own search ended are zeros (chunked batches run different numbers of steps)."""
         from vz_hip import beam as BM
+        from vz_hip import scores as SC
         eng = self.engine
         nb = int(num_beams)
         if do_sample:
@@ -591,25 +613,54 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if max(seqlens) + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         G = max(1, min(Bsz, min(eng.max_batch, 64) // nb))          # prompts per chunk: G * nb cache rows
-        hyps = []
+        replays, rows = [], []
         for b0 in range(0, Bsz, G):
-            hyps += self._beam_chunk(inputs_embeds[b0:b0 + G], seqlens[b0:b0 + G],
+            r, rw = self._beam_chunk(inputs_embeds[b0:b0 + G], seqlens[b0:b0 + G],
                                      None if position_ids is None else position_ids[b0:b0 + G], nb, max_new, eos,
-                                     float(length_penalty), early_stopping, nrs, max(1, int(sync_every)), timing)
+                                     float(length_penalty), early_stopping, max(1, int(sync_every)), timing, proc, what)
+            replays += r
+            rows.append(rw)
+        hyps = [r.best(nrs) for r in replays]
         seqs = DL.pad_parts([torch.tensor([t], dtype=torch.long) for h in hyps for t, _ in h], fill, "cpu").to(self.device)
         if return_dict_in_generate:
-            from vz_hip import scores as SC
             scores = torch.tensor([sc for h in hyps for _, sc in h], dtype=torch.float32, device=self.device)
-            return SC.output_classes()[1](sequences=seqs, sequences_scores=scores)      # HF's GenerateBeamDecoderOnlyOutput
+            idx = BM.flat_beam_indices([r.best_indices(nrs) for r in replays], nb).to(self.device)
+            T = max(r.cur_len for r in replays)          # the steps of the longest search: what a chunk's device ran past it is dropped
+
+            def per_step(key):          # the chunks' rows [steps_i, G_i * nb, V] side by side, cut or zero-padded to T steps: T x [Bsz * nb, V]
+                if rows[0][key] is None:
+                    return None
+                parts = [rw[key][:T] for rw in rows]
+                parts = [x if x.shape[0] == T else torch.cat([x, x.new_zeros((T - x.shape[0],) + tuple(x.shape[1:]))], 0) for x in parts]
+                full = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+                return tuple(full[t] for t in range(T))
+            return SC.output_classes()[1](sequences=seqs, sequences_scores=scores, scores=per_step("scores"), logits=per_step("logits"),
+                                          beam_indices=idx)      # HF's GenerateBeamDecoderOnlyOutput
         return seqs
 
-    def _beam_chunk(self, embeds, seqlens, position_ids, nb, max_new, eos, length_penalty, early_stopping, nrs, sync_every, timing=None):
+    def _beam_chunk(self, embeds, seqlens, position_ids, nb, max_new, eos, length_penalty, early_stopping, sync_every, timing=None,
+                    proc=None, what: int = 0):
+        """one chunk of G prompts x nb cache rows: (the prompts' finished replays, {"scores", "logits"}: the chunk's recorded rows fp32
+        [steps, G * nb, V] with zeros behind each prompt's own last step, or None when not asked for)"""
         from vz_hip import beam as BM
         from vz_hip import binding as B
+        from vz_hip import scores as SC
         eng = self.engine
         G = embeds.shape[0]
+        want_sc, want_raw = bool(what & SC.SCORE_WARPED), bool(what & SC.SCORE_RAW)
         last = DL.fan_prefill(eng, embeds, seqlens, position_ids, nb)          # one prefill per prompt into its first beam row
-        rec, tok, sc, _ = B.beam_select(last, None, 1, nb, eos)
+        fan = lambda x: x.repeat_interleave(nb, dim=0).unsqueeze(0)            # noqa: E731  (step 0: a prompt's one row, once per beam)
+        sc_rows, raw_rows = [], [fan(last)] if want_raw else []
+        if proc is not None or want_sc:
+            # HF: log_softmax, then the processors (no ids yet), then the choice among the first beam's continuations
+            lp = B.beam_logprob_rows(last)
+            if proc is not None:
+                B.logits_process(lp, proc)
+            if want_sc:
+                sc_rows.append(fan(lp))
+            rec, tok, sc, _ = B.beam_select(lp, None, 1, nb, eos, on_rows=True)
+        else:
+            rec, tok, sc, _ = B.beam_select(last, None, 1, nb, eos)
         replays = [BM.BeamReplay(nb, eos, max_new, length_penalty, early_stopping) for _ in range(G)]
         s0, t0, p0 = BM.decode_records(rec)
         if timing is not None:
@@ -619,7 +670,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if not all(r.done for r in replays):
             next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, nb)          # the prompt KV of each prompt into its beam rows
             hist = torch.empty(max(1, max_new - 1), G, BM.beam_k(nb, len(eos)), 3, dtype=torch.int32, device=self.device)
-            with DL.armed(eng, beam=(True, nb, G, eos, [int(v) for v in seqlens], sc, hist)) as begin:
+            rings = (max(1, min(sync_every, max_new - 1)), G * nb, want_sc, want_raw) if (want_sc or want_raw) else None
+            with DL.armed(eng, proc=proc, beam_rows=rings, beam=(True, nb, G, eos, [int(v) for v in seqlens], sc, hist)) as begin:
                 begin(tok, next_pos, ctx_len)
                 done_steps, remaining = 0, max_new - 1
                 while remaining > 0 and not all(r.done for r in replays):
@@ -628,11 +680,24 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     s, t, p = BM.decode_records(hist[done_steps:done_steps + n])      # the only host sync of the chunk
                     done_steps += n
                     remaining -= n
+                    if rings is not None:
+                        a, b = eng.beam_rows_steps(done_steps, n)
+                        if want_sc:
+                            sc_rows.append(a)
+                        if want_raw:
+                            raw_rows.append(b)
                     for i in range(n):
                         for g in range(G):
                             if not replays[g].done:
                                 replays[g].step(s[i, g], t[i, g], p[i, g])
-        return [r.best(nrs) for r in replays]
+        out = {"scores": None, "logits": None}
+        for key, parts in (("scores", sc_rows), ("logits", raw_rows)):
+            if parts:
+                x = torch.cat(parts, 0)                                        # [steps the device ran + 1, G * nb, V]
+                for g in range(G):
+                    x[replays[g].cur_len:, g * nb:(g + 1) * nb] = 0            # behind the prompt's own last step
+                out[key] = x
+        return replays, out
 
     # ---- continuous batching: the 23 K-item eval loop without waiting for a batch's longest answer ----
     @torch.no_grad()

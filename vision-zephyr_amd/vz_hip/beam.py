@@ -7,7 +7,12 @@ and stop at the step where HF stops (the device may have run past it; those step
 
 `select_reference` restates the device selection in torch (the tests' oracle); `BeamReplay` restates
 `_get_running_beams_for_next_iteration`, `_update_finished_beams`, `_check_early_stop_heuristic` and
-`_beam_search_has_unfinished_sequences` for one prompt with the same fp32 tensor arithmetic.
+`_beam_search_has_unfinished_sequences` for one prompt with the same fp32 tensor arithmetic.  It also keeps, per running beam and
+per finished hypothesis, the chain of parent beams its tokens were chosen from - HF's `beam_indices`, here as beam numbers inside the
+prompt (`best_indices`); `flat_beam_indices` turns them into HF's flattened rows `prompt * num_beams + beam`.
+
+With logits processors (csrc/logits_proc.hip) or recorded rows the selection runs on rows that are scores already - HF's
+`logits_processor(ids, log_softmax(logits))` - so `select_reference(..., on_rows=True)` adds the running scores and normalises nothing.
 
 Ties: torch.topk leaves the order of equal values unspecified.  Here, as on the device, equal scores go to the smaller flat index
 beam * V + token (candidates), and to the earlier entry (running beams, finished hypotheses: a stable sort).
@@ -24,13 +29,15 @@ def beam_k(num_beams: int, n_eos: int) -> int:
     return max(2, 1 + n_eos) * num_beams
 
 
-def select_reference(logits: torch.Tensor, scores: Optional[torch.Tensor], nb_in: int, nb_out: int, eos: Sequence[int] = ()):
+def select_reference(logits: torch.Tensor, scores: Optional[torch.Tensor], nb_in: int, nb_out: int, eos: Sequence[int] = (),
+                     on_rows: bool = False):
     """torch restatement of the device selection on fp32 logits [groups * nb_in, V] and running scores [groups * nb_in] (None = 0).
+    on_rows: the rows are scores already (processed log-prob rows) and are taken as they are.
     Returns (cand_scores fp32 [groups, K], cand_tokens int64 [groups, K], cand_parents int64 [groups, K],
     next_tokens, next_scores, next_parents [groups * nb_out])."""
     rows, V = logits.shape
     groups = rows // nb_in
-    lp = torch.log_softmax(logits.float(), dim=-1)
+    lp = logits.float() if on_rows else torch.log_softmax(logits.float(), dim=-1)
     if scores is not None:
         lp = lp + scores.to(lp.device, torch.float32)[:, None]
     flat = lp.reshape(groups, nb_in * V)
@@ -69,6 +76,10 @@ class BeamReplay:
         self.running_scores = torch.zeros(self.nb, dtype=torch.float32)
         self.running_scores[1:] = -1e9
         self.finished: List[List[int]] = [[] for _ in range(self.nb)]
+        # HF's running_beam_indices / beam_indices: the parent beam (inside the prompt) of every token of a running beam / a hypothesis,
+        # as a chain (rest, parent) from the last token back, None = empty - one cell per candidate and step, unrolled by `best_indices`
+        self.running_idx: list = [None] * self.nb
+        self.finished_idx: list = [None] * self.nb
         self.beam_scores = torch.full((self.nb,), -1e9, dtype=torch.float32)
         self.is_sent_finished = torch.zeros(self.nb, dtype=torch.bool)
         self.heuristic_unsatisfied = True
@@ -82,6 +93,7 @@ class BeamReplay:
         scores = scores.to(torch.float32)
         toks, pars = [int(t) for t in tokens], [int(p) for p in parents]
         topk_seqs = [self.running[p] + [t] for t, p in zip(toks, pars)]
+        topk_idx = [(self.running_idx[p], p) for p in pars]
         hits = torch.tensor([t in self.eos for t in toks], dtype=torch.bool)
         if self.cur_len + 1 >= self.max_length:                       # MaxLengthCriteria: every candidate stops
             hits[:] = True
@@ -89,6 +101,7 @@ class BeamReplay:
         run_lp = scores + hits.to(torch.float32) * -1.0e9
         nxt = _stable_topk(run_lp, nb)
         self.running = [topk_seqs[i] for i in nxt.tolist()]
+        self.running_idx = [topk_idx[i] for i in nxt.tolist()]
         self.running_scores = run_lp[nxt]
         # _update_finished_beams
         top_mask = torch.zeros(K, dtype=torch.bool)
@@ -101,9 +114,11 @@ class BeamReplay:
         lp = lp + (~did).to(torch.float32) * -1.0e9
         merged_scores = torch.cat([self.beam_scores, lp])
         merged_seqs = self.finished + topk_seqs
+        merged_idx = self.finished_idx + topk_idx
         merged_fin = torch.cat([self.is_sent_finished, did])
         sel = _stable_topk(merged_scores, nb)
         self.finished = [merged_seqs[i] for i in sel.tolist()]
+        self.finished_idx = [merged_idx[i] for i in sel.tolist()]
         self.beam_scores = merged_scores[sel]
         self.is_sent_finished = merged_fin[sel]
         self.cur_len += 1
@@ -124,6 +139,28 @@ class BeamReplay:
     def best(self, n: int) -> List[Tuple[List[int], float]]:
         """the n best hypotheses (tokens, sequences_score), best first."""
         return [(list(self.finished[i]), float(self.beam_scores[i])) for i in range(n)]
+
+    def best_indices(self, n: int) -> List[List[int]]:
+        """the parent beam of every token of the n best hypotheses (beam numbers inside the prompt), as long as the hypothesis"""
+        out = []
+        for i in range(n):
+            chain, cell = [], self.finished_idx[i]
+            while cell is not None:
+                cell, p = cell
+                chain.append(p)
+            out.append(chain[::-1])
+        return out
+
+
+def flat_beam_indices(chains: Sequence[Sequence[Sequence[int]]], num_beams: int) -> torch.Tensor:
+    """HF's `beam_indices` [prompts * n, longest hypothesis] int32 from every prompt's `BeamReplay.best_indices(n)`: the flattened row
+    prompt * num_beams + beam whose `scores[t]` row produced token t, -1 behind a hypothesis' end."""
+    rows = [[b * num_beams + p for p in chain] for b, per in enumerate(chains) for chain in per]
+    width = max((len(r) for r in rows), default=0)
+    out = torch.full((len(rows), width), -1, dtype=torch.int32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = torch.tensor(r, dtype=torch.int32)
+    return out
 
 
 def fill_value(pad_token_id, eos: Sequence[int]) -> int:

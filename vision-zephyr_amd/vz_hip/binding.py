@@ -156,6 +156,10 @@ SYMBOLS = {
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "vz_op_beam_logprob_rows": (_I, [_P, _I, _I, _P, _P]),
+    "vz_op_beam_select_rows": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vz_op_hist_beam_reorder": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "vz_llm_decode_beam_rows": (_I, [_P, _P, _P, _I]),
     "vz_llm_kv_copy_out": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "vz_llm_decode_spec": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P]),
     "vz_op_spec_draft": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
@@ -782,10 +786,33 @@ def beam_k(nb: int, n_eos: int) -> int:
     return max(2, 1 + n_eos) * nb
 
 
-def beam_select(logits, scores, nb_in: int, nb_out: int, eos=()):
+def beam_logprob_rows(logits, out=None):
+    """HF's log_softmax rows of fp32 logits [rows, V] with the beam select's own reductions (beam.hip): fp32 [rows, V]; out may be
+    `logits` (in place)."""
+    _need_cuda(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    out = torch.empty_like(logits) if out is None else out
+    assert out.dtype == torch.float32 and out.shape == logits.shape and out.is_contiguous()
+    check(lib().vz_op_beam_logprob_rows(ptr(logits), logits.shape[0], logits.shape[1], ptr(out), stream_ptr(logits.device)))
+    return out
+
+
+def hist_beam_reorder(hist_len, hist, nb: int, groups: int, parent):
+    """the processors' id histories follow the beams (beam.hip), in place: hist int32 [rows, stride] of hist_len int32 [rows] ids; row
+    g * nb + j of the first groups * nb rows takes the history and length of row g * nb + parent[g * nb + j]."""
+    _need_cuda(hist_len, hist, parent)
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.is_contiguous() and hist_len.dtype == torch.int32 and hist_len.is_contiguous()
+    assert hist.shape[0] >= nb * groups and hist_len.numel() >= nb * groups
+    parent = parent.to(torch.int32).contiguous()
+    assert parent.numel() >= nb * groups
+    check(lib().vz_op_hist_beam_reorder(ptr(hist_len), ptr(hist), hist.shape[1], int(nb), int(groups), ptr(parent), stream_ptr(hist.device)))
+
+
+def beam_select(logits, scores, nb_in: int, nb_out: int, eos=(), on_rows: bool = False):
     """the beam tail's selection on fp32 logits [groups * nb_in, V] with running scores [groups * nb_in] (None = 0) on the device
     (beam.hip).  Returns (records int32 [groups, K, 3] = {fp32 score bits, token, parent beam}, next tokens int32, next scores fp32,
-    next parents int32 [groups * nb_out])."""
+    next parents int32 [groups * nb_out]).  on_rows: `logits` are score rows already (`beam_logprob_rows`, maybe processed): they are
+    taken as they are, no normalisation."""
     _need_cuda(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and logits.shape[0] % nb_in == 0
     eos = [int(t) for t in eos]
@@ -799,7 +826,8 @@ def beam_select(logits, scores, nb_in: int, nb_out: int, eos=()):
     sc = torch.empty(groups * nb_out, dtype=torch.float32, device=dev)
     par = torch.empty(groups * nb_out, dtype=torch.int32, device=dev)
     arr = (C.c_int * max(1, len(eos)))(*eos)
-    check(lib().vz_op_beam_select(ptr(logits), logits.shape[0], logits.shape[1], int(nb_in), int(nb_out), arr, len(eos), ptr(scores),
+    op = lib().vz_op_beam_select_rows if on_rows else lib().vz_op_beam_select
+    check(op(ptr(logits), logits.shape[0], logits.shape[1], int(nb_in), int(nb_out), arr, len(eos), ptr(scores),
                                   ptr(rec), ptr(tok), ptr(sc), ptr(par), stream_ptr(dev)))
     return rec, tok, sc, par
 

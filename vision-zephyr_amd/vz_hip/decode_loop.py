@@ -70,10 +70,11 @@ def chunk_recorder(sink, rows: int, sync_every: int, max_new: int):
 
 
 @contextmanager
-def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None):
+def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None):
     """Arms what the call asked for in the one order the engine requires - logits processors, the step's tail (`sampling`: the arguments
     of `set_sampling`, or `sampling_rows`: the per-row table), the host token ring, the step recorder (`scores`: the arguments of
-    `set_scores`), the stop matcher, the beam tail (`beam`: the arguments of `set_beam`) - all in front of the batch's `decode_begin`,
+    `set_scores`), the stop matcher, the beam tail's row recorder (`beam_rows`: the arguments of `set_beam_rows`), the beam tail (`beam`:
+    the arguments of `set_beam`) - all in front of the batch's `decode_begin`,
     and yields `begin(first, next_pos, ctx_len)`: `decode_begin`, then the matcher takes the rows' first tokens.  On the way out,
     whatever happened (a failed arming included), exactly what was armed is disarmed, last first.  None = not asked for: not called."""
     undo = []
@@ -100,6 +101,8 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
             arm("set_scores", scores, (None,))
         if stop is not None:
             arm("set_stop", (stop,), (None,))
+        if beam_rows is not None:
+            arm("set_beam_rows", beam_rows, (None,))
         if beam is not None:
             arm("set_beam", beam, (False,))
         yield begin

@@ -79,6 +79,7 @@ class Engine:
         B.check(self.lib.vz_engine_set_rope(self.h, B.ptr(self._cos), B.ptr(self._sin), max_ctx))
         self.ready = False
         self._score = None                     # the step recorder's rings and step count while armed (set_scores)
+        self._beam_rows = None                 # the beam tail's row rings while armed (set_beam_rows)
 
     def set_prefill_fp8(self, on: bool = True):
         """weight_fp8 engines: run the Zephyr prefill linears on the fp8 MFMA (activations quantised to e4m3 per row on the device,
@@ -739,6 +740,29 @@ class Engine:
         ba = (C.c_int * len(base))(*[int(v) for v in base])
         B.check(self.lib.vz_llm_decode_beam(self.h, 1, int(num_beams), int(groups), ea, len(eos), ba, B.ptr(scores), B.ptr(hist),
                                             int(hist.shape[0]), self._s()))
+
+    def set_beam_rows(self, cap_steps: Optional[int] = None, rows: int = 0, scores: bool = False, raw: bool = False):
+        """the beam tail's row recorder (beam.hip): every beam step of a `rows`-row batch copies its processed log-prob rows (`scores`:
+        HF's scores[t]) and / or its logits rows (`raw`) into device rings of `cap_steps` steps, inside the step; read with
+        `beam_rows_steps`.  None = off.  The ring slot is the beam tail's history index, which `set_beam` restarts."""
+        if cap_steps is None or not (scores or raw):
+            self._beam_rows = None
+            B.check(self.lib.vz_llm_decode_beam_rows(self.h, None, None, 0))
+            return
+        cap, rows, V = int(cap_steps), int(rows), self.cfg.vocab
+        ring = lambda on: torch.empty(cap, rows, V, dtype=torch.float32, device=self.device) if on else None      # noqa: E731
+        br = {"cap": cap, "scores": ring(scores), "raw": ring(raw)}
+        B.check(self.lib.vz_llm_decode_beam_rows(self.h, B.ptr(br["scores"]), B.ptr(br["raw"]), cap))
+        self._beam_rows = br
+
+    def beam_rows_steps(self, count: int, n: int):
+        """the rows of the last `n` of the `count` beam steps run since `set_beam`: (scores [n, rows, V] or None, raw or None), device
+        tensors in step order"""
+        from . import scores as SC
+        br = self._beam_rows
+        assert br is not None, "beam_rows_steps: the row recorder is off (set_beam_rows)"
+        pick = lambda ring: None if ring is None else SC.ring_order(ring, count, n)      # noqa: E731
+        return pick(br["scores"]), pick(br["raw"])
 
     def kv_beam_reorder(self, num_beams: int, groups: int, base: Sequence[int], end: Sequence[int], parent: torch.Tensor):
         """for every group g: cache positions [base[g], end[g]) of row g * num_beams + j become those of row g * num_beams + parent[...]

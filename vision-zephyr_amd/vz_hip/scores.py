@@ -13,14 +13,23 @@ import torch
 SCORE_REC, SCORE_WARPED, SCORE_RAW = 1, 2, 4
 
 
-def check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams: int = 1) -> int:
+def check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams: int = 1, beam_extended: bool = False) -> int:
     """the recorder flags a generate() call needs: 0 = none (every path runs as without the keywords).  As in HF, `output_scores` /
-    `output_logits` / `output_logprobs` without `return_dict_in_generate` return the plain tensor, so nothing is recorded for them."""
+    `output_logits` / `output_logprobs` without `return_dict_in_generate` return the plain tensor, so nothing is recorded for them.
+    With num_beams > 1 the keywords are refused unless the call opts in (`beam_extended=True`): then `output_scores` / `output_logits`
+    give the flags of the rows the beam tail's own recorder keeps (csrc/beam.hip; no per-token records), and `output_logprobs` stays
+    refused - a beam step has no single chosen row to speak of."""
     asked = [k for k, v in (("output_scores", output_scores), ("output_logits", output_logits), ("output_logprobs", output_logprobs)) if v]
-    if num_beams != 1 and asked:
-        raise NotImplementedError(f"`{asked[0]}` with num_beams > 1 is not built (beam search returns `sequences` and `sequences_scores`)")
+    if num_beams != 1 and asked and not beam_extended:
+        raise NotImplementedError(f"`{asked[0]}` with num_beams > 1 needs `beam_extended=True` (without it beam search returns `sequences`, "
+                                  "`sequences_scores` and `beam_indices`)")
+    if num_beams != 1 and output_logprobs:
+        raise NotImplementedError("`output_logprobs` with num_beams > 1 is not built (a beam step has no single chosen row to speak of; "
+                                  "`output_scores` with `compute_transition_scores(..., beam_indices)` gives the tokens' scores)")
     if not return_dict_in_generate or not asked:
         return 0
+    if num_beams != 1:
+        return (SCORE_WARPED if output_scores else 0) | (SCORE_RAW if output_logits else 0)
     return SCORE_REC | (SCORE_WARPED if output_scores else 0) | (SCORE_RAW if output_logits else 0)
 
 
@@ -87,7 +96,7 @@ def transition_scores(sequences: torch.Tensor, scores, beam_indices=None, normal
     """HF's `GenerationMixin.compute_transition_scores` without beams (the same tensor operations in the same order, so the same fp32
     bits): the score of each generated token, [rows, len(scores)]; with `normalize_logits` the log-softmax of each step's row first."""
     if beam_indices is not None:
-        raise NotImplementedError("compute_transition_scores with `beam_indices` is not built (beam search returns no `scores`)")
+        raise NotImplementedError("`transition_scores` is the form without beams: with `beam_indices` use `beam_transition_scores`")
     n = len(scores)
     vocab = scores[0].shape[-1]
     beam_indices = torch.arange(scores[0].shape[0], device=sequences.device).view(-1, 1).expand(-1, n)
@@ -99,6 +108,33 @@ def transition_scores(sequences: torch.Tensor, scores, beam_indices=None, normal
     cut = sequences.shape[-1] - n
     indices = sequences[:, cut:] + beam_indices * vocab
     return s.gather(0, indices)
+
+
+def beam_transition_scores(sequences: torch.Tensor, scores, beam_indices=None, normalize_logits: bool = False, vocab_size: Optional[int] = None) -> torch.Tensor:
+    """HF's `GenerationMixin.compute_transition_scores` with `beam_indices` (the same tensor operations in the same order, so the same fp32 bits): the score
+    of each generated token, [rows, len(scores)]; with `normalize_logits` the log-softmax of each step's row first.  `beam_indices`
+    (beam search: the flattened row of `scores[t]` that produced token t of a hypothesis, -1 behind its end): the result is cut to the
+    longest hypothesis and 0 behind a hypothesis' end.  vocab_size: the model's (HF reads its config); default = the rows' width."""
+    n = len(scores)
+    vocab = scores[0].shape[-1] if vocab_size is None else int(vocab_size)
+    if beam_indices is None:
+        beam_indices = torch.arange(scores[0].shape[0]).view(-1, 1).to(sequences.device)
+        beam_indices = beam_indices.expand(-1, n)
+    s = torch.stack(tuple(scores)).reshape(n, -1).transpose(0, 1)
+    if normalize_logits:
+        s = s.reshape(-1, vocab, s.shape[-1])
+        s = torch.nn.functional.log_softmax(s, dim=1)
+        s = s.reshape(-1, s.shape[-1])
+    mask = beam_indices < 0
+    longest = (1 - mask.long()).sum(-1).max()
+    beam_indices = beam_indices.clone()[:, :longest]
+    mask = mask[:, :longest]
+    beam_indices[mask] = 0
+    cut = sequences.shape[-1] - longest
+    indices = sequences[:, cut:] + beam_indices * vocab
+    out = s.gather(0, indices)
+    out[mask] = 0
+    return out
 
 
 # ---- what a generate() call collects --------------------------------------------------------------------------------------------------
