@@ -788,6 +788,26 @@ int vz_op_beam_select_rows(const float* d_rows, int rows, int cols, int nb_in, i
 int vz_op_hist_beam_reorder(int* d_hist_len, int* d_hist, int hist_stride, int nb, int groups, const int* d_parent, vz_stream stream);
 int vz_llm_decode_beam_rows(vz_engine* e, float* d_scores, float* d_raw, int cap_steps);
 
+/* ---- classifier-free guidance (csrc/guidance.hip) ----
+ * hf:generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor, the first processor of HF's chain, with the two
+ * branches as two rows of one weight sweep.
+ * vz_llm_decode_guidance(enable=1, scale, pairs): from the next vz_llm_decode_begin on a decode batch is B = 2 * pairs rows: row r <
+ *   pairs is a prompt (the conditional branch), row pairs + r its negative prompt (the unconditional branch, with its own cache row).
+ *   Every step runs the model on all B rows; behind the logits, inside the per-token hipGraph: the raw-row recorder, then row r <-
+ *   scale * (lc - lu) + lu with lc / lu = log_softmax of row r / row pairs + r in fp32, then the logits processors, the tail (argmax,
+ *   sampler or per-row table), the step recorder and the stop matcher on the first `pairs` rows exactly as on a `pairs`-row batch, then
+ *   row pairs + r takes the token row r chose and its position / slot / length move on.  d_out_ids of vz_llm_decode_steps is
+ *   [pairs][n]; the token ring, the recorder's rings, the matcher's rows and the per-row table describe `pairs` rows.  The
+ *   unconditional rows are never recorded.  scale: any finite float (1 changes nothing but costs the step; callers pass enable=0).
+ *   vz_llm_decode_steps: VZ_ERR_ARG unless the batch has exactly 2 * pairs rows, VZ_ERR_UNSUPPORTED together with the beam or the
+ *   speculative tail.  Tensor-parallel engines: VZ_ERR_UNSUPPORTED.  scale and pairs are part of what a captured step freezes.
+ *   enable=0: off - the step is launch for launch what it is without this entry.
+ * vz_op_cfg_combine: the same kernel in place on d_logits_cond [pairs][cols] against d_logits_uncond [pairs][cols] (fp32, not
+ *   overlapping; only read).  Precondition: the unconditional rows are finite.  -inf in a conditional row stays -inf (scale > 0).
+ *   Two calls on equal inputs give equal bits. */
+int vz_llm_decode_guidance(vz_engine* e, int enable, float scale, int pairs, vz_stream stream);
+int vz_op_cfg_combine(float* d_logits_cond, const float* d_logits_uncond, int pairs, int cols, float scale, vz_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

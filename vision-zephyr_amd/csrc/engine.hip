@@ -1254,9 +1254,15 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
     }
     {
         ProfScope ps(e, K_OTHER, s);
+        // a guided batch (vz_llm_decode_guidance): the model part above ran on 2 * pairs rows, everything from here on sees the first
+        // `pairs` of them - the conditional rows, whose logits cfg_combine turns into the guided scores in front of everything else
+        const int rows_model = B;
+        const int B = e->cfg.on ? e->cfg.pairs : rows_model;      // (shadows the batch size on purpose: nothing below may touch the other rows)
         // per row: the token into d_out_ids (and the ring), position / slot / length one further
         const RowEmit emit{st.pos, st.slot, st.len, d_out_ids, out_stride, st.step, c.max_ctx, e->rope_max, e->ring.p, e->ring.n};
         if (e->score.what & VZ_SCORE_RAW) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, e->score.raw, e->score.d_slot, e->score.cap, s));
+        // guidance.hip: row r <- scale * (log_softmax(row r) - log_softmax(row pairs + r)) + log_softmax(row pairs + r), HF's first processor
+        if (e->cfg.on) RC(vz_launch_cfg_combine(e->d_logits, e->d_logits + (size_t)B * c.vocab, B, c.vocab, e->cfg.scale, s));
         // the beam tail with processors or with its processed rows recorded: the logits become log-prob rows in place first, as HF
         // hands log_softmax rows to the processors there; otherwise the fused select takes the logits as they are
         const BeamRowsArgs& br = e->beam.rows;
@@ -1308,6 +1314,8 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         }
         // stop.hip: the token the tail just left in st.cur through the rows' stop conditions (writes its own state only)
         if (e->stop.on) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s)); }      // (its own profiling scope: one more counted launch)
+        // guidance.hip: the unconditional rows take the tokens the conditional rows just chose and move on as they did
+        if (e->cfg.on) RC(vz_launch_cfg_follow(st.cur, st.pos, st.slot, st.len, B, c.max_ctx, e->rope_max, s));
         RC(vz_launch_step_advance(st.step, e->score.what ? e->score.d_slot : nullptr, s));
     }
     return VZ_OK;
@@ -1660,6 +1668,30 @@ extern "C" int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int
     return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (const int*)p, s);
 }
 
+// Classifier-free guidance in the step (hf:generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor; guidance.hip;
+// DESIGN.md section 6k): after vz_llm_decode_guidance(enable=1) a decode batch is 2 * pairs rows - row r < pairs a prompt, row pairs + r
+// its negative prompt - that share every weight sweep; behind the logits, row r's become scale * (lc - lu) + lu (lc / lu = the
+// log-softmax of row r / row pairs + r), then the processors, the tail, the recorder and the matcher run on the first `pairs` rows as
+// on a `pairs`-row batch (d_out_ids of vz_llm_decode_steps is [pairs, n]), and row pairs + r follows with the token row r chose.
+// The mode is orthogonal to the tail kind; vz_llm_decode_steps refuses it with the beam or the speculative tail.
+extern "C" int vz_llm_decode_guidance(vz_engine* e, int enable, float scale, int pairs, vz_stream stream) {
+    NEED_READY();
+    (void)stream;
+    if (!enable) { e->cfg.on = 0; e->cfg.pairs = 0; e->cfg.scale = 1.f; return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_guidance: guidance on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(std::isfinite(scale) && pairs >= 1 && decode_shape_ok(e->c, 2 * pairs, false), "decode_guidance: a finite scale (%g) and 1 <= pairs (%d) "
+                 "with 2 * pairs <= min(64, max_batch = %d) expected", (double)scale, pairs, e->c.max_batch);
+    e->cfg.on = 1; e->cfg.pairs = pairs; e->cfg.scale = scale;
+    return VZ_OK;
+}
+
+// the same kernel at op level, in place on d_logits_cond [pairs, cols] against d_logits_uncond [pairs, cols] (the first token of a guided
+// generation: the two branches' prefill logits; one [2 * pairs, cols] buffer: uncond = cond + pairs * cols)
+extern "C" int vz_op_cfg_combine(float* d_logits_cond, const float* d_logits_uncond, int pairs, int cols, float scale, vz_stream stream) {
+    VZ_CHECK_ARG(std::isfinite(scale), "cfg_combine: the scale %g is not finite", (double)scale);
+    return vz_launch_cfg_combine(d_logits_cond, d_logits_uncond, pairs, cols, scale, (hipStream_t)stream);
+}
+
 static int ensure_beam_state(vz_engine* e) {
     if (e->beam.d) return VZ_OK;
     VZ_CHECK_HIP(hipMalloc((void**)&e->beam.d, BEAM_INTS * sizeof(int)));
@@ -1908,6 +1940,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; k.proc_seq = e->proc.a.n_seq ? e->proc.d_seq : nullptr; }
     if (e->stop.on) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
+    if (e->cfg.on) { k.cfg_scale = e->cfg.scale; k.cfg_pairs = e->cfg.pairs; }
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
 }
@@ -1919,9 +1952,18 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(e->dec_B >= 1, "decode_steps: call vz_llm_decode_begin first");
     VZ_CHECK_ARG(n >= 1 && d_out_ids, "decode_steps: bad argument");
     const int B = e->dec_B;
-    VZ_CHECK_ARG(!e->ring.p || B <= e->ring.rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring.rows, B);
     const TailKind tail = tail_kind(e);
     const bool spec = tail == TAIL_SPEC;
+    if (e->cfg.on) {
+        if (tail == TAIL_BEAM || tail == TAIL_SPEC) {
+            vz_set_error("decode_steps: guidance (vz_llm_decode_guidance) runs in front of the argmax, the sampler or the per-row tail only, not with the "
+                         "beam or the speculative tail");
+            return VZ_ERR_UNSUPPORTED;
+        }
+        VZ_CHECK_ARG(B == 2 * e->cfg.pairs, "decode_steps: guidance needs a decode batch of exactly 2 x %d rows (it has %d)", e->cfg.pairs, B);
+    }
+    const int Bt = e->cfg.on ? e->cfg.pairs : B;      // the rows behind the logits: the tail, the token ring, the recorder, the matcher
+    VZ_CHECK_ARG(!e->ring.p || Bt <= e->ring.rows, "decode_steps: the token ring holds %d rows, the decode batch has %d", e->ring.rows, Bt);
     VZ_CHECK_ARG(tail != TAIL_BEAM || (B == e->beam.a.nb * e->beam.a.groups && !e->ring.p), "decode_steps: the beam tail needs a decode batch of exactly "
                  "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
@@ -1964,6 +2006,10 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         RC(vz_decode_persist_reset(e->tok, s));         // arrival counters restart with the step counter
         if (e->tok_poke_word >= 0) { RC(vz_decode_persist_poke(e->tok, e->tok_poke_word, e->tok_poke_value, s)); e->tok_poke_word = -1; }
         e->use_tok = true;
+    }
+    if (e->cfg.on && e->use_tok) {      // (a guided batch has >= 2 rows, the resident grid takes one: kept so that widening either shows up here)
+        vz_set_error("decode_steps: guidance (vz_llm_decode_guidance) on the persistent decode-token kernel is not built");
+        return VZ_ERR_UNSUPPORTED;
     }
     // Capacity (the cache append writes slot = len - 1 of the row, the rotary tables are read at pos): every live row must still fit
     // after n steps.  Parked rows (continuous batching) are not checked: the step tail saturates their slot / position on the device.

@@ -73,8 +73,9 @@ struct DecodeGraphKey {
     float *sc_rec, *sc_warped, *sc_raw; unsigned sc_what; int sc_cap;      // the step recorder behind the tail and its rings (zero when off)
     int* stop_state; StopArgs stop;      // the stop matcher behind the tail: its state, tables and dims (zero when off)
     BeamRowsArgs beam_rows;              // the beam tail's row recorder: its rings (zero when off)
+    float cfg_scale; int cfg_pairs;      // classifier-free guidance between the logits and the processors (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 &&
               sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
 
@@ -143,6 +144,9 @@ struct vz_engine {
     // ints [n | at | ring]; d_tab = the tables of the armed stop set [emb | target | seq] (a.emb / a.target / a.seq point into it)
     // h_tab = the host image of d_tab (an arming with the same stop set uploads nothing); h_init = the state with no row watched
     struct { int on = 0; StopArgs a{}; int* d_state = nullptr; int* d_tab = nullptr; size_t tab_ints = 0; std::vector<int> h_tab, h_init; } stop;
+    // classifier-free guidance (vz_llm_decode_guidance; guidance.hip): orthogonal to the tail - armed, the decode batch is 2 * pairs rows
+    // (row r < pairs a prompt, row pairs + r its negative prompt) and everything behind the logits runs on the first `pairs` rows
+    struct { int on = 0, pairs = 0; float scale = 1.f; } cfg;
     struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)

@@ -372,6 +372,12 @@ struct KvMoves { int n; int src[16], dst[16], len[16]; };
 int vz_launch_kv_move_rows(bf16_t* kv, size_t layer_elems, int n_layers, int max_batch, int Hkv, int max_ctx, int D, const KvMoves& mv,
                            hipStream_t s);
 int vz_launch_step_advance(int* step, int* also, hipStream_t s);      // also: one more word that counts the steps (the recorder's slot), or null
+// classifier-free guidance (guidance.hip).  cfg_combine: cond[r] <- scale * (lc - lu) + lu in place for r < pairs,
+// lc / lu = the fp32 log-softmax of cond[r] / uncond[r] ([pairs, cols] each, not overlapping; one [2 * pairs, cols] buffer: uncond = cond
+// + pairs * cols).  Precondition: the uncond rows are finite (raw model logits); they are only read.  -inf in a cond row stays -inf.
+int vz_launch_cfg_combine(float* cond, const float* uncond, int pairs, int cols, float scale, hipStream_t s);
+// cfg_follow: cur[pairs + r] = cur[r] for r < pairs, and row pairs + r's position / slot / length move on by vz_emit_advance's rule
+int vz_launch_cfg_follow(int* cur, int* pos, int* slot, int* len, int pairs, int max_ctx, int rope_max, hipStream_t s);
 // the step recorder (sampling.hip): a 16-byte record per row about the token the tail chose, optionally the warped score row
 int vz_launch_token_scores(const float* logits, int rows, int cols, const RowSample* tab, const RowSample& one, const int* ids, float* rec,
                            float* warped, const int* slot_word, int cap_steps, hipStream_t s);

@@ -318,6 +318,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported in this generate function.")
         mask_in = attention_mask
+        neg = self._negative_branch(input_ids, kwargs)
+        if neg is not None:
+            kwargs["_guidance"] = neg
         if images is not None:
             (_, position_ids, attention_mask, _, inputs_embeds, _) = self.prepare_inputs_labels_for_multimodal(
                 input_ids, position_ids, attention_mask, None, None, images, images_size)
@@ -329,6 +332,29 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             # built only once the call is known to run with drafts (_generate_from_embeds): every other call stays as it was
             kwargs["_spec_history"] = lambda: self._spec_history(input_ids, mask_in, images, inputs_embeds.shape[1])
         return self._generate_from_embeds(inputs_embeds, attention_mask, position_ids, **kwargs)
+
+    def _negative_branch(self, input_ids, kwargs):
+        """takes the guidance keywords out of a generate() call's `kwargs`: None = guidance is off, else the call's unconditional branch
+        (vz_hip.guidance.Negative) - `negative_prompt_ids` embedded as prompts are: text only, or, with `negative_images` (this package's
+        extension for the degraded-image contrast), spliced by `prepare_inputs_labels_for_multimodal`; right-padded like the prompts."""
+        from vz_hip import guidance as GD
+        from vis_zephyr.constants import IMAGE_TOKEN_INDEX
+        scale, ids, mask, imgs, sizes = (kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask",
+                                                                       "negative_images", "negative_images_size"))
+        parsed = GD.parse(scale, ids, mask, imgs, 0 if input_ids is None else input_ids.shape[0], self.generation_config, IMAGE_TOKEN_INDEX)
+        if parsed is None:
+            return None
+        scale, ids, mask = parsed
+        ids = ids.to(self.device)
+        mask = None if mask is None else mask.to(self.device)
+        pos = None
+        emb = None
+        if imgs is not None:
+            (_, pos, mask, _, emb, _) = self.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, imgs, sizes)
+        if emb is None:
+            emb = self.get_model().embed_tokens(ids)
+        emb, mask, pos, _ = self._to_right_padded(emb, mask, pos)
+        return GD.Negative(scale, emb, self._seqlens(mask, emb.shape[0], emb.shape[1]), pos)
 
     def _spec_history(self, input_ids, attention_mask, images, n_positions: int) -> List[int]:
         """one id per position of the (spliced) prompt for the prompt-lookup drafts (vz_hip.spec): text ids, -1 where a visual token sits."""
@@ -360,7 +386,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True,
                               min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
                               eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, beam_extended: bool = False,
-                              **unused):
+                              _guidance=None, **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -400,7 +426,17 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         act behind temperature / top-k / top-p in HF's order, inside the device-side sampler (csrc/sampling.hip), on every sampled
         route; a greedy call ignores them, as HF does.  HF's `sequence_bias` and `bad_words_ids` (default: the generation config's) join
         the logits processors (csrc/logits_proc.hip), over the generated ids only, in HF's positions: the bias in front of the
-        repetition penalty, the bad words behind the n-gram ban; up to 64 sequences of up to 8 ids, NotImplementedError beyond."""
+        repetition penalty, the bad words behind the n-gram ban; up to 64 sequences of up to 8 ids, NotImplementedError beyond.
+
+        Classifier-free guidance (vz_hip/guidance.py; csrc/guidance.hip): HF's `guidance_scale` (default: the
+        generation config's; None or 1 = off) with `negative_prompt_ids` [Bsz, L] (+ `negative_prompt_attention_mask`; required - generation
+        starts from embeddings, so HF's fallback to the last prompt id does not exist) and, ours, `negative_images` / `negative_images_size`,
+        which splice the negative prompt as `images` splice the prompt.  Every sequence takes two cache rows, the prompt's and the negative
+        prompt's, that share each step's weight sweep; behind the logits the conditional row becomes `s * (lc - lu) + lu` of the two
+        log-softmax rows, in front of the processors, and the token chosen on it is fed to both rows.  Greedy and sampled, batched,
+        `num_return_sequences`, streamer, processors, scores and device stops all take it; `output_logits` rows are the conditional raw
+        logits, `output_scores` rows and the log-probs are taken behind the combine.  `num_beams > 1` and tensor-parallel engines raise
+        NotImplementedError, `max_batch < 2` ValueError; `prompt_lookup_num_tokens` takes the guided greedy path."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
         from vz_hip import stop as ST
@@ -422,6 +458,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                       "log-softmax scores there, and so does the beam step then)")
         if proc is not None and self.engine.tp_size > 1:
             raise NotImplementedError("logits processors on a tensor-parallel engine are not built")
+        neg = _guidance
+        if neg is not None:
+            from vz_hip import guidance as GD
+            if num_beams != 1:
+                raise NotImplementedError("guidance_scale with num_beams > 1 is not built: the beam tail owns every row of its batch")
+            if self.engine.tp_size > 1:
+                raise NotImplementedError("guidance_scale on a tensor-parallel engine is not built")
+            GD.prompts_per_chunk(self.engine.max_batch)          # ValueError: fewer than two cache rows
+            if max(neg.seqlens) + d.max_new > self.engine.max_ctx:
+                raise ValueError(f"negative prompt ({max(neg.seqlens)}) + max_new_tokens ({d.max_new}) exceeds the engine's max_ctx ({self.engine.max_ctx})")
         if num_beams != 1:
             return self._generate_beam(inputs_embeds, attention_mask, position_ids, num_beams, max_new_tokens, max_length, do_sample,
                                        eos_token_id, pad_token_id, streamer, stopping_criteria, sync_every, timing=timing,
@@ -430,6 +476,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         max_new_tokens, pad_token_id = d.max_new, d.fill
         greedy = (not do_sample) or temperature is None or temperature <= 0
         nrs = sample_rows.check_return_sequences(num_return_sequences, greedy, self.engine.max_batch, streamer, stopping_criteria)
+        if neg is not None:
+            GD.prompts_per_chunk(self.engine.max_batch, nrs)     # ValueError: 2 * nrs cache rows do not exist
         if top_k == -1:                      # not passed: HF's generation-config default (50); None / 0 = no top-k filter
             top_k = self.generation_config.top_k
         if top_p is None:
@@ -448,8 +496,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         done = lambda seqs: self._generate_output(seqs, sink, eos, return_dict_in_generate)      # noqa: E731  (the plain tensor unless asked)
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
-                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp))
-        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None:      # (with processors, scores or device stops: the plain greedy path, same ids)
+                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp, neg=neg))
+        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None and neg is None:      # (with processors, scores, device stops or guidance: the plain / guided greedy path)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
@@ -464,13 +512,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                           _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
                 return done(torch.tensor([out], dtype=torch.long, device=self.device))
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
-            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop))
+            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop, neg))
         outs = []
         for b in range(Bsz):               # per-token host callbacks / sampling: one sequence at a time
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
-                                           stopping_criteria, seed + b, sync_every, timing, proc, sink, stop, warp))
+                                           stopping_criteria, seed + b, sync_every, timing, proc, sink, stop, warp,
+                                           None if neg is None else neg.rows(b, b + 1)))
         return done(DL.pad_parts([torch.tensor([o], dtype=torch.long, device=self.device) for o in outs], pad_token_id, self.device))
 
     def _generate_output(self, seqs, sink, eos, return_dict_in_generate):
@@ -512,57 +561,76 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return out
 
     def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None, sink=None,
-                          stop=None) -> torch.Tensor:
+                          stop=None, neg=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step
         streams the weights once for all rows (the KV cache, positions and lengths are per slot).  Rows that hit eos keep
         their slot but emit `pad_token_id` from then on, as HF does.  `proc`: HF's logits processors (vz_hip.logits_proc) on the
         prefill logits and, armed in the engine, on every step's.  `stop`: the stop conditions the engine's matcher decides per row
-        (vz_hip.stop.Plan): a row that stops is treated as a row that emitted eos."""
+        (vz_hip.stop.Plan): a row that stops is treated as a row that emitted eos.  `neg`: the prompts' unconditional branch
+        (vz_hip.guidance.Negative): every prompt takes a second cache row for its negative prompt, so half as many decode together."""
         eng = self.engine
         Bsz, S = embeds.shape[0], embeds.shape[1]
-        cap = min(eng.max_batch, 64)
+        cap = min(eng.max_batch, 64) if neg is None else min(eng.max_batch, 64) // 2
         if Bsz > cap:
             part = lambda lo, hi, tm: self._generate_batched(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi],      # noqa: E731
-                                                             max_new, eos, pad_token_id, sync_every, tm, proc, sink, stop)
+                                                             max_new, eos, pad_token_id, sync_every, tm, proc, sink, stop,
+                                                             None if neg is None else neg.rows(lo, hi))
             return DL.run_parts(part, Bsz, cap, pad_token_id, self.device, timing)
         if S + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         from vz_hip.sample_rows import GREEDY
-        _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
-        next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
-        first, first_cpu, blk = DL.first_tokens(last, [GREEDY] * Bsz, proc, sink, timing)
-        with DL.armed(eng, proc=proc, scores=DL.chunk_recorder(sink, Bsz, sync_every, max_new), stop=stop) as begin:
-            begin(first, next_pos, list(seqlens))
+        if neg is None:
+            _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
+            next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
+            ctx_len, uncond = list(seqlens), None
+        else:
+            last, last_u, next_pos, ctx_len = DL.pair_prefill(eng, embeds, seqlens, position_ids, neg)
+            uncond = (last_u, neg.scale)
+        first, first_cpu, blk = DL.first_tokens(last, [GREEDY] * Bsz, proc, sink, timing, uncond=uncond)
+        with DL.armed(eng, proc=proc, scores=DL.chunk_recorder(sink, Bsz, sync_every, max_new), stop=stop,
+                      guidance=None if neg is None else neg.config(Bsz)) as begin:
+            begin(first, next_pos, ctx_len)
             return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
-                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None, warp=None) -> torch.Tensor:
+                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None, warp=None, neg=None) -> torch.Tensor:
         """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
-        `seed + b * n + j` (vz_hip.sample_rows.row_seed) with its own counter, so it gets the tokens that seed gives it alone."""
+        `seed + b * n + j` (vz_hip.sample_rows.row_seed) with its own counter, so it gets the tokens that seed gives it alone.  `neg`
+        (vz_hip.guidance.Negative): each negative prompt is prefilled once as well and spread over the n unconditional rows of its prompt."""
         from vz_hip import sample_rows as SR
         eng = self.engine
         if eng.tp_size > 1:
             raise NotImplementedError("num_return_sequences > 1 on a tensor-parallel engine (tp_size > 1) is not built")
         Bsz = embeds.shape[0]
-        G = SR.prompts_per_chunk(n, eng.max_batch)
+        if neg is None:
+            G = SR.prompts_per_chunk(n, eng.max_batch)
+        else:
+            from vz_hip.guidance import prompts_per_chunk
+            G = prompts_per_chunk(eng.max_batch, n)
         if Bsz > G:
             part = lambda lo, hi, tm: self._generate_samples(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi], n,      # noqa: E731
                                                              max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, tm, proc,
-                                                             prompt0 + lo, sink, stop, warp)
+                                                             prompt0 + lo, sink, stop, warp, None if neg is None else neg.rows(lo, hi))
             return DL.run_parts(part, Bsz, G, pad_token_id, self.device, timing)
         if max(seqlens) + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         R = Bsz * n
-        last = DL.fan_prefill(eng, embeds, seqlens, position_ids, n)
+        uncond = None
+        if neg is None:
+            last = DL.fan_prefill(eng, embeds, seqlens, position_ids, n)
+        else:
+            last, last_u, next_pos, ctx_len = DL.pair_prefill(eng, embeds, seqlens, position_ids, neg, n)
+            uncond = (last_u, neg.scale)
         params = [SR.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
                                SR.row_seed(seed, prompt0 + r // n, n, r % n), 0, **(warp or {})) for r in range(R)]
-        first, first_cpu, blk = DL.first_tokens(last, params, proc, sink, timing)
-        next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, n)
+        first, first_cpu, blk = DL.first_tokens(last, params, proc, sink, timing, uncond=uncond)
+        if neg is None:
+            next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, n)
         with DL.armed(eng, proc=proc, sampling_rows=[p.at(1) for p in params], scores=DL.chunk_recorder(sink, R, sync_every, max_new),
-                      stop=stop) as begin:
+                      stop=stop, guidance=None if neg is None else neg.config(R)) as begin:
             begin(first, next_pos, ctx_len)
             return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
 
@@ -769,6 +837,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         exhausted = False
 
         def embed(idx, req):
+            if req.get("guidance_scale") is not None or req.get("negative_prompt_ids") is not None:
+                raise NotImplementedError(f"request {idx}: guidance_scale / negative_prompt_ids per request are not built in generate_stream "
+                                          "(a guided sequence takes two cache rows); use generate()")
             ids = req["input_ids"]
             ids = ids if ids.dim() == 2 else ids.unsqueeze(0)
             images = req.get("images")
@@ -892,20 +963,25 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None, warp=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None, warp=None, neg=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
         keeps ONE step in flight and reads token t from a host-visible ring when the event behind step t fires, so the callbacks
         of token t run under step t+1 and no logits ever travel.  `proc`: HF's logits processors (vz_hip.logits_proc) run on the
-        prefill logits before the first token is chosen and, armed in the engine, in front of every step's tail."""
+        prefill logits before the first token is chosen and, armed in the engine, in front of every step's tail.  `neg`
+        (vz_hip.guidance.Negative of this one sequence): the negative prompt is prefilled into cache row 1 and steps beside the prompt."""
         from vz_hip.sample_rows import GREEDY, RowParams
         eng = self.engine
         S = embeds.shape[1]
         if S + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
-        _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
-        next_pos = S if position_ids is None else int(position_ids[0, -1]) + 1
+        if neg is None:
+            _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
+            next_pos, ctx_len, uncond, guid = [S if position_ids is None else int(position_ids[0, -1]) + 1], [S], None, None
+        else:
+            last, last_u, next_pos, ctx_len = DL.pair_prefill(eng, embeds, [S], position_ids, neg)
+            uncond, guid = (last_u, neg.scale), neg.config(1)
         per_token = streamer is not None or stopping_criteria is not None
         if streamer is not None:
             # HF hands the (empty, since generation starts from embeddings) prompt ids to the streamer first;
@@ -913,7 +989,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             streamer.put(torch.empty((1, 0), dtype=torch.long))
         par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0, **(warp or {}))
         more = () if par.warp is None else (par.warp,)      # the further warpers' column, named only when one is active
-        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed) + more)
+        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed) + more, uncond)
         out: List[int] = [int(first_cpu[0])]
         if self._emit(out, streamer, stopping_criteria, None, eos) or max_new <= 1:
             return self._finish(out, streamer)
@@ -922,14 +998,15 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if not per_token:
             # no host callbacks: steps are enqueued back to back, the host looks at the ids every `sync_every` tokens only to honour eos
             # and the stop conditions the device decides (vz_hip.stop)
-            with DL.armed(eng, proc=proc, sampling=tail, scores=DL.chunk_recorder(sink, 1, sync_every, max_new), stop=stop) as begin:
-                begin(first, [next_pos], [S])
+            with DL.armed(eng, proc=proc, sampling=tail, scores=DL.chunk_recorder(sink, 1, sync_every, max_new), stop=stop, guidance=guid) as begin:
+                begin(first, next_pos, ctx_len)
                 return DL.decode_rows(eng, first_cpu, max_new, eos, 0, sync_every, blk, stop is not None)[0].tolist()
         ring = self._token_ring()
         R = ring.numel()
         # with a sink: a device ring of max_new slots, read once at the end - no step waits for its record
-        with DL.armed(eng, proc=proc, sampling=tail, ring=ring, scores=None if blk is None else (max_new, 1, sink.warped, sink.raw)) as begin:
-            begin(first, [next_pos], [S])
+        with DL.armed(eng, proc=proc, sampling=tail, ring=ring, scores=None if blk is None else (max_new, 1, sink.warped, sink.raw),
+                      guidance=guid) as begin:
+            begin(first, next_pos, ctx_len)
             dev_out = torch.empty(1, 1, dtype=torch.int32, device=self.device)
             events = {}
 

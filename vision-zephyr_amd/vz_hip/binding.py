@@ -151,6 +151,8 @@ SYMBOLS = {
     "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
+    "vz_llm_decode_guidance": (_I, [_P, _I, _F, _I, _P]),
+    "vz_op_cfg_combine": (_I, [_P, _P, _I, _I, _F, _P]),
     "vz_llm_decode_logits_proc_seq": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "vz_op_logits_process_seq": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -648,6 +650,18 @@ def argmax(logits):
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
     check(lib().vz_op_argmax(ptr(logits), logits.shape[0], logits.shape[1], ptr(ids), stream_ptr(logits.device)))
     return ids
+
+
+def cfg_combine(cond, uncond, scale: float):
+    """HF's classifier-free guidance (guidance.hip) IN PLACE on the conditional rows: cond[r] <- scale * (lc - lu) + lu, lc / lu = the fp32
+    log-softmax of cond[r] / uncond[r]; fp32 [pairs, V] each on the device (two tensors, or the halves of one [2 * pairs, V] tensor).
+    The unconditional rows must be finite and are only read.  Returns `cond`."""
+    _need_cuda(cond, uncond)
+    for t in (cond, uncond):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+    assert cond.shape == uncond.shape and cond.device == uncond.device
+    check(lib().vz_op_cfg_combine(ptr(cond), ptr(uncond), cond.shape[0], cond.shape[1], float(scale), stream_ptr(cond.device)))
+    return cond
 
 
 def proc_lists(cfg):

@@ -34,15 +34,19 @@ def resolve_defaults(gen, eos_token_id=None, max_new_tokens=None, max_length=Non
     return CallDefaults(eos, set(eos), int(max_new_tokens), pad_token_id, pad_token_id if pad_token_id is not None else min(eos, default=0))
 
 
-def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None):
+def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None, uncond=None):
     """The first token of every row, chosen on the prefill logits `last` [prompts, V] (processed in place by `proc`, whose first step
-    sees an empty history): (first - device, first - host, the sink's block of these rows or None).  params: one
+    sees an empty history): (first - device, first - host, the sink's block of these rows or None).  uncond = (the negative prompts'
+    prefill logits [prompts, V], guidance scale): `last` becomes HF's guided scores in front of `proc` (B.cfg_combine; the sink's raw
+    rows stay the conditional logits).  params: one
     vz_hip.sample_rows.RowParams per row; with n times as many rows as prompts each prompt's logits row serves its n adjacent rows.
     The choice is B.argmax when no row samples, else B.sample_rows; draw = (temperature, top_k, top_p, seed[, warp]): the serial sampled
     sequence's B.sample(..., seed, 0[, warp]) instead (`params` then only describes the row to the sink).  timing: stamped once the host
     holds the tokens."""
     keep_raw = sink is not None and sink.raw
-    raw = last.clone() if keep_raw and proc is not None else last
+    raw = last.clone() if keep_raw and (proc is not None or uncond is not None) else last
+    if uncond is not None:
+        B.cfg_combine(last, uncond[0], uncond[1])
     if proc is not None:
         B.logits_process(last, proc)
     n = len(params) // last.shape[0]
@@ -70,8 +74,10 @@ def chunk_recorder(sink, rows: int, sync_every: int, max_new: int):
 
 
 @contextmanager
-def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None):
-    """Arms what the call asked for in the one order the engine requires - logits processors, the step's tail (`sampling`: the arguments
+def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None, guidance=None):
+    """Arms what the call asked for in the one order the engine requires - logits processors, classifier-free guidance (`guidance`: a
+    vz_hip.guidance.GuidanceConfig; `begin` then takes the first tokens of the conditional rows and the positions of all 2 * pairs rows,
+    and hands each first token to both rows of its pair), the step's tail (`sampling`: the arguments
     of `set_sampling`, or `sampling_rows`: the per-row table), the host token ring, the step recorder (`scores`: the arguments of
     `set_scores`), the stop matcher, the beam tail's row recorder (`beam_rows`: the arguments of `set_beam_rows`), the beam tail (`beam`:
     the arguments of `set_beam`) - all in front of the batch's `decode_begin`,
@@ -84,13 +90,15 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
         undo.append((name, off))
 
     def begin(first, next_pos, ctx_len):
-        eng.decode_begin(first, next_pos, ctx_len)
+        eng.decode_begin(first if guidance is None else torch.cat([first, first]), next_pos, ctx_len)
         if stop is not None:
             eng.stop_rows(0, first)
 
     try:
         if proc is not None:
             arm("set_logits_proc", (proc,), (None,))
+        if guidance is not None:
+            arm("set_guidance", (guidance,), (None,))
         if sampling is not None:
             arm("set_sampling", sampling, (False,))
         if sampling_rows is not None:
@@ -187,6 +195,31 @@ def fan_spread(eng, seqlens, position_ids, n: int):
     ctx_len = [int(seqlens[r // n]) for r in range(G * n)]
     next_pos = list(ctx_len) if position_ids is None else [int(position_ids[r // n, ctx_len[r] - 1]) + 1 for r in range(G * n)]
     return next_pos, ctx_len
+
+
+def pair_prefill(eng, embeds, seqlens, position_ids, neg, n: int = 1):
+    """A guided chunk (vz_hip.guidance): the G prompts `embeds` into the conditional rows, their negative prompts
+    `neg` (vz_hip.guidance.Negative of the same G prompts) into the unconditional rows behind them, each sequence prefilled once and,
+    with n > 1, its KV spread over its n rows.  Returns (the prompts' last-position logits [G, V], the negative prompts' [G, V],
+    next_pos, ctx_len of all 2 * G * n rows for `begin`).  The first tokens are chosen on the two logits blocks; with n > 1 the rows stay
+    parked until `begin`, as in `fan_prefill`."""
+    from .guidance import pair_layout
+    G = embeds.shape[0]
+    lay = pair_layout(seqlens, neg.seqlens, position_ids, neg.position_ids, n)
+    if n == 1:
+        _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
+        last_u = eng.prefill_rows(G, neg.embeds, neg.seqlens, neg.position_ids)
+        return last, last_u, lay.next_pos, lay.ctx_len
+    R = 2 * lay.pairs
+    eng.decode_begin(torch.zeros(R, dtype=torch.int32), [0] * R, [0] * R)          # every row parked: the cache moves below touch parked rows only
+    last, last_u = [], []
+    for g in range(G):
+        Sg, Ng = int(seqlens[g]), int(neg.seqlens[g])
+        last.append(eng.prefill_rows(lay.cond_first[g], embeds[g:g + 1, :Sg], [Sg], None if position_ids is None else position_ids[g:g + 1, :Sg]))
+        last_u.append(eng.prefill_rows(lay.uncond_first[g], neg.embeds[g:g + 1, :Ng], [Ng],
+                                       None if neg.position_ids is None else neg.position_ids[g:g + 1, :Ng]))
+    eng.kv_move_rows(lay.src, lay.dst, lay.lens)
+    return torch.cat(last, 0).contiguous(), torch.cat(last_u, 0).contiguous(), lay.next_pos, lay.ctx_len
 
 
 def pad_parts(parts, fill, device) -> torch.Tensor:

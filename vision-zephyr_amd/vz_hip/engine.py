@@ -79,6 +79,7 @@ class Engine:
         B.check(self.lib.vz_engine_set_rope(self.h, B.ptr(self._cos), B.ptr(self._sin), max_ctx))
         self.ready = False
         self._score = None                     # the step recorder's rings and step count while armed (set_scores)
+        self._guid = None                      # the armed vz_hip.guidance.GuidanceConfig (set_guidance)
         self._beam_rows = None                 # the beam tail's row rings while armed (set_beam_rows)
 
     def set_prefill_fp8(self, on: bool = True):
@@ -589,12 +590,13 @@ class Engine:
             sp["records"].extend(rec.tolist())
             ids = host[B.SPEC_CTL_WORDS + w0:B.SPEC_CTL_WORDS + w1].clone()
             return (ids, lg) if return_logits else ids
+        rows = Bn if self._guid is None else self._guid.pairs      # a guided batch: ids and records of its conditional rows only
         if out is None:
-            out = torch.empty(Bn, n, dtype=torch.int32, device=self.device)
+            out = torch.empty(rows, n, dtype=torch.int32, device=self.device)
         lg = torch.empty(n, Bn, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logits else None
         sc = self._score
-        if sc is not None and sc["rows"] != Bn:          # the rings are [cap_steps][rows]: the recorder writes one record per row of the batch
-            raise ValueError(f"decode_steps: the step recorder was armed for {sc['rows']} rows (set_scores), the decode batch has {Bn}")
+        if sc is not None and sc["rows"] != rows:        # the rings are [cap_steps][rows]: the recorder writes one record per row of the batch
+            raise ValueError(f"decode_steps: the step recorder was armed for {sc['rows']} rows (set_scores), the decode batch has {rows}")
         B.check(self.lib.vz_llm_decode_steps(self.h, n, B.ptr(out), B.ptr(lg), self._s()))
         if sc is not None:
             sc["count"] += n
@@ -682,6 +684,18 @@ class Engine:
         ea, ne, sa, ns = B.proc_lists(cfg)
         B.check(self.lib.vz_llm_decode_logits_proc_seq(self.h, 1, float(cfg.penalty), int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns,
                                                        *B.proc_seq(cfg), self._s()))
+
+    def set_guidance(self, cfg=None):
+        """HF's classifier-free guidance in every decode step (guidance.hip; cfg = vz_hip.guidance.GuidanceConfig, None = off): the NEXT
+        `decode_begin` takes 2 * cfg.pairs rows - row r < pairs a prompt, row pairs + r its negative prompt - and every step combines each
+        pair's logits into row r's in front of the processors and the tail, which then run on the first `pairs` rows only: `decode_steps`
+        returns [pairs, n] ids, and `set_scores` / `set_sampling_rows` / `stop_rows` / `set_ring` describe `pairs` rows."""
+        if cfg is None:
+            self._guid = None
+            B.check(self.lib.vz_llm_decode_guidance(self.h, 0, 1.0, 0, self._s()))
+            return
+        B.check(self.lib.vz_llm_decode_guidance(self.h, 1, float(cfg.scale), int(cfg.pairs), self._s()))
+        self._guid = cfg
 
     def set_ring(self, ring: Optional[torch.Tensor]):
         """host-visible (pinned) int32 ring the step tails write their tokens to: [slots] for a one-row batch or [rows, slots]
