@@ -171,6 +171,20 @@ int vz_op_attention_split(const void* d_q, const void* d_k, const void* d_v, voi
                           float scale, int causal, int q_pos0, int window, const int* d_kv_len,
                           float* d_workspace, long workspace_floats, vz_stream stream);
 
+/* Append attention (attn_append.hip): d_new[b] query tokens of cache row b behind d_past[b] cached positions (int32 [B], device), the new
+ * tokens' K / V already at cache slots past[b] .. past[b] + new[b] - 1.  d_q rotated bf16 [B, T, Hq, 128] by element strides, caches
+ * [B][Hkv][max_ctx][128].  Token i of row b sees the slots j <= past[b] + i (window > 0: and j > past[b] + i - window); token rows
+ * i >= new[b] are not written, no slot at or behind past[b] + new[b] is read.  The Hq / Hkv query heads of a KV head share one query tile
+ * and the keys are split over workgroups: kv_max = max_b(past[b] + new[b]) on the host chooses the split (nsplit = 0) or nsplit >= 1
+ * forces it (cut to the 64-key tiles of kv_max and to 64).  The workspace holds the fp32 partials: vz_op_attention_append_ws_floats(...) floats
+ * cover every split the rule can choose up to max_ctx (pure host arithmetic; 0 = a shape the op refuses); a forced split needs
+ * B * Hq * nsplit * T * 132.  head_dim 128 only. */
+int vz_op_attention_append(const void* d_q, const void* d_kcache, const void* d_vcache, void* d_o, const int* d_past, const int* d_new,
+                           int B, int T, int Hq, int Hkv, int head_dim, int max_ctx, int kv_max,
+                           long q_bs, long q_ss, long q_hs, long o_bs, long o_ss, long o_hs,
+                           float scale, int window, int nsplit, float* d_workspace, long workspace_floats, vz_stream stream);
+long vz_op_attention_append_ws_floats(int B, int T, int Hq, int Hkv, int max_ctx);
+
 /* Attention BACKWARD, tile-resident (attn_bwd_flash.hip): dQ, dK, dV of softmax(scale Q K^T + mask) V without an Sq x Sk tensor in memory - the
  * form the reference trains through (ref:vis_zephyr/train/zephyr_flash_attn_monkey_patch.py:100-124; masks as vz_op_attention: causal,
  * sliding window, per-sample key count).  head_dim 128.  q, dO, dq [B,Sq,Hq,D] bf16; k, v [B,Hkv,Sk,D] bf16; dk, dv [B,Hkv,Sk,D] fp32
@@ -298,7 +312,9 @@ int vz_engine_destroy(vz_engine* e);
  *   VZ_STAGE_QFORMER  n = T, n2 = n_samples, Lmax;  VZ_WS_QF_KV_CONTIG: the blocks' ca_kv weights lie back to back (vz_qformer's layout
  *                     hint), so the K|V projections of all blocks share one buffer unless the 2 GiB cap or knob 25 says otherwise
  *   VZ_STAGE_PREFILL  n = B, n2 = S
- *   VZ_STAGE_DECODE   n = B rows of the running batch;  VZ_WS_SPEC_TAIL: verify steps of the speculative tail (B = R in 2..8) */
+ *   VZ_STAGE_DECODE   n = B rows of the running batch;  VZ_WS_SPEC_TAIL: verify steps of the speculative tail (B = R in 2..8)
+ *   VZ_STAGE_APPEND   n = B, n2 = T new token rows per cache row (vz_llm_prefill_append) */
+#define VZ_STAGE_APPEND 4
 #define VZ_STAGE_CLIP 0
 #define VZ_STAGE_QFORMER 1
 #define VZ_STAGE_PREFILL 2
@@ -461,6 +477,15 @@ int vz_engine_unset_weight(vz_engine* e, const char* name);
 int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds, int B, int S, const int* h_seqlens, const int* d_pos,
                         float* d_logits_all, float* d_logits_last, vz_stream stream);
 int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_pos, int ctx_len, vz_stream stream);
+/* Append prefill: T new embedding rows per cache row behind what the row already holds.  Cache rows row0 .. row0+B-1 keep their slots
+ * [0, h_past[b]); token t < h_new[b] of sample b is appended at slot h_past[b] + t at rotary position d_pos[b, t] and sees the slots
+ * <= its own (sliding window as the prefill).  One pass of the prefill's layer loop over the B*T rows; the attention is
+ * vz_op_attention_append (or, for more than 256 rows per sample, the prefill's flash kernel once per run of rows with equal past).
+ * d_logits_all NULL or fp32 [B,T,vocab] (rows t >= h_new[b] are computed from padding: ignore them), d_logits_last NULL or fp32
+ * [B,vocab] = row h_new[b] - 1.  VZ_ERR_ARG unless 1 <= h_new[b] <= T, h_past[b] >= 0, h_past[b] + h_new[b] <= max_ctx and the rotary
+ * tables cover max_ctx; tensor-parallel engines: VZ_ERR_UNSUPPORTED. */
+int vz_llm_prefill_append(vz_engine* e, int row0, const void* d_embeds, int B, int T, const int* h_new, const int* h_past, const int* d_pos,
+                          float* d_logits_all, float* d_logits_last, vz_stream stream);
 /* Per-row tail (csrc/sampling.hip: sample_rows_kernel): every row of the decode batch chooses its next token by its own entry of a table
  * in device memory - mode 0 = greedy (first maximal index), 1 = sample with the row's own temperature > 0, top_k >= 0, 0 < top_p <= 1,
  * 64-bit seed and draw counter >= 0 (the kernel counts it up after every step).  A sampled row gets the bits vz_op_sample gives a ONE-row
@@ -533,6 +558,14 @@ int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, int emb_rows,
                        const int* h_target, const int* h_seq, int n_seq, vz_stream stream);
 int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const int* d_first_ids, vz_stream stream);
 int vz_llm_decode_stop_read(vz_engine* e, int row0, int rows, int* d_at, vz_stream stream);
+/* Seeded histories (a generate() call that continues on a kept cache; host ids, stream-ordered; behind the arming, in front of
+ * vz_llm_decode_begin / vz_llm_decode_stop_rows).  vz_llm_decode_stop_seed: the last min(n, 63) of the n ids fed before generation begins
+ * enter row `row`'s ring in front of its first generated token, so a stop string may begin in them as in the tail of HF's input_ids; the
+ * id sequences still match generated ids only and `at` still counts generated tokens.  vz_llm_decode_logits_proc_seed: the n <= max_ctx
+ * ids become row `row`'s history - they count for the penalty, the n-grams and the id sequences as a prompt's ids do in HF - while
+ * min_new_tokens counts the ids behind them. */
+int vz_llm_decode_stop_seed(vz_engine* e, int row, const int* h_ids, int n, vz_stream stream);
+int vz_llm_decode_logits_proc_seed(vz_engine* e, int row, const int* h_ids, int n, vz_stream stream);
 int vz_op_stop_match(int* d_state, int rows, const int* d_ids, int reset, const int* d_emb, int emb_rows, int vec, int n_str, int max_pos,
                      int max_end, int window, const int* d_target, const int* d_seq, int n_seq, vz_stream stream);
 /* Batched admissions: prefill several requests together into spare cache rows (row0 >= the running batch), then move each one's

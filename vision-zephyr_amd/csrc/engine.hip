@@ -204,6 +204,20 @@ extern "C" int vz_op_attention_split(const void* q, const void* k, const void* v
     a.part = ws; a.part_floats = (size_t)ws_floats;
     return vz_launch_attention(a, (hipStream_t)s);
 }
+extern "C" int vz_op_attention_append(const void* q, const void* kc, const void* vc, void* o, const int* d_past, const int* d_new, int B, int T,
+                                      int Hq, int Hkv, int head_dim, int max_ctx, int kv_max, long q_bs, long q_ss, long q_hs, long o_bs,
+                                      long o_ss, long o_hs, float scale, int window, int nsplit, float* ws, long ws_floats, vz_stream s) {
+    VZ_CHECK_ARG(ws_floats >= 0 && (ws || ws_floats == 0), "attention_append: bad workspace");
+    AttnAppendArgs a;
+    a.q = (const bf16_t*)q; a.kc = (const bf16_t*)kc; a.vc = (const bf16_t*)vc; a.o = (bf16_t*)o; a.part = ws; a.part_floats = (size_t)ws_floats;
+    a.past = d_past; a.nnew = d_new;
+    a.B = B; a.T = T; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = head_dim; a.max_ctx = max_ctx; a.window = window; a.kv_max = kv_max; a.nsplit = nsplit;
+    a.q_bs = q_bs; a.q_ss = q_ss; a.q_hs = q_hs; a.o_bs = o_bs; a.o_ss = o_ss; a.o_hs = o_hs; a.scale = scale;
+    return vz_launch_attention_append(a, (hipStream_t)s);
+}
+extern "C" long vz_op_attention_append_ws_floats(int B, int T, int Hq, int Hkv, int max_ctx) {
+    return (long)vz_attn_append_ws_floats(B, T, Hq, Hkv, max_ctx);
+}
 // two helpers of the training step at op level (parity tests): dst[c][r] = src[r][c], and out[c] += sum_r y[r][c] through `part`
 extern "C" int vz_op_transpose(const void* src, long src_ld, void* dst, long dst_ld, int R, int C, vz_stream s) {
     return vz_launch_transpose((const bf16_t*)src, src_ld, 0, 0, (bf16_t*)dst, dst_ld, 0, 0, R, C, 1, 1, 0, (hipStream_t)s);
@@ -1058,6 +1072,125 @@ extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds,
 }
 
 // ------------------------------------------------------------------------------------------------
+// a12b: append prefill - T new rows per cache row behind the positions the row keeps
+// ------------------------------------------------------------------------------------------------
+// More new rows per sample than this run the prefill's flash kernel with a scalar q_pos0, once per run of cache rows with equal past;
+// at or below it the key-split kernel of attn_append.hip.  Measured behind 2048 cached positions (profiles/append.txt): the key-split
+// kernel + combine take 48 us against 67 at T = 256, 61 against 68 at 320, 76 against 71 at 384 and 87 against 74 at 512: the crossover
+// lies between 320 and 384, and 256 sits inside the range it wins by a clear margin.
+// vz_tune_set(36, rows).
+static int g_append_flash_min_t = 256;
+static bool append_shape_ok(const vz_config& c, int row0, int B, int T) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && T >= 1 && T <= c.max_ctx; }
+struct AppendWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; float* part; size_t part_floats; };
+static AppendWs carve_append(Carver& m, const vz_config& c, const Shard& sh, int B, int T) {
+    const size_t rows = (size_t)B * T, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, QKV = (size_t)(sh.Hq + 2 * sh.Hkv) * c.head_dim, I = sh.I;
+    AppendWs w;
+    w.x = m.take<bf16_t>(rows * H);
+    w.y = m.take<bf16_t>(rows * H);
+    w.qkv = m.take<bf16_t>(rows * QKV);
+    w.q = m.take<bf16_t>(rows * A);
+    w.att = m.take<bf16_t>(rows * A);
+    w.act = m.take<bf16_t>(rows * I);
+    w.ints = m.take<int>(rows + 3 * (size_t)B + 16);                          // slot[rows] | kv_len[B] | past[B] | new[B]
+    w.ylast = m.take<bf16_t>((size_t)B * H * 2);
+    w.part_floats = vz_attn_append_ws_floats(B, T, sh.Hq, sh.Hkv, c.max_ctx);
+    w.part = m.take<float>(w.part_floats);
+    return w;
+}
+
+extern "C" int vz_llm_prefill_append(vz_engine* e, int row0, const void* d_embeds, int B, int T, const int* h_new, const int* h_past, const int* d_pos,
+                                     float* d_logits_all, float* d_logits_last, vz_stream stream) {
+    NEED_READY();
+    const vz_config& c = e->c;
+    hipStream_t s = (hipStream_t)stream;
+    if (e->tp > 1) { vz_set_error("prefill_append: the append prefill on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(d_embeds && h_new && h_past && d_pos && append_shape_ok(c, row0, B, T),
+                 "prefill_append: rows %d..%d, T=%d outside capacity (max_batch %d, max_ctx %d)", row0, row0 + B - 1, T, c.max_batch, c.max_ctx);
+    VZ_CHECK_ARG(e->cosT && e->rope_max >= c.max_ctx, "prefill_append: rotary tables not set or shorter than max_ctx");
+    int kv_max = 0;
+    for (int b = 0; b < B; ++b) {
+        VZ_CHECK_ARG(h_new[b] >= 1 && h_new[b] <= T, "prefill_append: new[%d]=%d outside [1,%d]", b, h_new[b], T);
+        VZ_CHECK_ARG(h_past[b] >= 0 && h_past[b] <= c.max_ctx - h_new[b], "prefill_append: past[%d]=%d + new %d outside max_ctx %d", b, h_past[b], h_new[b], c.max_ctx);
+        kv_max = std::max(kv_max, h_past[b] + h_new[b]);
+    }
+    const size_t row_elems = (size_t)e->Hkv_l * c.max_ctx * c.head_dim;           // cache rows are [kv head][max_ctx][128] blocks
+    const size_t row_off = (size_t)row0 * row_elems;
+    const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
+    const int rows = B * T;
+    AppendWs w;
+    RC(carve_stage(e, "prefill_append", [&](Carver& m) { return carve_append(m, c, Shard{Hq, Hkv, I}, B, T); }, &w));
+    bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
+    int *d_slot = w.ints, *d_len = w.ints + rows, *d_past = d_len + B, *d_new = d_past + B;
+    {
+        std::vector<int> h(rows + 3 * B);
+        for (int b = 0; b < B; ++b) {
+            for (int t = 0; t < T; ++t) h[b * T + t] = t < h_new[b] ? h_past[b] + t : -1;
+            h[rows + b] = h_past[b] + h_new[b]; h[rows + B + b] = h_past[b]; h[rows + 2 * B + b] = h_new[b];
+        }
+        RC(upload_ints(e, h.data(), h.size(), w.ints, s));
+    }
+    auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
+        if (norm_w) { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(Ain, K, y, K, norm_w, rows, K, c.rms_eps, s)); }
+        return linear(e, 0, norm_w ? y : Ain, K, bare(W.w), K, Cout, ldc, rows, N, K, res, H, act, 0, s);
+    };
+    const bool flash = T > g_append_flash_min_t;
+    bool padded = false;
+    for (int b = 0; b < B; ++b) padded = padded || h_new[b] < T;
+    // token rows >= new[b] are never written by the key-split kernel in any layer: keep what the O projection reads of them finite
+    if (padded && !flash) VZ_CHECK_HIP(hipMemsetAsync(att, 0, (size_t)rows * A * sizeof(bf16_t), s));
+    { ProfScope ps(e, K_OTHER, s); RC(vz_launch_copy_rows((const bf16_t*)d_embeds, H, x, H, rows, H, s)); }
+    for (int i = 0; i < c.n_layers; ++i) {
+        const LlmLayerW& W = e->llm[i];
+        RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
+        // RoPE + the KV append at slot past + t; the attention reads the rotated copy q
+        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, q, kc_of(e, i) + row_off, vc_of(e, i) + row_off, e->cosT, e->sinT, d_pos, d_slot, B, T, Hq, Hkv, D, c.max_ctx, s)); }
+        if (flash) {
+            ProfScope ps(e, K_ATTN, s);
+            for (int b0 = 0; b0 < B;) {
+                int b1 = b0 + 1;
+                while (b1 < B && h_past[b1] == h_past[b0]) ++b1;
+                AttnArgs a;
+                a.q = q + (size_t)b0 * T * A; a.k = kc_of(e, i) + row_off + b0 * row_elems; a.v = vc_of(e, i) + row_off + b0 * row_elems; a.o = att + (size_t)b0 * T * A;
+                a.B = b1 - b0; a.Sq = T; a.Sk = std::min(h_past[b0] + T, c.max_ctx); a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D;
+                a.q_bs = (long)T * A; a.q_ss = A; a.q_hs = D;
+                a.k_bs = a.v_bs = (long)row_elems; a.k_ss = a.v_ss = D; a.k_hs = a.v_hs = (long)c.max_ctx * D;
+                a.o_bs = (long)T * A; a.o_ss = A; a.o_hs = D;
+                a.scale = ATTN_SCALE;
+                a.causal = 1; a.q_pos0 = h_past[b0]; a.window = c.sliding_window; a.kv_len = d_len + b0;
+                RC(vz_launch_attention(a, s));
+                b0 = b1;
+            }
+        } else {
+            ProfScope ps(e, K_ATTN, s);
+            AttnAppendArgs a;
+            a.q = q; a.kc = kc_of(e, i) + row_off; a.vc = vc_of(e, i) + row_off; a.o = att; a.part = w.part; a.part_floats = w.part_floats;
+            a.past = d_past; a.nnew = d_new;
+            a.B = B; a.T = T; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D; a.max_ctx = c.max_ctx; a.window = c.sliding_window; a.kv_max = kv_max; a.nsplit = 0;
+            a.q_bs = a.o_bs = (long)T * A; a.q_ss = a.o_ss = A; a.q_hs = a.o_hs = D;
+            a.scale = ATTN_SCALE;
+            RC(vz_launch_attention_append(a, s));
+        }
+        RC(plin(att, nullptr, W.o, H, A, x, H, x, VZ_ACT_NONE));
+        RC(plin(x, W.post_norm, W.gu, 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
+        RC(plin(act, nullptr, W.down, H, I, x, H, x, VZ_ACT_NONE));
+    }
+    const float* fn = e->top.norm;
+    if (d_logits_all) {
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(x, H, y, H, fn, rows, H, c.rms_eps, s)); }
+        RC(lm_head_logits(e, y, rows, d_logits_all, s, nullptr));
+    }
+    if (d_logits_last) {
+        {
+            ProfScope ps(e, K_OTHER, s);
+            for (int b = 0; b < B; ++b) RC(vz_launch_copy_rows(x + ((size_t)b * T + h_new[b] - 1) * H, H, ylast + (size_t)b * H, H, 1, H, s));
+        }
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(ylast, H, ylast + (size_t)B * H, H, fn, B, H, c.rms_eps, s)); }
+        RC(lm_head_logits(e, ylast + (size_t)B * H, B, d_logits_last, s, nullptr));
+    }
+    return VZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // a13: greedy decode
 // ------------------------------------------------------------------------------------------------
 static bool decode_shape_ok(const vz_config& c, int B, bool spec) { return B >= 1 && B <= c.max_batch && B <= 64 && (!spec || (B >= 2 && B <= 8)); }
@@ -1147,9 +1280,13 @@ extern "C" int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const 
     return VZ_OK;
 }
 
-// the logits processors' buffer (vz_engine::proc.d): the rows' history lengths, then the histories [max_batch][max_ctx]
+// the logits processors' buffer (vz_engine::proc.d): the rows' history lengths, how many ids of each history were seeded before generation
+// began (vz_llm_decode_logits_proc_seed; 0 otherwise), then the histories [max_batch][max_ctx]
 static size_t proc_len_ints(const vz_config& c) { return align_up((size_t)c.max_batch, 64); }
-static int* proc_hist(const vz_engine* e) { return e->proc.d + proc_len_ints(e->c); }
+static int* proc_base(const vz_engine* e) { return e->proc.d + proc_len_ints(e->c); }
+static int* proc_hist(const vz_engine* e) { return e->proc.d + 2 * proc_len_ints(e->c); }
+// the stop matcher's per-row count of ids its ring was seeded with (vz_llm_decode_stop_seed): behind the rows' states
+static int* stop_pre(const vz_engine* e) { return e->stop.d_state + (size_t)e->c.max_batch * VZ_STOP_ROW; }
 static int proc_args_of(float penalty, int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, ProcArgs* out) {
     VZ_CHECK_ARG(penalty > 0.f && ngram >= 0 && ngram <= 8 && min_new >= 0, "logits_proc: repetition penalty %g > 0, 0 <= n-gram size %d <= 8, "
                  "min_new_tokens %d >= 0 expected", (double)penalty, ngram, min_new);
@@ -1271,7 +1408,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         if (beam_lp) RC(vz_launch_beam_logprob_rows(e->d_logits, B, c.vocab, e->d_logits, s));
         if (e->proc.on && tail_takes_proc(tail)) {
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
-            RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, e->proc.a.n_seq ? e->proc.d_seq : nullptr, s));
+            RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, e->proc.a.n_seq ? e->proc.d_seq : nullptr, s, proc_base(e)));
         }
         if (beam_lp && br.scores) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, br.scores, beam_view(e->beam.d).hidx, br.cap, s));
         switch (tail) {
@@ -1313,7 +1450,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
                                       (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
         }
         // stop.hip: the token the tail just left in st.cur through the rows' stop conditions (writes its own state only)
-        if (e->stop.on) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s)); }      // (its own profiling scope: one more counted launch)
+        if (e->stop.on) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s, stop_pre(e))); }      // (its own profiling scope: one more counted launch)
         // guidance.hip: the unconditional rows take the tokens the conditional rows just chose and move on as they did
         if (e->cfg.on) RC(vz_launch_cfg_follow(st.cur, st.pos, st.slot, st.len, B, c.max_ctx, e->rope_max, s));
         RC(vz_launch_step_advance(st.step, e->score.what ? e->score.d_slot : nullptr, s));
@@ -1345,7 +1482,7 @@ extern "C" int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, in
     hipStream_t s = (hipStream_t)stream;
     const int mb = e->c.max_batch;
     if (!e->stop.d_state) {
-        e->stop.h_init.assign((size_t)mb * VZ_STOP_ROW, 0);
+        e->stop.h_init.assign((size_t)mb * VZ_STOP_ROW + mb, 0);          // the rows' states, then the rows' seeded-id counts (stop_pre)
         for (int r = 0; r < mb; ++r) e->stop.h_init[(size_t)r * VZ_STOP_ROW + 1] = VZ_STOP_UNARMED;
         VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_state, e->stop.h_init.size() * sizeof(int)));
     }
@@ -1385,7 +1522,22 @@ extern "C" int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const i
     NEED_READY();
     VZ_CHECK_ARG(e->stop.on, "decode_stop_rows: the stop matcher is off (vz_llm_decode_stop)");
     VZ_CHECK_ARG(row0 >= 0 && rows >= 1 && row0 + rows <= e->c.max_batch && d_first_ids, "decode_stop_rows: rows [%d, %d) outside max_batch = %d", row0, row0 + rows, e->c.max_batch);
-    return vz_launch_stop_match(e->stop.a, e->stop.d_state + (size_t)row0 * VZ_STOP_ROW, rows, d_first_ids, 1, (hipStream_t)stream);
+    return vz_launch_stop_match(e->stop.a, e->stop.d_state + (size_t)row0 * VZ_STOP_ROW, rows, d_first_ids, 1, (hipStream_t)stream, stop_pre(e) + row0);
+}
+
+// Seeds row `row`'s ring with the last ids that were fed before generation begins (a call that continues on a kept cache), newest last:
+// a stop string may then begin in them, as it may in the tail of HF's input_ids; the id sequences (rule 2) still look at generated ids
+// only.  Behind the arming (which clears every row), in front of vz_llm_decode_stop_rows (which keeps the ring); stream-ordered.
+extern "C" int vz_llm_decode_stop_seed(vz_engine* e, int row, const int* h_ids, int n, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->stop.on && e->stop.d_state, "decode_stop_seed: the stop matcher is off (vz_llm_decode_stop)");
+    VZ_CHECK_ARG(row >= 0 && row < e->c.max_batch && n >= 0 && (h_ids || n == 0), "decode_stop_seed: row %d outside max_batch = %d, or %d ids", row, e->c.max_batch, n);
+    int img[VZ_STOP_W + 1] = {0};
+    const int k = std::min(n, VZ_STOP_W - 1);
+    for (int j = 0; j < k; ++j) img[VZ_STOP_W - 1 - j] = h_ids[n - 1 - j];          // the first generated token takes slot 0, its predecessor is slot 63
+    img[VZ_STOP_W] = k;
+    RC(upload_ints(e, img, VZ_STOP_W, e->stop.d_state + (size_t)row * VZ_STOP_ROW + 2, (hipStream_t)stream));
+    return upload_ints(e, img + VZ_STOP_W, 1, stop_pre(e) + row, (hipStream_t)stream);
 }
 
 // at[row0 .. row0 + rows) -> d_at (device), stream-ordered behind the steps: rides with the chunk's ids at the host's sync
@@ -1621,8 +1773,8 @@ extern "C" int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float rep
     RC(proc_args_of(repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, &a));
     VZ_CHECK_ARG(c.vocab <= 65536, "decode_logits_proc: vocabulary of %d, the kernel's bitmaps hold 65536", c.vocab);
     hipStream_t s = (hipStream_t)stream;
-    if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
-    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, proc_len_ints(c) * sizeof(int), s));
+    if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (2 * proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
+    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, 2 * proc_len_ints(c) * sizeof(int), s));
     RC(proc_seq_check(h_seq, n_seq));
     if (n_seq) {
         std::vector<int> tab(h_seq, h_seq + (size_t)n_seq * VZ_PROC_SEQ_STRIDE);
@@ -1637,6 +1789,21 @@ extern "C" int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float rep
     }
     e->proc.on = 1; e->proc.a = a;
     return VZ_OK;
+}
+
+// Seeds row `row`'s history with n ids that were fed before generation begins (a call that continues on a kept cache: the conversation so
+// far): they count for the penalty, the n-grams and the id sequences as a prompt's ids do in HF; min_new_tokens counts the ids behind
+// them.  Behind the arming (which empties every history), in front of vz_llm_decode_begin; stream-ordered.
+extern "C" int vz_llm_decode_logits_proc_seed(vz_engine* e, int row, const int* h_ids, int n, vz_stream stream) {
+    NEED_READY();
+    const vz_config& c = e->c;
+    VZ_CHECK_ARG(e->proc.on && e->proc.d, "decode_logits_proc_seed: the logits processors are off (vz_llm_decode_logits_proc)");
+    VZ_CHECK_ARG(row >= 0 && row < c.max_batch && n >= 0 && n <= c.max_ctx && (h_ids || n == 0), "decode_logits_proc_seed: row %d, %d ids outside max_batch %d / max_ctx %d", row, n, c.max_batch, c.max_ctx);
+    hipStream_t s = (hipStream_t)stream;
+    if (n) RC(upload_ints(e, h_ids, (size_t)n, proc_hist(e) + (size_t)row * c.max_ctx, s));
+    const int two[2] = {n, n};
+    RC(upload_ints(e, two, 1, e->proc.d + row, s));
+    return upload_ints(e, two + 1, 1, proc_base(e) + row, s);
 }
 
 // the same kernel on fp32 logits [rows, cols] in place, over the caller's histories d_hist [rows][hist_stride] of d_hist_len[row] ids
@@ -2145,6 +2312,7 @@ extern "C" long vz_op_stage_ws_bytes(const vz_config* cfg, int stage, int n, int
     case VZ_STAGE_QFORMER: if (!qf_shape_ok(c, n, n2, Lmax)) return -1; carve_qformer(m, c, n, n2, Lmax, qf_kv_all(c, n, (flags & VZ_WS_QF_KV_CONTIG) != 0)); break;
     case VZ_STAGE_PREFILL: if (!prefill_shape_ok(c, 0, n, n2)) return -1; carve_prefill(m, c, shard_of(c), n, n2); break;
     case VZ_STAGE_DECODE: if (!decode_shape_ok(c, n, spec)) return -1; carve_decode(m, c, shard_of(c), n, spec); break;
+    case VZ_STAGE_APPEND: if (!append_shape_ok(c, 0, n, n2)) return -1; carve_append(m, c, shard_of(c), n, n2); break;
     default: return -1;
     }
     return (long)m.off;
@@ -2203,7 +2371,7 @@ static int tune_set(int knob, int value) {
         {11, &g_gemm256_drain}, {14, &g_decode_tile_rows}, {15, &g_decode_sk_short}, {16, &g_attn_stamp_on}, {19, &g_wide_mode}, {21, &g_fp8_gemm_choice},
         {22, &g_fp8_prefill_min_rows}, {23, nullptr, vz_set_attn_split}, {24, nullptr, vz_set_splitk_cap}, {25, &g_qf_kv_all}, {26, nullptr, vz_set_splitk_mid},
         {27, &g_wide_fp8_splits}, {28, &g_persist_decode}, {29, &g_oneshot}, {30, &g_attn_o}, {31, &g_attn_o_delay}, {32, &g_flash_bwd}, {33, &g_rope_in_attn},
-        {34, &g_gemm256_persist}, {35, &g_skinny_even},
+        {34, &g_gemm256_persist}, {35, &g_skinny_even}, {36, &g_append_flash_min_t},
     };
     for (const auto& k : knobs) {
         if (k.knob != knob) continue;

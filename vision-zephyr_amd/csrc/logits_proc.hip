@@ -18,7 +18,8 @@
 //   `biased`, and the sweep adds, in fp32 and in table order, the biases of the acting sequences that end in it: x + (((0 + b1) + b2) ...),
 //   HF's zero-initialised bias row - then the penalty, which acts on the biased score, then -inf.  Still one writer per logit.
 // One 1024-thread workgroup per row, in place.  Inside a decode step the kernel first appends cur[row] - the token the previous tail
-// published - to the row's history (saturating at hist_stride), so no tail kernel has to know about the history.
+// published - to the row's history (saturating at hist_stride), so no tail kernel has to know about the history.  base (optional): per
+// row, how many ids of the history were seeded before generation began; min-new counts the ids behind them.
 #include "vz_common.h"
 
 namespace {
@@ -31,7 +32,7 @@ __device__ __forceinline__ void mark(unsigned* bm, int tok, int cols) {
 
 __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict__ logits, int cols, int* __restrict__ hist, int hist_stride,
                                                               int* __restrict__ hist_len, const int* __restrict__ cur, ProcArgs a,
-                                                              const int* __restrict__ seqtab) {
+                                                              const int* __restrict__ seqtab, const int* __restrict__ base) {
     __shared__ unsigned seen[PROC_WORDS], ban[PROC_WORDS], biased[PROC_WORDS];
     __shared__ int s_tok[VZ_PROC_MAX_SEQ];          // the id sequence k biases in this row, -1: none (it does not act, or it bans)
     __shared__ float s_bias[VZ_PROC_MAX_SEQ];
@@ -45,6 +46,9 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
     const bool app = cur != nullptr && n0 < hist_stride;
     const int c = cur ? cur[row] : -1;
     const int n_seq = seqtab ? a.n_seq : 0;
+    // ids the history was seeded with before the first generated one (a call that continues on a kept cache: the cached conversation);
+    // they count for the penalty, the n-grams and the id sequences, as a prompt's ids do in HF, but not as NEW tokens
+    const int n_base = base ? min(max(base[row], 0), n0) : 0;
     for (int w = tid; w < W; w += 1024) { seen[w] = 0; ban[w] = 0; if (n_seq) biased[w] = 0; }
     __syncthreads();
     if (app && tid == 0) { h[n0] = c; hist_len[row] = n0 + 1; }
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
             }
         }
     }
-    if (tid < 4 && tid < a.eos.n && n < a.min_new) mark(ban, a.eos.id[tid], cols);
+    if (tid < 4 && tid < a.eos.n && n - n_base < a.min_new) mark(ban, a.eos.id[tid], cols);
     if (tid >= 64 && tid < 64 + 16 && tid - 64 < a.n_suppress) mark(ban, a.suppress[tid - 64], cols);
     if (tid >= 128 && tid - 128 < n_seq) {          // one thread per sequence of the table
         const int* q = seqtab + (tid - 128) * VZ_PROC_SEQ_STRIDE;
@@ -136,14 +140,14 @@ __global__ __launch_bounds__(1024) void logits_process_kernel(float* __restrict_
 }  // namespace
 
 int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
-                             const ProcArgs& a, const int* seqtab, hipStream_t s) {
+                             const ProcArgs& a, const int* seqtab, hipStream_t s, const int* base) {
     VZ_CHECK_ARG(logits && hist && hist_len && rows > 0 && cols > 0 && hist_stride >= 1, "logits_process: bad argument");
     VZ_CHECK_ARG(cols <= PROC_MAX_COLS, "logits_process: %d columns, the LDS bitmaps hold %d", cols, PROC_MAX_COLS);
     VZ_CHECK_ARG(a.penalty > 0.f && a.ngram >= 0 && a.ngram <= PROC_G && a.min_new >= 0 && a.eos.n >= 0 && a.eos.n <= 4 && a.n_suppress >= 0 &&
                  a.n_suppress <= 16, "logits_process: penalty %g > 0, 0 <= ngram %d <= 8, min_new %d >= 0, <= 4 eos ids (%d), <= 16 suppressed ids (%d) expected",
                  (double)a.penalty, a.ngram, a.min_new, a.eos.n, a.n_suppress);
     VZ_CHECK_ARG(a.n_seq >= 0 && a.n_seq <= VZ_PROC_MAX_SEQ && (a.n_seq == 0 || seqtab), "logits_process: %d id sequences, 0..%d with their table expected", a.n_seq, VZ_PROC_MAX_SEQ);
-    hipLaunchKernelGGL(logits_process_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, hist, hist_stride, hist_len, cur, a, seqtab);
+    hipLaunchKernelGGL(logits_process_kernel, dim3(rows), dim3(1024), 0, s, logits, cols, hist, hist_stride, hist_len, cur, a, seqtab, base);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

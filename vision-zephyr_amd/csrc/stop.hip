@@ -17,7 +17,8 @@
 
 #define STOP_MAX_VEC (VZ_STOP_MAX_STR * (VZ_STOP_MAX_POS + VZ_STOP_MAX_END) + 1)
 
-__global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restrict__ state, const int* __restrict__ ids, int reset) {
+__global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restrict__ state, const int* __restrict__ ids, int reset,
+                                                        const int* __restrict__ pre) {
     __shared__ int rowsL[(VZ_STOP_W - 1) * STOP_MAX_VEC];
     const int lane = threadIdx.x;
     int* st = state + (size_t)blockIdx.x * VZ_STOP_ROW;
@@ -61,7 +62,11 @@ __global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restr
     // rule 1
     const bool live = end_len > 0;
     bool hit1 = live && end_len >= target;
-    const int L = n1 < a.window ? n1 : a.window;            // window: the newest token and L - 1 older ones
+    // window: the newest token and L - 1 older ones.  pre (optional): ids the ring was seeded with in front of the first generated token,
+    // slots 63, 62, .. = the newest first (a call that continues on a kept cache): HF's criterion sees them as the tail of its input_ids,
+    // so a stop string may begin in them; rule 2 looks at generated ids only, as the reference's criterion does behind its start length
+    const int n_seen = n1 + (pre ? min(max(pre[blockIdx.x], 0), VZ_STOP_W - 1) : 0);
+    const int L = n_seen < a.window ? n_seen : a.window;
     if (L > 1 && __any(live && !hit1)) {
         const int total = (L - 1) * a.vec;
         for (int base = 0; base < total; base += 64 * 8) {
@@ -116,10 +121,10 @@ static int stop_args_ok(const StopArgs& a) {
     return VZ_OK;
 }
 
-int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s) {
+int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre) {
     VZ_CHECK_ARG(state && ids && rows >= 1, "stop_match: bad argument");
     { int r = stop_args_ok(a); if (r) return r; }
-    hipLaunchKernelGGL(stop_match_kernel, dim3(rows), dim3(64), 0, s, a, state, ids, reset);
+    hipLaunchKernelGGL(stop_match_kernel, dim3(rows), dim3(64), 0, s, a, state, ids, reset, pre);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -251,6 +251,25 @@ void vz_set_attn_version(int v);
 int vz_attn_version();
 void vz_set_attn_split(int v);
 
+// append attention (attn_append.hip): nnew[b] query tokens of cache row b behind past[b] cached positions whose K / V are in the cache
+struct AttnAppendArgs {
+    const bf16_t* q;      // rotated queries, strided [B, T, Hq, D]
+    const bf16_t* kc;     // cache base of the first row: [B][Hkv][max_ctx][D]
+    const bf16_t* vc;
+    bf16_t* o;            // strided [B, T, Hq, D]; token rows >= nnew[b] are left alone
+    float* part;          // fp32 workspace of part_floats elements (vz_attn_append_ws_floats)
+    size_t part_floats;
+    const int *past, *nnew;   // device int32 [B]
+    int B, T, Hq, Hkv, head_dim, max_ctx, window;
+    int kv_max;           // host: max over the rows of past + new (chooses the key split)
+    int nsplit;           // 0 = the host rule, n >= 1 forced
+    long q_bs, q_ss, q_hs, o_bs, o_ss, o_hs;
+    float scale;
+};
+int vz_launch_attention_append(const AttnAppendArgs& a, hipStream_t s);
+int vz_attn_append_nsplit(int B, int T, int Hq, int Hkv, int kv_max);
+size_t vz_attn_append_ws_floats(int B, int T, int Hq, int Hkv, int max_ctx);
+
 // decode attention: one query token per slot against the KV cache; lengths live on the device
 struct AttnDecodeArgs {
     const bf16_t* q;      // [B, Hq, D]
@@ -388,7 +407,7 @@ int vz_launch_score_raw_rows(const float* logits, int rows, int cols, float* raw
 struct StopArgs { const int* emb; const int* target; const int* seq; int emb_rows, vec, n_str, max_pos, max_end, window, n_seq, pad; };
 static_assert(sizeof(StopArgs) == 3 * 8 + 8 * 4, "padding in StopArgs");
 // one new id per row (ids[row]) through the matcher; reset != 0: the rows start clean (n = 0, at = -1) and are armed
-int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s);
+int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre = nullptr);
 // beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
 struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);
@@ -403,9 +422,9 @@ enum { VZ_PROC_MAX_SEQ = 64, VZ_PROC_SEQ_IDS = 8, VZ_PROC_SEQ_STRIDE = 12 };
 struct ProcArgs { float penalty; int ngram, min_new; BeamEos eos; int n_suppress; int suppress[16]; int n_seq, seq_epoch; };
 static_assert(sizeof(ProcArgs) == 6 * 4 + sizeof(BeamEos) + 16 * 4, "padding in ProcArgs");
 // in place on fp32 logits [rows, cols <= 65536]; the row's history hist[row * hist_stride + 0 .. hist_len[row]); cur != null: cur[row] is
-// appended first (saturating at hist_stride)
+// appended first (saturating at hist_stride); base != null: base[row] ids of the history were seeded, min_new counts those behind them
 int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
-                             const ProcArgs& a, const int* seqtab, hipStream_t s);
+                             const ProcArgs& a, const int* seqtab, hipStream_t s, const int* base = nullptr);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
                           int* next_parent, const RowEmit& emit, bool on_rows, hipStream_t s);      // on_rows: `logits` are log-prob rows already

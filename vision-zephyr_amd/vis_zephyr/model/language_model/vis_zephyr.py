@@ -93,10 +93,14 @@ class VisZephyrModel(VisZephyrMetaModel):
 
 class PastKeyValues:
     """The KV cache lives in the engine ([layer][k|v][slot][kv_head][pos][128] bf16); this handle records how
-    many positions of each slot are filled."""
+    many positions of each slot are filled.  A handle that generate() returns also remembers the ids those positions stand for
+    (the prompt ids as given - an image is one id - plus every emitted id but the last) and each row's next rotary position, so that
+    generate(<the whole conversation>, past_key_values=handle) can tell the cached part from the new one (vz_hip/append.py)."""
 
-    def __init__(self, lengths: Sequence[int], owner=None, epoch: int = 0, continuable: bool = False):
+    def __init__(self, lengths: Sequence[int], owner=None, epoch: int = 0, continuable: bool = False, ids=None, next_pos=None):
         self.lengths = list(lengths)
+        self.ids = None if ids is None else [list(r) for r in ids]
+        self.next_pos = None if next_pos is None else list(next_pos)
         # which model's cache this describes and at which point of its history: the engine owns ONE cache, so a handle is live only
         # until the next forward / generate (forward(past_key_values=...) checks it)
         self.owner, self.epoch, self.continuable = owner, epoch, continuable
@@ -246,17 +250,23 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return SimpleNamespace(loss=loss, logits=logits, past_key_values=PastKeyValues(seqlens, self, self._kv_epoch, shifts is None and Bsz <= mb),
                                hidden_states=None, attentions=None)
 
+    def _check_handle(self, past_key_values, who: str):
+        if not isinstance(past_key_values, PastKeyValues) or past_key_values.owner is not self or past_key_values.epoch != self._kv_epoch:
+            raise ValueError(f"{who}(past_key_values=...): this cache handle is stale - the engine owns ONE cache, and a later forward / "
+                             "generate call has overwritten it")
+        if not past_key_values.continuable:
+            raise NotImplementedError(f"{who}(past_key_values=...) after a left-padded or chunked batch: re-run the prompt right-padded")
+
     def _forward_continue(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, labels, images):
         """forward(input_ids [B, T], past_key_values=<handle of the previous forward>): HF's step API (hf:models/mistral/modeling_mistral.py
         forward with a cache).  The KV cache is the engine's, so only the handle of the LATEST forward on this model is live; the new
-        tokens run as decode steps on top of it (teacher-forced), logits [B, T, V] and a handle T positions longer come back."""
-        if not isinstance(past_key_values, PastKeyValues) or past_key_values.owner is not self or past_key_values.epoch != self._kv_epoch:
-            raise ValueError("forward(past_key_values=...): this cache handle is stale - the engine owns ONE cache, and a later forward / "
-                             "generate call has overwritten it")
-        if not past_key_values.continuable:
-            raise NotImplementedError("forward(past_key_values=...) after a left-padded or chunked batch: re-run the prompt right-padded")
+        tokens run on top of it (teacher-forced), logits [B, T, V] and a handle T positions longer come back.  Fewer than
+        `vz_hip.append.APPEND_MIN_NEW` new tokens run as decode steps; from there on ONE append prefill (`Engine.prefill_append`, DESIGN.md
+        section 6l) puts all T behind the cache in a single weight sweep.  Rows may differ in cached length."""
+        self._check_handle(past_key_values, "forward")
         if images is not None or inputs_embeds is not None or labels is not None or input_ids is None:
             raise NotImplementedError("forward(past_key_values=...) takes new input_ids only (the decode step embeds token ids on the device)")
+        from vz_hip.append import APPEND_MIN_NEW
         ids = input_ids.to(self.device)
         Bsz, T = ids.shape
         if Bsz != len(past_key_values.lengths):
@@ -266,14 +276,27 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         lens = list(past_key_values.lengths)
         if max(lens) + T > self.engine.max_ctx:
             raise ValueError(f"forward(past_key_values=...): {max(lens) + T} positions exceed max_ctx = {self.engine.max_ctx}")
-        out = torch.empty(Bsz, T, self.arch.vocab, dtype=torch.float32, device=self.device)
-        for t in range(T):
-            pos = [int(position_ids[b, t]) for b in range(Bsz)] if position_ids is not None else [l + t for l in lens]
-            self.engine.decode_begin(ids[:, t].to(torch.int32).contiguous(), pos, [l + t for l in lens])
-            _, lg = self.engine.decode_steps(1, return_logits=True)
-            out[:, t] = lg[0]
+        pos0 = lens if past_key_values.next_pos is None else list(past_key_values.next_pos)
+        if T >= APPEND_MIN_NEW:
+            if self.engine.tp_size > 1:
+                raise NotImplementedError(f"forward(past_key_values=...) with {T} >= {APPEND_MIN_NEW} new tokens on a tensor-parallel engine is not built")
+            pos = position_ids if position_ids is not None else \
+                torch.tensor([[p + t for t in range(T)] for p in pos0], dtype=torch.int32)
+            if int(pos.max()) >= self.engine.max_ctx:
+                raise ValueError(f"forward(past_key_values=...): rotary position {int(pos.max())} exceeds max_ctx = {self.engine.max_ctx}")
+            out, _ = self.engine.prefill_append(0, self.get_model().embed_tokens(ids), [T] * Bsz, lens, pos, all_logits=True, last_logits=False)
+        else:
+            out = torch.empty(Bsz, T, self.arch.vocab, dtype=torch.float32, device=self.device)
+            for t in range(T):
+                pos = [int(position_ids[b, t]) for b in range(Bsz)] if position_ids is not None else [p + t for p in pos0]
+                self.engine.decode_begin(ids[:, t].to(torch.int32).contiguous(), pos, [l + t for l in lens])
+                _, lg = self.engine.decode_steps(1, return_logits=True)
+                out[:, t] = lg[0]
         self._kv_epoch += 1
-        return SimpleNamespace(loss=None, logits=out, past_key_values=PastKeyValues([l + T for l in lens], self, self._kv_epoch, True),
+        nxt = [int(position_ids[b, -1]) + 1 for b in range(Bsz)] if position_ids is not None else [p + T for p in pos0]
+        known = None if past_key_values.ids is None else [r + ids[b].tolist() for b, r in enumerate(past_key_values.ids)]
+        return SimpleNamespace(loss=None, logits=out,
+                               past_key_values=PastKeyValues([l + T for l in lens], self, self._kv_epoch, True, known, nxt),
                                hidden_states=None, attentions=None)
 
     __call__ = forward
@@ -312,12 +335,18 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, images=None, images_size=None, **kwargs):
         self._ensure_ready()
+        if kwargs.get("past_key_values") is not None:
+            return self._generate_continue(input_ids, kwargs.pop("past_key_values"), kwargs)
+        kwargs.pop("past_key_values", None)
         self._kv_epoch += 1
         position_ids = kwargs.pop("position_ids", None)
         attention_mask = kwargs.pop("attention_mask", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported in this generate function.")
         mask_in = attention_mask
+        if kwargs.get("return_dict_in_generate") and input_ids is not None:      # what the returned cache handle remembers (vz_hip/append.py)
+            from vz_hip import append as AP
+            kwargs["_prompt_rows"] = lambda: AP.masked_rows(input_ids, mask_in)
         neg = self._negative_branch(input_ids, kwargs)
         if neg is not None:
             kwargs["_guidance"] = neg
@@ -332,6 +361,46 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             # built only once the call is known to run with drafts (_generate_from_embeds): every other call stays as it was
             kwargs["_spec_history"] = lambda: self._spec_history(input_ids, mask_in, images, inputs_embeds.shape[1])
         return self._generate_from_embeds(inputs_embeds, attention_mask, position_ids, **kwargs)
+
+    def _generate_continue(self, input_ids, handle, kwargs):
+        """generate(input_ids=<the whole conversation so far>, past_key_values=<the handle the previous call returned>): HF's way to
+        continue a conversation.  The cached positions stay as they were computed (the reference re-conditions the Q-Former on the whole
+        conversation every turn; a caller who hands over a cache gets HF's semantics instead - DESIGN.md section 6l); only the new ids
+        are embedded and put behind them by one append prefill, and the call goes on as any other from the first token.  `images` is
+        ignored: the cached part holds them, as HF drops pixel values after its first step."""
+        from vz_hip import append as AP
+        from vis_zephyr.constants import IMAGE_TOKEN_INDEX
+        self._check_handle(handle, "generate")
+        eng = self.engine
+        if "inputs_embeds" in kwargs:
+            raise NotImplementedError("`inputs_embeds` is not supported in this generate function.")
+        if (kwargs.get("num_beams") or 1) != 1:
+            raise NotImplementedError("generate(past_key_values=...) with num_beams > 1 is not built: the beams' rows start from one prompt prefill")
+        scale = kwargs.get("guidance_scale", getattr(self.generation_config, "guidance_scale", None))
+        if (scale is not None and scale != 1) or kwargs.get("negative_prompt_ids") is not None:      # (checked before anything is embedded)
+            raise NotImplementedError("generate(past_key_values=...) with guidance_scale is not built: the negative prompt's cache row is not kept")
+        for k in ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_images", "negative_images_size"):
+            kwargs.pop(k, None)
+        if (kwargs.get("num_return_sequences") or 1) != 1:
+            raise NotImplementedError("generate(past_key_values=...) with num_return_sequences > 1 is not built: one cache row per conversation is kept")
+        if eng.tp_size > 1:
+            raise NotImplementedError("generate(past_key_values=...) on a tensor-parallel engine is not built")
+        if input_ids is None or input_ids.shape[0] > min(eng.max_batch, 64):
+            raise NotImplementedError(f"generate(past_key_values=...) needs input_ids of at most max_batch = {min(eng.max_batch, 64)} rows")
+        attention_mask = kwargs.pop("attention_mask", None)
+        kwargs.pop("position_ids", None)          # the cached part fixes every row's positions
+        rows = AP.masked_rows(input_ids, attention_mask)
+        plan = AP.plan(rows, handle.lengths, handle.ids, handle.next_pos, IMAGE_TOKEN_INDEX)
+        Bsz, T = len(rows), plan.width          # (the handle goes stale in `_generate_from_embeds`, behind that function's own refusals)
+        ids = torch.zeros(Bsz, T, dtype=torch.long)
+        mask = torch.zeros(Bsz, T, dtype=torch.long)
+        for b, new in enumerate(plan.suffix):
+            ids[b, :len(new)] = torch.tensor(new, dtype=torch.long)
+            mask[b, :len(new)] = 1
+        pos = torch.tensor([[min(p + t, eng.max_ctx - 1) for t in range(T)] for p in plan.next_pos], dtype=torch.int32)      # (padding stays inside the rotary tables)
+        kwargs["_prompt_rows"] = lambda: rows
+        return self._generate_from_embeds(self.get_model().embed_tokens(ids.to(self.device)), mask.to(self.device), pos.to(self.device),
+                                          _append=plan, **kwargs)
 
     def _negative_branch(self, input_ids, kwargs):
         """takes the guidance keywords out of a generate() call's `kwargs`: None = guidance is off, else the call's unconditional branch
@@ -386,7 +455,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True,
                               min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
                               eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, beam_extended: bool = False,
-                              _guidance=None, **unused):
+                              _guidance=None, _append=None, _prompt_rows=None, **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -436,7 +505,19 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         log-softmax rows, in front of the processors, and the token chosen on it is fed to both rows.  Greedy and sampled, batched,
         `num_return_sequences`, streamer, processors, scores and device stops all take it; `output_logits` rows are the conditional raw
         logits, `output_scores` rows and the log-probs are taken behind the combine.  `num_beams > 1` and tensor-parallel engines raise
-        NotImplementedError, `max_batch < 2` ValueError; `prompt_lookup_num_tokens` takes the guided greedy path."""
+        NotImplementedError, `max_batch < 2` ValueError; `prompt_lookup_num_tokens` takes the guided greedy path.
+
+        The cache handle (vz_hip/append.py): with `return_dict_in_generate=True` the output's `past_key_values` is a
+        live handle whenever the rows of the call are the engine's cache rows - one sequence, or a greedy batch that decodes together;
+        None for beams, guidance, `num_return_sequences > 1`, prompt lookup and batches run in parts.  It records per row the cached
+        positions (the spliced prompt plus every emitted token but the last, as HF leaves its cache), the next rotary position and the
+        ids those positions stand for.  `generate(<the whole conversation so far>, past_key_values=handle)` (`_generate_continue`) puts
+        only the new ids behind the cache.  The logits processors' histories and the stop matcher's rings of such a call start from the
+        conversation so far (`Engine.seed_history`): `repetition_penalty`, the n-gram ban, `sequence_bias` and `bad_words_ids` see the cached
+        ids as HF's see a prompt's, a stop string may begin in them, host-side criteria get them in front of the new ids; `min_new_tokens`
+        and the id-sequence stops count generated ids only.  `num_beams > 1`, guidance, `num_return_sequences > 1`, more rows than
+        `max_batch`, tensor-parallel engines and a sampled or per-token batch of several rows raise NotImplementedError - all before the
+        handle goes stale; `prompt_lookup_num_tokens` takes the plain path."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
         from vz_hip import stop as ST
@@ -446,7 +527,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         what = SC.check_outputs(return_dict_in_generate, output_scores, output_logits, output_logprobs, num_beams, bool(beam_extended))
         sink = SC.Sink(what) if what else None
         Bsz, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length, S, pad_token_id)
+        app = _append                        # continuing on a kept cache (vz_hip.append.Plan): the embeddings are the new suffix only
+        d = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens, max_length,
+                                S if app is None else max(p + n for p, n in zip(app.past, app.new_lens)), pad_token_id)
         eos = d.eos
         # HF's logits processors (csrc/logits_proc.hip): None = none of the four keywords is active, every path below is as it was
         gcf = self.generation_config
@@ -493,11 +576,22 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                       device=generator.device if generator is not None else "cpu").item())
         inputs_embeds, attention_mask, position_ids, _ = self._to_right_padded(inputs_embeds, attention_mask, position_ids)
         seqlens = self._seqlens(attention_mask, Bsz, S)
-        done = lambda seqs: self._generate_output(seqs, sink, eos, return_dict_in_generate)      # noqa: E731  (the plain tensor unless asked)
+        def done(seqs, cached: bool = False):      # the plain tensor unless asked; cached: the call's rows are the engine's cache rows
+            out = self._generate_output(seqs, sink, eos, return_dict_in_generate)
+            if return_dict_in_generate and cached and _prompt_rows is not None:
+                out.past_key_values = self._handle_after(seqs, eos, pad_token_id if stop is not None and Bsz > 1 else None, _prompt_rows())
+            return out
+        if app is not None:                  # every refusal of a continued call lies in front of this line: a refused call leaves the handle live
+            if Bsz > 1 and not (greedy and streamer is None and stopping_criteria is None):
+                raise NotImplementedError("generate(past_key_values=...): a sampled batch, or one with a streamer or stopping criteria, runs one "
+                                          "sequence at a time through cache row 0 and cannot continue several kept rows")
+            if max(app.past) + S + max_new_tokens > self.engine.max_ctx:
+                raise ValueError(f"prompt ({max(app.past) + S}) + max_new_tokens ({max_new_tokens}) exceeds the engine's max_ctx ({self.engine.max_ctx})")
+            self._kv_epoch += 1
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
                                                pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp, neg=neg))
-        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None and neg is None:      # (with processors, scores, device stops or guidance: the plain / guided greedy path)
+        if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None and neg is None and app is None:      # (with processors, scores, device stops or guidance: the plain / guided greedy path)
             # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
@@ -512,15 +606,26 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                           _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
                 return done(torch.tensor([out], dtype=torch.long, device=self.device))
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
-            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop, neg))
+            return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop, neg, app),
+                        cached=neg is None and Bsz <= min(self.engine.max_batch, 64))
         outs = []
         for b in range(Bsz):               # per-token host callbacks / sampling: one sequence at a time
             outs.append(self._generate_one(inputs_embeds[b:b + 1, :seqlens[b]],
                                            None if position_ids is None else position_ids[b:b + 1, :seqlens[b]],
                                            max_new_tokens, greedy, temperature, top_p, top_k, eos, streamer if Bsz == 1 else None,
                                            stopping_criteria, seed + b, sync_every, timing, proc, sink, stop, warp,
-                                           None if neg is None else neg.rows(b, b + 1)))
-        return done(DL.pad_parts([torch.tensor([o], dtype=torch.long, device=self.device) for o in outs], pad_token_id, self.device))
+                                           None if neg is None else neg.rows(b, b + 1), app))
+        return done(DL.pad_parts([torch.tensor([o], dtype=torch.long, device=self.device) for o in outs], pad_token_id, self.device),
+                    cached=neg is None and Bsz == 1)
+
+    def _handle_after(self, seqs, eos, fill, prompt_rows):
+        """the cache handle of a finished generate() call whose rows are the engine's cache rows (vz_hip.append.after_generate)"""
+        from vz_hip import append as AP
+        rows = seqs.tolist()
+        emitted = [r[:n] for r, n in zip(rows, AP.emitted_counts(rows, eos, fill))]
+        next_pos, ctx_len = self._begin_state
+        lengths, pos, ids = AP.after_generate(prompt_rows, ctx_len, next_pos, emitted)
+        return PastKeyValues(lengths, self, self._kv_epoch, True, ids, pos)
 
     def _generate_output(self, seqs, sink, eos, return_dict_in_generate):
         """what generate() returns for the new tokens `seqs` [rows, T]: the tensor, or HF's output object with what `sink` recorded"""
@@ -561,7 +666,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return out
 
     def _generate_batched(self, embeds, seqlens, position_ids, max_new, eos, pad_token_id, sync_every, timing=None, proc=None, sink=None,
-                          stop=None, neg=None) -> torch.Tensor:
+                          stop=None, neg=None, app=None) -> torch.Tensor:
         """Greedy decoding of up to `max_batch` (<= 64) sequences at once: one right-padded prefill, then every decode step
         streams the weights once for all rows (the KV cache, positions and lengths are per slot).  Rows that hit eos keep
         their slot but emit `pad_token_id` from then on, as HF does.  `proc`: HF's logits processors (vz_hip.logits_proc) on the
@@ -576,18 +681,19 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                                              max_new, eos, pad_token_id, sync_every, tm, proc, sink, stop,
                                                              None if neg is None else neg.rows(lo, hi))
             return DL.run_parts(part, Bsz, cap, pad_token_id, self.device, timing)
-        if S + max_new > eng.max_ctx:
-            raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
+        if S + max_new + (0 if app is None else max(app.past)) > eng.max_ctx:
+            raise ValueError(f"prompt ({S + (0 if app is None else max(app.past))}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         from vz_hip.sample_rows import GREEDY
         if neg is None:
-            _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
-            next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
-            ctx_len, uncond = list(seqlens), None
+            last, next_pos, ctx_len = DL.prefill_or_append(eng, embeds, seqlens, position_ids, app)
+            self._begin_state = (list(next_pos), list(ctx_len))      # what the rows hold in front of the first emitted token: for the call's cache handle
+            uncond = None
         else:
             last, last_u, next_pos, ctx_len = DL.pair_prefill(eng, embeds, seqlens, position_ids, neg)
             uncond = (last_u, neg.scale)
-        first, first_cpu, blk = DL.first_tokens(last, [GREEDY] * Bsz, proc, sink, timing, uncond=uncond)
-        with DL.armed(eng, proc=proc, scores=DL.chunk_recorder(sink, Bsz, sync_every, max_new), stop=stop,
+        hist = None if app is None else app.history
+        first, first_cpu, blk = DL.first_tokens(last, [GREEDY] * Bsz, proc, sink, timing, uncond=uncond, history=hist)
+        with DL.armed(eng, proc=proc, scores=DL.chunk_recorder(sink, Bsz, sync_every, max_new), stop=stop, history=hist,
                       guidance=None if neg is None else neg.config(Bsz)) as begin:
             begin(first, next_pos, ctx_len)
             return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
@@ -963,7 +1069,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         return self._ring
 
     def _generate_one(self, embeds, position_ids, max_new, greedy, temperature, top_p, top_k, eos, streamer,
-                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None, warp=None, neg=None) -> List[int]:
+                      stopping_criteria, seed, sync_every, timing=None, proc=None, sink=None, stop=None, warp=None, neg=None, app=None) -> List[int]:
         """One sequence.  The first token comes from the prefill logits (argmax / one draw of the device sampler with counter 0),
         every later one from a replay of the per-token hipGraph whose tail is the argmax or the sampling kernel - also on the path
         `script/run_cli.sh` takes (streamer + stopping criteria + do_sample, ref:vis_zephyr/serve/cli.py:155-182): there the host
@@ -974,11 +1080,12 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         from vz_hip.sample_rows import GREEDY, RowParams
         eng = self.engine
         S = embeds.shape[1]
-        if S + max_new > eng.max_ctx:
-            raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
+        if S + max_new + (0 if app is None else app.past[0]) > eng.max_ctx:
+            raise ValueError(f"prompt ({S + (0 if app is None else app.past[0])}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
         if neg is None:
-            _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
-            next_pos, ctx_len, uncond, guid = [S if position_ids is None else int(position_ids[0, -1]) + 1], [S], None, None
+            last, next_pos, ctx_len = DL.prefill_or_append(eng, embeds, [S], position_ids, app)
+            self._begin_state = (list(next_pos), list(ctx_len))
+            uncond, guid = None, None
         else:
             last, last_u, next_pos, ctx_len = DL.pair_prefill(eng, embeds, [S], position_ids, neg)
             uncond, guid = (last_u, neg.scale), neg.config(1)
@@ -989,23 +1096,27 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             streamer.put(torch.empty((1, 0), dtype=torch.long))
         par = GREEDY if greedy else RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), 0, 0, **(warp or {}))
         more = () if par.warp is None else (par.warp,)      # the further warpers' column, named only when one is active
-        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed) + more, uncond)
+        hist = None if app is None else app.history          # continuing on a kept cache: what the row was fed so far (the filters' histories)
+        seen = [] if hist is None else hist[0]                # ... and what host-side stopping criteria see in front of the new tokens
+        first, first_cpu, blk = DL.first_tokens(last, [par], proc, sink, timing, None if greedy else (temperature, top_k, top_p, seed) + more, uncond,
+                                                history=hist)
         out: List[int] = [int(first_cpu[0])]
-        if self._emit(out, streamer, stopping_criteria, None, eos) or max_new <= 1:
+        if self._emit(out, streamer, stopping_criteria, None, eos, seen) or max_new <= 1:
             return self._finish(out, streamer)
         # the step's tail: a greedy call names it only with the ring, whose slot is the draw counter that `set_sampling` starts at 1
         tail = None if greedy and not per_token else (not greedy, 1.0 if greedy else temperature, top_k, top_p, seed, 1) + more
         if not per_token:
             # no host callbacks: steps are enqueued back to back, the host looks at the ids every `sync_every` tokens only to honour eos
             # and the stop conditions the device decides (vz_hip.stop)
-            with DL.armed(eng, proc=proc, sampling=tail, scores=DL.chunk_recorder(sink, 1, sync_every, max_new), stop=stop, guidance=guid) as begin:
+            with DL.armed(eng, proc=proc, sampling=tail, scores=DL.chunk_recorder(sink, 1, sync_every, max_new), stop=stop, guidance=guid,
+                          history=hist) as begin:
                 begin(first, next_pos, ctx_len)
                 return DL.decode_rows(eng, first_cpu, max_new, eos, 0, sync_every, blk, stop is not None)[0].tolist()
         ring = self._token_ring()
         R = ring.numel()
         # with a sink: a device ring of max_new slots, read once at the end - no step waits for its record
         with DL.armed(eng, proc=proc, sampling=tail, ring=ring, scores=None if blk is None else (max_new, 1, sink.warped, sink.raw),
-                      guidance=guid) as begin:
+                      guidance=guid, history=hist) as begin:
             begin(first, next_pos, ctx_len)
             dev_out = torch.empty(1, 1, dtype=torch.int32, device=self.device)
             events = {}
@@ -1023,7 +1134,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     launch(t + 1)        # speculative: its cache slot / ring slot are simply ignored if token t stops the sequence
                 events.pop(t).synchronize()
                 out.append(int(ring[t % R]))
-                if self._emit(out, streamer, stopping_criteria, None, eos) or len(out) >= max_new:
+                if self._emit(out, streamer, stopping_criteria, None, eos, seen) or len(out) >= max_new:
                     break
                 t += 1
             torch.cuda.current_stream(self.device).synchronize()      # a speculative step may still be running
@@ -1032,13 +1143,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                 blk.add(*eng.scores_steps(len(out) - 1, first=0))     # (a speculative step's record behind them is not read)
             return self._finish(out, streamer)
 
-    def _emit(self, out, streamer, stopping_criteria, scores, eos) -> bool:
-        """per-token host callbacks; returns True when generation must stop."""
+    def _emit(self, out, streamer, stopping_criteria, scores, eos, seen=()) -> bool:
+        """per-token host callbacks; returns True when generation must stop.  seen: the ids in front of `out` that the criteria see with it
+        (a call that continues on a kept cache: the conversation so far, as HF's criteria see its input_ids)."""
         if streamer is not None:
             streamer.put(torch.tensor([out[-1]], dtype=torch.long))
         stop = out[-1] in eos
         if stopping_criteria is not None and not stop:
-            ids = torch.tensor([out], dtype=torch.long, device=self.device)
+            ids = torch.tensor([list(seen) + out], dtype=torch.long, device=self.device)
             crits = stopping_criteria if isinstance(stopping_criteria, (list, tuple)) else [stopping_criteria]
             for c in crits:
                 r = c(ids, scores)

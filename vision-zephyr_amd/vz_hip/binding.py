@@ -66,6 +66,8 @@ SYMBOLS = {
     "vz_op_transpose": (_I, [_P, _L, _P, _L, _I, _I, _P]),
     "vz_op_colsum": (_I, [_P, _I, _L, _I, _P, _L, _P, _P]),
     "vz_op_colsum_groups": (_I, [_L]),
+    "vz_op_attention_append": (_I, [_P] * 6 + [_I] * 7 + [_L] * 6 + [_F, _I, _I, _P, _L, _P]),
+    "vz_op_attention_append_ws_floats": (_L, [_I] * 5),
     "vz_op_attention_bwd": (_I, [_P] * 7 + [_I] * 7 + [_F, _I, _I, _P, _P, _L, _P]),
     "vz_op_attention_split": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I] + [_L] * 12 + [_F, _I, _I, _I, _P, _P, _L, _P]),
     "vz_op_argmax": (_I, [_P, _I, _I, _P, _P]),
@@ -86,6 +88,7 @@ SYMBOLS = {
     "vz_embed_splice": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "vz_llm_prefill": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int), _P, _P, _P, _P]),
     "vz_llm_prefill_rows": (_I, [_P, _I, _P, _I, _I, C.POINTER(C.c_int), _P, _P, _P, _P]),
+    "vz_llm_prefill_append": (_I, [_P, _I, _P, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, _P, _P, _P]),
     "vz_llm_decode_set_row": (_I, [_P, _I, _I, _I, _I, _P]),
     "vz_llm_kv_move_rows": (_I, [_P, _I, _P, _P, _P, _P]),
     "vz_llm_decode_begin": (_I, [_P, _I, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
@@ -147,6 +150,8 @@ SYMBOLS = {
     "vz_op_token_scores_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vz_llm_decode_stop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_stop_rows": (_I, [_P, _I, _I, _P, _P]),
+    "vz_llm_decode_stop_seed": (_I, [_P, _I, C.POINTER(C.c_int), _I, _P]),
+    "vz_llm_decode_logits_proc_seed": (_I, [_P, _I, C.POINTER(C.c_int), _I, _P]),
     "vz_llm_decode_stop_read": (_I, [_P, _I, _I, _P, _P]),
     "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
@@ -382,7 +387,7 @@ def linear_route(M: int, N: int, K: int, lda: Optional[int] = None, ldw: Optiona
     return (LIN_ROUTES[r] if 0 <= r < len(LIN_ROUTES) else "NONE"), bool(pre.value), sk.value
 
 
-STAGE_CLIP, STAGE_QFORMER, STAGE_PREFILL, STAGE_DECODE = range(4)
+STAGE_CLIP, STAGE_QFORMER, STAGE_PREFILL, STAGE_DECODE, STAGE_APPEND = range(5)
 WS_CALLER_HIDDEN, WS_QF_KV_CONTIG, WS_SPEC_TAIL = 1, 2, 4
 
 
@@ -871,6 +876,30 @@ def rope_kv(qkv, cos, sin, pos, slot, kcache, vcache, B_, S, Hq, Hkv, D):
     check(lib().vz_op_rope_kv(ptr(qkv), qkv.stride(0), ptr(q), ptr(kcache), ptr(vcache), ptr(cos), ptr(sin), ptr(pos),
                               ptr(slot), B_, S, Hq, Hkv, D, kcache.shape[2], stream_ptr(qkv.device)))
     return q
+
+
+def attention_append_ws_floats(B, T, Hq, Hkv, max_ctx) -> int:
+    """fp32 workspace elements that cover every key split vz_op_attention_append's host rule can choose; needs no GPU."""
+    return lib().vz_op_attention_append_ws_floats(B, T, Hq, Hkv, max_ctx)
+
+
+def attention_append(q, kcache, vcache, past, new, scale, kv_max, window=0, nsplit=0, out=None):
+    """q rotated bf16 [B,T,Hq,128] (unit stride on D); caches [B,Hkv,max_ctx,128] holding the new tokens' K / V at slots past[b] ..
+    past[b]+new[b]-1; past / new int32 [B] on the device; kv_max = max(past + new) (host) -> o [B,T,Hq,128] (`out` or a new tensor;
+    token rows >= new[b] are not written).  nsplit 0 = the host rule, n >= 1 forced."""
+    _need_cuda(q, kcache, vcache, past, new)
+    B, T, Hq, D = q.shape
+    Hkv, max_ctx = kcache.shape[1], kcache.shape[2]
+    assert q.dtype == torch.bfloat16 and q.stride(3) == 1 and kcache.is_contiguous() and vcache.is_contiguous()
+    assert past.dtype == torch.int32 and new.dtype == torch.int32 and past.numel() == B and new.numel() == B
+    o = torch.empty(B, T, Hq, D, dtype=torch.bfloat16, device=q.device) if out is None else out
+    assert o.dtype == torch.bfloat16 and o.stride(3) == 1 and tuple(o.shape) == (B, T, Hq, D)
+    floats = max(attention_append_ws_floats(B, T, Hq, Hkv, max_ctx), B * Hq * T * min(nsplit, (kv_max + 63) // 64) * (D + 4), 1)
+    ws = torch.empty(floats, dtype=torch.float32, device=q.device)
+    check(lib().vz_op_attention_append(ptr(q), ptr(kcache), ptr(vcache), ptr(o), ptr(past), ptr(new), B, T, Hq, Hkv, D, max_ctx, int(kv_max),
+                                       q.stride(0), q.stride(1), q.stride(2), o.stride(0), o.stride(1), o.stride(2),
+                                       float(scale), window, nsplit, ptr(ws), ws.numel(), stream_ptr(q.device)))
+    return o
 
 
 def attention_decode(q, kcache, vcache, ctx_len, scale, nsplit=8, window=0):

@@ -34,7 +34,19 @@ def resolve_defaults(gen, eos_token_id=None, max_new_tokens=None, max_length=Non
     return CallDefaults(eos, set(eos), int(max_new_tokens), pad_token_id, pad_token_id if pad_token_id is not None else min(eos, default=0))
 
 
-def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None, uncond=None):
+def prefill_or_append(eng, embeds, seqlens, position_ids=None, app=None):
+    """The prompts into cache rows 0 .. (`Engine.prefill`) or, continuing on a kept cache (app: vz_hip.append.Plan), the new suffixes
+    behind what the rows hold (`Engine.prefill_append`): (last-position logits [B, V], next_pos, ctx_len) as `begin` takes them."""
+    Bsz = embeds.shape[0]
+    if app is None:
+        _, last = eng.prefill(embeds, seqlens, position_ids, all_logits=False, last_logits=True)
+        next_pos = [int(seqlens[b]) if position_ids is None else int(position_ids[b, seqlens[b] - 1]) + 1 for b in range(Bsz)]
+        return last, next_pos, list(seqlens)
+    _, last = eng.prefill_append(0, embeds, seqlens, app.past, position_ids, all_logits=False, last_logits=True)
+    return last, [app.next_pos[b] + int(seqlens[b]) for b in range(Bsz)], [app.past[b] + int(seqlens[b]) for b in range(Bsz)]
+
+
+def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None, uncond=None, history=None):
     """The first token of every row, chosen on the prefill logits `last` [prompts, V] (processed in place by `proc`, whose first step
     sees an empty history): (first - device, first - host, the sink's block of these rows or None).  uncond = (the negative prompts'
     prefill logits [prompts, V], guidance scale): `last` becomes HF's guided scores in front of `proc` (B.cfg_combine; the sink's raw
@@ -42,13 +54,26 @@ def first_tokens(last, params, proc=None, sink=None, timing=None, draw=None, unc
     vz_hip.sample_rows.RowParams per row; with n times as many rows as prompts each prompt's logits row serves its n adjacent rows.
     The choice is B.argmax when no row samples, else B.sample_rows; draw = (temperature, top_k, top_p, seed[, warp]): the serial sampled
     sequence's B.sample(..., seed, 0[, warp]) instead (`params` then only describes the row to the sink).  timing: stamped once the host
-    holds the tokens."""
+    holds the tokens.  history (a call that continues on a kept cache): per row the ids fed so far - `proc` then sees them as HF's
+    processors see a prompt's ids, while min_new_tokens, which counts generated ids, runs over an empty history in a pass of its own
+    (it only writes -inf, so the two passes commute)."""
     keep_raw = sink is not None and sink.raw
     raw = last.clone() if keep_raw and (proc is not None or uncond is not None) else last
     if uncond is not None:
         B.cfg_combine(last, uncond[0], uncond[1])
-    if proc is not None:
+    if proc is not None and history is None:
         B.logits_process(last, proc)
+    elif proc is not None:
+        import dataclasses
+        seen = dataclasses.replace(proc, min_new=0, eos=())
+        if seen.penalty != 1.0 or seen.ngram or seen.suppress or seen.seq:
+            width = max(1, max(len(h) for h in history))
+            hist = torch.zeros(len(history), width, dtype=torch.int32)
+            for r, h in enumerate(history):
+                hist[r, :len(h)] = torch.tensor([int(t) for t in h], dtype=torch.int32)
+            B.logits_process(last, seen, hist.to(last.device), torch.tensor([len(h) for h in history], dtype=torch.int32, device=last.device))
+        if proc.min_new > 0:
+            B.logits_process(last, type(proc)(min_new=proc.min_new, eos=proc.eos))
     n = len(params) // last.shape[0]
     if n > 1:                                                    # a prompt's one logits row, once per sample
         last, raw = last.repeat_interleave(n, dim=0).contiguous(), raw.repeat_interleave(n, dim=0) if keep_raw else None
@@ -74,7 +99,8 @@ def chunk_recorder(sink, rows: int, sync_every: int, max_new: int):
 
 
 @contextmanager
-def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None, guidance=None):
+def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None, guidance=None,
+          history=None):
     """Arms what the call asked for in the one order the engine requires - logits processors, classifier-free guidance (`guidance`: a
     vz_hip.guidance.GuidanceConfig; `begin` then takes the first tokens of the conditional rows and the positions of all 2 * pairs rows,
     and hands each first token to both rows of its pair), the step's tail (`sampling`: the arguments
@@ -82,7 +108,9 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
     `set_scores`), the stop matcher, the beam tail's row recorder (`beam_rows`: the arguments of `set_beam_rows`), the beam tail (`beam`:
     the arguments of `set_beam`) - all in front of the batch's `decode_begin`,
     and yields `begin(first, next_pos, ctx_len)`: `decode_begin`, then the matcher takes the rows' first tokens.  On the way out,
-    whatever happened (a failed arming included), exactly what was armed is disarmed, last first.  None = not asked for: not called."""
+    whatever happened (a failed arming included), exactly what was armed is disarmed, last first.  None = not asked for: not called.
+    history (a call that continues on a kept cache): per row the ids fed before the first token - the processors' histories and the stop
+    matcher's rings start from them (`Engine.seed_history`)."""
     undo = []
 
     def arm(name, args, off):
@@ -97,6 +125,8 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
     try:
         if proc is not None:
             arm("set_logits_proc", (proc,), (None,))
+            if history is not None:
+                eng.seed_history(history, proc=True)
         if guidance is not None:
             arm("set_guidance", (guidance,), (None,))
         if sampling is not None:
@@ -109,6 +139,8 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
             arm("set_scores", scores, (None,))
         if stop is not None:
             arm("set_stop", (stop,), (None,))
+            if history is not None:
+                eng.seed_history(history, stop=True)
         if beam_rows is not None:
             arm("set_beam_rows", beam_rows, (None,))
         if beam is not None:

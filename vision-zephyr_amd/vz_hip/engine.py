@@ -551,6 +551,29 @@ class Engine:
         B.check(self.lib.vz_llm_prefill_rows(self.h, int(row0), B.ptr(x), Bn, S, sl, B.ptr(pos), None, B.ptr(ll), self._s()))
         return ll
 
+    def prefill_append(self, row0: int, embeds: torch.Tensor, new_lens: Sequence[int], past_lens: Sequence[int],
+                       position_ids: Optional[torch.Tensor] = None, all_logits: bool = False, last_logits: bool = True):
+        """embeds bf16 [B,T,H] right-padded: new_lens[b] rows go behind the past_lens[b] positions cache row row0+b keeps, at cache
+        slots past+t and rotary positions position_ids[b,t] (default past+t).  Returns (logits_all fp32 [B,T,V] | None, logits_last
+        fp32 [B,V] | None); logits_all rows t >= new_lens[b] come from padding."""
+        cfg = self.cfg
+        x = embeds.to(self.device, torch.bfloat16).contiguous()
+        Bn, T = x.shape[0], x.shape[1]
+        if len(new_lens) != Bn or len(past_lens) != Bn:
+            raise ValueError(f"prefill_append: {Bn} samples, {len(new_lens)} new lengths, {len(past_lens)} past lengths")
+        if position_ids is None:
+            position_ids = (torch.tensor([int(p) for p in past_lens], dtype=torch.int32).unsqueeze(1)
+                            + torch.arange(T, dtype=torch.int32).unsqueeze(0)).clamp_(max=self.max_ctx - 1)      # (padding rows stay inside the rotary tables)
+        pos = position_ids.to(self.device, torch.int32).contiguous()
+        if tuple(pos.shape) != (Bn, T):
+            raise ValueError(f"prefill_append: position_ids {tuple(pos.shape)}, expected {(Bn, T)}")
+        la = torch.empty(Bn, T, cfg.vocab, dtype=torch.float32, device=self.device) if all_logits else None
+        ll = torch.empty(Bn, cfg.vocab, dtype=torch.float32, device=self.device) if last_logits else None
+        nl = (C.c_int * Bn)(*[int(v) for v in new_lens])
+        pl = (C.c_int * Bn)(*[int(v) for v in past_lens])
+        B.check(self.lib.vz_llm_prefill_append(self.h, int(row0), B.ptr(x), Bn, T, nl, pl, B.ptr(pos), B.ptr(la), B.ptr(ll), self._s()))
+        return la, ll
+
     def kv_move_rows(self, src: Sequence[int], dst: Sequence[int], lens: Sequence[int]):
         """first lens[i] cache positions of row src[i] -> row dst[i] (all layers), stream-ordered behind the prefill that wrote them."""
         n = len(src)
@@ -647,6 +670,19 @@ class Engine:
         kernel: call it where `decode_begin` / `decode_set_row` arm those rows"""
         ids = first_ids.to(self.device, torch.int32).contiguous().view(-1)
         B.check(self.lib.vz_llm_decode_stop_rows(self.h, int(row0), ids.numel(), B.ptr(ids), self._s()))
+
+    def seed_history(self, rows, proc: bool = False, stop: bool = False):
+        """rows: per cache row the ids that were fed before generation begins (a call that continues on a kept cache).  proc: they become
+        the logits processors' histories (min_new_tokens still counts generated ids only); stop: their tails enter the stop matcher's
+        rings, so a stop string may begin in them.  Behind `set_logits_proc` / `set_stop`, in front of `decode_begin` / `stop_rows`."""
+        for r, ids in enumerate(rows):
+            ids = [int(t) for t in ids]
+            if proc:
+                tail = ids[-self.max_ctx:]
+                B.check(self.lib.vz_llm_decode_logits_proc_seed(self.h, r, (C.c_int * len(tail))(*tail), len(tail), self._s()))
+            if stop:
+                tail = ids[-63:]
+                B.check(self.lib.vz_llm_decode_stop_seed(self.h, r, (C.c_int * len(tail))(*tail), len(tail), self._s()))
 
     def stop_at(self, row0: int, rows: int) -> torch.Tensor:
         """int32 [rows] (device): per row -1, or the 0-based index of the generated token at which a stop condition first held"""
