@@ -1,4 +1,4 @@
-"""The memory plan of the four inference stages (csrc/engine.hip: carve_clip, carve_qformer, carve_prefill, carve_decode) through
+"""The memory plan of the inference stages (csrc/engine.hip: carve_clip, carve_qformer, carve_prefill, carve_append, carve_decode) through
 vz_op_stage_ws_bytes - no GPU needed.  Each stage has one carving function that both sizes the arena and lays it out; the query runs the
 same function over a null arena.
 
@@ -87,6 +87,14 @@ def _prefill_takes(a, tp, Bn, S):
             (Bn * H * 2, BF16), (rows * max(H, A, inter), U8), (rows, F32)]
 
 
+def _append_takes(B, a, tp, Bn, T, max_ctx):
+    """the six row buffers, slot[rows] | kv_len[B] | past[B] | new[B], the last rows, the key-split kernel's partials"""
+    hq, hkv, inter, QKV, A = _shard(a, tp)
+    H, rows = a.hidden, Bn * T
+    return [(rows * H, BF16), (rows * H, BF16), (rows * QKV, BF16), (rows * A, BF16), (rows * A, BF16), (rows * inter, BF16), (rows + 3 * Bn + 16, I32),
+            (Bn * H * 2, BF16), (B.attention_append_ws_floats(Bn, T, hq, hkv, max_ctx), F32)]
+
+
 def _decode_takes(a, tp, Bn, spec):
     _, _, inter, QKV, A = _shard(a, tp)
     takes = [(Bn * a.hidden, BF16), (Bn * QKV, BF16), (Bn * A, BF16), (Bn * inter, BF16)]
@@ -123,6 +131,14 @@ def test_prefill_takes_what_it_took(B, tp):
     a, cfg = _arch(), _cfg(B, tp)
     for Bn, S in ((1, 1), (1, 40), (2, 96), (2, 512)):
         assert B.stage_ws_bytes(cfg, B.STAGE_PREFILL, Bn, S) == _carved(_prefill_takes(a, tp, Bn, S)), (Bn, S)
+
+
+@pytest.mark.parametrize("tp", TP_SIZES)
+def test_append_takes_what_it_took(B, tp):
+    a, cfg = _arch(), _cfg(B, tp)
+    for Bn, T in ((1, 1), (1, 20), (2, 260), (2, 512)):
+        assert B.stage_ws_bytes(cfg, B.STAGE_APPEND, Bn, T) == _carved(_append_takes(B, a, tp, Bn, T, CAP["max_ctx"])), (Bn, T)
+    assert B.stage_ws_bytes(cfg, B.STAGE_APPEND, 0, 8) == -1 and B.stage_ws_bytes(cfg, B.STAGE_APPEND, 1, CAP["max_ctx"] + 1) == -1
 
 
 @pytest.mark.parametrize("tp", TP_SIZES)

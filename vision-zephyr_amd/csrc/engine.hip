@@ -363,7 +363,7 @@ static int ensure_arena(vz_engine* e, size_t bytes) {
     return VZ_OK;
 }
 
-// A stage's workspace: its ONE carve function (carve_clip, carve_qformer, carve_prefill, carve_decode below; each takes dimensions, not
+// A stage's workspace: its ONE carve function (carve_clip, carve_qformer, carve_prefill, carve_append, carve_decode below; each takes dimensions, not
 // the engine, so vz_op_stage_ws_bytes asks the same function without a device) sizes the arena over a null base and then lays out the
 // real one; the mark it reaches is the stage's need (vz_engine_ws_info).
 template <typename Ws, typename Carve> static int carve_stage(vz_engine* e, const char* stage, Carve carve, Ws* ws) {
@@ -950,27 +950,178 @@ extern "C" int vz_tp_all_gather(vz_engine* e, const void* d_send, void* d_recv, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// a12: Zephyr prefill
+// a12: Zephyr prefill and append prefill - T rows per sample through the decoder stack (llm_rows_forward)
 // ------------------------------------------------------------------------------------------------
 static bf16_t* kc_of(vz_engine* e, int layer) { return e->kv + (size_t)layer * e->kv_layer_elems; }
 static bf16_t* vc_of(vz_engine* e, int layer) { return kc_of(e, layer) + e->kv_layer_elems / 2; }
 
-static bool prefill_shape_ok(const vz_config& c, int row0, int B, int S) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && S >= 1 && S <= c.max_ctx; }
-struct PrefillWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; unsigned char* q8; float* qs; };
-static PrefillWs carve_prefill(Carver& m, const vz_config& c, const Shard& sh, int B, int S) {
-    const size_t rows = (size_t)B * S, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, QKV = (size_t)(sh.Hq + 2 * sh.Hkv) * c.head_dim, I = sh.I;
-    PrefillWs w;
+static bool rows_shape_ok(const vz_config& c, int row0, int B, int T) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && T >= 1 && T <= c.max_ctx; }
+// q8, qs: carve_prefill only; part, part_floats: carve_append only
+struct RowsWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; unsigned char* q8 = nullptr; float* qs = nullptr; float* part = nullptr; size_t part_floats = 0; };
+// what both carvings begin with; `tables` = the [B] int tables behind slot[rows]
+static RowsWs carve_rows_head(Carver& m, const vz_config& c, const Shard& sh, int B, int T, int tables) {
+    const size_t rows = (size_t)B * T, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, QKV = (size_t)(sh.Hq + 2 * sh.Hkv) * c.head_dim, I = sh.I;
+    RowsWs w;
     w.x = m.take<bf16_t>(rows * H);
     w.y = m.take<bf16_t>(rows * H);
     w.qkv = m.take<bf16_t>(rows * QKV);
     w.q = m.take<bf16_t>(rows * A);
     w.att = m.take<bf16_t>(rows * A);
     w.act = m.take<bf16_t>(rows * I);
-    w.ints = m.take<int>(rows + B + 16);                                      // slot[rows] | seqlens[B]
+    w.ints = m.take<int>(rows + (size_t)tables * B + 16);
     w.ylast = m.take<bf16_t>((size_t)B * H * 2);
+    return w;
+}
+static RowsWs carve_prefill(Carver& m, const vz_config& c, const Shard& sh, int B, int S) {
+    const size_t rows = (size_t)B * S, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, I = sh.I;
+    RowsWs w = carve_rows_head(m, c, sh, B, S, 1);                            // slot[rows] | kv_len[B]
     w.q8 = m.take<unsigned char>(rows * std::max(std::max(H, A), I));         // e4m3 copy of a linear's input rows + their scales
     w.qs = m.take<float>(rows);                                               // (fp8 MFMA prefill only)
     return w;
+}
+static RowsWs carve_append(Carver& m, const vz_config& c, const Shard& sh, int B, int T) {
+    RowsWs w = carve_rows_head(m, c, sh, B, T, 3);                            // slot[rows] | kv_len[B] | past[B] | new[B]
+    w.part_floats = vz_attn_append_ws_floats(B, T, sh.Hq, sh.Hkv, c.max_ctx);
+    w.part = m.take<float>(w.part_floats);
+    return w;
+}
+
+// the checks the two entry points share; `who` and `dim` keep each one's own error text
+static int rows_entry_check(vz_engine* e, const char* who, char dim, bool pointers, int row0, int B, int T) {
+    const vz_config& c = e->c;
+    VZ_CHECK_ARG(pointers && rows_shape_ok(c, row0, B, T), "%s: rows %d..%d, %c=%d outside capacity (max_batch %d, max_ctx %d)", who, row0, row0 + B - 1, dim, T,
+                 c.max_batch, c.max_ctx);
+    VZ_CHECK_ARG(e->cosT && e->rope_max >= c.max_ctx, "%s: rotary tables not set or shorter than max_ctx", who);
+    return VZ_OK;
+}
+
+// More new rows per sample than this run the append on the prefill's flash kernel with a scalar q_pos0, once per run of cache rows with
+// equal past; at or below it the key-split kernel of attn_append.hip.  Measured behind 2048 cached positions (profiles/append.txt): the
+// key-split kernel + combine take 48 us against 67 at T = 256, 61 against 68 at 320, 76 against 71 at 384 and 87 against 74 at 512: the
+// crossover lies between 320 and 384, and 256 sits inside the range it wins by a clear margin.
+// vz_tune_set(36, rows).
+static int g_append_flash_min_t = 256;
+
+// One call: T embed rows per sample; sample b's first h_new[b] rows are valid and go behind the h_past[b] positions cache row row0 + b
+// keeps (slots past + t).  The plain prefill is the call with past = 0 everywhere.
+struct RowsCall {
+    int row0, B, T;
+    const int *h_new, *h_past, *d_pos;
+    const void* d_embeds;
+    float *d_logits_all, *d_logits_last;
+    hipStream_t s;
+};
+
+static int llm_rows_forward(vz_engine* e, const RowsWs& w, const RowsCall& k, bool append) {
+    const vz_config& c = e->c;
+    hipStream_t s = k.s;
+    const int B = k.B, T = k.T, rows = B * T;
+    const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
+    const size_t row_elems = (size_t)Hkv * c.max_ctx * D;                         // cache rows are [kv head][max_ctx][128] blocks
+    const size_t row_off = (size_t)k.row0 * row_elems;
+    const bool lead = e->rank == 0;   // the row-parallel partial sums carry the residual on one rank only
+    bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
+    // The attention, chosen once: the key-split kernel (short appends), or flash launches over runs of cache rows with equal past.  The
+    // plain prefill is one such run at past 0, and the only one whose flash launch may rotate Q in its own load (g_rope_in_attn; the
+    // others read the rotated copy q that rope_kv writes).
+    const bool keysplit = append && !(T > g_append_flash_min_t);
+    const bool rope_q_late = !append && g_rope_in_attn && D == 128 && vz_attn_version() != 1;
+    int* d_slot = w.ints;
+    int* d_len = w.ints + rows;
+    int kv_max = 0;
+    bool padded = false;
+    {
+        std::vector<int> h(rows + (keysplit ? 3 : 1) * B);          // slot[rows] | kv_len[B], and for the key-split kernel | past[B] | new[B]
+        for (int b = 0; b < B; ++b) {
+            for (int t = 0; t < T; ++t) h[b * T + t] = t < k.h_new[b] ? k.h_past[b] + t : -1;
+            h[rows + b] = k.h_past[b] + k.h_new[b];
+            if (keysplit) { h[rows + B + b] = k.h_past[b]; h[rows + 2 * B + b] = k.h_new[b]; }
+            kv_max = std::max(kv_max, h[rows + b]);
+            padded = padded || k.h_new[b] < T;
+        }
+        RC(upload_ints(e, h.data(), h.size(), w.ints, s));
+    }
+    // one linear of the stack: bf16 tile GEMM, or - weight_fp8 engine with vz_engine_prefill_fp8 on - the input rows quantised to e4m3
+    // (one power-of-two scale per row) and the product on the fp8 MFMA against the e4m3 weight copy (gemm_fp8.hip)
+    // (below ~768 rows the quantiser launches and the shallow grids cost more than the fp8 MFMA saves: 330 rows 20.4 vs 18.6 ms, 1320 rows 37.5 vs 43.6)
+    // The plain prefill only: carve_append takes no q8 / qs, and nobody has measured or tested an append on the fp8 route - on a
+    // prefill_fp8 engine it keeps the bf16 linears.
+    const bool f8 = !append && e->prefill_fp8 && rows >= g_fp8_prefill_min_rows && tp_local(e) && vz_gemm_fp8_ok(rows, QKV, H, H, H) && vz_gemm_fp8_ok(rows, H, I, I, I) && vz_gemm_fp8_ok(rows, H, A, A, A);
+    // norm_w != null: Ain is the residual stream and the RMSNorm belongs to this linear (fp8: norm + quantiser in one launch)
+    auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
+        if (f8) {
+            {
+                ProfScope ps(e, K_NORM, s);
+                if (norm_w) RC(vz_launch_rmsnorm_quant_fp8(Ain, K, norm_w, c.rms_eps, w.q8, K, w.qs, rows, K, s));
+                else RC(vz_launch_quant_rows_fp8(Ain, K, w.q8, K, w.qs, rows, K, s));
+            }
+            Fp8LinearArgs f;
+            f.A8 = w.q8; f.lda = K; f.ascale = w.qs; f.W8 = W.w8; f.ldw = K; f.wscale = W.ws; f.C = Cout; f.ldc = ldc; f.M = rows; f.N = N; f.K = K;
+            f.bias = nullptr; f.residual = res; f.ldr = H; f.act = act; f.out_fp32 = 0;
+            ProfScope ps(e, K_GEMM, s);
+            return vz_launch_gemm_fp8(f, s);
+        }
+        if (norm_w) { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(Ain, K, y, K, norm_w, rows, K, c.rms_eps, s)); }
+        return linear(e, 0, norm_w ? y : Ain, K, bare(W.w), K, Cout, ldc, rows, N, K, res, H, act, 0, s);      // (the bf16 matrix only: prefill never streams the e4m3 copy)
+    };
+    // token rows >= new[b] are never written by the key-split kernel in any layer: keep what the O projection reads of them finite
+    if (padded && keysplit) VZ_CHECK_HIP(hipMemsetAsync(att, 0, (size_t)rows * A * sizeof(bf16_t), s));
+    { ProfScope ps(e, K_OTHER, s); RC(vz_launch_copy_rows((const bf16_t*)k.d_embeds, H, x, H, rows, H, s)); }
+    for (int i = 0; i < c.n_layers; ++i) {
+        const LlmLayerW& W = e->llm[i];
+        bf16_t *kc = kc_of(e, i) + row_off, *vc = vc_of(e, i) + row_off;
+        RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
+        // RoPE of K + the KV append at slot past + t; the rotated copy q of the queries unless the attention rotates them in its own load
+        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, rope_q_late ? nullptr : q, kc, vc, e->cosT, e->sinT, k.d_pos, d_slot, B, T, Hq, Hkv, D, c.max_ctx, s)); }
+        if (keysplit) {
+            ProfScope ps(e, K_ATTN, s);
+            AttnAppendArgs a;
+            a.q = q; a.kc = kc; a.vc = vc; a.o = att; a.part = w.part; a.part_floats = w.part_floats;
+            a.past = d_len + B; a.nnew = d_len + 2 * B;
+            a.B = B; a.T = T; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D; a.max_ctx = c.max_ctx; a.window = c.sliding_window; a.kv_max = kv_max; a.nsplit = 0;
+            a.q_bs = a.o_bs = (long)T * A; a.q_ss = a.o_ss = A; a.q_hs = a.o_hs = D;
+            a.scale = ATTN_SCALE;
+            RC(vz_launch_attention_append(a, s));
+        } else {
+            ProfScope ps(e, K_ATTN, s);
+            const bf16_t* qsrc = rope_q_late ? qkv : q;
+            const long q_ld = rope_q_late ? QKV : A;
+            for (int b0 = 0; b0 < B;) {
+                int b1 = b0 + 1;
+                while (b1 < B && k.h_past[b1] == k.h_past[b0]) ++b1;
+                AttnArgs a;
+                a.q = qsrc + (size_t)b0 * T * q_ld; a.k = kc + b0 * row_elems; a.v = vc + b0 * row_elems; a.o = att + (size_t)b0 * T * A;
+                a.B = b1 - b0; a.Sq = T; a.Sk = std::min(k.h_past[b0] + T, c.max_ctx); a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D;
+                a.q_bs = T * q_ld; a.q_ss = q_ld; a.q_hs = D;
+                if (rope_q_late) { a.rope_cos = e->cosT; a.rope_sin = e->sinT; a.rope_pos = k.d_pos; }      // (one run: b0 = 0)
+                a.k_bs = a.v_bs = (long)row_elems; a.k_ss = a.v_ss = D; a.k_hs = a.v_hs = (long)c.max_ctx * D;
+                a.o_bs = (long)T * A; a.o_ss = A; a.o_hs = D;
+                a.scale = ATTN_SCALE;
+                a.causal = 1; a.q_pos0 = k.h_past[b0]; a.window = c.sliding_window; a.kv_len = d_len + b0;
+                RC(vz_launch_attention(a, s));
+                b0 = b1;
+            }
+        }
+        RC(plin(att, nullptr, W.o, H, A, x, H, lead ? x : nullptr, VZ_ACT_NONE));
+        RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
+        RC(plin(x, W.post_norm, W.gu, 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
+        RC(plin(act, nullptr, W.down, H, I, x, H, lead ? x : nullptr, VZ_ACT_NONE));
+        RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
+    }
+    const float* fn = e->top.norm;
+    if (k.d_logits_all) {
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(x, H, y, H, fn, rows, H, c.rms_eps, s)); }
+        RC(lm_head_logits(e, y, rows, k.d_logits_all, s, nullptr));
+    }
+    if (k.d_logits_last) {
+        {
+            ProfScope ps(e, K_OTHER, s);
+            for (int b = 0; b < B; ++b) RC(vz_launch_copy_rows(x + ((size_t)b * T + k.h_new[b] - 1) * H, H, ylast + (size_t)b * H, H, 1, H, s));
+        }
+        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(ylast, H, ylast + (size_t)B * H, H, fn, B, H, c.rms_eps, s)); }
+        RC(lm_head_logits(e, ylast + (size_t)B * H, B, k.d_logits_last, s, nullptr));
+    }
+    return VZ_OK;
 }
 
 extern "C" int vz_llm_prefill(vz_engine* e, const void* d_embeds, int B, int S, const int* h_seqlens, const int* d_pos,
@@ -983,211 +1134,29 @@ extern "C" int vz_llm_prefill(vz_engine* e, const void* d_embeds, int B, int S, 
 extern "C" int vz_llm_prefill_rows(vz_engine* e, int row0, const void* d_embeds, int B, int S, const int* h_seqlens, const int* d_pos,
                                    float* d_logits_all, float* d_logits_last, vz_stream stream) {
     NEED_READY();
-    const vz_config& c = e->c;
-    hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(d_embeds && h_seqlens && d_pos && prefill_shape_ok(c, row0, B, S),
-                 "prefill: rows %d..%d, S=%d outside capacity (max_batch %d, max_ctx %d)", row0, row0 + B - 1, S, c.max_batch, c.max_ctx);
-    const size_t row_off = (size_t)row0 * e->Hkv_l * c.max_ctx * c.head_dim;      // cache rows are [kv head][max_ctx][128] blocks
-    VZ_CHECK_ARG(e->cosT && e->rope_max >= c.max_ctx, "prefill: rotary tables not set or shorter than max_ctx");
+    RC(rows_entry_check(e, "prefill", 'S', d_embeds && h_seqlens && d_pos, row0, B, S));
     for (int b = 0; b < B; ++b) VZ_CHECK_ARG(h_seqlens[b] >= 1 && h_seqlens[b] <= S, "prefill: seqlen[%d]=%d outside [1,%d]", b, h_seqlens[b], S);
-    const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
-    const bool lead = e->rank == 0;   // the row-parallel partial sums carry the residual on one rank only
-    const int rows = B * S;
-    PrefillWs w;
-    RC(carve_stage(e, "prefill", [&](Carver& m) { return carve_prefill(m, c, Shard{Hq, Hkv, I}, B, S); }, &w));
-    bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
-    unsigned char* q8 = w.q8;
-    float* qs = w.qs;
-    int* d_ints = w.ints;
-    int* d_slot = d_ints;
-    int* d_len = d_ints + rows;
-    {
-        std::vector<int> h(rows + B);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < S; ++t) h[b * S + t] = t < h_seqlens[b] ? t : -1;
-        for (int b = 0; b < B; ++b) h[rows + b] = h_seqlens[b];
-        RC(upload_ints(e, h.data(), h.size(), d_ints, s));
-    }
-    // one Zephyr prefill linear: bf16 tile GEMM, or - weight_fp8 engine with vz_engine_prefill_fp8 on - the input rows quantised to e4m3
-    // (one power-of-two scale per row) and the product on the fp8 MFMA against the e4m3 weight copy (gemm_fp8.hip)
-    // (below ~768 rows the quantiser launches and the shallow grids cost more than the fp8 MFMA saves: 330 rows 20.4 vs 18.6 ms, 1320 rows 37.5 vs 43.6)
-    const bool f8 = e->prefill_fp8 && rows >= g_fp8_prefill_min_rows && tp_local(e) && vz_gemm_fp8_ok(rows, QKV, H, H, H) && vz_gemm_fp8_ok(rows, H, I, I, I) && vz_gemm_fp8_ok(rows, H, A, A, A);
-    // norm_w != null: Ain is the residual stream and the RMSNorm belongs to this linear (fp8: norm + quantiser in one launch)
-    auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
-        if (f8) {
-            {
-                ProfScope ps(e, K_NORM, s);
-                if (norm_w) RC(vz_launch_rmsnorm_quant_fp8(Ain, K, norm_w, c.rms_eps, q8, K, qs, rows, K, s));
-                else RC(vz_launch_quant_rows_fp8(Ain, K, q8, K, qs, rows, K, s));
-            }
-            Fp8LinearArgs f;
-            f.A8 = q8; f.lda = K; f.ascale = qs; f.W8 = W.w8; f.ldw = K; f.wscale = W.ws; f.C = Cout; f.ldc = ldc; f.M = rows; f.N = N; f.K = K;
-            f.bias = nullptr; f.residual = res; f.ldr = H; f.act = act; f.out_fp32 = 0;
-            ProfScope ps(e, K_GEMM, s);
-            return vz_launch_gemm_fp8(f, s);
-        }
-        if (norm_w) { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(Ain, K, y, K, norm_w, rows, K, c.rms_eps, s)); }
-        return linear(e, 0, norm_w ? y : Ain, K, bare(W.w), K, Cout, ldc, rows, N, K, res, H, act, 0, s);      // (the bf16 matrix only: prefill never streams the e4m3 copy)
-    };
-    { ProfScope ps(e, K_OTHER, s); RC(vz_launch_copy_rows((const bf16_t*)d_embeds, H, x, H, rows, H, s)); }
-    for (int i = 0; i < c.n_layers; ++i) {
-        const LlmLayerW& W = e->llm[i];
-        RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
-        // RoPE of K + the KV append; the queries are rotated by the attention's own Q load (g_rope_in_attn; else a rotated copy q as before)
-        const bool rope_q_late = g_rope_in_attn && D == 128 && vz_attn_version() != 1;
-        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, rope_q_late ? nullptr : q, kc_of(e, i) + row_off, vc_of(e, i) + row_off, e->cosT, e->sinT, d_pos, d_slot, B, S, Hq, Hkv, D, c.max_ctx, s)); }
-        {
-            ProfScope ps(e, K_ATTN, s);
-            AttnArgs a;
-            a.q = rope_q_late ? qkv : q; a.k = kc_of(e, i) + row_off; a.v = vc_of(e, i) + row_off; a.o = att;
-            a.B = B; a.Sq = S; a.Sk = S; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D;
-            a.q_bs = rope_q_late ? (long)S * QKV : (long)S * A; a.q_ss = rope_q_late ? QKV : A; a.q_hs = D;
-            if (rope_q_late) { a.rope_cos = e->cosT; a.rope_sin = e->sinT; a.rope_pos = d_pos; }
-            a.k_bs = a.v_bs = (long)Hkv * c.max_ctx * D; a.k_ss = a.v_ss = D; a.k_hs = a.v_hs = (long)c.max_ctx * D;
-            a.o_bs = (long)S * A; a.o_ss = A; a.o_hs = D;
-            a.scale = ATTN_SCALE;
-            a.causal = 1; a.q_pos0 = 0; a.window = c.sliding_window; a.kv_len = d_len;
-            RC(vz_launch_attention(a, s));
-        }
-        RC(plin(att, nullptr, W.o, H, A, x, H, lead ? x : nullptr, VZ_ACT_NONE));
-        RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
-        RC(plin(x, W.post_norm, W.gu, 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
-        RC(plin(act, nullptr, W.down, H, I, x, H, lead ? x : nullptr, VZ_ACT_NONE));
-        RC(tp_allreduce_bf16(e, x, (size_t)rows * H, s));
-    }
-    const float* fn = e->top.norm;
-    if (d_logits_all) {
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(x, H, y, H, fn, rows, H, c.rms_eps, s)); }
-        RC(lm_head_logits(e, y, rows, d_logits_all, s, nullptr));
-    }
-    if (d_logits_last) {
-        {
-            ProfScope ps(e, K_OTHER, s);
-            for (int b = 0; b < B; ++b) RC(vz_launch_copy_rows(x + ((size_t)b * S + h_seqlens[b] - 1) * H, H, ylast + (size_t)b * H, H, 1, H, s));
-        }
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(ylast, H, ylast + (size_t)B * H, H, fn, B, H, c.rms_eps, s)); }
-        RC(lm_head_logits(e, ylast + (size_t)B * H, B, d_logits_last, s, nullptr));
-    }
-    return VZ_OK;
+    const std::vector<int> past(B, 0);
+    RowsWs w;
+    RC(carve_stage(e, "prefill", [&](Carver& m) { return carve_prefill(m, e->c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, S); }, &w));
+    return llm_rows_forward(e, w, RowsCall{row0, B, S, h_seqlens, past.data(), d_pos, d_embeds, d_logits_all, d_logits_last, (hipStream_t)stream}, false);
 }
 
-// ------------------------------------------------------------------------------------------------
-// a12b: append prefill - T new rows per cache row behind the positions the row keeps
-// ------------------------------------------------------------------------------------------------
-// More new rows per sample than this run the prefill's flash kernel with a scalar q_pos0, once per run of cache rows with equal past;
-// at or below it the key-split kernel of attn_append.hip.  Measured behind 2048 cached positions (profiles/append.txt): the key-split
-// kernel + combine take 48 us against 67 at T = 256, 61 against 68 at 320, 76 against 71 at 384 and 87 against 74 at 512: the crossover
-// lies between 320 and 384, and 256 sits inside the range it wins by a clear margin.
-// vz_tune_set(36, rows).
-static int g_append_flash_min_t = 256;
-static bool append_shape_ok(const vz_config& c, int row0, int B, int T) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && T >= 1 && T <= c.max_ctx; }
-struct AppendWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; float* part; size_t part_floats; };
-static AppendWs carve_append(Carver& m, const vz_config& c, const Shard& sh, int B, int T) {
-    const size_t rows = (size_t)B * T, H = c.hidden, A = (size_t)sh.Hq * c.head_dim, QKV = (size_t)(sh.Hq + 2 * sh.Hkv) * c.head_dim, I = sh.I;
-    AppendWs w;
-    w.x = m.take<bf16_t>(rows * H);
-    w.y = m.take<bf16_t>(rows * H);
-    w.qkv = m.take<bf16_t>(rows * QKV);
-    w.q = m.take<bf16_t>(rows * A);
-    w.att = m.take<bf16_t>(rows * A);
-    w.act = m.take<bf16_t>(rows * I);
-    w.ints = m.take<int>(rows + 3 * (size_t)B + 16);                          // slot[rows] | kv_len[B] | past[B] | new[B]
-    w.ylast = m.take<bf16_t>((size_t)B * H * 2);
-    w.part_floats = vz_attn_append_ws_floats(B, T, sh.Hq, sh.Hkv, c.max_ctx);
-    w.part = m.take<float>(w.part_floats);
-    return w;
-}
-
+// append prefill: T new rows per cache row behind the positions the row keeps
 extern "C" int vz_llm_prefill_append(vz_engine* e, int row0, const void* d_embeds, int B, int T, const int* h_new, const int* h_past, const int* d_pos,
                                      float* d_logits_all, float* d_logits_last, vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
-    hipStream_t s = (hipStream_t)stream;
+    // (llm_rows_forward holds the all-reduces and the lead-rank residual of the plain prefill, but no test has run an append through them)
     if (e->tp > 1) { vz_set_error("prefill_append: the append prefill on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
-    VZ_CHECK_ARG(d_embeds && h_new && h_past && d_pos && append_shape_ok(c, row0, B, T),
-                 "prefill_append: rows %d..%d, T=%d outside capacity (max_batch %d, max_ctx %d)", row0, row0 + B - 1, T, c.max_batch, c.max_ctx);
-    VZ_CHECK_ARG(e->cosT && e->rope_max >= c.max_ctx, "prefill_append: rotary tables not set or shorter than max_ctx");
-    int kv_max = 0;
+    RC(rows_entry_check(e, "prefill_append", 'T', d_embeds && h_new && h_past && d_pos, row0, B, T));
     for (int b = 0; b < B; ++b) {
         VZ_CHECK_ARG(h_new[b] >= 1 && h_new[b] <= T, "prefill_append: new[%d]=%d outside [1,%d]", b, h_new[b], T);
         VZ_CHECK_ARG(h_past[b] >= 0 && h_past[b] <= c.max_ctx - h_new[b], "prefill_append: past[%d]=%d + new %d outside max_ctx %d", b, h_past[b], h_new[b], c.max_ctx);
-        kv_max = std::max(kv_max, h_past[b] + h_new[b]);
     }
-    const size_t row_elems = (size_t)e->Hkv_l * c.max_ctx * c.head_dim;           // cache rows are [kv head][max_ctx][128] blocks
-    const size_t row_off = (size_t)row0 * row_elems;
-    const int H = c.hidden, D = c.head_dim, Hq = e->Hq_l, Hkv = e->Hkv_l, QKV = (Hq + 2 * Hkv) * D, I = e->I_l, A = Hq * D;
-    const int rows = B * T;
-    AppendWs w;
-    RC(carve_stage(e, "prefill_append", [&](Carver& m) { return carve_append(m, c, Shard{Hq, Hkv, I}, B, T); }, &w));
-    bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
-    int *d_slot = w.ints, *d_len = w.ints + rows, *d_past = d_len + B, *d_new = d_past + B;
-    {
-        std::vector<int> h(rows + 3 * B);
-        for (int b = 0; b < B; ++b) {
-            for (int t = 0; t < T; ++t) h[b * T + t] = t < h_new[b] ? h_past[b] + t : -1;
-            h[rows + b] = h_past[b] + h_new[b]; h[rows + B + b] = h_past[b]; h[rows + 2 * B + b] = h_new[b];
-        }
-        RC(upload_ints(e, h.data(), h.size(), w.ints, s));
-    }
-    auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
-        if (norm_w) { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(Ain, K, y, K, norm_w, rows, K, c.rms_eps, s)); }
-        return linear(e, 0, norm_w ? y : Ain, K, bare(W.w), K, Cout, ldc, rows, N, K, res, H, act, 0, s);
-    };
-    const bool flash = T > g_append_flash_min_t;
-    bool padded = false;
-    for (int b = 0; b < B; ++b) padded = padded || h_new[b] < T;
-    // token rows >= new[b] are never written by the key-split kernel in any layer: keep what the O projection reads of them finite
-    if (padded && !flash) VZ_CHECK_HIP(hipMemsetAsync(att, 0, (size_t)rows * A * sizeof(bf16_t), s));
-    { ProfScope ps(e, K_OTHER, s); RC(vz_launch_copy_rows((const bf16_t*)d_embeds, H, x, H, rows, H, s)); }
-    for (int i = 0; i < c.n_layers; ++i) {
-        const LlmLayerW& W = e->llm[i];
-        RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
-        // RoPE + the KV append at slot past + t; the attention reads the rotated copy q
-        { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, q, kc_of(e, i) + row_off, vc_of(e, i) + row_off, e->cosT, e->sinT, d_pos, d_slot, B, T, Hq, Hkv, D, c.max_ctx, s)); }
-        if (flash) {
-            ProfScope ps(e, K_ATTN, s);
-            for (int b0 = 0; b0 < B;) {
-                int b1 = b0 + 1;
-                while (b1 < B && h_past[b1] == h_past[b0]) ++b1;
-                AttnArgs a;
-                a.q = q + (size_t)b0 * T * A; a.k = kc_of(e, i) + row_off + b0 * row_elems; a.v = vc_of(e, i) + row_off + b0 * row_elems; a.o = att + (size_t)b0 * T * A;
-                a.B = b1 - b0; a.Sq = T; a.Sk = std::min(h_past[b0] + T, c.max_ctx); a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D;
-                a.q_bs = (long)T * A; a.q_ss = A; a.q_hs = D;
-                a.k_bs = a.v_bs = (long)row_elems; a.k_ss = a.v_ss = D; a.k_hs = a.v_hs = (long)c.max_ctx * D;
-                a.o_bs = (long)T * A; a.o_ss = A; a.o_hs = D;
-                a.scale = ATTN_SCALE;
-                a.causal = 1; a.q_pos0 = h_past[b0]; a.window = c.sliding_window; a.kv_len = d_len + b0;
-                RC(vz_launch_attention(a, s));
-                b0 = b1;
-            }
-        } else {
-            ProfScope ps(e, K_ATTN, s);
-            AttnAppendArgs a;
-            a.q = q; a.kc = kc_of(e, i) + row_off; a.vc = vc_of(e, i) + row_off; a.o = att; a.part = w.part; a.part_floats = w.part_floats;
-            a.past = d_past; a.nnew = d_new;
-            a.B = B; a.T = T; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D; a.max_ctx = c.max_ctx; a.window = c.sliding_window; a.kv_max = kv_max; a.nsplit = 0;
-            a.q_bs = a.o_bs = (long)T * A; a.q_ss = a.o_ss = A; a.q_hs = a.o_hs = D;
-            a.scale = ATTN_SCALE;
-            RC(vz_launch_attention_append(a, s));
-        }
-        RC(plin(att, nullptr, W.o, H, A, x, H, x, VZ_ACT_NONE));
-        RC(plin(x, W.post_norm, W.gu, 2 * I, H, act, I, nullptr, VZ_ACT_SWIGLU));
-        RC(plin(act, nullptr, W.down, H, I, x, H, x, VZ_ACT_NONE));
-    }
-    const float* fn = e->top.norm;
-    if (d_logits_all) {
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(x, H, y, H, fn, rows, H, c.rms_eps, s)); }
-        RC(lm_head_logits(e, y, rows, d_logits_all, s, nullptr));
-    }
-    if (d_logits_last) {
-        {
-            ProfScope ps(e, K_OTHER, s);
-            for (int b = 0; b < B; ++b) RC(vz_launch_copy_rows(x + ((size_t)b * T + h_new[b] - 1) * H, H, ylast + (size_t)b * H, H, 1, H, s));
-        }
-        { ProfScope ps(e, K_NORM, s); RC(vz_launch_rmsnorm(ylast, H, ylast + (size_t)B * H, H, fn, B, H, c.rms_eps, s)); }
-        RC(lm_head_logits(e, ylast + (size_t)B * H, B, d_logits_last, s, nullptr));
-    }
-    return VZ_OK;
+    RowsWs w;
+    RC(carve_stage(e, "prefill_append", [&](Carver& m) { return carve_append(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, T); }, &w));
+    return llm_rows_forward(e, w, RowsCall{row0, B, T, h_new, h_past, d_pos, d_embeds, d_logits_all, d_logits_last, (hipStream_t)stream}, true);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2310,9 +2279,9 @@ extern "C" long vz_op_stage_ws_bytes(const vz_config* cfg, int stage, int n, int
     switch (stage) {
     case VZ_STAGE_CLIP: if (!clip_shape_ok(c, n)) return -1; carve_clip(m, c, n, !(flags & VZ_WS_CALLER_HIDDEN)); break;
     case VZ_STAGE_QFORMER: if (!qf_shape_ok(c, n, n2, Lmax)) return -1; carve_qformer(m, c, n, n2, Lmax, qf_kv_all(c, n, (flags & VZ_WS_QF_KV_CONTIG) != 0)); break;
-    case VZ_STAGE_PREFILL: if (!prefill_shape_ok(c, 0, n, n2)) return -1; carve_prefill(m, c, shard_of(c), n, n2); break;
+    case VZ_STAGE_PREFILL: if (!rows_shape_ok(c, 0, n, n2)) return -1; carve_prefill(m, c, shard_of(c), n, n2); break;
     case VZ_STAGE_DECODE: if (!decode_shape_ok(c, n, spec)) return -1; carve_decode(m, c, shard_of(c), n, spec); break;
-    case VZ_STAGE_APPEND: if (!append_shape_ok(c, 0, n, n2)) return -1; carve_append(m, c, shard_of(c), n, n2); break;
+    case VZ_STAGE_APPEND: if (!rows_shape_ok(c, 0, n, n2)) return -1; carve_append(m, c, shard_of(c), n, n2); break;
     default: return -1;
     }
     return (long)m.off;

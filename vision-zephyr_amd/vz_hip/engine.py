@@ -527,28 +527,29 @@ class Engine:
     def prefill(self, embeds: torch.Tensor, seqlens: Sequence[int], position_ids: Optional[torch.Tensor] = None,
                 all_logits: bool = False, last_logits: bool = True):
         """embeds bf16 [B,S,H] right-padded.  Returns (logits_all fp32 [B,S,V] | None, logits_last fp32 [B,V] | None)."""
-        cfg = self.cfg
-        x = embeds.to(self.device, torch.bfloat16).contiguous()
-        Bn, S = x.shape[0], x.shape[1]
-        if position_ids is None:
-            position_ids = torch.arange(S, dtype=torch.int32, device=self.device).unsqueeze(0).expand(Bn, S)
-        pos = position_ids.to(self.device, torch.int32).contiguous()
-        la = torch.empty(Bn, S, cfg.vocab, dtype=torch.float32, device=self.device) if all_logits else None
-        ll = torch.empty(Bn, cfg.vocab, dtype=torch.float32, device=self.device) if last_logits else None
-        sl = (C.c_int * Bn)(*[int(v) for v in seqlens])
-        B.check(self.lib.vz_llm_prefill(self.h, B.ptr(x), Bn, S, sl, B.ptr(pos), B.ptr(la), B.ptr(ll), self._s()))
+        x, pos, la, ll, (sl,) = self._rows_call(embeds, position_ids, None, all_logits, last_logits, seqlens)
+        B.check(self.lib.vz_llm_prefill(self.h, B.ptr(x), x.shape[0], x.shape[1], sl, B.ptr(pos), B.ptr(la), B.ptr(ll), self._s()))
         return la, ll
+
+    def _rows_call(self, embeds, position_ids, past_lens, all_logits, last_logits, *lens):
+        """what the prefill calls hand the library: embeds as contiguous bf16 [B,T,H], int32 positions [B,T] (default past + t, the
+        padding rows of an append kept inside the rotary tables), the two logits outputs (or None), each of `lens` as a c_int array."""
+        x = embeds.to(self.device, torch.bfloat16).contiguous()
+        Bn, T = x.shape[0], x.shape[1]
+        if position_ids is None and past_lens is None:
+            position_ids = torch.arange(T, dtype=torch.int32, device=self.device).unsqueeze(0).expand(Bn, T)
+        elif position_ids is None:
+            position_ids = (torch.tensor([int(p) for p in past_lens], dtype=torch.int32).unsqueeze(1)
+                            + torch.arange(T, dtype=torch.int32).unsqueeze(0)).clamp_(max=self.max_ctx - 1)
+        pos = position_ids.to(self.device, torch.int32).contiguous()
+        la = torch.empty(Bn, T, self.cfg.vocab, dtype=torch.float32, device=self.device) if all_logits else None
+        ll = torch.empty(Bn, self.cfg.vocab, dtype=torch.float32, device=self.device) if last_logits else None
+        return x, pos, la, ll, [(C.c_int * Bn)(*[int(v) for v in l]) for l in lens]
 
     def prefill_rows(self, row0: int, embeds: torch.Tensor, seqlens: Sequence[int], position_ids: Optional[torch.Tensor] = None):
         """`prefill` into KV-cache rows row0 .. row0+B-1 (continuous batching); returns the last-position logits fp32 [B,V]."""
-        x = embeds.to(self.device, torch.bfloat16).contiguous()
-        Bn, S = x.shape[0], x.shape[1]
-        if position_ids is None:
-            position_ids = torch.arange(S, dtype=torch.int32, device=self.device).unsqueeze(0).expand(Bn, S)
-        pos = position_ids.to(self.device, torch.int32).contiguous()
-        ll = torch.empty(Bn, self.cfg.vocab, dtype=torch.float32, device=self.device)
-        sl = (C.c_int * Bn)(*[int(v) for v in seqlens])
-        B.check(self.lib.vz_llm_prefill_rows(self.h, int(row0), B.ptr(x), Bn, S, sl, B.ptr(pos), None, B.ptr(ll), self._s()))
+        x, pos, _, ll, (sl,) = self._rows_call(embeds, position_ids, None, False, True, seqlens)
+        B.check(self.lib.vz_llm_prefill_rows(self.h, int(row0), B.ptr(x), x.shape[0], x.shape[1], sl, B.ptr(pos), None, B.ptr(ll), self._s()))
         return ll
 
     def prefill_append(self, row0: int, embeds: torch.Tensor, new_lens: Sequence[int], past_lens: Sequence[int],
@@ -556,21 +557,12 @@ class Engine:
         """embeds bf16 [B,T,H] right-padded: new_lens[b] rows go behind the past_lens[b] positions cache row row0+b keeps, at cache
         slots past+t and rotary positions position_ids[b,t] (default past+t).  Returns (logits_all fp32 [B,T,V] | None, logits_last
         fp32 [B,V] | None); logits_all rows t >= new_lens[b] come from padding."""
-        cfg = self.cfg
-        x = embeds.to(self.device, torch.bfloat16).contiguous()
-        Bn, T = x.shape[0], x.shape[1]
+        Bn, T = embeds.shape[0], embeds.shape[1]
         if len(new_lens) != Bn or len(past_lens) != Bn:
             raise ValueError(f"prefill_append: {Bn} samples, {len(new_lens)} new lengths, {len(past_lens)} past lengths")
-        if position_ids is None:
-            position_ids = (torch.tensor([int(p) for p in past_lens], dtype=torch.int32).unsqueeze(1)
-                            + torch.arange(T, dtype=torch.int32).unsqueeze(0)).clamp_(max=self.max_ctx - 1)      # (padding rows stay inside the rotary tables)
-        pos = position_ids.to(self.device, torch.int32).contiguous()
+        x, pos, la, ll, (nl, pl) = self._rows_call(embeds, position_ids, past_lens, all_logits, last_logits, new_lens, past_lens)
         if tuple(pos.shape) != (Bn, T):
             raise ValueError(f"prefill_append: position_ids {tuple(pos.shape)}, expected {(Bn, T)}")
-        la = torch.empty(Bn, T, cfg.vocab, dtype=torch.float32, device=self.device) if all_logits else None
-        ll = torch.empty(Bn, cfg.vocab, dtype=torch.float32, device=self.device) if last_logits else None
-        nl = (C.c_int * Bn)(*[int(v) for v in new_lens])
-        pl = (C.c_int * Bn)(*[int(v) for v in past_lens])
         B.check(self.lib.vz_llm_prefill_append(self.h, int(row0), B.ptr(x), Bn, T, nl, pl, B.ptr(pos), B.ptr(la), B.ptr(ll), self._s()))
         return la, ll
 
