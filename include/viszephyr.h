@@ -393,39 +393,85 @@ int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d_logits_dbg
 /* vz_llm_decode_steps rejects (VZ_ERR_ARG) a call whose n steps would take a live row past max_ctx keys or past the rotary
  * tables; rows parked by vz_llm_decode_set_row(ctx_len 0) saturate on the device instead.
  *
- * Sampling tail (hf:generation/utils.py `_sample`, do_sample=True; ref:vis_zephyr/serve/cli.py:171-182 = temperature 0.2 +
- * HF's default top_k 50): after vz_llm_decode_sampling(enable=1) every decode step draws its token on the device -
- * logits / temperature, top-k, top-p, then a Gumbel race keyed by Philox4x32-10(seed; vocab index, row, draw counter) - inside
- * the same per-token hipGraph, so a streamer / stopping-criteria loop reads back 4 bytes per token.  `first_counter` is the
- * draw counter the next vz_llm_decode_begin starts from.  vz_op_sample: the same kernel on arbitrary fp32 logits rows
- * (the first token, drawn from the prefill logits with counter 0; tests).  Restated in oracle/sampling_oracle.py. */
-int vz_llm_decode_sampling(vz_engine* e, int enable, float temperature, int top_k, float top_p, unsigned long long seed,
-                           int first_counter);
+ * How one row chooses its next token: the record every sampling entry point takes (ABI 11: it replaces the loose scalars, the parallel
+ * host arrays and the *_warp twins of ABI 10).  48 bytes, the entry of the per-row table in device memory as it is:
+ *   offset 0 mode, 4 temperature, 8 top_k, 12 top_p, 16 seed (low word first), 24 counter, 28 reserved,
+ *   32 min_p, 36 typical_p, 40 epsilon_cutoff, 44 eta_cutoff
+ * mode = VZ_ROW_GREEDY: first maximal index; only `counter` is read besides.  mode = VZ_ROW_SAMPLE: logits / temperature, top-k, top-p,
+ * then the warpers hf:generation/utils.py `_get_logits_processor` puts behind TopPLogitsWarper, in its order (csrc/sampling.hip step
+ * 3b):
+ *   min_p           drop p_i < min_p * p_max                              0 <= min_p <= 1; 0 = off
+ *   typical_p       ascending in |-log p_i - H| keep the shortest prefix whose mass reaches typical_p (it may leave out the most
+ *                   likely token)                                           0 or >= 1 = off
+ *   epsilon_cutoff  drop p_i < epsilon                                    0 or >= 1 = off
+ *   eta_cutoff      drop p_i < min(eta, sqrt(eta) * exp(-H))              0 or >= 1 = off
+ * each over the set the one before it left (p = softmax over that set, H its entropy) and each keeping at least the largest score
+ * of that set; then a Gumbel race keyed by Philox4x32-10(seed; vocab index, row, draw counter).  The kept set is a key interval of x;
+ * the draw and the step recorder (lse_kept, n_kept, warped rows) take the same one.
+ * One check for every entry point, before it touches the device (VZ_ERR_ARG): mode 0 or 1; counter >= 0; a sampled record needs
+ * temperature > 0, top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off), 0 <= min_p <= 1, typical_p / epsilon_cutoff / eta_cutoff >= 0; a NaN
+ * fails.  (ABI 10 let vz_op_sample pass top_k < 0, top_p > 1 and counter < 0, refused its temperature <= 0 only after device calls,
+ * and let vz_op_token_scores pass counter < 0.) */
+#define VZ_ROW_GREEDY 0
+#define VZ_ROW_SAMPLE 1
+typedef struct vz_sample_params {
+    int mode;
+    float temperature;
+    int top_k;
+    float top_p;
+    unsigned long long seed;
+    int counter;       /* the draw counter of the row's next token */
+    int reserved;
+    float min_p, typical_p, epsilon_cutoff, eta_cutoff;
+} vz_sample_params;
+/* Sampling tail (hf:generation/utils.py `_sample`, do_sample=True; ref:vis_zephyr/serve/cli.py:171-182 = temperature 0.2 +
+ * HF's default top_k 50): after vz_llm_decode_sampling with a VZ_ROW_SAMPLE record every decode step draws its token on the device
+ * by that record, inside the same per-token hipGraph, so a streamer / stopping-criteria loop reads back 4 bytes per token.
+ * p->counter is the draw counter the next vz_llm_decode_begin starts from; it is kept for a VZ_ROW_GREEDY record (= the argmax again)
+ * too, whose other fields are not looked at.  vz_op_sample: the same kernel on arbitrary fp32 logits rows, one VZ_ROW_SAMPLE record
+ * for all of them, the row index in the Philox counter (the first token, drawn from the prefill logits with counter 0; tests).
+ * Restated in oracle/sampling_oracle.py. */
+int vz_llm_decode_sampling(vz_engine* e, const vz_sample_params* p);
 /* Streamer / stopping-criteria loop (ref:vis_zephyr/serve/cli.py:155-182 passes a TextStreamer and a KeywordsStoppingCriteria:
  * one host callback per token): every step's tail also writes its token to ring[row * ring_n + (draw counter mod ring_n)], a
  * device-visible HOST buffer of ring_rows x ring_n ints, so the host keeps a step in flight and reads token t when the event behind
  * step t fires.  vz_llm_decode_steps refuses a decode batch with more rows than the ring holds (ABI 10: ring_rows). */
 int vz_llm_decode_ring(vz_engine* e, int* host_visible_ring, int ring_n, int ring_rows);
-int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, unsigned long long seed,
-                 int counter, int* d_ids, vz_stream stream);
-/* Logits processors in the step (hf:generation/logits_process.py, in the order of `_get_logits_processor`: repetition penalty,
- * no-repeat-n-gram, min-new-tokens, suppress-tokens, then the sampler's warpers): after vz_llm_decode_logits_proc(enable=1) every
- * decode step whose tail is the argmax or the sampler first runs them on its fp32 logits, on the device and inside the per-token
+int vz_op_sample(const float* d_logits, int rows, int cols, const vz_sample_params* p, int* d_ids, vz_stream stream);
+/* Logits processors in the step (hf:generation/logits_process.py, in the order of `_get_logits_processor`: sequence bias, repetition
+ * penalty, no-repeat-n-gram, bad words, min-new-tokens, suppress-tokens, then the sampler's warpers): after vz_llm_decode_logits_proc
+ * with a record every decode step whose tail is the argmax or the sampler first runs them on its fp32 logits, on the device and inside the per-token
  * hipGraph (the parameters are part of what a captured step freezes: a change captures again).  They see the ids generated so
  * far, never the prompt (the reference generates from inputs_embeds): a per-row history kept on the device, emptied here
  * (stream-ordered) and extended at every step by the row's input token - so arm it before vz_llm_decode_begin, after the first
  * token was chosen on logits that went through vz_op_logits_process with empty histories.  repetition_penalty > 0 (1 = off),
  * 0 <= no_repeat_ngram <= 8 (0 = off), the <= 4 eos ids are -inf while fewer than min_new_tokens ids were generated, the <= 16
  * suppressed ids always; vocabularies up to 65536.  vz_llm_decode_steps refuses the mode together with the speculative tail
- * (with the beam tail: see "beam search: processors and rows" below); tensor-parallel engines are VZ_ERR_UNSUPPORTED.  enable = 0:
+ * (with the beam tail: see "beam search: processors and rows" below); tensor-parallel engines are VZ_ERR_UNSUPPORTED.  p = NULL:
  * off (no launch is added to the step).
+ * seq: the id sequences of hf:SequenceBiasLogitsProcessor (first in HF's chain, in front of the repetition penalty) and
+ * hf:NoBadWordsLogitsProcessor (behind the n-gram ban), int32 [n_seq][12] =
+ *   [len 1..8 | kind: 0 = bias, 1 = bad word | bias, fp32 bits | 0 | ids[8]],  n_seq <= 64 (0: seq may be NULL)
+ * with the one-id sequences first and each group in the caller's order - the order HF adds the biases in.  A one-id sequence acts at
+ * every step; a longer one acts on its last id when the ids generated so far end in its first len - 1 ids and (HF's length check) at
+ * least len ids were generated.  Biases that land on one id add up in fp32 in table order, then the penalty acts on the biased score,
+ * then the bans write -inf; a bad word bans without arithmetic.  Ids outside [0, cols) are ignored.  The engine keeps the table in its
+ * own device memory: an arming with the table of the previous arming uploads nothing, a new table is uploaded outside any capture and
+ * the next vz_llm_decode_steps captures again.
  * vz_op_logits_process: the same kernel in place on fp32 logits [rows, cols] over the caller's histories d_hist [rows][hist_stride]
- * (int32) of d_hist_len[row] ids each; ids outside [0, cols) are ignored.  Bit-identical to HF's processors on fp32. */
-int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
-                              const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream);
-int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
-                         int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
-                         vz_stream stream);
+ * (int32) of d_hist_len[row] ids each; ids outside [0, cols) are ignored.  Bit-identical to HF's processors on fp32.
+ * Both check the whole record before they touch the device (VZ_ERR_ARG). */
+typedef struct vz_logits_proc_params {
+    float repetition_penalty;
+    int no_repeat_ngram, min_new_tokens;
+    int n_eos, n_suppress, n_seq;
+    const int* eos;        /* n_eos ids                          */
+    const int* suppress;   /* n_suppress ids                     */
+    const int* seq;        /* n_seq entries of 12 ints, or NULL  */
+} vz_logits_proc_params;
+int vz_llm_decode_logits_proc(vz_engine* e, const vz_logits_proc_params* p, vz_stream stream);
+int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len,
+                         const vz_logits_proc_params* p, vz_stream stream);
 /* how the last vz_llm_decode_steps ran: *graph = 1 when a captured hipGraph was replayed; *comm_in_graph = 1 when the RCCL
  * collectives of a tensor-parallel engine are part of that graph (0 = eager steps, e.g. after RCCL refused the capture) */
 int vz_llm_decode_mode(vz_engine* e, int* graph, int* comm_in_graph);
@@ -487,22 +533,19 @@ int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_pos, int ct
 int vz_llm_prefill_append(vz_engine* e, int row0, const void* d_embeds, int B, int T, const int* h_new, const int* h_past, const int* d_pos,
                           float* d_logits_all, float* d_logits_last, vz_stream stream);
 /* Per-row tail (csrc/sampling.hip: sample_rows_kernel): every row of the decode batch chooses its next token by its own entry of a table
- * in device memory - mode 0 = greedy (first maximal index), 1 = sample with the row's own temperature > 0, top_k >= 0, 0 < top_p <= 1,
- * 64-bit seed and draw counter >= 0 (the kernel counts it up after every step).  A sampled row gets the bits vz_op_sample gives a ONE-row
+ * in device memory, a vz_sample_params record with its own 64-bit seed and draw counter (the kernel counts it up after every step).
+ * A sampled row gets the bits vz_op_sample gives a ONE-row
  * call with the same parameters: its Philox counter is (vocab index, 0, draw counter), so the draws of a request do not depend on the cache
  * row it decodes in.  The captured step reads the table through a pointer: changing an entry changes no kernel argument and captures nothing.
- * vz_llm_decode_sampling_rows(enable=1): arms the tail and keeps `rows` entries (0..max_batch; the rows behind them greedy) for the NEXT
- * vz_llm_decode_begin to upload; enable = 0: the argmax / the sampler again.  vz_llm_decode_set_row_sampling: one row's entry of the running
+ * vz_llm_decode_sampling_rows(enable=1): arms the tail and keeps the `rows` records h_rows (0..max_batch; the rows behind them greedy)
+ * for the NEXT vz_llm_decode_begin to upload; enable = 0: the argmax / the sampler again.  vz_llm_decode_set_row_sampling: one row's entry of the running
  * batch, stream-ordered - the counterpart of vz_llm_decode_set_row.  The logits processors may sit in front of the tail as in front of
  * the sampler; vz_llm_decode_steps refuses it together with the beam or the speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.
  * vz_op_sample_rows: the same kernel on fp32 logits [rows <= 64, cols] (the first token of each sequence from the prefill logits with
  * counter 0; tests). */
-int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                const float* h_top_p, const unsigned long long* h_seed, const int* h_counter);
-int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, unsigned long long seed,
-                                   int counter, vz_stream stream);
-int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                      const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream);
+int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const vz_sample_params* h_rows);
+int vz_llm_decode_set_row_sampling(vz_engine* e, int row, const vz_sample_params* p, vz_stream stream);
+int vz_op_sample_rows(const float* d_logits, int rows, int cols, const vz_sample_params* h_rows, int* d_ids, vz_stream stream);
 /* Step recorder (csrc/sampling.hip: token_scores_kernel): per-token scores and log-probs of a generation, recorded
  * on the device.  After vz_llm_decode_scores(what != 0) every decode step writes, behind its tail (argmax, sampler or per-row tail) and
  * inside the per-token hipGraph, one record of four 32-bit words per row about the token the tail chose:
@@ -518,15 +561,15 @@ int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mo
  * device; vz_llm_decode_set_row leaves it alone.  The pointers, `what` and cap_steps are frozen by a captured step: a change captures
  * again, and with the recorder off no launch is added.  vz_llm_decode_steps refuses n > cap_steps and the recorder together with the beam
  * or the speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.  what = 0: off.
- * vz_op_token_scores: the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by h_mode[r] (0 =
- * greedy, 1 = sampled) and its temperature / top_k / top_p as vz_op_sample_rows takes them: d_rec [rows][4], d_warped [rows][cols] or
+ * vz_op_token_scores: the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by the record
+ * h_rows[r] as vz_op_sample_rows takes it (seed and counter are checked, not read): d_rec [rows][4], d_warped [rows][cols] or
  * null (the first token of a generation, chosen from the prefill logits; tests). */
 #define VZ_SCORE_REC    1u   /* the 16-byte records            */
 #define VZ_SCORE_WARPED 2u   /* + processed, warped score rows */
 #define VZ_SCORE_RAW    4u   /* + raw logits rows              */
 int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, float* d_warped, float* d_raw, int cap_steps, vz_stream stream);
-int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
-                       const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream);
+int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const vz_sample_params* h_rows, float* d_rec,
+                       float* d_warped, vz_stream stream);
 /* Stop matcher (csrc/stop.hip: stop_match_kernel): stop strings and keyword stops decided on the device.  After
  * vz_llm_decode_stop(enable = 1) every decode step runs, behind its tail (argmax, sampler or per-row tail; behind the step recorder if
  * that is armed) and inside the per-token hipGraph, one 64-lane wave per row over the row's state: n = generated tokens seen, at = -1
@@ -754,58 +797,15 @@ int vz_prof_gemm_stamps(long long* host_out, int max_wgs, int* n_wgs);
  * of per-workgroup schedule: start, end (s_memrealtime, 100 MHz), XCC id << 32 | HW_ID, query block << 32 | tiles.  host buffer: 16 + 8192 int64 */
 int vz_prof_attn_stamps(long long* host16);
 
-/* ---- HF's warpers behind top-k / top-p (csrc/sampling.hip step 3b) ----
- * The sampling entry points above with one more column: the warpers hf:generation/utils.py `_get_logits_processor` puts behind
- * TopPLogitsWarper, in its order - h_warp [4] (one sequence) or [rows][4] (per row) = (min_p, typical_p, epsilon_cutoff, eta_cutoff):
- *   min_p           drop p_i < min_p * p_max                              0 <= min_p <= 1; 0 = off
- *   typical_p       ascending in |-log p_i - H| keep the shortest prefix whose mass reaches typical_p (it may leave out the most
- *                   likely token)                                           0 or >= 1 = off
- *   epsilon_cutoff  drop p_i < epsilon                                    0 or >= 1 = off
- *   eta_cutoff      drop p_i < min(eta, sqrt(eta) * exp(-H))              0 or >= 1 = off
- * each over the set the one before it left (p = softmax over that set, H its entropy) and each keeping at least the largest score
- * of that set.  The kept set is a key interval of x; the draw and the step recorder (lse_kept, n_kept, warped rows) take the same
- * one.  A greedy row ignores the column.  h_warp = NULL: all off - then every call below is the entry point it extends, which keep
- * their signatures and meaning.  A negative or NaN entry, or min_p > 1: VZ_ERR_ARG. */
-int vz_llm_decode_sampling_warp(vz_engine* e, int enable, float temperature, int top_k, float top_p, const float* h_warp,
-                                unsigned long long seed, int first_counter);
-int vz_op_sample_warp(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, const float* h_warp,
-                      unsigned long long seed, int counter, int* d_ids, vz_stream stream);
-int vz_llm_decode_sampling_rows_warp(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                     const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter);
-int vz_llm_decode_set_row_sampling_warp(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, const float* h_warp,
-                                        unsigned long long seed, int counter, vz_stream stream);
-int vz_op_sample_rows_warp(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                           const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter, int* d_ids,
-                           vz_stream stream);
-int vz_op_token_scores_warp(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
-                            const int* h_top_k, const float* h_top_p, const float* h_warp, float* d_rec, float* d_warped, vz_stream stream);
-
-/* ---- sequence_bias and bad_words_ids in the processor filter (csrc/logits_proc.hip) ----
- * vz_llm_decode_logits_proc / vz_op_logits_process with one more table: the id sequences of hf:SequenceBiasLogitsProcessor (first in
- * HF's chain, in front of the repetition penalty) and hf:NoBadWordsLogitsProcessor (behind the n-gram ban), h_seq [n_seq][12] ints =
- *   [len 1..8 | kind: 0 = bias, 1 = bad word | bias, fp32 bits | 0 | ids[8]],  n_seq <= 64
- * with the one-id sequences first and each group in the caller's order - the order HF adds the biases in.  A one-id sequence acts at
- * every step; a longer one acts on its last id when the ids generated so far end in its first len - 1 ids and (HF's length check) at
- * least len ids were generated.  Biases that land on one id add up in fp32 in table order, then the penalty acts on the biased score,
- * then the bans write -inf; a bad word bans without arithmetic.  Ids outside [0, cols) are ignored.  The engine keeps the table in its
- * own device memory: an arming with the table of the previous arming uploads nothing, a new table is uploaded outside any capture and
- * the next vz_llm_decode_steps captures again.  n_seq = 0: the entry points they extend, which keep their signatures and meaning. */
-int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
-                                  const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, const int* h_seq, int n_seq,
-                                  vz_stream stream);
-int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
-                             int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
-                             const int* h_seq, int n_seq, vz_stream stream);
-
 /* ---- beam search: processors and rows (csrc/beam.hip, csrc/logits_proc.hip) ----
- * vz_llm_decode_logits_proc[_seq] may be armed together with vz_llm_decode_beam.  HF's `_beam_search` hands the processors the
+ * vz_llm_decode_logits_proc may be armed together with vz_llm_decode_beam.  HF's `_beam_search` hands the processors the
  * log-softmax row of every running beam and that beam's own ids, so a beam step then runs: log-prob rows in place (the reductions
  * and the fp32 association of the fused select), the processor kernel on them, the select on the rows as they are (s_i = row_i +
  * score[row]), the KV reorder, the reorder of the id histories (a row whose parent is another row takes its parent's history,
  * length included; the processor kernel appends the row's own token at the next step), the history index.  Without processors and
  * without recorded score rows the step is the fused select on the logits, launch for launch.  Log-prob rows followed by the select on
  * rows give the records and next beams of the fused select bit for bit.  The first step runs at op level on the prefill logits:
- * vz_op_beam_logprob_rows, vz_op_logits_process_seq with empty histories, vz_op_beam_select_rows with nb_in = 1.
+ * vz_op_beam_logprob_rows, vz_op_logits_process with empty histories, vz_op_beam_select_rows with nb_in = 1.
  * vz_op_beam_logprob_rows: d_lp [rows][cols] = (x - max) - log(sum exp(x - max)) of fp32 logits; d_lp may be d_logits.
  * vz_op_beam_select_rows: vz_op_beam_select on rows that hold scores already (no normalisation).
  * vz_op_hist_beam_reorder: groups x nb (<= 16) histories d_hist [groups * nb][hist_stride] of d_hist_len[row] ids follow d_parent

@@ -328,9 +328,9 @@ def test_refusals(model, prompt):
     eng = model.engine
     for bad in ((0.0, 0, 0), (1.2, 9, 0), (1.2, -1, 0), (1.2, 0, -1)):
         with pytest.raises(ValueError):
-            B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, 1, bad[0], bad[1], bad[2], None, 0, None, 0, None))
+            B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, B.C.byref(B.VzLogitsProcParams(bad[0], bad[1], bad[2], 0, 0, 0, None, None, None)), None))
     ids = (B.C.c_int * 17)(*range(17))
     with pytest.raises(ValueError):
-        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, 1, 1.2, 0, 0, ids, 5, None, 0, None))
+        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, B.C.byref(B.VzLogitsProcParams(1.2, 0, 0, 5, 0, 0, ids, None, None)), None))
     with pytest.raises(ValueError):
-        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, 1, 1.2, 0, 0, None, 0, ids, 17, None))
+        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, B.C.byref(B.VzLogitsProcParams(1.2, 0, 0, 0, 17, 0, None, ids, None)), None))

@@ -116,7 +116,8 @@ def test_op_refuses_what_the_table_cannot_hold():
 
     def call(tab, n):
         arr = (B.C.c_int * len(tab))(*tab)
-        B.check(B.lib().vz_op_logits_process_seq(B.ptr(x), 1, 1000, B.ptr(h), 8, B.ptr(hl), 1.0, 0, 0, None, 0, None, 0, arr, n, B.stream_ptr(x.device)))
+        rec = B.VzLogitsProcParams(1.0, 0, 0, 0, 0, n, None, None, arr)
+        B.check(B.lib().vz_op_logits_process(B.ptr(x), 1, 1000, B.ptr(h), 8, B.ptr(hl), B.C.byref(rec), B.stream_ptr(x.device)))
 
     one = [1, 0, 0, 0, 5, 0, 0, 0, 0, 0, 0, 0]
     call(one * 64, 64)
@@ -301,7 +302,7 @@ def test_refusals(model):
     eng = model.engine
     bad = (B.C.c_int * 12)(9, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8)
     with pytest.raises(ValueError):
-        B.check(eng.lib.vz_llm_decode_logits_proc_seq(eng.h, 1, 1.0, 0, 0, None, 0, None, 0, bad, 1, None))
+        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, B.C.byref(B.VzLogitsProcParams(1.0, 0, 0, 0, 0, 1, None, None, bad)), None))
     with pytest.raises(ValueError):
-        B.check(eng.lib.vz_llm_decode_logits_proc_seq(eng.h, 1, 1.0, 0, 0, None, 0, None, 0, None, 65, None))
+        B.check(eng.lib.vz_llm_decode_logits_proc(eng.h, B.C.byref(B.VzLogitsProcParams(1.0, 0, 0, 0, 0, 65, None, None, None)), None))
     eng.set_logits_proc(None)

@@ -32,7 +32,7 @@ void vz_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* vz_last_error(void) { return g_err; }
-extern "C" int vz_abi_version(void) { return 10; }
+extern "C" int vz_abi_version(void) { return 11; }
 extern "C" const char* vz_target_arch(void) { return "gfx950"; }
 
 // ------------------------------------------------------------------------------------------------
@@ -1191,7 +1191,7 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
         hs.slot[b] = h_ctx_len[b];         // slot the next token is written to
         hs.len[b] = h_ctx_len[b] + 1;      // keys visible to the next token
     }
-    *hs.ctr = e->samp.ctr0; hs.seed[0] = e->samp.seed[0]; hs.seed[1] = e->samp.seed[1];      // (step = 0)
+    *hs.ctr = e->samp.rec.ctr; hs.seed[0] = e->samp.rec.seed[0]; hs.seed[1] = e->samp.rec.seed[1];      // (step = 0)
     for (size_t r = 0; r < e->rows.tab.size(); ++r) hs.samp[r] = e->rows.tab[r];            // (never set: zeros = every row greedy)
     RC(upload_ints(e, hs.pos, h.size() - mb, ds.pos, s));
     VZ_CHECK_HIP(hipMemcpyAsync(ds.cur, d_first_ids, B * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1256,17 +1256,6 @@ static int* proc_base(const vz_engine* e) { return e->proc.d + proc_len_ints(e->
 static int* proc_hist(const vz_engine* e) { return e->proc.d + 2 * proc_len_ints(e->c); }
 // the stop matcher's per-row count of ids its ring was seeded with (vz_llm_decode_stop_seed): behind the rows' states
 static int* stop_pre(const vz_engine* e) { return e->stop.d_state + (size_t)e->c.max_batch * VZ_STOP_ROW; }
-static int proc_args_of(float penalty, int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, ProcArgs* out) {
-    VZ_CHECK_ARG(penalty > 0.f && ngram >= 0 && ngram <= 8 && min_new >= 0, "logits_proc: repetition penalty %g > 0, 0 <= n-gram size %d <= 8, "
-                 "min_new_tokens %d >= 0 expected", (double)penalty, ngram, min_new);
-    VZ_CHECK_ARG(n_eos >= 0 && n_eos <= 4 && (n_eos == 0 || h_eos), "logits_proc: 0..4 eos ids expected, got %d", n_eos);
-    VZ_CHECK_ARG(n_suppress >= 0 && n_suppress <= 16 && (n_suppress == 0 || h_suppress), "logits_proc: 0..16 suppressed ids expected, got %d", n_suppress);
-    memset(out, 0, sizeof(*out));
-    out->penalty = penalty; out->ngram = ngram; out->min_new = min_new; out->eos.n = n_eos; out->n_suppress = n_suppress;
-    for (int i = 0; i < 4; ++i) out->eos.id[i] = i < n_eos ? h_eos[i] : -1;
-    for (int i = 0; i < 16; ++i) out->suppress[i] = i < n_suppress ? h_suppress[i] : -1;
-    return VZ_OK;
-}
 // the id-sequence table of sequence_bias / bad_words_ids as the entry points take it (vz_common.h: ProcArgs)
 static int proc_seq_check(const int* h_seq, int n_seq) {
     VZ_CHECK_ARG(n_seq >= 0 && n_seq <= VZ_PROC_MAX_SEQ && (n_seq == 0 || h_seq), "logits_proc: 0..%d id sequences expected, got %d", VZ_PROC_MAX_SEQ, n_seq);
@@ -1276,6 +1265,21 @@ static int proc_seq_check(const int* h_seq, int n_seq) {
                      k, q[0], VZ_PROC_SEQ_IDS, q[1]);
         for (int j = 0; j < q[0]; ++j) VZ_CHECK_ARG(q[4 + j] >= 0, "logits_proc: id sequence %d holds the negative id %d", k, q[4 + j]);
     }
+    return VZ_OK;
+}
+// the one check of a processor record (include/viszephyr.h: vz_logits_proc_params), its id-sequence table included: what the kernel
+// takes by value (seq_epoch is the business of whoever owns the table's device memory)
+static int proc_args_of(const vz_logits_proc_params& p, ProcArgs* out) {
+    VZ_CHECK_ARG(p.repetition_penalty > 0.f && p.no_repeat_ngram >= 0 && p.no_repeat_ngram <= 8 && p.min_new_tokens >= 0, "logits_proc: repetition penalty %g > 0, "
+                 "0 <= n-gram size %d <= 8, min_new_tokens %d >= 0 expected", (double)p.repetition_penalty, p.no_repeat_ngram, p.min_new_tokens);
+    VZ_CHECK_ARG(p.n_eos >= 0 && p.n_eos <= 4 && (p.n_eos == 0 || p.eos), "logits_proc: 0..4 eos ids expected, got %d", p.n_eos);
+    VZ_CHECK_ARG(p.n_suppress >= 0 && p.n_suppress <= 16 && (p.n_suppress == 0 || p.suppress), "logits_proc: 0..16 suppressed ids expected, got %d", p.n_suppress);
+    RC(proc_seq_check(p.seq, p.n_seq));
+    memset(out, 0, sizeof(*out));
+    out->penalty = p.repetition_penalty; out->ngram = p.no_repeat_ngram; out->min_new = p.min_new_tokens; out->eos.n = p.n_eos;
+    out->n_suppress = p.n_suppress; out->n_seq = p.n_seq;
+    for (int i = 0; i < 4; ++i) out->eos.id[i] = i < p.n_eos ? p.eos[i] : -1;
+    for (int i = 0; i < 16; ++i) out->suppress[i] = i < p.n_suppress ? p.suppress[i] : -1;
     return VZ_OK;
 }
 
@@ -1405,7 +1409,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             RC(vz_launch_sample_rows(e->d_logits, B, c.vocab, st.samp, st.cur, emit, s));
             break;
         case TAIL_SAMPLE:
-            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, e->samp.a.warp, st.seed, st.ctr, 0, st.cur, emit, s));
+            RC(vz_launch_sample(e->d_logits, B, c.vocab, e->samp.rec.temp, e->samp.rec.top_k, e->samp.rec.top_p, e->samp.rec.warp, st.seed, st.ctr, 0, st.cur, emit, s));
             break;
         case TAIL_GREEDY:
             RC(vz_launch_argmax(e->d_logits, B, c.vocab, st.cur, emit, s));
@@ -1413,9 +1417,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         }
         if (e->score.what) {
             // sampling.hip: the record of the token the tail just left in st.cur, by the parameters the tail took it with
-            const RowSample one = tail == TAIL_SAMPLE ? RowSample{VZ_ROW_SAMPLE, e->samp.a.temp, e->samp.a.top_k, e->samp.a.top_p, {0u, 0u}, 0, 0, e->samp.a.warp}
-                                                      : RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0};
-            RC(vz_launch_token_scores(e->d_logits, B, c.vocab, tail == TAIL_ROWS ? st.samp : nullptr, one, st.cur, e->score.rec,
+            RC(vz_launch_token_scores(e->d_logits, B, c.vocab, tail == TAIL_ROWS ? st.samp : nullptr, tail == TAIL_SAMPLE ? e->samp.rec : ROW_GREEDY, st.cur, e->score.rec,
                                       (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
         }
         // stop.hip: the token the tail just left in st.cur through the rows' stop conditions (writes its own state only)
@@ -1427,7 +1429,38 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
     return VZ_OK;
 }
 
-static int row_sample_of(int mode, float temperature, int top_k, float top_p, const float* warp, unsigned long long seed, int counter, RowSample* out);
+// The one check of a sampler record (include/viszephyr.h: vz_sample_params).  The checked, normalised copy is what the kernels read: an entry
+// of the per-row table, the sampler's arguments, the recorder's `one`.  A greedy record becomes the canonical greedy entry with its counter,
+// its other fields neither checked nor kept.
+static int row_sample_of(const vz_sample_params& p, RowSample* out) {
+    VZ_CHECK_ARG((p.mode == VZ_ROW_GREEDY || p.mode == VZ_ROW_SAMPLE) && p.counter >= 0, "row sampling: mode %d (0 = greedy, 1 = sample), counter %d >= 0 expected", p.mode, p.counter);
+    *out = ROW_GREEDY; out->ctr = p.counter;
+    if (p.mode == VZ_ROW_GREEDY) return VZ_OK;
+    // (written so that a NaN fails)
+    VZ_CHECK_ARG(p.temperature > 0.f && p.top_k >= 0 && p.top_p > 0.f && p.top_p <= 1.f,
+                 "row sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)p.temperature, p.top_k, (double)p.top_p);
+    VZ_CHECK_ARG(p.min_p >= 0.f && p.min_p <= 1.f && p.typical_p >= 0.f && p.epsilon_cutoff >= 0.f && p.eta_cutoff >= 0.f,
+                 "sampling warpers: 0 <= min_p %g <= 1, typical_p %g >= 0, epsilon_cutoff %g >= 0, eta_cutoff %g >= 0 expected", (double)p.min_p,
+                 (double)p.typical_p, (double)p.epsilon_cutoff, (double)p.eta_cutoff);
+    // HF's off values arm nothing: typical_p >= 1, a cutoff outside (0, 1)
+    const auto off_at_1 = [](float v) { return v < 1.f ? v : 0.f; };
+    *out = RowSample{VZ_ROW_SAMPLE, p.temperature, p.top_k, p.top_p, {(unsigned)p.seed, (unsigned)(p.seed >> 32)}, p.counter, 0,
+                     {p.min_p, off_at_1(p.typical_p), off_at_1(p.epsilon_cutoff), off_at_1(p.eta_cutoff)}};
+    return VZ_OK;
+}
+// `rows` <= 64 records of an op-level call, checked, as a table in this (device, stream)'s own scratch
+static int row_samples_to_device(const char* who, const vz_sample_params* h_rows, int rows, hipStream_t s, RowSample** d_tab) {
+    VZ_CHECK_ARG(h_rows, "row sampling: null parameter array");
+    RowSample tab[64];
+    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_rows[r], tab + r));
+    void* p = nullptr; size_t have = 0;
+    RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
+    VZ_CHECK_ARG(p && have >= sizeof(tab), "%s: first use of a stream inside a capture (call it once before capturing)", who);
+    VZ_CHECK_HIP(hipMemcpyAsync(p, tab, (size_t)rows * sizeof(RowSample), hipMemcpyHostToDevice, s));
+    VZ_CHECK_HIP(hipStreamSynchronize(s));          // the table is on this frame: it has been read before the call returns
+    *d_tab = (RowSample*)p;
+    return VZ_OK;
+}
 
 // The stop matcher (stop.hip: stop_match_kernel): armed, every decode step whose tail is the argmax, the sampler or the
 // per-row tail passes, behind that tail (and the recorder) and inside the per-token hipGraph, the token each row just chose through the
@@ -1549,117 +1582,56 @@ extern "C" int vz_llm_decode_scores(vz_engine* e, unsigned what, float* d_rec, f
     return VZ_OK;
 }
 
-// the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by (h_mode[r] 0 = greedy / 1 = sampled,
-// temperature, top_k, top_p) as vz_op_sample_rows takes them: d_rec [rows][4], d_warped [rows][cols] or null (the first token's record,
-// taken from the prefill logits; tests)
-extern "C" int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
-                                  const int* h_top_k, const float* h_top_p, float* d_rec, float* d_warped, vz_stream stream) {
-    return vz_op_token_scores_warp(d_logits, rows, cols, d_ids, h_mode, h_temperature, h_top_k, h_top_p, nullptr, d_rec, d_warped, stream);
-}
-// ... with the rows' further warpers h_warp [rows][4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff), 0 = off; null: all off
-extern "C" int vz_op_token_scores_warp(const float* d_logits, int rows, int cols, const int* d_ids, const int* h_mode, const float* h_temperature,
-                                       const int* h_top_k, const float* h_top_p, const float* h_warp, float* d_rec, float* d_warped, vz_stream stream) {
+// the same kernel on fp32 logits [rows <= 64, cols] about the tokens d_ids [rows] (int32), row r by the record h_rows[r] as
+// vz_op_sample_rows takes it: d_rec [rows][4], d_warped [rows][cols] or null (the first token's record, taken from the prefill logits; tests)
+extern "C" int vz_op_token_scores(const float* d_logits, int rows, int cols, const int* d_ids, const vz_sample_params* h_rows, float* d_rec,
+                                  float* d_warped, vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_ids && d_rec && rows >= 1 && rows <= 64 && cols >= 1, "token_scores: bad argument (1..64 rows)");
-    VZ_CHECK_ARG(h_mode && h_temperature && h_top_k && h_top_p, "token_scores: null parameter array");
-    RowSample tab[64];
-    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_warp ? h_warp + 4 * r : nullptr, 0ull, 0, tab + r));
-    void* p = nullptr; size_t have = 0;
-    RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
-    VZ_CHECK_ARG(p && have >= sizeof(tab), "token_scores: first use of a stream inside a capture (call it once before capturing)");
-    VZ_CHECK_HIP(hipMemcpyAsync(p, tab, (size_t)rows * sizeof(RowSample), hipMemcpyHostToDevice, s));
-    VZ_CHECK_HIP(hipStreamSynchronize(s));          // the table is on this frame: it has been read before the call returns
-    return vz_launch_token_scores(d_logits, rows, cols, (const RowSample*)p, tab[0], d_ids, d_rec, d_warped, nullptr, 0, s);
+    RowSample* tab = nullptr;
+    RC(row_samples_to_device("token_scores", h_rows, rows, s, &tab));
+    return vz_launch_token_scores(d_logits, rows, cols, tab, ROW_GREEDY, d_ids, d_rec, d_warped, nullptr, 0, s);
 }
 
-// Sampling instead of argmax as the tail of every decode step (hf:generation/utils.py `_sample`, do_sample=True; see
-// sampling.hip): temperature > 0, top_k (0 = off; HF's default 50 is the caller's business), top_p (1 = off), a 64-bit seed and
-// the draw counter the NEXT vz_llm_decode_begin starts from (the caller drew token 0 from the prefill logits with vz_op_sample
-// and counter 0, so it passes 1).  enable = 0: greedy.
-static int sample_warp_of(const float* w, SampleWarp* out) {
-    *out = SampleWarp{0.f, 0.f, 0.f, 0.f};
-    if (!w) return VZ_OK;
-    // (written so that a NaN fails)
-    VZ_CHECK_ARG(w[0] >= 0.f && w[0] <= 1.f && w[1] >= 0.f && w[2] >= 0.f && w[3] >= 0.f,
-                 "sampling warpers: 0 <= min_p %g <= 1, typical_p %g >= 0, epsilon_cutoff %g >= 0, eta_cutoff %g >= 0 expected", (double)w[0], (double)w[1],
-                 (double)w[2], (double)w[3]);
-    // HF's off values arm nothing: typical_p >= 1, a cutoff outside (0, 1)
-    *out = SampleWarp{w[0], w[1] < 1.f ? w[1] : 0.f, w[2] < 1.f ? w[2] : 0.f, w[3] < 1.f ? w[3] : 0.f};
-    return VZ_OK;
-}
-
-extern "C" int vz_llm_decode_sampling(vz_engine* e, int enable, float temperature, int top_k, float top_p, unsigned long long seed,
-                                      int first_counter) {
-    return vz_llm_decode_sampling_warp(e, enable, temperature, top_k, top_p, nullptr, seed, first_counter);
-}
-// ... with HF's further warpers h_warp [4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff) behind top-p, 0 = off; null: all off
-extern "C" int vz_llm_decode_sampling_warp(vz_engine* e, int enable, float temperature, int top_k, float top_p, const float* h_warp,
-                                           unsigned long long seed, int first_counter) {
-    VZ_CHECK_ARG(e && first_counter >= 0, "decode_sampling: null engine / negative counter");
-    e->samp.ctr0 = first_counter;        // the draw counter also indexes the host-visible token ring of a greedy streamer loop
-    if (!enable) { e->samp.on = 0; return VZ_OK; }
-    VZ_CHECK_ARG(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f && first_counter >= 0,
-                 "decode_sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
-    SampleWarp wp;
-    RC(sample_warp_of(h_warp, &wp));
-    e->samp.on = 1; e->samp.a = SampleArgs{top_k, temperature, top_p, wp};
-    e->samp.seed[0] = (unsigned)seed; e->samp.seed[1] = (unsigned)(seed >> 32);
+// Sampling instead of argmax as the tail of every decode step (hf:generation/utils.py `_sample`, do_sample=True; see sampling.hip) by a
+// VZ_ROW_SAMPLE record: temperature, top_k (HF's default 50 is the caller's business), top_p, the warpers, a 64-bit seed and the draw
+// counter the NEXT vz_llm_decode_begin starts from (the caller drew token 0 from the prefill logits with vz_op_sample and counter 0,
+// so it passes 1).  A VZ_ROW_GREEDY record: greedy.
+extern "C" int vz_llm_decode_sampling(vz_engine* e, const vz_sample_params* p) {
+    VZ_CHECK_ARG(e && p, "decode_sampling: null engine / record");
+    RowSample r;
+    RC(row_sample_of(*p, &r));
+    // (the draw counter also indexes the host-visible token ring of a greedy streamer loop)
+    if (r.mode == VZ_ROW_GREEDY) { e->samp.on = 0; e->samp.rec.ctr = r.ctr; return VZ_OK; }
+    e->samp.on = 1; e->samp.rec = r;
     return VZ_OK;
 }
 
 // The per-row tail: every row of the decode batch chooses its next token by its own entry of a table in device memory (sampling.hip:
 // sample_rows_kernel) - greedy, or sampled with its own temperature / top-k / top-p, 64-bit seed and draw counter.  Rows are independent
-// requests (continuous batching) or the n samples of one prompt.  An entry is checked as vz_llm_decode_sampling checks its arguments.
-static int row_sample_of(int mode, float temperature, int top_k, float top_p, const float* warp, unsigned long long seed, int counter, RowSample* out) {
-    VZ_CHECK_ARG((mode == VZ_ROW_GREEDY || mode == VZ_ROW_SAMPLE) && counter >= 0, "row sampling: mode %d (0 = greedy, 1 = sample), counter %d >= 0 expected", mode, counter);
-    VZ_CHECK_ARG(mode == VZ_ROW_GREEDY || (temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f),
-                 "row sampling: temperature %g > 0, top_k %d >= 0, 0 < top_p %g <= 1 expected", (double)temperature, top_k, (double)top_p);
-    SampleWarp wp;
-    RC(sample_warp_of(mode == VZ_ROW_GREEDY ? nullptr : warp, &wp));
-    *out = mode == VZ_ROW_GREEDY ? RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, counter, 0, wp}
-                                 : RowSample{VZ_ROW_SAMPLE, temperature, top_k, top_p, {(unsigned)seed, (unsigned)(seed >> 32)}, counter, 0, wp};
-    return VZ_OK;
-}
-static int row_samples_of(int rows, const int* h_mode, const float* h_temperature, const int* h_top_k, const float* h_top_p, const float* h_warp,
-                          const unsigned long long* h_seed, const int* h_counter, RowSample* out) {
-    VZ_CHECK_ARG(rows == 0 || (h_mode && h_temperature && h_top_k && h_top_p && h_seed && h_counter), "row sampling: null parameter array");
-    for (int r = 0; r < rows; ++r)
-        RC(row_sample_of(h_mode[r], h_temperature[r], h_top_k[r], h_top_p[r], h_warp ? h_warp + 4 * r : nullptr, h_seed[r], h_counter[r], out + r));
-    return VZ_OK;
-}
-
-// enable = 1: the tail of every decode step is the per-row kernel, and the NEXT vz_llm_decode_begin uploads these `rows` entries (row r =
-// the r-th element of each array; the rows behind them greedy, rows = 0: every row greedy until vz_llm_decode_set_row_sampling arms it).
+// requests (continuous batching) or the n samples of one prompt.
+// enable = 1: the tail of every decode step is the per-row kernel, and the NEXT vz_llm_decode_begin uploads these `rows` entries (the rows
+// behind them greedy, rows = 0: every row greedy until vz_llm_decode_set_row_sampling arms it).
 // The table is device memory the captured step reads through a pointer: a changed entry needs no new graph.  enable = 0: off.
-extern "C" int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                           const float* h_top_p, const unsigned long long* h_seed, const int* h_counter) {
-    return vz_llm_decode_sampling_rows_warp(e, enable, rows, h_mode, h_temperature, h_top_k, h_top_p, nullptr, h_seed, h_counter);
-}
-// ... with the rows' further warpers h_warp [rows][4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff), 0 = off; null: all off
-extern "C" int vz_llm_decode_sampling_rows_warp(vz_engine* e, int enable, int rows, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                                const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter) {
+extern "C" int vz_llm_decode_sampling_rows(vz_engine* e, int enable, int rows, const vz_sample_params* h_rows) {
     VZ_CHECK_ARG(e, "decode_sampling_rows: null engine");
     if (!enable) { e->rows.on = 0; e->rows.tab.clear(); return VZ_OK; }
     if (e->tp > 1) { vz_set_error("decode_sampling_rows: the per-row tail on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(rows >= 0 && rows <= e->c.max_batch, "decode_sampling_rows: %d rows outside [0, max_batch = %d]", rows, e->c.max_batch);
-    std::vector<RowSample> tab((size_t)e->c.max_batch, RowSample{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0});
-    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_warp, h_seed, h_counter, tab.data()));
+    VZ_CHECK_ARG(rows == 0 || h_rows, "row sampling: null parameter array");
+    std::vector<RowSample> tab((size_t)e->c.max_batch, ROW_GREEDY);
+    for (int r = 0; r < rows; ++r) RC(row_sample_of(h_rows[r], &tab[r]));
     e->rows.tab.swap(tab);
     e->rows.on = 1;
     return VZ_OK;
 }
 
 // The sampling counterpart of vz_llm_decode_set_row: one row's entry of the running batch, stream-ordered, the other rows untouched.
-extern "C" int vz_llm_decode_set_row_sampling(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, unsigned long long seed,
-                                              int counter, vz_stream stream) {
-    return vz_llm_decode_set_row_sampling_warp(e, row, mode, temperature, top_k, top_p, nullptr, seed, counter, stream);
-}
-extern "C" int vz_llm_decode_set_row_sampling_warp(vz_engine* e, int row, int mode, float temperature, int top_k, float top_p, const float* h_warp,
-                                                   unsigned long long seed, int counter, vz_stream stream) {
+extern "C" int vz_llm_decode_set_row_sampling(vz_engine* e, int row, const vz_sample_params* p, vz_stream stream) {
     NEED_READY();
-    VZ_CHECK_ARG(e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row_sampling: row %d outside the running batch of %d", row, e->dec_B);
+    VZ_CHECK_ARG(p && e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row_sampling: row %d outside the running batch of %d", row, e->dec_B);
     RowSample rs;
-    RC(row_sample_of(mode, temperature, top_k, top_p, h_warp, seed, counter, &rs));
+    RC(row_sample_of(*p, &rs));
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(e->h_pinned && e->h_pinned_ints >= (size_t)DecodeState::SAMPLE_INTS, "decode_set_row_sampling: no staging buffer (vz_llm_decode_begin allocates it)");
     VZ_CHECK_HIP(hipStreamSynchronize(s));                        // previous use of the staging buffer has drained
@@ -1670,23 +1642,12 @@ extern "C" int vz_llm_decode_set_row_sampling_warp(vz_engine* e, int row, int mo
 
 // one token per row of fp32 logits [rows, cols] with the per-row kernel, rows <= 64 (the first tokens of sampled sequences, drawn from
 // the prefill logits with counter 0; tests).  The table goes through this (device, stream)'s own scratch.
-extern "C" int vz_op_sample_rows(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                 const float* h_top_p, const unsigned long long* h_seed, const int* h_counter, int* d_ids, vz_stream stream) {
-    return vz_op_sample_rows_warp(d_logits, rows, cols, h_mode, h_temperature, h_top_k, h_top_p, nullptr, h_seed, h_counter, d_ids, stream);
-}
-extern "C" int vz_op_sample_rows_warp(const float* d_logits, int rows, int cols, const int* h_mode, const float* h_temperature, const int* h_top_k,
-                                      const float* h_top_p, const float* h_warp, const unsigned long long* h_seed, const int* h_counter, int* d_ids,
-                                      vz_stream stream) {
+extern "C" int vz_op_sample_rows(const float* d_logits, int rows, int cols, const vz_sample_params* h_rows, int* d_ids, vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(d_logits && d_ids && rows >= 1 && rows <= 64 && cols >= 1, "sample_rows: bad argument (1..64 rows)");
-    RowSample tab[64];
-    RC(row_samples_of(rows, h_mode, h_temperature, h_top_k, h_top_p, h_warp, h_seed, h_counter, tab));
-    void* p = nullptr; size_t have = 0;
-    RC(vz_stream_ws(6, s, sizeof(tab), false, &p, &have));
-    VZ_CHECK_ARG(p && have >= sizeof(tab), "sample_rows: first use of a stream inside a capture (call it once before capturing)");
-    VZ_CHECK_HIP(hipMemcpyAsync(p, tab, (size_t)rows * sizeof(RowSample), hipMemcpyHostToDevice, s));
-    VZ_CHECK_HIP(hipStreamSynchronize(s));          // the table is on this frame: it has been read before the call returns
-    return vz_launch_sample_rows(d_logits, rows, cols, (RowSample*)p, d_ids, {}, s);
+    RowSample* tab = nullptr;
+    RC(row_samples_to_device("sample_rows", h_rows, rows, s, &tab));
+    return vz_launch_sample_rows(d_logits, rows, cols, tab, d_ids, {}, s);
 }
 
 // Streamer / stopping-criteria path: besides d_out_ids every step's tail also writes its token to ring[row * ring_n + (draw
@@ -1698,25 +1659,22 @@ extern "C" int vz_llm_decode_ring(vz_engine* e, int* ring, int ring_n, int ring_
     return VZ_OK;
 }
 
-// one draw per row of fp32 logits [rows, cols] with the same kernel (the first token of a sampled generation; tests)
-extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p,
-                            unsigned long long seed, int counter, int* d_ids, vz_stream stream) {
-    return vz_op_sample_warp(d_logits, rows, cols, temperature, top_k, top_p, nullptr, seed, counter, d_ids, stream);
-}
-extern "C" int vz_op_sample_warp(const float* d_logits, int rows, int cols, float temperature, int top_k, float top_p, const float* h_warp,
-                                 unsigned long long seed, int counter, int* d_ids, vz_stream stream) {
+// one draw per row of fp32 logits [rows, cols] with the sampler's kernel, every row by the one VZ_ROW_SAMPLE record (the first token of a
+// sampled generation; tests)
+extern "C" int vz_op_sample(const float* d_logits, int rows, int cols, const vz_sample_params* p, int* d_ids, vz_stream stream) {
     // [counter, seed lo, seed hi, -] in this (device, stream)'s own scratch words: launches on other streams or devices have theirs
     hipStream_t s = (hipStream_t)stream;
-    VZ_CHECK_ARG(d_logits && d_ids && rows >= 1 && cols >= 1, "sample: bad argument");
-    SampleWarp wp;
-    RC(sample_warp_of(h_warp, &wp));
+    VZ_CHECK_ARG(d_logits && d_ids && p && rows >= 1 && cols >= 1, "sample: bad argument");
+    RowSample r;
+    RC(row_sample_of(*p, &r));
+    VZ_CHECK_ARG(r.mode == VZ_ROW_SAMPLE, "sample: a VZ_ROW_SAMPLE record expected (greedy: vz_op_argmax)");
     int* d_scratch = nullptr;
     { void* p = nullptr; size_t have = 0; int r = vz_stream_ws(4, s, 64, true, &p, &have); if (r) return r;
       VZ_CHECK_ARG(p && have >= 16, "sample: first use of a stream inside a capture (call it once before capturing)"); d_scratch = (int*)p; }
-    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)d_scratch, counter, 1, s));
-    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 1), (int)(unsigned)seed, 1, s));
-    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 2), (int)(unsigned)(seed >> 32), 1, s));
-    return vz_launch_sample(d_logits, rows, cols, temperature, top_k, top_p, wp, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
+    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)d_scratch, r.ctr, 1, s));
+    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 1), (int)r.seed[0], 1, s));
+    VZ_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(d_scratch + 2), (int)r.seed[1], 1, s));
+    return vz_launch_sample(d_logits, rows, cols, r.temp, r.top_k, r.top_p, r.warp, (const unsigned*)(d_scratch + 1), d_scratch, 0, d_ids, {}, s);
 }
 
 // Logits processors in the step (hf:generation/logits_process.py; logits_proc.hip): after
@@ -1724,29 +1682,22 @@ extern "C" int vz_op_sample_warp(const float* d_logits, int rows, int cols, floa
 // no-repeat-n-gram (0 = off), min-new-tokens (the eos ids at -inf while fewer ids were generated) and suppress-tokens on its logits, over
 // the ids generated so far: each row's history lives on the device, restarts empty here (stream-ordered) and grows by the row's input
 // token at every step.  The mode is orthogonal to the tail; vz_llm_decode_steps refuses it together with the speculative tail.  With the
-// beam tail the kernel runs on the log-prob rows, as HF's processors do there.
-extern "C" int vz_llm_decode_logits_proc(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
-                                         const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, vz_stream stream) {
-    return vz_llm_decode_logits_proc_seq(e, enable, repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, nullptr, 0, stream);
-}
-// ... with the id sequences of HF's sequence_bias / bad_words_ids, h_seq [n_seq][VZ_PROC_SEQ_STRIDE] (include/viszephyr.h).  The table is
-// copied into the engine's own device memory here, outside any capture; the table of the previous arming again: nothing is uploaded.
-extern "C" int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float repetition_penalty, int no_repeat_ngram, int min_new_tokens,
-                                             const int* h_eos, int n_eos, const int* h_suppress, int n_suppress, const int* h_seq, int n_seq,
-                                             vz_stream stream) {
+// beam tail the kernel runs on the log-prob rows, as HF's processors do there.  The id sequences of HF's
+// sequence_bias / bad_words_ids are copied into the engine's own device memory here, outside any capture; the table of the previous
+// arming again: nothing is uploaded.  p = null: off.
+extern "C" int vz_llm_decode_logits_proc(vz_engine* e, const vz_logits_proc_params* p, vz_stream stream) {
     NEED_READY();
-    if (!enable) { e->proc.on = 0; return VZ_OK; }
+    if (!p) { e->proc.on = 0; return VZ_OK; }
     const vz_config& c = e->c;
     if (e->tp > 1) { vz_set_error("decode_logits_proc: logits processors on a tensor-parallel engine are not built"); return VZ_ERR_UNSUPPORTED; }
     ProcArgs a;
-    RC(proc_args_of(repetition_penalty, no_repeat_ngram, min_new_tokens, h_eos, n_eos, h_suppress, n_suppress, &a));
+    RC(proc_args_of(*p, &a));
     VZ_CHECK_ARG(c.vocab <= 65536, "decode_logits_proc: vocabulary of %d, the kernel's bitmaps hold 65536", c.vocab);
     hipStream_t s = (hipStream_t)stream;
     if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (2 * proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
     VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, 2 * proc_len_ints(c) * sizeof(int), s));
-    RC(proc_seq_check(h_seq, n_seq));
-    if (n_seq) {
-        std::vector<int> tab(h_seq, h_seq + (size_t)n_seq * VZ_PROC_SEQ_STRIDE);
+    if (a.n_seq) {
+        std::vector<int> tab(p->seq, p->seq + (size_t)a.n_seq * VZ_PROC_SEQ_STRIDE);
         if (!(e->proc.d_seq && tab == e->proc.h_seq)) {
             VZ_CHECK_HIP(hipStreamSynchronize(s));      // steps still in flight read the table of the previous arming
             if (!e->proc.d_seq) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d_seq, (size_t)VZ_PROC_MAX_SEQ * VZ_PROC_SEQ_STRIDE * sizeof(int)));
@@ -1754,7 +1705,7 @@ extern "C" int vz_llm_decode_logits_proc_seq(vz_engine* e, int enable, float rep
             e->proc.h_seq.swap(tab);
             e->proc.seq_epoch += 1;
         }
-        a.n_seq = n_seq; a.seq_epoch = e->proc.seq_epoch;
+        a.seq_epoch = e->proc.seq_epoch;
     }
     e->proc.on = 1; e->proc.a = a;
     return VZ_OK;
@@ -1776,32 +1727,24 @@ extern "C" int vz_llm_decode_logits_proc_seed(vz_engine* e, int row, const int* 
 }
 
 // the same kernel on fp32 logits [rows, cols] in place, over the caller's histories d_hist [rows][hist_stride] of d_hist_len[row] ids
-// each; nothing is appended (the first token of a generation: the prefill logits and empty histories; tests)
-extern "C" int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
-                                    int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
-                                    vz_stream stream) {
-    return vz_op_logits_process_seq(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, penalty, ngram, min_new, h_eos, n_eos, h_suppress, n_suppress,
-                                    nullptr, 0, stream);
-}
-// ... with the id sequences h_seq [n_seq][VZ_PROC_SEQ_STRIDE]; the table goes through this (device, stream)'s own scratch
-extern "C" int vz_op_logits_process_seq(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, float penalty,
-                                        int ngram, int min_new, const int* h_eos, int n_eos, const int* h_suppress, int n_suppress,
-                                        const int* h_seq, int n_seq, vz_stream stream) {
+// each; nothing is appended (the first token of a generation: the prefill logits and empty histories; tests).  The id-sequence table goes
+// through this (device, stream)'s own scratch
+extern "C" int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len,
+                                    const vz_logits_proc_params* p, vz_stream stream) {
     hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(p, "logits_process: null record");
     ProcArgs a;
-    RC(proc_args_of(penalty, ngram, min_new, h_eos, n_eos, h_suppress, n_suppress, &a));
-    RC(proc_seq_check(h_seq, n_seq));
-    void* p = nullptr;
-    if (n_seq) {
+    RC(proc_args_of(*p, &a));
+    void* d_seq = nullptr;
+    if (a.n_seq) {
         size_t have = 0;
         const size_t need = (size_t)VZ_PROC_MAX_SEQ * VZ_PROC_SEQ_STRIDE * sizeof(int);
-        RC(vz_stream_ws(7, s, need, false, &p, &have));
-        VZ_CHECK_ARG(p && have >= need, "logits_process: first use of a stream inside a capture (call it once before capturing)");
+        RC(vz_stream_ws(7, s, need, false, &d_seq, &have));
+        VZ_CHECK_ARG(d_seq && have >= need, "logits_process: first use of a stream inside a capture (call it once before capturing)");
         VZ_CHECK_HIP(hipStreamSynchronize(s));          // an earlier call's kernel has read its table
-        VZ_CHECK_HIP(hipMemcpy(p, h_seq, (size_t)n_seq * VZ_PROC_SEQ_STRIDE * sizeof(int), hipMemcpyHostToDevice));
-        a.n_seq = n_seq;
+        VZ_CHECK_HIP(hipMemcpy(d_seq, p->seq, (size_t)a.n_seq * VZ_PROC_SEQ_STRIDE * sizeof(int), hipMemcpyHostToDevice));
     }
-    return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (const int*)p, s);
+    return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (const int*)d_seq, s);
 }
 
 // Classifier-free guidance in the step (hf:generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor; guidance.hip;
@@ -1896,7 +1839,7 @@ extern "C" int vz_op_beam_select(const float* d_logits, int rows, int cols, int 
                                  vz_stream stream) {
     return beam_select_op(d_logits, rows, cols, nb_in, nb_out, h_eos, n_eos, d_scores_in, d_records, d_next_tok, d_next_score, d_next_parent, false, stream);
 }
-// ... on rows that hold scores already (vz_op_beam_logprob_rows, then maybe vz_op_logits_process_seq): s_i = row_i + d_scores_in[row],
+// ... on rows that hold scores already (vz_op_beam_logprob_rows, then maybe vz_op_logits_process): s_i = row_i + d_scores_in[row],
 // no normalisation.  On log-prob rows as they are it gives the records and next beams of vz_op_beam_select on the logits, bit for bit.
 extern "C" int vz_op_beam_select_rows(const float* d_rows, int rows, int cols, int nb_in, int nb_out, const int* h_eos, int n_eos,
                                       const float* d_scores_in, int* d_records, int* d_next_tok, float* d_next_score, int* d_next_parent,
@@ -2071,7 +2014,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     switch (k.kind) {
     case TAIL_SPEC: k.spec = e->spec.a; break;
     case TAIL_BEAM: k.beam = e->beam.a; k.beam_rows = e->beam.rows; break;
-    case TAIL_SAMPLE: k.samp = e->samp.a; break;
+    case TAIL_SAMPLE: k.samp = SampleArgs{e->samp.rec.top_k, e->samp.rec.temp, e->samp.rec.top_p, e->samp.rec.warp}; break;
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; k.proc_seq = e->proc.a.n_seq ? e->proc.d_seq : nullptr; }

@@ -53,6 +53,7 @@ static DecodeState decode_state(int* base, int mb) {
 // they go into the graph key as they are; they are laid out without padding (the key is compared with memcmp).
 enum TailKind { TAIL_GREEDY = 0, TAIL_SAMPLE, TAIL_BEAM, TAIL_SPEC, TAIL_ROWS };      // TAIL_ROWS takes nothing by value: its table is device memory
 struct SampleArgs { int top_k; float temp, top_p; SampleWarp warp; };
+static constexpr RowSample ROW_GREEDY{VZ_ROW_GREEDY, 1.f, 0, 1.f, {0u, 0u}, 0, 0, {0.f, 0.f, 0.f, 0.f}};      // the canonical greedy entry (row_sample_of)
 struct BeamArgs { int* hist; int nb, groups, hist_cap; BeamEos eos; };      // hist = the caller's history records, hist_cap steps
 // the beam tail's row recorder (vz_llm_decode_beam_rows): rings of `cap` steps x (groups * nb) rows x vocab fp32, written at the beam
 // tail's history index mod cap - scores = the processed log-prob rows (HF's scores[t]), raw = the logits rows; null = not recorded
@@ -122,8 +123,8 @@ struct vz_engine {
     // row is parked (continuous batching: ctx_len 0, steps harmlessly, never checked against the capacity)
     std::vector<int> h_len, h_pos; std::vector<char> h_parked;
     // the step's tail (tail_kind): each mode is armed on its own, so disarming one falls back to the next armed one
-    // sampling (vz_llm_decode_sampling): ctr0 / seed = the draw counter and the key the next vz_llm_decode_begin uploads
-    struct { int on = 0, ctr0 = 0; unsigned seed[2] = {0, 0}; SampleArgs a{0, 1.f, 1.f, {0.f, 0.f, 0.f, 0.f}}; } samp;
+    // sampling (vz_llm_decode_sampling): the checked record; its ctr / seed = the draw counter and the key the next vz_llm_decode_begin uploads
+    struct { int on = 0; RowSample rec = ROW_GREEDY; } samp;
     // per-row table (vz_llm_decode_sampling_rows): tab = the max_batch entries the next vz_llm_decode_begin uploads (all greedy until set)
     struct { int on = 0; std::vector<RowSample> tab; } rows;
     // beam search (vz_llm_decode_beam): a.groups x a.nb rows; d = the device state (beam_view)

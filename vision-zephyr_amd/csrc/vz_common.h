@@ -372,10 +372,15 @@ __device__ __forceinline__ void vz_emit_advance(const RowEmit& t, int row, int t
 // epsilon_cutoff in (0, 1), eta_cutoff in (0, 1).
 struct SampleWarp { float min_p, typical_p, epsilon, eta; };
 // One decode row's entry of the per-row tail's table (sampling.hip: sample_rows_kernel), 48 bytes in device memory: how the row's next
-// token is chosen, and the row's own Philox key and draw counter (the kernel counts it up).
-enum { VZ_ROW_GREEDY = 0, VZ_ROW_SAMPLE = 1 };
+// token is chosen, and the row's own Philox key and draw counter (the kernel counts it up).  A checked vz_sample_params
+// (include/viszephyr.h; engine.hip: row_sample_of) under the kernels' field names.
 struct RowSample { int mode; float temp; int top_k; float top_p; unsigned seed[2]; int ctr; int pad; SampleWarp warp; };
 static_assert(sizeof(RowSample) == 48, "RowSample is read as three 16-byte words");
+static_assert(sizeof(vz_sample_params) == sizeof(RowSample) && offsetof(vz_sample_params, mode) == offsetof(RowSample, mode) &&
+              offsetof(vz_sample_params, temperature) == offsetof(RowSample, temp) && offsetof(vz_sample_params, top_k) == offsetof(RowSample, top_k) &&
+              offsetof(vz_sample_params, top_p) == offsetof(RowSample, top_p) && offsetof(vz_sample_params, seed) == offsetof(RowSample, seed) &&
+              offsetof(vz_sample_params, counter) == offsetof(RowSample, ctr) && offsetof(vz_sample_params, reserved) == offsetof(RowSample, pad) &&
+              offsetof(vz_sample_params, min_p) == offsetof(RowSample, warp), "vz_sample_params is the table entry");
 int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* tab, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const SampleWarp& warp, const unsigned* seed,

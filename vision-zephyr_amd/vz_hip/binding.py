@@ -20,7 +20,7 @@ VZ_ASYNC_STREAMK = 2
 VZ_ASYNC_PERSIST = 3
 VZ_ASYNC_ONESHOT = 4
 VZ_ASYNC_ATTN_O = 5
-ABI_VERSION = 10
+ABI_VERSION = 11
 SCORE_REC, SCORE_WARPED, SCORE_RAW = 1, 2, 4          # vz_llm_decode_scores `what`
 SPEC_CTL_WRITE, SPEC_CTL_HIST, SPEC_CTL_DONE, SPEC_CTL_DRAFTED, SPEC_CTL_STEPS, SPEC_CTL_IDS, SPEC_CTL_WORDS = 0, 1, 2, 3, 4, 8, 16
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF, ACT_SWIGLU = 0, 1, 2, 3
@@ -39,6 +39,27 @@ class VzConfig(C.Structure):
         ("fusion_groups", C.c_int), ("fusion_layers_per_group", C.c_int),
         ("max_batch", C.c_int), ("max_ctx", C.c_int), ("max_tiles", C.c_int), ("max_text", C.c_int),
         ("tp_size", C.c_int), ("tp_rank", C.c_int), ("clip_keep_cls", C.c_int), ("weight_fp8", C.c_int),
+    ]
+
+
+ROW_GREEDY, ROW_SAMPLE = 0, 1
+
+
+class VzSampleParams(C.Structure):
+    """vz_sample_params: how one row chooses its next token (48 bytes, the entry of the per-row table in device memory)"""
+    _fields_ = [
+        ("mode", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float),
+        ("seed", C.c_ulonglong), ("counter", C.c_int), ("reserved", C.c_int),
+        ("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float),
+    ]
+
+
+class VzLogitsProcParams(C.Structure):
+    """vz_logits_proc_params: the logits processors' parameters and id lists (the lists are host memory the caller keeps alive)"""
+    _fields_ = [
+        ("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int), ("min_new_tokens", C.c_int),
+        ("n_eos", C.c_int), ("n_suppress", C.c_int), ("n_seq", C.c_int),
+        ("eos", C.POINTER(C.c_int)), ("suppress", C.POINTER(C.c_int)), ("seq", C.POINTER(C.c_int)),
     ]
 
 
@@ -117,7 +138,7 @@ SYMBOLS = {
     "vz_op_async_error": (_I, [_P, C.POINTER(_I)]),
     "vz_test_corrupt_streamk": (_I, [_P, _I, _I, _I]),
     "vz_engine_unset_weight": (_I, [_P, C.c_char_p]),
-    "vz_llm_decode_sampling": (_I, [_P, _I, _F, _I, _F, C.c_ulonglong, _I]),
+    "vz_llm_decode_sampling": (_I, [_P, _P]),
     "vz_llm_decode_ring": (_I, [_P, _P, _I, _I]),
     "vz_train_create": (_I, [_P, C.POINTER(_P), _P]),
     "vz_train_destroy": (_I, [_P]),
@@ -136,30 +157,22 @@ SYMBOLS = {
     "vz_train_lora_set_counter": (_I, [_P, _I, _L, _L]),
     "vz_op_lora_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _I, _I, C.c_ulonglong, _F, _F, _P]),
     "vz_op_vip_point": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_uint, _P]),
-    "vz_op_sample": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P, _P]),
-    "vz_llm_decode_sampling_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "vz_llm_decode_set_row_sampling": (_I, [_P, _I, _I, _F, _I, _F, C.c_ulonglong, _I, _P]),
-    "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_op_sample": (_I, [_P, _I, _I, _P, _P, _P]),
+    "vz_llm_decode_sampling_rows": (_I, [_P, _I, _I, _P]),
+    "vz_llm_decode_set_row_sampling": (_I, [_P, _I, _P, _P]),
+    "vz_op_sample_rows": (_I, [_P, _I, _I, _P, _P, _P]),
     "vz_llm_decode_scores": (_I, [_P, C.c_uint, _P, _P, _P, _I, _P]),
-    "vz_op_token_scores": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "vz_llm_decode_sampling_warp": (_I, [_P, _I, _F, _I, _F, _P, C.c_ulonglong, _I]),
-    "vz_op_sample_warp": (_I, [_P, _I, _I, _F, _I, _F, _P, C.c_ulonglong, _I, _P, _P]),
-    "vz_llm_decode_sampling_rows_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "vz_llm_decode_set_row_sampling_warp": (_I, [_P, _I, _I, _F, _I, _F, _P, C.c_ulonglong, _I, _P]),
-    "vz_op_sample_rows_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "vz_op_token_scores_warp": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vz_op_token_scores": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "vz_llm_decode_stop": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_stop_rows": (_I, [_P, _I, _I, _P, _P]),
     "vz_llm_decode_stop_seed": (_I, [_P, _I, C.POINTER(C.c_int), _I, _P]),
     "vz_llm_decode_logits_proc_seed": (_I, [_P, _I, C.POINTER(C.c_int), _I, _P]),
     "vz_llm_decode_stop_read": (_I, [_P, _I, _I, _P, _P]),
     "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
-    "vz_llm_decode_logits_proc": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P]),
-    "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P]),
+    "vz_llm_decode_logits_proc": (_I, [_P, _P, _P]),
+    "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
     "vz_llm_decode_guidance": (_I, [_P, _I, _F, _I, _P]),
     "vz_op_cfg_combine": (_I, [_P, _P, _I, _I, _F, _P]),
-    "vz_llm_decode_logits_proc_seq": (_I, [_P, _I, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
-    "vz_op_logits_process_seq": (_I, [_P, _I, _I, _P, _I, _P, _F, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vz_llm_kv_beam_reorder": (_I, [_P, _I, _I, _P, _P, _P, _P]),
@@ -669,19 +682,12 @@ def cfg_combine(cond, uncond, scale: float):
     return cond
 
 
-def proc_lists(cfg):
-    """(eos array, n_eos, suppress array, n_suppress) of a vz_hip.logits_proc config for the C entry points."""
-    eos, sup = list(cfg.eos), list(cfg.suppress)
-    return (C.c_int * max(1, len(eos)))(*eos), len(eos), (C.c_int * max(1, len(sup)))(*sup), len(sup)
-
-
-def proc_seq(cfg):
-    """(table, n_seq) of a config's sequence_bias / bad_words_ids sequences for the *_seq entry points; (NULL, 0) without any"""
+def proc_params(cfg):
+    """the vz_logits_proc_params record of a vz_hip.logits_proc config (it owns its id lists); pass it with C.byref"""
+    ints = lambda v: (C.c_int * len(v))(*v) if v else None      # noqa: E731  (an empty list: NULL)
     seq = getattr(cfg, "seq", ())
-    if not seq:
-        return None, 0
-    tab = cfg.seq_table()
-    return (C.c_int * len(tab))(*tab), len(seq)
+    return VzLogitsProcParams(float(cfg.penalty), int(cfg.ngram), int(cfg.min_new), len(cfg.eos), len(cfg.suppress), len(seq),
+                              ints(cfg.eos), ints(cfg.suppress), ints(cfg.seq_table()) if seq else None)
 
 
 def logits_process(logits, cfg, hist=None, hist_len=None):
@@ -697,19 +703,21 @@ def logits_process(logits, cfg, hist=None, hist_len=None):
     assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.is_contiguous() and hist.shape[0] == rows and hist.shape[1] >= 1
     assert hist_len.dtype == torch.int32 and hist_len.is_contiguous() and hist_len.numel() == rows
     assert hist.device == logits.device and hist_len.device == logits.device
-    ea, ne, sa, ns = proc_lists(cfg)
-    check(lib().vz_op_logits_process_seq(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), float(cfg.penalty),
-                                         int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns, *proc_seq(cfg), stream_ptr(logits.device)))
+    check(lib().vz_op_logits_process(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), C.byref(proc_params(cfg)),
+                                     stream_ptr(logits.device)))
     return logits
 
 
-def warp_array(warps):
-    """the `h_warp` column of the *_warp entry points: warps = one (min_p, typical_p, epsilon_cutoff, eta_cutoff) per row, 0 = off
-    (vz_hip.sample_rows.RowParams.warp), or None for a row without any; NULL when no row has one"""
-    if all(w is None for w in warps):
-        return None
-    flat = [float(v) for w in warps for v in (w or (0.0, 0.0, 0.0, 0.0))]
-    return (C.c_float * len(flat))(*flat)
+def sample_params(params):
+    """the vz_sample_params records of a list of vz_hip.sample_rows.RowParams, one per row: (min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    = the row's `warp`, 0 = off"""
+    recs = (VzSampleParams * max(1, len(params)))()
+    for rec, p in zip(recs, params):
+        w = getattr(p, "warp", None) or (0.0, 0.0, 0.0, 0.0)
+        rec.mode, rec.temperature, rec.top_k, rec.top_p = int(p.sample), float(p.temperature), int(p.top_k), float(p.top_p)
+        rec.seed, rec.counter = int(p.seed) & 0xFFFFFFFFFFFFFFFF, int(p.counter)
+        rec.min_p, rec.typical_p, rec.epsilon_cutoff, rec.eta_cutoff = (float(v) for v in w)
+    return recs
 
 
 def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, counter: int = 0, warp=None):
@@ -718,24 +726,11 @@ def sample(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, seed:
     _need_cuda(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    check(lib().vz_op_sample_warp(ptr(logits), logits.shape[0], logits.shape[1], float(temperature), int(top_k or 0),
-                                  float(1.0 if top_p is None else top_p), warp_array([warp]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter),
-                                  ptr(ids), stream_ptr(logits.device)))
+    w = warp or (0.0, 0.0, 0.0, 0.0)
+    rec = VzSampleParams(ROW_SAMPLE, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                         int(counter), 0, *(float(v) for v in w))
+    check(lib().vz_op_sample(ptr(logits), logits.shape[0], logits.shape[1], C.byref(rec), ptr(ids), stream_ptr(logits.device)))
     return ids
-
-
-def row_sample_arrays(params):
-    """the six parameter arrays of the per-row entry points from a list of vz_hip.sample_rows.RowParams"""
-    n = max(1, len(params))
-    return ((C.c_int * n)(*[int(p.sample) for p in params]), (C.c_float * n)(*[float(p.temperature) for p in params]),
-            (C.c_int * n)(*[int(p.top_k) for p in params]), (C.c_float * n)(*[float(p.top_p) for p in params]),
-            (C.c_ulonglong * n)(*[int(p.seed) & 0xFFFFFFFFFFFFFFFF for p in params]), (C.c_int * n)(*[int(p.counter) for p in params]))
-
-
-def row_sample_columns(params):
-    """the seven columns of the per-row *_warp entry points: `row_sample_arrays` with the warpers' column behind top_p"""
-    a = row_sample_arrays(params)
-    return a[:4] + (warp_array([getattr(p, "warp", None) for p in params]),) + a[4:]
 
 
 def sample_rows(logits, params):
@@ -744,8 +739,7 @@ def sample_rows(logits, params):
     _need_cuda(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(params) == logits.shape[0]
     ids = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    check(lib().vz_op_sample_rows_warp(ptr(logits), logits.shape[0], logits.shape[1], *row_sample_columns(params), ptr(ids),
-                                       stream_ptr(logits.device)))
+    check(lib().vz_op_sample_rows(ptr(logits), logits.shape[0], logits.shape[1], sample_params(params), ptr(ids), stream_ptr(logits.device)))
     return ids
 
 
@@ -762,9 +756,8 @@ def token_scores(logits, ids, params, warped=False):
     w = torch.empty(rows, V, dtype=torch.float32, device=logits.device) if warped else None
     for r0 in range(0, rows, 64):          # the op takes up to 64 rows
         r1 = min(rows, r0 + 64)
-        mode, temp, top_k, top_p, warp, _, _ = row_sample_columns(params[r0:r1])
-        check(lib().vz_op_token_scores_warp(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), mode, temp, top_k, top_p, warp, ptr(rec[r0:r1]),
-                                            ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
+        check(lib().vz_op_token_scores(ptr(logits[r0:r1]), r1 - r0, V, ptr(ids[r0:r1]), sample_params(params[r0:r1]), ptr(rec[r0:r1]),
+                                       ptr(w[r0:r1]) if warped else None, stream_ptr(logits.device)))
     return (rec, w) if warped else rec
 
 

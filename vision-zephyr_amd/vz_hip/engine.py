@@ -686,32 +686,31 @@ class Engine:
                      warp=None):
         """tail of every decode step: greedy argmax (off) or the device-side sampler (sampling.hip); applies from the next decode_begin.
         warp: None, or (min_p, typical_p, epsilon_cutoff, eta_cutoff) behind top-p, 0 = off (vz_hip.sample_rows.RowParams.warp)."""
-        B.check(self.lib.vz_llm_decode_sampling_warp(self.h, int(on), float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
-                                                     B.warp_array([warp]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_counter)))
+        w = warp or (0.0, 0.0, 0.0, 0.0)
+        rec = B.VzSampleParams(B.ROW_SAMPLE if on else B.ROW_GREEDY, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_counter), 0, *(float(v) for v in w))
+        B.check(self.lib.vz_llm_decode_sampling(self.h, C.byref(rec)))
 
     def set_sampling_rows(self, params=None):
         """the per-row tail (sampling.hip: sample_rows_kernel): params = a list of vz_hip.sample_rows.RowParams, one per row of the NEXT
         decode_begin (rows behind the list, or an empty list: greedy until `decode_set_row_sampling` arms them); None = off."""
         if params is None:
-            B.check(self.lib.vz_llm_decode_sampling_rows_warp(self.h, 0, 0, None, None, None, None, None, None, None))
+            B.check(self.lib.vz_llm_decode_sampling_rows(self.h, 0, 0, None))
             return
-        B.check(self.lib.vz_llm_decode_sampling_rows_warp(self.h, 1, len(params), *B.row_sample_columns(params)))
+        B.check(self.lib.vz_llm_decode_sampling_rows(self.h, 1, len(params), B.sample_params(params)))
 
     def decode_set_row_sampling(self, row: int, p):
         """one row's entry of the running batch's per-row table (p: vz_hip.sample_rows.RowParams), stream-ordered like `decode_set_row`."""
-        B.check(self.lib.vz_llm_decode_set_row_sampling_warp(self.h, int(row), int(p.sample), float(p.temperature), int(p.top_k), float(p.top_p),
-                                                             B.warp_array([p.warp]), int(p.seed) & 0xFFFFFFFFFFFFFFFF, int(p.counter), self._s()))
+        B.check(self.lib.vz_llm_decode_set_row_sampling(self.h, int(row), B.sample_params([p]), self._s()))
 
     def set_logits_proc(self, cfg=None):
         """HF's logits processors in front of the argmax / the sampler of every decode step (logits_proc.hip; cfg =
         vz_hip.logits_proc.parse(...), None = off).  Arming empties every row's history of generated ids: call it before
         `decode_begin`, after the first token was chosen on logits that went through `binding.logits_process`."""
         if cfg is None:
-            B.check(self.lib.vz_llm_decode_logits_proc(self.h, 0, 1.0, 0, 0, None, 0, None, 0, self._s()))
+            B.check(self.lib.vz_llm_decode_logits_proc(self.h, None, self._s()))
             return
-        ea, ne, sa, ns = B.proc_lists(cfg)
-        B.check(self.lib.vz_llm_decode_logits_proc_seq(self.h, 1, float(cfg.penalty), int(cfg.ngram), int(cfg.min_new), ea, ne, sa, ns,
-                                                       *B.proc_seq(cfg), self._s()))
+        B.check(self.lib.vz_llm_decode_logits_proc(self.h, C.byref(B.proc_params(cfg)), self._s()))
 
     def set_guidance(self, cfg=None):
         """HF's classifier-free guidance in every decode step (guidance.hip; cfg = vz_hip.guidance.GuidanceConfig, None = off): the NEXT
