@@ -658,7 +658,15 @@ int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* byte
  * A query's reduction order is a function of key positions only - and the output therefore bit-independent of the drafts - while a
  * split is exactly 128 keys, i.e. while the context bucket has no more 128-key chunks than splits (<= 32 with the default split limit:
  * max_ctx <= 4096).  Beyond that a split is a larger multiple of 128 that follows the host's worst-case bound, and results agree to
- * bf16 rounding only. */
+ * bf16 rounding only.
+ * Sampled verify steps (HF: do_sample=True with prompt_lookup_num_tokens, `_assisted_decoding` without candidate logits): behind the
+ * decode-spec call (enable = 1), vz_llm_decode_spec_sampling with a VZ_ROW_SAMPLE record replaces "argmax of row i" by "the draw of row
+ * i": the record's temperature / top-k / top-p / warpers and seed, Philox stream-row word 0 and draw counter w + 1 + i, w =
+ * d_ctl[VZ_SPEC_CTL_WRITE] - the index, in the generated sequence, of the token row i would emit (the caller drew token 0 from the
+ * prefill logits with counter 0).  The ids are therefore a function of (seed, logits) only, not of the drafts.  The record's `counter`
+ * field is IGNORED, whatever its value (it is not checked either): the control words carry the counter.  NULL or a VZ_ROW_GREEDY record: argmax verify; the decode-spec call (either
+ * value of enable) and vz_llm_decode_begin clear the record.  The record is part of what a captured step freezes.
+ * vz_op_spec_accept_sampled = vz_op_spec_accept with those draws in front instead of the argmax (they land in words 8..15). */
 #define VZ_SPEC_CTL_WRITE 0
 #define VZ_SPEC_CTL_HIST 1
 #define VZ_SPEC_CTL_DONE 2
@@ -673,6 +681,9 @@ int vz_op_spec_draft(const int* d_hist, int hist_len, int D, int max_ngram, cons
                      vz_stream stream);
 int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist, int hist_cap,
                       const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream);
+int vz_llm_decode_spec_sampling(vz_engine* e, const vz_sample_params* p);
+int vz_op_spec_accept_sampled(const float* d_logits, int R, int cols, const vz_sample_params* p, int* d_state, int* d_ctl, int* d_out, int budget,
+                              int* d_hist, int hist_cap, const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream);
 long vz_op_spec_part_floats(int R, int Hkv, int nsplit);
 int vz_op_attention_verify(const void* qkv, void* kc, void* vc, void* o, void* q_rot, float* ws, unsigned* ticket, const float* cosT,
                            const float* sinT, const int* pos, const int* slot, int R, int Hq, int Hkv, int D, int max_ctx, int nsplit,

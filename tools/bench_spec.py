@@ -9,7 +9,11 @@ acceptance 0: T steps, acceptance 1: N steps).  Drafts come from an id stream (d
 is the true continuation that acceptance 1 is then fed with.  The variants alternate and the whole series runs `--series` times.  The
 decode attention's split count is pinned (knob 10 = 32, the partition every context above 2048 keys gets anyway) so that no call has to
 capture a second graph inside its timed part.
-    python tools/bench_spec.py [--D 1,3,7] [--steps 100] [--series 2] [--layers 32] [--out profiles/spec_bench.json]"""
+    python tools/bench_spec.py [--D 1,3,7] [--steps 100] [--series 2] [--layers 32] [--out profiles/spec_bench.json]
+
+--sample: the sampled mode instead (temperature 0.7, top-k 50, top-p 0.9, one seed), same model and protocol.  Per (weights, D): the
+plain SAMPLED 1-row step (`set_sampling`), the greedy verify step, and the sampled verify step at acceptance 0 (an id stream that is
+always wrong: the ids of a first run + 1) and at acceptance 1 (the ids of that run fed back as the stream, same seed)."""
 import argparse
 import json
 import os
@@ -31,6 +35,7 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--S", type=int, default=2048)
 ap.add_argument("--weights", default="bf16,e4m3")
 ap.add_argument("--out", default="")
+ap.add_argument("--sample", action="store_true", help="the sampled legs: plain sampled step, greedy verify, sampled verify at acceptance 0 / 1")
 a = ap.parse_args()
 
 from vis_zephyr.model import VisZephyrConfig, VisZephyrForCausalLM  # noqa: E402
@@ -63,9 +68,11 @@ def timed(fn):
     return e0.elapsed_time(e1), out
 
 
-def prefill(eng, rows):
+def prefill(eng, rows, sample=None):
     emb = eng.embed_tokens(ids.expand(rows, -1).contiguous())
     _, last = eng.prefill(emb, [a.S] * rows, all_logits=False, last_logits=True)
+    if sample is not None:          # token 0 of a sampled sequence: one draw with counter 0
+        return int(B.sample(last[0:1].contiguous(), sample.temperature, sample.top_k, sample.top_p, sample.seed, 0, sample.warp)[0])
     return int(last[0].argmax())
 
 
@@ -79,12 +86,27 @@ def greedy_rows(eng, rows, T):
     return ms / T
 
 
-def verify(eng, D, n, stream, budget):
-    """verify steps fed from `stream`: n steps to warm up, n steps timed -> (ms per step, ids of both calls, ids per timed step)"""
-    first = prefill(eng, 1)
+def sampled_row(eng, T, par):
+    """the plain SAMPLED tail on one row: T steps to warm up, T steps timed"""
+    first = prefill(eng, 1, par)
+    eng.set_sampling(True, par.temperature, par.top_k, par.top_p, par.seed, 1, par.warp)
+    try:
+        eng.decode_begin(torch.tensor([first], dtype=torch.int32), [a.S], [a.S])
+        eng.decode_steps(T)
+        ms, _ = timed(lambda: eng.decode_steps(T))
+        eng.check_async()
+        return ms / T
+    finally:
+        eng.set_sampling(False)
+
+
+def verify(eng, D, n, stream, budget, sample=None):
+    """verify steps fed from `stream`: n steps to warm up, n steps timed -> (ms per step, ids of both calls, ids per timed step);
+    sample (vz_hip.sample_rows.RowParams): sampled verify steps"""
+    first = prefill(eng, 1, sample)
     R = D + 1
     eng.decode_begin(torch.tensor([first] + [0] * D, dtype=torch.int32), [a.S + i for i in range(R)], [a.S + i for i in range(R)])
-    eng.set_spec(True, D=D, history=[first], budget=budget, source=1, stream=stream)
+    eng.set_spec(True, D=D, history=[first], budget=budget, source=1, stream=stream, sample=sample)
     try:
         warm = eng.decode_steps(n).tolist()
         ms, got = timed(lambda: eng.decode_steps(n))
@@ -100,6 +122,23 @@ for series in range(a.series):
     for w, eng in engines.items():
         for D in DS:
             R, T = D + 1, N * (D + 1)
+            if a.sample:
+                from vz_hip.sample_rows import RowParams
+                par = RowParams(True, 0.7, 50, 0.9, 1234, 0)
+                plain = sampled_row(eng, T, par)
+                greedy0, _, _ = verify(eng, D, T, [0] * (2 * T), 2 * T)
+                _, truth, _ = verify(eng, D, T, [0] * (2 * T), 2 * T, par)         # a first run: the ids of this seed
+                acc0, ids0, per0 = verify(eng, D, T, [(t + 1) % eng.cfg.vocab for t in truth], 2 * T, par)
+                acc1, ids1, per1 = verify(eng, D, N, truth, 2 * T, par)
+                r = dict(series=series, weights=w, D=D, rows=R, sampled=True, steps_timed=dict(plain=T, greedy_verify=T, accept0=T, accept1=N),
+                         plain_sampled_ms=round(plain, 4), greedy_verify_ms=round(greedy0, 4), verify_accept0_ms=round(acc0, 4),
+                         verify_accept1_ms=round(acc1, 4), ids_per_step_accept0=round(per0, 3), ids_per_step_accept1=round(per1, 3),
+                         same_ids=ids0 == truth and ids1 == truth[:len(ids1)], sampled_over_greedy_verify=round(acc0 / greedy0, 4),
+                         accept1_over_accept0=round(acc1 / acc0, 4), plain_tok_s=round(1e3 / plain, 1), accept0_tok_s=round(1e3 * per0 / acc0, 1),
+                         accept1_tok_s=round(1e3 * per1 / acc1, 1), break_even_ids_per_step=round(max(acc0, acc1) / plain, 4))
+                rows.append(r)
+                print(json.dumps(r), flush=True)
+                continue
             plain = greedy_rows(eng, 1, T)
             batched = greedy_rows(eng, R, T)
             acc0, truth, per0 = verify(eng, D, T, [0] * (2 * T), 2 * T)            # id 0 is never the argmax here: every guess is wrong

@@ -1198,6 +1198,7 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     if (e->score.d_slot) VZ_CHECK_HIP(hipMemsetAsync(e->score.d_slot, 0, sizeof(int), s));      // the step recorder's ring restarts with the batch
     e->dec_B = B;
     e->spec.on = 0;          // a new batch starts with the plain tail: vz_llm_decode_spec is armed AFTER this call
+    e->spec.a.samp = ROW_GREEDY;      // ... and its sampling record (vz_llm_decode_spec_sampling) behind that
     e->h_len.assign(B, 0); e->h_pos.assign(B, 0); e->h_parked.assign(B, 0);
     for (int b = 0; b < B; ++b) { e->h_len[b] = h_ctx_len[b] + 1; e->h_pos[b] = h_next_pos[b]; e->h_parked[b] = h_ctx_len[b] == 0 && h_next_pos[b] == 0; }
     return VZ_OK;
@@ -1386,9 +1387,12 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         if (beam_lp && br.scores) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, br.scores, beam_view(e->beam.d).hidx, br.cap, s));
         switch (tail) {
         case TAIL_SPEC: {
-            // spec.hip: per-row argmax, then acceptance + state advance (its own, multi-row rule) + the next step's draft in one small launch
+            // spec.hip: per-row argmax - or, with a sampling record armed, per-row draw at the counter of the row's position in the generated
+            // sequence (sampling.hip: spec_sample_kernel) - then acceptance + state advance (its own, multi-row rule) + the next step's draft
+            // in one small launch
             int* g = e->spec.a.ctl + VZ_SPEC_CTL_IDS;
-            RC(vz_launch_argmax(e->d_logits, B, c.vocab, g, {}, s));
+            if (e->spec.a.samp.mode == VZ_ROW_SAMPLE) RC(vz_launch_spec_sample(e->d_logits, B, c.vocab, e->spec.a.samp, e->spec.a.ctl, g, s));
+            else RC(vz_launch_argmax(e->d_logits, B, c.vocab, g, {}, s));
             RC(launch_spec_tail(e, g, s));
             break;
         }
@@ -1897,7 +1901,7 @@ extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram
                                   int* d_out, int budget, int* d_ctl, int* d_stats, int stats_cap, int source, const int* d_stream, int stream_len,
                                   vz_stream stream) {
     NEED_READY();
-    if (!enable) { e->spec.on = 0; return VZ_OK; }
+    if (!enable) { e->spec.on = 0; e->spec.a.samp = ROW_GREEDY; return VZ_OK; }
     const vz_config& c = e->c;
     if (e->tp > 1) { vz_set_error("decode_spec: speculative decoding on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     const int R = D + 1;
@@ -1919,8 +1923,22 @@ extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram
     h[VZ_SPEC_CTL_HIST] = d_hist ? hist_len : 0; h[VZ_SPEC_CTL_DONE] = budget == 0;
     RC(upload_ints(e, h, VZ_SPEC_CTL_WORDS, d_ctl, s));
     e->spec.on = 1; e->spec.R = R; e->spec.base_len = e->h_len[0]; e->spec.base_pos = e->h_pos[0];
-    e->spec.a = SpecArgs{d_hist, d_out, d_ctl, d_stats, d_stream, max_ngram, source, budget, d_hist ? hist_cap : 0, stats_cap, stream_len, 0, eos};
+    e->spec.a = SpecArgs{d_hist, d_out, d_ctl, d_stats, d_stream, max_ngram, source, budget, d_hist ? hist_cap : 0, stats_cap, stream_len, 0, eos, ROW_GREEDY};
     return launch_spec_tail(e, nullptr, s);      // the first draft into rows 1..D
+}
+
+// Sampled verify steps: behind vz_llm_decode_spec(enable = 1), a VZ_ROW_SAMPLE record makes every verify step draw its R rows instead of
+// taking their argmax - row i with the record's temperature / top-k / top-p / warpers and seed, stream-row word 0 and draw counter
+// ctl[VZ_SPEC_CTL_WRITE] + 1 + i, the index of the token that row would emit (sampling.hip: spec_sample_kernel).  The record's own counter
+// field is ignored: the control words carry the counter, nothing else does.  The record is a kernel argument, so it is part of what a
+// captured step freezes (SpecArgs).  NULL or a VZ_ROW_GREEDY record: argmax verify again.
+extern "C" int vz_llm_decode_spec_sampling(vz_engine* e, const vz_sample_params* p) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->spec.on, "decode_spec_sampling: arm the speculative tail first (vz_llm_decode_spec with enable = 1)");
+    RowSample r = ROW_GREEDY;
+    if (p) { vz_sample_params q = *p; q.counter = 0; RC(row_sample_of(q, &r)); }      // (the counter is ignored: zeroed in front of the check)
+    e->spec.a.samp = r.mode == VZ_ROW_SAMPLE ? r : ROW_GREEDY;
+    return VZ_OK;
 }
 
 // the draft rule alone on a device history of hist_len ids: d_draft [D] (padded with 0), the count in d_ctl[VZ_SPEC_CTL_DRAFTED]
@@ -1941,20 +1959,39 @@ extern "C" int vz_op_spec_draft(const int* d_hist, int hist_len, int D, int max_
 
 // argmax of R logit rows + the acceptance step on caller-provided state: d_state = [cur | pos | slot | len] x R, d_ctl the control words
 // (the argmax ids land in words 8..), d_stats [3] = this step's record (NULL = none; the record index is the ctl step count)
-extern "C" int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist, int hist_cap,
-                                 const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream) {
-    hipStream_t s = (hipStream_t)stream;
+// (samp = null: the argmax; else the checked VZ_ROW_SAMPLE record the rows are drawn by, counters from d_ctl[VZ_SPEC_CTL_WRITE])
+static int op_spec_accept(const float* d_logits, int R, int cols, const RowSample* samp, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist,
+                          int hist_cap, const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, hipStream_t s) {
     VZ_CHECK_ARG(d_logits && d_state && d_ctl && d_out && R >= 2 && R <= 8 && cols >= 1 && budget >= 0 && max_ctx >= 1 && rope_max >= 1, "spec_accept: bad argument");
     BeamEos eos;
     RC(beam_eos_of(h_eos, n_eos, &eos));
     int* g = d_ctl + VZ_SPEC_CTL_IDS;
-    RC(vz_launch_argmax(d_logits, R, cols, g, {}, s));
+    if (samp) RC(vz_launch_spec_sample(d_logits, R, cols, *samp, d_ctl, g, s));
+    else RC(vz_launch_argmax(d_logits, R, cols, g, {}, s));
     const DecodeState st = decode_state(d_state, R);
     SpecTailArgs t;
     t.g = g; t.cur = st.cur; t.draft = st.cur + 1; t.pos = st.pos; t.slot = st.slot; t.len = st.len; t.ctl = d_ctl; t.out = d_out; t.budget = budget;
     t.hist = d_hist; t.hist_cap = d_hist ? hist_cap : 0; t.stats = d_stats; t.stats_cap = d_stats ? 0x7fffffff / 4 : 0; t.stream = nullptr; t.stream_len = 0; t.eos = eos;
     t.R = R; t.max_ngram = 1; t.source = 0; t.max_ctx = max_ctx; t.rope_max = rope_max; t.do_accept = 1; t.do_draft = 0;
     return vz_launch_spec_tail(t, s);
+}
+
+extern "C" int vz_op_spec_accept(const float* d_logits, int R, int cols, int* d_state, int* d_ctl, int* d_out, int budget, int* d_hist, int hist_cap,
+                                 const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream) {
+    return op_spec_accept(d_logits, R, cols, nullptr, d_state, d_ctl, d_out, budget, d_hist, hist_cap, h_eos, n_eos, d_stats, max_ctx, rope_max, (hipStream_t)stream);
+}
+
+// vz_op_spec_accept with the draws of a sampled verify step in front instead of the argmax: row i by the VZ_ROW_SAMPLE record `p` (its
+// counter ignored) at draw counter d_ctl[VZ_SPEC_CTL_WRITE] + 1 + i; the draws land in d_ctl[VZ_SPEC_CTL_IDS ..]
+extern "C" int vz_op_spec_accept_sampled(const float* d_logits, int R, int cols, const vz_sample_params* p, int* d_state, int* d_ctl, int* d_out, int budget,
+                                         int* d_hist, int hist_cap, const int* h_eos, int n_eos, int* d_stats, int max_ctx, int rope_max, vz_stream stream) {
+    VZ_CHECK_ARG(p, "spec_accept_sampled: null record");
+    RowSample r;
+    vz_sample_params q = *p;
+    q.counter = 0;          // ignored: zeroed in front of the check
+    RC(row_sample_of(q, &r));
+    VZ_CHECK_ARG(r.mode == VZ_ROW_SAMPLE, "spec_accept_sampled: a VZ_ROW_SAMPLE record expected (greedy: vz_op_spec_accept)");
+    return op_spec_accept(d_logits, R, cols, &r, d_state, d_ctl, d_out, budget, d_hist, hist_cap, h_eos, n_eos, d_stats, max_ctx, rope_max, (hipStream_t)stream);
 }
 
 extern "C" long vz_op_spec_part_floats(int R, int Hkv, int nsplit) { return (long)vz_spec_part_floats(R, Hkv, nsplit); }
@@ -2046,7 +2083,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     VZ_CHECK_ARG(tail != TAIL_BEAM || (B == e->beam.a.nb * e->beam.a.groups && !e->ring.p), "decode_steps: the beam tail needs a decode batch of exactly "
                  "%d x %d rows (it has %d) and no token ring", e->beam.a.groups, e->beam.a.nb, B);
     VZ_CHECK_ARG(tail != TAIL_SPEC || (B == e->spec.R && !e->ring.p && !e->beam.on && !e->samp.on), "decode_steps: the speculative tail needs a decode batch of "
-                 "exactly %d rows (it has %d), greedy, without beams or a token ring", e->spec.R, B);
+                 "exactly %d rows (it has %d), without the sampler tail (sampled verify steps: vz_llm_decode_spec_sampling), beams or a token ring", e->spec.R, B);
     VZ_CHECK_ARG(!e->proc.on || tail_takes_proc(tail), "decode_steps: the logits processors (vz_llm_decode_logits_proc) run in "
                  "front of the argmax, the sampler or the beam tail, not with the speculative tail");
     VZ_CHECK_ARG(tail != TAIL_BEAM || !(e->beam.rows.scores || e->beam.rows.raw) || n <= e->beam.rows.cap, "decode_steps: %d steps, the beam row "

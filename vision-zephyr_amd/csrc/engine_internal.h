@@ -63,6 +63,7 @@ struct SpecArgs {
     int ngram, source, budget, hist_cap, stats_cap, stream_len;
     int key_bound;      // keys the steps being launched can reach (fixes the verify attention's absolute splits)
     BeamEos eos;
+    RowSample samp;     // ROW_GREEDY: argmax verify; a VZ_ROW_SAMPLE record (vz_llm_decode_spec_sampling; its ctr 0): spec_sample_kernel draws the rows
 };
 // Everything decode_step_launch hands to a kernel that can differ between two vz_llm_decode_steps calls: a replayed graph is only
 // valid while all of it is unchanged.  The *Args of the modes that are off stay zero.
@@ -78,7 +79,7 @@ struct DecodeGraphKey {
 };
 static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 &&
               sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
-              sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos), "padding in the graph key");
+              sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos) + sizeof(RowSample), "padding in the graph key");
 
 // The beam tail's device state, BEAM_ROWS rows: [score (fp32) | parent | base | hidx, pad | base, end of a standalone reorder | candidate
 // scores | candidate tokens (BEAM_K per row)]

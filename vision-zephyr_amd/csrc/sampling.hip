@@ -400,6 +400,32 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     }
 }
 
+// The sampled verify step of prompt-lookup speculation (spec.hip): the R rows are R consecutive positions of ONE
+// sequence, and row i draws the token that position would have drawn in a one-row step - Philox counter (vocab index, 0, w + 1 + i,
+// 0x565a) under the call's seed, w = ctl[VZ_SPEC_CTL_WRITE] = the ids generated behind the first.  The stream-row word is 0 for every row:
+// the row sits in the draw counter, which is the index of the token in the generated sequence, so the draws do not depend on what was
+// guessed.  The record comes by value (scalar registers); the kernel leaves the R ids in g and publishes nothing else - acceptance and
+// every state advance are spec_tail_kernel's.  The load of w is requested here, in front of the row's staging loads, as a vector
+// load in their queue, and w is first used by the race.  Two things keep it there: the load is an atomic one, which the compiler
+// leaves where it stands (the plain scalar load was sunk behind the staging's wait: a round trip of its own), and its address goes
+// through a zero the compiler cannot see through, so w counts as a per-lane value and stays in a vector register (a load it knows to
+// be uniform is waited for and moved to a scalar register at once: the same round trip, at the head).
+template <bool REG>
+__global__ __launch_bounds__(1024) void spec_sample_kernel(const float* __restrict__ logits, int cols, RowSample rec, const int* __restrict__ ctl,
+                                                           int* __restrict__ g) {
+    __shared__ SampleShared sh;
+    const int row = blockIdx.x;
+    int zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));          // (no memory access: nothing to count or wait for)
+    const int w = __hip_atomic_load(ctl + VZ_SPEC_CTL_WRITE + zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    float bv;
+    int bi;
+    sample_row_race<REG>(logits + (size_t)row * cols, cols, rec.temp, rec.top_k, rec.top_p, rec.warp, rec.seed[0], rec.seed[1], 0u,
+                         (unsigned)(w + 1 + row), sh, bv, bi);
+    bi = block_first_best(bv, bi, sh);
+    if (threadIdx.x == 0) g[row] = bi;
+}
+
 // ---- the step recorder -------------------------------------------------------------------------------------------
 // Behind the tail: one 16-byte record per row about the token the tail chose, ids[row]:
 //   x_tok    = logits[row, tok] as it stands (in a step: after the logits processors, before temperature); NaN if tok is outside [0, cols)
@@ -536,6 +562,7 @@ int vz_init_sampling_kernels() {
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)sample_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     VZ_CHECK_HIP(hipFuncSetAttribute((const void*)token_scores_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
+    VZ_CHECK_HIP(hipFuncSetAttribute((const void*)spec_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * (int)sizeof(float)));
     g_sample_lds_ok = true;
     return VZ_OK;
 }
@@ -561,6 +588,20 @@ int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* ta
         hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, tab, ids, emit);
     else
         hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, cols, tab, ids, emit);
+    VZ_LAUNCH_CHECK();
+    return VZ_OK;
+}
+
+// the draws of a sampled verify step: R = 2..8 rows of one sequence by the one checked VZ_ROW_SAMPLE record (its counter is not read: the
+// counters come from ctl[VZ_SPEC_CTL_WRITE]), the ids into g [R]
+int vz_launch_spec_sample(const float* logits, int R, int cols, const RowSample& rec, const int* ctl, int* g, hipStream_t s) {
+    VZ_CHECK_ARG(logits && ctl && g && R >= 2 && R <= 8 && cols > 0, "spec_sample: bad argument (2..8 rows)");
+    VZ_CHECK_ARG(rec.mode == VZ_ROW_SAMPLE && rec.temp > 0.f && rec.top_p > 0.f, "spec_sample: a VZ_ROW_SAMPLE record with temperature %g > 0 and top_p %g > 0 expected", (double)rec.temp, (double)rec.top_p);
+    { int r = vz_init_sampling_kernels(); if (r) return r; }
+    if (cols <= 32768 && g_sample_lds_ok)
+        hipLaunchKernelGGL(spec_sample_kernel<true>, dim3(R), dim3(1024), (size_t)cols * sizeof(float), s, logits, cols, rec, ctl, g);
+    else
+        hipLaunchKernelGGL(spec_sample_kernel<false>, dim3(R), dim3(1024), 0, s, logits, cols, rec, ctl, g);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

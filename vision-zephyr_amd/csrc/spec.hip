@@ -9,7 +9,8 @@
 //        chunk.  Splits and 64-key chunks sit at ABSOLUTE key positions (split s = keys [s * per, (s + 1) * per)), masked keys contribute
 //        exact zeros, and the partials of a query are merged in split order by the last arriver of the KV head: a query's reduction order
 //        is a function of key positions only - not of the row it ran in, nor of what the other rows guessed.
-//   spec_tail_kernel         after argmax_kernel has reduced the R logit rows: acceptance scan, eos / budget clamp, append of the emitted
+//   spec_tail_kernel         after argmax_kernel has reduced the R logit rows (a sampled sequence: after spec_sample_kernel, sampling.hip,
+//        has drawn them - row i the draw its position has anyway; the tail does not care how the ids g were chosen): acceptance scan, eos / budget clamp, append of the emitted
 //        ids to the output buffer and the history at device-side indices, advance of cur / pos / slot / len of all R rows, one stats
 //        record per step; then the draft of the NEXT step - leftmost earlier occurrence of the last n ids (n = max_ngram .. 1, an
 //        atomicMin over match positions), or the ids that follow the step's own position in a caller-provided stream (tests, benchmark).

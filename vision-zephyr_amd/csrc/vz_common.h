@@ -385,6 +385,8 @@ int vz_launch_argmax(const float* logits, int rows, int cols, int* ids, const Ro
 int vz_launch_sample_rows(const float* logits, int rows, int cols, RowSample* tab, int* ids, const RowEmit& emit, hipStream_t s);
 int vz_launch_sample(const float* logits, int rows, int cols, float temperature, int top_k, float top_p, const SampleWarp& warp, const unsigned* seed,
                      const int* ctr, int ctr_add, int* ids, const RowEmit& emit, hipStream_t s);
+// the draws of a sampled verify step (sampling.hip: spec_sample_kernel): row i of R by `rec` with draw counter ctl[VZ_SPEC_CTL_WRITE] + 1 + i
+int vz_launch_spec_sample(const float* logits, int R, int cols, const RowSample& rec, const int* ctl, int* g, hipStream_t s);
 // set dynamic-LDS limits of every kernel up front (never inside a stream capture)
 int vz_init_gemm_kernels();
 int vz_init_attention_kernels();

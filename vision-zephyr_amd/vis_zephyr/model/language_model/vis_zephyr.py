@@ -464,7 +464,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         every step also runs the step recorder behind its tail, inside the per-token graph (csrc/sampling.hip: token_scores_kernel;
         vz_hip/scores.py); without `return_dict_in_generate` they are ignored, as in HF.  Positions behind a row's eos are 0.0 in both
         log-prob tensors; their `scores` / `logits` rows are whatever the parked row produced.  With any of the three,
-        `prompt_lookup_num_tokens` takes the plain greedy path (the ids are the same by construction).  With a streamer or stopping
+        `prompt_lookup_num_tokens` takes the plain path (greedy: the ids are the same by construction; sampled: the same draws on
+        the 1-row routes' logits).  With a streamer or stopping
         criteria the records wait in a device ring of `max_new_tokens` slots that is allocated up front: 16 bytes per slot, and with
         `output_scores` / `output_logits` another V fp32 per slot and output (260 MB each at V = 32000, max_new_tokens = 2048), even if
         a criterion stops the call after a few tokens - HF's [T, rows, V] outputs cost that; `output_logprobs` does not.
@@ -505,7 +506,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         log-softmax rows, in front of the processors, and the token chosen on it is fed to both rows.  Greedy and sampled, batched,
         `num_return_sequences`, streamer, processors, scores and device stops all take it; `output_logits` rows are the conditional raw
         logits, `output_scores` rows and the log-probs are taken behind the combine.  `num_beams > 1` and tensor-parallel engines raise
-        NotImplementedError, `max_batch < 2` ValueError; `prompt_lookup_num_tokens` takes the guided greedy path.
+        NotImplementedError, `max_batch < 2` ValueError; `prompt_lookup_num_tokens` takes the guided path.
+
+        Prompt lookup (vz_hip/spec.py): `prompt_lookup_num_tokens=k` (+ `max_matching_ngram_size`) runs one
+        sequence - greedy or sampled - in verify steps of up to 8 rows.  A sampled call draws row i of a step at the draw counter of the
+        token that row would emit, so its ids are a function of (seed, logits) and not of the guesses; against the same call without
+        the keyword the logits differ to bf16 rounding (R-row routes instead of 1-row routes), so ids under one seed can differ at a
+        near-tie of the race, while the distribution is the same.  With processors, a streamer, stopping criteria or device stops,
+        scores, guidance, `past_key_values`, beams, several sequences or `num_return_sequences > 1` the keyword is without effect.
 
         The cache handle (vz_hip/append.py): with `return_dict_in_generate=True` the output's `past_key_values` is a
         live handle whenever the rows of the call are the engine's cache rows - one sequence, or a greedy batch that decodes together;
@@ -592,18 +600,21 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
                                                pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp, neg=neg))
         if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None and neg is None and app is None:      # (with processors, scores, device stops or guidance: the plain / guided greedy path)
-            # HF's prompt lookup decoding: same greedy ids, several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
+            # HF's prompt lookup decoding: the ids the call yields anyway - the argmax, or in a sampled call the draw of each position under
+            # the call's seed - several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
             from vz_hip import spec
             ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
             D = spec.draft_slots(prompt_lookup_num_tokens, ngram, n_seq=Bsz, greedy=greedy, num_beams=num_beams, streamer=streamer,
                                  stopping_criteria=stopping_criteria, tp_size=self.engine.tp_size, max_batch=self.engine.max_batch,
                                  prompt_len=seqlens[0], max_new=max_new_tokens, max_ctx=self.engine.max_ctx, n_eos=len(eos),
-                                 heads_per_kv=self.arch.n_heads // max(1, self.arch.n_kv_heads))
+                                 heads_per_kv=self.arch.n_heads // max(1, self.arch.n_kv_heads), sampled=not greedy)
             if D:
                 _spec_history = _spec_history()
                 assert len(_spec_history) == seqlens[0], f"history of {len(_spec_history)} ids for a prompt of {seqlens[0]} positions"
+                par = None if greedy else sample_rows.RowParams(True, float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p),
+                                                                int(seed), 0, **warp)
                 out = self._generate_spec(inputs_embeds[0:1, :seqlens[0]], None if position_ids is None else position_ids[0:1, :seqlens[0]],
-                                          _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing)
+                                          _spec_history, D, ngram, max_new_tokens, eos, sync_every, timing, par)
                 return done(torch.tensor([out], dtype=torch.long, device=self.device))
         if Bsz > 1 and greedy and streamer is None and stopping_criteria is None:
             return done(self._generate_batched(inputs_embeds, seqlens, position_ids, max_new_tokens, eos, pad_token_id, sync_every, timing, proc, sink, stop, neg, app),
@@ -647,20 +658,24 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             return SC.transition_scores(sequences, scores, None, normalize_logits)
         return SC.beam_transition_scores(sequences, scores, beam_indices, normalize_logits, self.config.vocab_size)
 
-    def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None) -> List[int]:
-        """One greedy sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
-        (csrc/spec.hip), `sync_every` per host sync."""
+    def _generate_spec(self, embeds, position_ids, history, D, max_ngram, max_new, eos, sync_every, timing=None, par=None) -> List[int]:
+        """One sequence with prompt-lookup drafts: the first token from the prefill as always, then verify steps of D + 1 rows
+        (csrc/spec.hip), `sync_every` per host sync.  par = None: greedy; a sampled vz_hip.sample_rows.RowParams: the first token is one
+        draw of the device sampler with counter 0, as `_generate_one` draws it, and the verify steps draw their rows by the same record."""
         from vz_hip import binding as B
         from vz_hip import spec
         eng = self.engine
         S = embeds.shape[1]
         _, last = eng.prefill(embeds, [S], position_ids, all_logits=False, last_logits=True)
         next_pos = S if position_ids is None else int(position_ids[0, -1]) + 1
-        tok = int(B.argmax(last)[0])          # int(): the host holds the first token here
+        if par is None:
+            tok = int(B.argmax(last)[0])          # int(): the host holds the first token here
+        else:
+            tok = int(B.sample(last, par.temperature, par.top_k, par.top_p, par.seed, 0, par.warp)[0])
         if timing is not None:
             timing["t_first_token"] = time.perf_counter()
         report = {}
-        out = spec.decode(eng, tok, next_pos, S, history, D, max_new, eos, max_ngram, max(1, int(sync_every)), report=report)
+        out = spec.decode(eng, tok, next_pos, S, history, D, max_new, eos, max_ngram, max(1, int(sync_every)), report=report, sample=par)
         if timing is not None:
             timing["spec"] = report
         return out

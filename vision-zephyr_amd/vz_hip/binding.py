@@ -184,6 +184,8 @@ SYMBOLS = {
     "vz_llm_decode_spec": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P]),
     "vz_op_spec_draft": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
     "vz_op_spec_accept": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
+    "vz_llm_decode_spec_sampling": (_I, [_P, _P]),
+    "vz_op_spec_accept_sampled": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "vz_op_spec_part_floats": (_L, [_I, _I, _I]),
     "vz_op_attention_verify": (_I, [_P] * 11 + [_I] * 8 + [_F, _P]),
     "vz_op_transpose_batched": (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _I, _I, _P]),
@@ -936,13 +938,21 @@ def spec_draft(history, D: int, max_ngram: int = 2, eos=()):
     return draft[:int(ctl[SPEC_CTL_DRAFTED])].tolist()
 
 
-def spec_accept(logits, state, ctl, out, budget: int, hist=None, eos=(), stats=None, max_ctx: int = 1 << 20, rope_max: int = 1 << 20):
+def spec_accept(logits, state, ctl, out, budget: int, hist=None, eos=(), stats=None, max_ctx: int = 1 << 20, rope_max: int = 1 << 20,
+                sample=None):
     """argmax of the R logit rows + one acceptance step on caller-provided buffers, all updated in place: state int32 [4, R] =
-    cur | pos | slot | len, ctl int32 [SPEC_CTL_WORDS], out int32 [>= budget], hist int32 or None, stats int32 [3] or None."""
+    cur | pos | slot | len, ctl int32 [SPEC_CTL_WORDS], out int32 [>= budget], hist int32 or None, stats int32 [3] or None.
+    sample (a sampled vz_hip.sample_rows.RowParams; its counter is not read): row i is drawn at counter ctl[SPEC_CTL_WRITE] + 1 + i
+    instead (sampling.hip: spec_sample_kernel)."""
     _need_cuda(logits, state, ctl, out)
     R, V = logits.shape
     assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 4 * R and ctl.numel() >= SPEC_CTL_WORDS and out.numel() >= budget
     arr, n_eos = _eos_arr(eos)
+    if sample is not None:
+        check(lib().vz_op_spec_accept_sampled(ptr(logits), R, V, sample_params([sample]), ptr(state), ptr(ctl), ptr(out), int(budget), ptr(hist),
+                                              0 if hist is None else hist.numel(), arr, n_eos, ptr(stats), int(max_ctx), int(rope_max),
+                                              stream_ptr(logits.device)))
+        return
     check(lib().vz_op_spec_accept(ptr(logits), R, V, ptr(state), ptr(ctl), ptr(out), int(budget), ptr(hist), 0 if hist is None else hist.numel(),
                                   arr, n_eos, ptr(stats), int(max_ctx), int(rope_max), stream_ptr(logits.device)))
 

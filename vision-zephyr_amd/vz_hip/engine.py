@@ -735,12 +735,14 @@ class Engine:
         B.check(self.lib.vz_llm_decode_ring(self.h, B.ptr(ring), slots, rows))
 
     def set_spec(self, on: bool, D: int = 0, max_ngram: int = 2, history: Sequence[int] = (), eos: Sequence[int] = (), budget: int = 0,
-                 source: int = 0, stream: Optional[Sequence[int]] = None):
+                 source: int = 0, stream: Optional[Sequence[int]] = None, sample=None):
         """prompt-lookup speculative decoding (spec.hip) for the R = D + 1 rows `decode_begin` just armed (one sequence: row i at
         position p + i, context L + i): every decode step becomes a verify step that emits 1..R ids, at most `budget` in all, and
         stops at the first of `eos`.  history = one id per position of the sequence so far, the token of row 0 included (-1 = no text
         id there).  source 0 drafts by the n-gram rule; 1 drafts the ids of `stream` that follow the step's own position (stream[t]
-        = the t-th id these steps are expected to emit: tests, benchmarks).  off: the plain tail again."""
+        = the t-th id these steps are expected to emit: tests, benchmarks).  sample (a sampled vz_hip.sample_rows.RowParams; its
+        counter is not read): the verify steps draw their rows instead of taking the argmax, row i at the draw counter of the token it
+        would emit (sampling.hip: spec_sample_kernel).  off: the plain tail again."""
         if not on:
             self._spec = None
             B.check(self.lib.vz_llm_decode_spec(self.h, 0, 0, 0, None, 0, 0, None, 0, None, 0, None, None, 0, 0, None, 0, self._s()))
@@ -755,6 +757,8 @@ class Engine:
         B.check(self.lib.vz_llm_decode_spec(self.h, 1, int(D), int(max_ngram), B.ptr(hist), len(history), 0 if hist is None else hist.numel(),
                                             ea, len(eos), B.ptr(out), budget, B.ptr(buf), B.ptr(stats), budget, int(source), B.ptr(sids),
                                             0 if sids is None else sids.numel() - 1, self._s()))
+        if sample is not None and sample.sample:
+            B.check(self.lib.vz_llm_decode_spec_sampling(self.h, B.sample_params([sample])))
         self._spec = {"buf": buf, "out": out, "hist": hist, "stream": sids, "head": head, "budget": budget, "D": int(D), "w": 0, "steps": 0,
                       "done": budget == 0, "records": []}
 

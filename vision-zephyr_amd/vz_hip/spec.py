@@ -1,8 +1,9 @@
-"""Prompt-lookup speculative decoding for greedy `generate` (HF: `prompt_lookup_num_tokens`, `max_matching_ngram_size`).
+"""Prompt-lookup speculative decoding for greedy and sampled `generate` (HF: `prompt_lookup_num_tokens`, `max_matching_ngram_size`).
 
 The device side is csrc/spec.hip: a verify step runs the last emitted token plus D guessed continuations of ONE sequence as D + 1 rows,
-keeps the longest prefix of guesses that equals the argmax the model produces anyway, and drafts the next guesses from the ids already
-in the context - all inside the per-token graph.  This module holds the host side: the draft rule in plain Python (the reference the
+keeps the longest prefix of guesses that equals the argmax the model produces anyway - in a sampled call: the draw each position would
+have had anyway, the counter-based sampler's token t of the sequence (csrc/sampling.hip: spec_sample_kernel) - and drafts the next
+guesses from the ids already in the context - all inside the per-token graph.  This module holds the host side: the draft rule in plain Python (the reference the
 device kernel is tested against), the history of a spliced multimodal prompt, the eligibility rule and the chunked loop.
 """
 from __future__ import annotations
@@ -52,13 +53,22 @@ def spliced_history(input_ids: Sequence[int], tiles_per_image: Sequence[int], im
     return out if max_len is None else out[:max_len]
 
 
+def accept_count(draft: Sequence[int], chosen: Sequence[int]) -> int:
+    """hf:generation/utils.py `_assisted_decoding`, n_matches: the longest prefix of `draft` that equals the ids the model chose at those
+    positions (`chosen` holds one more: the id behind the last guess)."""
+    a = 0
+    while a < len(draft) and int(draft[a]) == int(chosen[a]):
+        a += 1
+    return a
+
+
 def draft_slots(k, max_ngram, *, n_seq: int, greedy: bool, num_beams: int, streamer, stopping_criteria, tp_size: int, max_batch: int,
-                prompt_len: int, max_new: int, max_ctx: int, n_eos: int = 0, heads_per_kv: int = 4) -> int:
+                prompt_len: int, max_new: int, max_ctx: int, n_eos: int = 0, heads_per_kv: int = 4, sampled: bool = False) -> int:
     """D, the draft slots a `generate(prompt_lookup_num_tokens=k)` call runs with, or 0 = the call takes the plain path (the kwarg is
-    without effect, as before): one greedy sequence, no beams / streamer / stopping criteria / tensor parallelism, an engine with
-    >= 2 rows, n-gram size 1..4, at most 4 eos ids and 4 query heads per KV head (what the device tail / the verify attention take) and
-    prompt + max_new_tokens + D inside the cache."""
-    if k is None or int(k) < 1 or n_seq != 1 or not greedy or num_beams != 1 or streamer is not None or stopping_criteria is not None:
+    without effect, as before): one sequence - greedy, or sampled when the caller runs sampled verify steps (`sampled`) - no beams /
+    streamer / stopping criteria / tensor parallelism, an engine with >= 2 rows, n-gram size 1..4, at most 4 eos ids and 4 query heads
+    per KV head (what the device tail / the verify attention take) and prompt + max_new_tokens + D inside the cache."""
+    if k is None or int(k) < 1 or n_seq != 1 or not (greedy or sampled) or num_beams != 1 or streamer is not None or stopping_criteria is not None:
         return 0
     if tp_size != 1 or not 1 <= int(max_ngram) <= 4 or n_eos > 4 or heads_per_kv != 4:
         return 0
@@ -70,15 +80,21 @@ def draft_slots(k, max_ngram, *, n_seq: int, greedy: bool, num_beams: int, strea
 
 def decode(eng, first_tok: int, next_pos: int, ctx_len: int, history: Sequence[int], D: int, max_new: int, eos: Sequence[int] = (),
            max_ngram: int = 2, sync_every: int = 16, source: int = 0, stream: Optional[Sequence[int]] = None,
-           report: Optional[dict] = None) -> List[int]:
+           report: Optional[dict] = None, sample=None) -> List[int]:
     """The decode loop behind `generate(prompt_lookup_num_tokens=...)`: `first_tok` came from the prefill of `ctx_len` positions
     (`history`: one id each); chunks of `sync_every` verify steps, one readback per chunk.  Returns the generated ids, `first_tok`
-    included, at most `max_new`, ending with the first eos id.  `report` receives {used, D, steps, drafted, accepted, tokens}."""
+    included, at most `max_new`, ending with the first eos id.  `report` receives {used, D, steps, drafted, accepted, tokens}.
+    `sample` (a sampled vz_hip.sample_rows.RowParams: temperature, top_k, top_p, seed, warpers): `first_tok` was drawn with counter 0
+    and every verify step draws its rows - row i of a step behind w generated ids at counter w + 1 + i - instead of taking their
+    argmax; the report then also carries "sampled": True."""
     import torch
     out = [int(first_tok)]
     eos = set(int(t) for t in eos)
+    sampled = sample is not None and bool(sample.sample)
     if report is not None:
         report.update({"used": True, "D": D, "steps": 0, "drafted": 0, "accepted": 0, "tokens": 1})
+        if sampled:
+            report["sampled"] = True
     if out[0] in eos or max_new <= 1:
         return out
     if len(history) != ctx_len:
@@ -89,7 +105,7 @@ def decode(eng, first_tok: int, next_pos: int, ctx_len: int, history: Sequence[i
     first = torch.tensor([out[0]] + [0] * D, dtype=torch.int32)
     eng.decode_begin(first, [next_pos + i for i in range(R)], [ctx_len + i for i in range(R)])
     eng.set_spec(True, D=D, max_ngram=max_ngram, history=list(history) + [out[0]], eos=sorted(eos), budget=max_new - 1, source=source,
-                 stream=stream)
+                 stream=stream, **({"sample": sample} if sampled else {}))
     try:
         stop = False
         while not stop and len(out) < max_new:
