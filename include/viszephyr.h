@@ -771,28 +771,46 @@ int vz_op_vip_point(void* d_image_u8, int h, int w, int x0, int y0, int x1, int 
 /* argmax over fp32 logits rows: ids int32 [rows] (first maximal index) */
 int vz_op_argmax(const float* d_logits, int rows, int cols, int* d_ids, vz_stream stream);
 
-/* A/B hook of the bench tools (process-wide; production values in brackets).  A knob change takes effect on the next
- * vz_llm_decode_steps, which captures its graph again.  Knobs:
- *   0  GEMV variant [0 = production choice; 1.. = alternatives compiled in: rows per wave, chunks in flight, non-temporal loads]
- *   1  tile GEMM choice [0 = by grid size; 1 = always 128^2; 2 = always 256^2]      2  prefill attention generation [3]
- *   3  split-K of M <= 512 linears [0 = auto; 1 = never]                             4  256^2 GEMM stream-K tail [1; 0 = whole tiles only; 2 = forced]
- *   5  stream-K skew in K-tiles                                                     6  record 256^2 GEMM phase stamps (vz_prof_gemm_stamps)
- *   7  route the collectives of a tp_size == 1 engine holding a one-rank communicator through RCCL (self-test; 2 = shape rehearsal)
- *   9  2..16-row linears [1 = MFMA weight stream; 0 = GEMV / tile GEMM; 5 = ignore the tiled weight copies]
- *  10  context splits of the fused decode attention [0 = engine default; 1..64]     11  256^2 GEMM workgroups wait for their stores (experiment) [0]
- *  14  rows from which a decode step's linears take the 128^2 tile GEMM [29]          15  split-K factor of the K = 4096 projections on that route [8]
- *  16  record stage stamps of the prefill attention kernel (vz_prof_attn_stamps)    19  gemm_wide.hip for 17..64-row gate|up / lm_head [1]
- *  21  fp8 tile GEMM choice [0 = by grid size; 1 = 128^2; 2 = 256^2]                22  rows from which vz_engine_prefill_fp8 engines take the fp8 MFMA [768]
- *  23  key split of few-row head_dim-512 attention [0 = every 96 keys; 1 = never; n >= 2 = n splits]
- *  24  most K slices of an M <= 512 linear [8]                                      25  Q-Former cross-attention K|V of all blocks as one GEMM [1]
- *  26  K slices for tile-GEMM grids that leave a CU one workgroup (M > 512, < 256 tiles) [1; 0 = whole-K tiles: batch-invariant]
- *  27  K splits of the e4m3 17..64-row stream [0 = by shape]                        28  batch-1 decode steps as ONE resident grid per token (decode_persist.hip) [0]
- *  29  one-shot all-reduce for the TP decode step when peer areas are attached [1]   30  batch-1 decode attention + O projection as one launch (attn_o_fused.hip) [1]
- *  31  that launch's O role: wait (x ~0.2 us) before it requests its weights [12]    32  training step: tile-resident attention backward for head_dim 128 [1]
- *  33  prefill: RoPE of the queries inside the attention's Q load [1; 0 = a rotated copy of Q from rope_kv_kernel; bit-identical]
- *  34  256^2 GEMM: persistent whole-tile workgroups when a launch has more whole tiles than CUs [1; 0 = one workgroup per tile; bit-identical]
- *  35  3..16-row persistent weight stream: the same number of row groups on every workgroup [1; 0 = one workgroup per CU; bit-identical] */
+/* A/B hook of the bench tools and the tests (process-wide).  A knob change takes effect on the next vz_llm_decode_steps, which captures
+ * its graph again (also when the value set is the one the knob had).  A value outside the knob's range is refused with VZ_ERR_ARG.
+ * Defaults and ranges are not repeated here: vz_tune_info enumerates the table (csrc/tune.h).  Knobs (number  name  meaning):
+ *   0  gemv_variant          GEMV variant: 0 = production choice; 1..10 = alternatives compiled in (rows per wave, chunks in flight, non-temporal loads, waves per workgroup; tools/bench_kernels.py)
+ *   1  gemm_choice           tile GEMM choice: 0 = by grid size; 1 = always 128^2; 2 = always 256^2
+ *   2  attn_version          prefill attention generation: 1 = v1 kernel for every head_dim (tests / A-B); 2 = v2 (head_dim 64 / 128) with the classic online-softmax step; 3 = v2 with the deferred-maximum step (production)
+ *   3  splitk_mode           split-K of M <= 512 linears: 0 = auto; 1 = never
+ *   4  gemm256_streamk       256^2 GEMM stream-K tail: 1 = a last round that fills at most half of the CUs; 0 = whole tiles only; 2 = forced for any tail (tests)
+ *   5  gemm256_skew          K-tiles by which even / odd stream-K workgroups lead / lag
+ *   6  gemm256_stamps        record 256^2 GEMM phase stamps (vz_prof_gemm_stamps)
+ *   7  force_comm            1 = route the collectives of a tp_size == 1 engine holding a one-rank communicator through RCCL (self-test); 2 = shape rehearsal of one rank of a tp_size > 1 engine, collectives skipped
+ *   9  skinny_mode           2..64-row linears, SkinnyMode of linear_route.h: 1 = MFMA weight stream; 0 = GEMV / tile GEMM; 5 = ignore the tiled weight copies
+ *  10  attn_nsplit           context splits of the fused decode attention: 0 = engine default
+ *  11  gemm256_drain         256^2 GEMM workgroups wait for their stores before ending (experiment)
+ *  14  decode_tile_rows      rows from which a decode step's linears take the 128^2 tile GEMM (65 = never)
+ *  15  decode_sk_short       split-K factor of the K = 4096 decode projections (QKV, O) on that route
+ *  16  attn_stamps           record stage stamps of the prefill attention kernel (vz_prof_attn_stamps)
+ *  19  wide_mode             gemm_wide.hip for 17..64-row decode steps: 0 = off (they keep the earlier routes)
+ *  21  fp8_gemm_choice       fp8 tile GEMM choice: 0 = by grid size; 1 = always the 128^2 kernel; 2 = always the 256^2 pipeline
+ *  22  fp8_prefill_min_rows  fewest prefill rows that take the fp8 MFMA path of a prefill_fp8 engine
+ *  23  attn_split            key split of few-row head_dim-512 attention: 0 = automatic (every 96 keys); 1 = never; n >= 2 = n splits
+ *  24  splitk_cap            most K slices of a weight-streaming (M <= 512) linear; values outside 1..16 are clamped
+ *  25  qf_kv_all             Q-Former cross-attention K|V projections of all blocks as one GEMM: 0 = one block at a time (A/B)
+ *  26  splitk_mid            K slices for tile-GEMM grids that leave a CU one workgroup (M > 512, < 256 tiles): 0 = whole-K tiles (batch-invariant)
+ *  27  wide_fp8_splits       K splits of the e4m3 17..64-row stream: 0 = by shape (A/B)
+ *  28  persist_decode        batch-1 decode steps as ONE resident grid per token (decode_persist.hip) instead of the launch chain
+ *  29  oneshot               one-shot all-reduce for the TP decode step when peer areas are attached: 0 = keep RCCL
+ *  30  attn_o                batch-1 decode attention + O projection as one launch (attn_o_fused.hip): 0 = two launches
+ *  31  attn_o_delay          that launch's O role waits n x ~0.21 us before requesting its weights, so that the attention blocks' K / V loads reach the memory system first
+ *  32  flash_bwd             training step: tile-resident attention backward for head_dim 128; 0 = the materialising batched-GEMM route (A/B)
+ *  33  rope_in_attn          prefill: RoPE of the queries inside the attention's Q load; 0 = a rotated copy of Q from rope_kv_kernel (bit-identical)
+ *  34  gemm256_persist       256^2 GEMM: persistent whole-tile workgroups when a launch has more whole tiles than CUs; 0 = one workgroup per tile (bit-identical)
+ *  35  skinny_even           3..16-row persistent weight stream: the same number of row groups on every workgroup; 0 = one workgroup per CU (bit-identical)
+ *  36  append_flash_min_t    append prefill: more new rows per sample than this run on the prefill's flash kernel, fewer on the key-split kernel of attn_append.hip */
 int vz_tune_set(int knob, int value);
+/* the knob's current value */
+int vz_tune_get(int knob, int* value);
+/* entry `index` (0, 1, ...) of the knob table: number, name (static storage), default, lowest and highest accepted value.  VZ_ERR_ARG past
+ * the last entry. */
+int vz_tune_info(int index, int* knob, const char** name, int* dflt, int* lo, int* hi);
 
 /* per-kernel-class timing of the engine's launches with HIP events on the launch stream (bench.py's roofline
  * leg).  enable=1 disables graph replay and brackets every launch of class `klass` with events.

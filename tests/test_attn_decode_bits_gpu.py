@@ -6,7 +6,7 @@ bit for bit against the commit before its head and merge were turned into single
    exactly full, a second call on the same ticket buffer).  Cache rows >= len and row `slot` itself hold NaN bit patterns before each
    call: the reference never read them, and a clamped or unconditional load of one that reaches a result turns it non-finite.
 2. The fused attention + O launch on the 2-layer engine at S = 2900 and 3990 (23 and 32 splits; tests/test_persist_gpu.py stops at 2200)
-   against the two launches (vz_tune_set(30, 0)): logits and ids EQUAL, eager and through the captured graph, check_async() clean."""
+   against the two launches (knob 30 (attn_o) = 0): logits and ids EQUAL, eager and through the captured graph, check_async() clean."""
 import os
 import sys
 
@@ -69,8 +69,7 @@ def test_fused_attention_o_launch_at_long_contexts(B, long_ctx, S):
     emb = eng.embed_tokens(synth.synth_ids(S, cfg.vocab, image_pos=-1, seed=700 + S).unsqueeze(0))
     res = {}
     for fused in (1, 0):
-        B.check(B.lib().vz_tune_set(30, fused))
-        try:
+        with B.tuned(attn_o=fused):
             _, last = eng.prefill(emb, [S], all_logits=False, last_logits=True)
             eng.decode_begin(last.argmax(-1).to(torch.int32), [S], [S])
             ids, lg = eng.decode_steps(5, return_logits=True)
@@ -80,8 +79,6 @@ def test_fused_attention_o_launch_at_long_contexts(B, long_ctx, S):
             torch.cuda.synchronize()
             eng.check_async()
             res[fused] = (ids[0].clone(), lg[:, 0].clone(), ids_g[0].clone())
-        finally:
-            B.check(B.lib().vz_tune_set(30, 1))
     assert torch.isfinite(res[1][1]).all()
     assert torch.equal(res[1][0], res[0][0]) and torch.equal(res[1][2], res[0][2])
     assert torch.equal(res[1][1], res[0][1]), f"S={S}: max |diff| {float((res[1][1] - res[0][1]).abs().max()):.3e}"

@@ -246,14 +246,11 @@ def test_beam_batches_and_returns(env):
             ids[r, n - len(x):] = x
             mask[r, n - len(x):] = 1
         return ids, mask
-    B.check(B.lib().vz_tune_set(26, 0))
-    try:
+    with B.tuned(splitk_mid=0):
         kw = dict(num_beams=4, max_new_tokens=12, return_dict_in_generate=True)
         ab = model.generate(input_ids=batch(a, b)[0], attention_mask=batch(a, b)[1], **kw)
         aa = model.generate(input_ids=batch(a, a)[0], attention_mask=batch(a, a)[1], **kw)
         bb = model.generate(input_ids=batch(b, b)[0], attention_mask=batch(b, b)[1], **kw)
-    finally:
-        B.check(B.lib().vz_tune_set(26, 1))
     # 8 rows in every call: each prompt's beams are what that prompt gives next to itself
     assert ab.sequences[0].tolist() == aa.sequences[0].tolist() and ab.sequences[1].tolist() == bb.sequences[0].tolist()
     assert ab.sequences_scores.tolist() == [aa.sequences_scores[0].item(), bb.sequences_scores[0].item()]

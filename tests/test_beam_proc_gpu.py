@@ -310,12 +310,9 @@ def test_batches_in_chunks_global_rows_and_zeros_behind_a_prompts_end(env):
     # bias lifts the eos id (log-prob about -11 in this model) to just above the model's best tokens (about -6), not far beyond them
     kw = dict(num_beams=nb, num_return_sequences=nrs, max_new_tokens=max_new, return_dict_in_generate=True, output_scores=True, beam_extended=True,
               output_logits=True, sequence_bias={(EOS,): 5.0}, min_new_tokens=3, repetition_penalty=PENALTY, sync_every=4)
-    B.check(B.lib().vz_tune_set(26, 0))          # one kernel route for every row count (tests/test_beam_gpu.py::test_beam_batches_and_returns)
-    try:
+    with B.tuned(splitk_mid=0):          # one kernel route for every row count (tests/test_beam_gpu.py::test_beam_batches_and_returns)
         batch = model.generate(input_ids=ids, attention_mask=mask, **kw)
         singles = [model.generate(input_ids=p.unsqueeze(0), **kw) for p in prompts]
-    finally:
-        B.check(B.lib().vz_tune_set(26, 1))
     steps = [len(s.scores) for s in singles]
     record("beam_proc_batch", steps=steps, lens=[int((s.beam_indices[0] >= 0).sum()) for s in singles])
     assert len(set(steps)) > 1, f"the searches all took the same number of steps, the zeros rule is not exercised: {steps}"

@@ -51,14 +51,11 @@ def _ref(x, w, act=0, norm_w=None, eps=1e-5):
 
 
 def _run(B, x, w, nw, act, fp32, residual):
-    B.check(B.lib().vz_tune_set(9, 0))
-    try:
+    with B.tuned(skinny_mode=0):
         if nw is not None:
             out = B.linear_rmsnorm(x, nw, 1e-5, w, residual=residual, act=act, out_fp32=fp32)
         else:
             out = B.linear(x, w, residual=residual, act=act, out_fp32=fp32, impl=1)
-    finally:
-        B.check(B.lib().vz_tune_set(9, 1))
     torch.cuda.synchronize()
     return out
 

@@ -56,17 +56,9 @@ def _ref(x, w, bias=None, residual=None, act=0, norm_w=None, eps=1e-5):
     return y.float()
 
 
-class _Knob9:
-    """knob 9 = 0 for the block: 2..8 rows stay on the GEMV"""
-
-    def __init__(self, B):
-        self.B = B
-
-    def __enter__(self):
-        self.B.check(self.B.lib().vz_tune_set(9, 0))
-
-    def __exit__(self, *a):
-        self.B.check(self.B.lib().vz_tune_set(9, 1))
+def _Knob9(B):
+    """knob 9 (skinny_mode) = 0 for the block: 2..8 rows stay on the GEMV"""
+    return B.tuned(skinny_mode=0)
 
 
 # K x N x M through the plain launch: bias + residual in bf16, and fp32 output (8 rows fit the 160 KiB of LDS up to K = 10224: 9728 is

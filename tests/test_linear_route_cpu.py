@@ -11,7 +11,7 @@ import pytest
 
 from util import REPO
 
-KNOB_DEFAULTS = {9: 1, 14: 29, 19: 1}
+ROUTE_KNOBS = (9, 14, 19)      # skinny_mode, decode_tile_rows, wide_mode: the golden table's k9 / k14 / k19 columns
 
 
 @pytest.fixture(scope="module")
@@ -19,9 +19,8 @@ def B():
     from test_abi_cpu import _ensure_built
     from vz_hip import binding
     binding.load_library(_ensure_built())
-    yield binding
-    for k, v in KNOB_DEFAULTS.items():
-        binding.check(binding.lib().vz_tune_set(k, v))
+    with binding.tuned(*[(k, binding.tune_get(k)) for k in ROUTE_KNOBS]):       # whatever a test leaves, the module puts back what it found
+        yield binding
 
 
 def _zephyr_decode_shapes():
@@ -45,16 +44,11 @@ def test_route_table_is_the_one_from_before_the_planner(B):
     assert len(table) >= 2000
     assert {t["route"] for t in table} >= set(B.LIN_ROUTES)          # the sweep reached every kernel family
     wrong = []
-    try:
-        for t in table:
-            for k in KNOB_DEFAULTS:
-                B.check(B.lib().vz_tune_set(k, t[f"k{k}"]))
+    for t in table:
+        with B.tuned(*[(k, t[f"k{k}"]) for k in ROUTE_KNOBS]):
             got = B.linear_route(t["M"], t["N"], t["K"], t["lda"], t["ldw"], t["act"], t["out_fp32"], t["flags"], t["entry"])[0]
-            if got != t["route"]:
-                wrong.append((t, got))
-    finally:
-        for k, v in KNOB_DEFAULTS.items():
-            B.check(B.lib().vz_tune_set(k, v))
+        if got != t["route"]:
+            wrong.append((t, got))
     assert not wrong, f"{len(wrong)} of {len(table)} routes differ, first: {wrong[:5]}"
 
 

@@ -257,11 +257,8 @@ def test_attention_key_split_q_former_cross(B, T, Sq, Sk, split):
     k[0, Sk - 5] = (q[0, 3] * 3).bfloat16()                       # one dominating key inside the last split
     nsplit = split if split >= 2 else ((Sk + 31) // 32 + 2) // 3
     ws = torch.empty(T * H * nsplit * Sq * 516, dtype=torch.float32, device="cuda")
-    B.check(B.lib().vz_tune_set(23, split))
-    try:
+    with B.tuned(attn_split=split):
         out = B.attention(q, k, v, D ** -0.5, workspace=ws)
-    finally:
-        B.check(B.lib().vz_tune_set(23, 0))
     one = B.attention(q, k, v, D ** -0.5)
     ref = _ref_attention(q, k, v, D ** -0.5, False, 0, 0, None)
     check_close(f"attention key-split T{T} {Sq}x{Sk}", out, ref, 8e-3, 4e-3)
@@ -385,11 +382,8 @@ GEMM256_SHAPES = [(2048, 6144, 4096), (2048, 4096, 14336), (2885, 4096, 1024), (
 def _whole_k(B, fn):
     """the 128^2 kernel with every tile summing its whole K in one workgroup (knob 26 = 0: no K slices for small grids), the
     order the 256^2 kernel's whole tiles reproduce bit for bit"""
-    B.check(B.lib().vz_tune_set(26, 0))
-    try:
+    with B.tuned(splitk_mid=0):
         return fn()
-    finally:
-        B.check(B.lib().vz_tune_set(26, 1))
 
 
 @pytest.mark.parametrize("M,N,K", GEMM256_SHAPES)
@@ -405,9 +399,8 @@ def test_gemm256_matches_gemm128(B, M, N, K):
     ref = _whole_k(B, lambda: B.linear(x, w, out_fp32=True, impl=0))
     check_close(f"gemm128 ref {M}x{N}x{K}", ref, _ref_linear(x, w, None, None, 0), 1e-4, 1e-4)
     scale = float(ref.abs().max())
-    try:
-        for streamk in (2, 1, 0):          # stream-K tail forced / production heuristic / whole tiles only
-            B.check(B.lib().vz_tune_set(4, streamk))
+    for streamk in (2, 1, 0):          # stream-K tail forced / production heuristic / whole tiles only
+        with B.tuned(gemm256_streamk=streamk):
             first = None
             for rep in range(6):
                 if rep % 2:
@@ -422,8 +415,6 @@ def test_gemm256_matches_gemm128(B, M, N, K):
                     if first is None:
                         first = out.clone()
                     assert torch.equal(out, first), f"stream-K rep {rep}: result changed between launches"
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
 
 
 @pytest.mark.parametrize("M,N,K", [(700, 1024, 1024), (520, 1024, 4096)])     # whole tiles / 4 K-slices per tile
@@ -434,20 +425,14 @@ def test_gemm256_epilogues(B, act, M, N, K):
     bias = None if act == 3 else _rand((N,), 0.5, 64)
     n_out = N // 2 if act == 3 else N
     res = _rand((M, n_out), 1.0, 65).bfloat16()
-    B.check(B.lib().vz_tune_set(4, 2))        # stream-K tail forced
-    try:
+    with B.tuned(gemm256_streamk=2):          # stream-K tail forced
         out = B.linear(x, w, bias=bias, residual=res, act=act, impl=2)
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
     ref128 = _whole_k(B, lambda: B.linear(x, w, bias=bias, residual=res, act=act, impl=0))
     check_close(f"gemm256 epilogue act{act}", out, _ref_linear(x, w, bias, res, act), BF16_MAX, BF16_L2)
     # stream-K re-associates the fp32 sum: a handful of outputs may round to the neighbouring bf16 value
     assert float((out.float() - ref128.float()).abs().max()) <= 2 ** -7 * float(ref128.float().abs().max())
-    B.check(B.lib().vz_tune_set(4, 0))
-    try:
+    with B.tuned(gemm256_streamk=0):
         assert torch.equal(B.linear(x, w, bias=bias, residual=res, act=act, impl=2), ref128)
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
 
 
 def test_gemm256_identity_asymmetric(B):
@@ -470,13 +455,10 @@ def test_attention_v2_matches_v1(B, case):
     k = _rand((Bn, Sk, Hkv, D), 1.0, 71).bfloat16()
     v = _rand((Bn, Sk, Hkv, D), 1.0, 72).bfloat16()
     kv_len = torch.tensor([Sk, Sk // 2 + 3][:Bn], dtype=torch.int32, device="cuda") if ragged else None
-    try:
-        B.check(B.lib().vz_tune_set(2, 1))
+    with B.tuned(attn_version=1):
         o1 = B.attention(q, k, v, D ** -0.5, causal, q_pos0, window, kv_len)
-        B.check(B.lib().vz_tune_set(2, 2))
+    with B.tuned(attn_version=2):
         o2 = B.attention(q, k, v, D ** -0.5, causal, q_pos0, window, kv_len)      # classic online-softmax step
-    finally:
-        B.check(B.lib().vz_tune_set(2, 3))
     o3 = B.attention(q, k, v, D ** -0.5, causal, q_pos0, window, kv_len)          # production: deferred-maximum step
     if ragged:
         for b in range(Bn):
@@ -499,11 +481,8 @@ def test_gemm_splitk_small_m(B, M, N, K, act):
     res = _rand((M, N), 1.0, 83).bfloat16()
     out = B.linear(x, w, bias=bias, residual=res, act=act, impl=0)
     check_close(f"gemm split-K {M}x{N}x{K}", out, _ref_linear(x, w, bias, res, act), BF16_MAX, BF16_L2)
-    try:
-        B.check(B.lib().vz_tune_set(3, 1))
+    with B.tuned(splitk_mode=1):
         plain = B.linear(x, w, bias=bias, residual=res, act=act, impl=0)
-    finally:
-        B.check(B.lib().vz_tune_set(3, 0))
     check_close(f"gemm split-K vs single pass {M}x{N}x{K}", out, plain.float(), 8e-3, 5e-4)
     o32 = B.linear(x, w, out_fp32=True, impl=0)
     check_close(f"gemm split-K fp32 {M}x{N}x{K}", o32, _ref_linear(x, w, None, None, 0), 1e-4, 1e-4)
@@ -532,12 +511,9 @@ def test_gemv_fp8_weights(B, M, N, K, act):
     for mode in (1, 0):          # 2..16 rows: MFMA weight stream (gemm_skinny.hip) / the GEMV form (M <= 8); 1 row: always the GEMV
         if mode == 0 and M > 8:
             continue
-        try:
-            B.check(B.lib().vz_tune_set(9, mode))
+        with B.tuned(skinny_mode=mode):
             out32 = B.linear_fp8(x, w8, scale, act=act, out_fp32=True)
             out = B.linear_fp8(x, w8, scale, bias=bias, residual=res, act=act)
-        finally:
-            B.check(B.lib().vz_tune_set(9, 1))
         check_close(f"fp8 fp32 {M}x{N}x{K} act{act} mode{mode}", out32, _ref_linear(x, wq, None, None, act), 1e-4, 1e-4)
         check_close(f"fp8 {M}x{N}x{K} act{act} mode{mode}", out, _ref_linear(x, wq, bias, res, act), BF16_MAX, BF16_L2)
     same = B.linear(x, wq.bfloat16(), bias=bias, residual=res, act=act, impl=1 if M <= 8 else 3)
@@ -617,11 +593,8 @@ def test_skinny_gemm_fused_rmsnorm(B, M, act):
         assert torch.equal(out, unfused)
     # and, with the knob off, the GEMV path fuses the norm the same way (M <= 8)
     if M <= 8:
-        try:
-            B.check(B.lib().vz_tune_set(9, 0))
+        with B.tuned(skinny_mode=0):
             gv = B.linear_rmsnorm(x, nw, 1e-5, w, act=act, out_fp32=True)
-        finally:
-            B.check(B.lib().vz_tune_set(9, 1))
         check_close(f"gemv vs skinny fused norm M{M}", gv, out, 1e-4, 1e-4)
 
 
@@ -674,11 +647,8 @@ def test_skinny_persistent_fused_norm(B, M, N, act):
             check_close(f"persistent skinny M{M} N{N} act{act}", out, _ref_linear(xn, w, None, None, act), 2e-2, 3e-3)
         assert torch.equal(out, first), "result changed between launches"
         torch.randn(1 << 21, device="cuda").sum()
-    try:
-        B.check(B.lib().vz_tune_set(9, 2))
+    with B.tuned(skinny_mode=2):
         old = B.linear_rmsnorm(x, nw, 1e-5, w, act=act, out_fp32=True)
-    finally:
-        B.check(B.lib().vz_tune_set(9, 1))
     if groups < 512:
         assert torch.equal(old, first), f"{(old != first).sum().item()} elements differ from the one-group-per-workgroup kernel"
     else:
@@ -760,7 +730,7 @@ def test_attention_shape_fuzz(B, case):
 @pytest.mark.parametrize("M,N,K,act", [(8192, 4096, 512, 0), (2048, 28672, 1024, 3), (5000, 6144, 768, 1), (12736, 4096, 256, 0)])
 def test_gemm256_persistent_tiles_equal_one_workgroup_per_tile(B, M, N, K, act):
     """Round 3: with more whole tiles than CUs, 256 workgroups walk the tiles (tile b, b + 256, ...) instead of one workgroup each
-    (gemm256.hip::plan_and_launch, vz_tune_set(34, 0) = off).  Same tile arithmetic, same stream-K tail: bit-identical outputs - with bias,
+    (gemm256.hip::plan_and_launch, knob 34 (gemm256_persist) = 0 = off).  Same tile arithmetic, same stream-K tail: bit-identical outputs - with bias,
     residual and the fused activations, a partial last row tile (M = 5000) and a stream-K remainder (896 tiles = 3.5 rounds)."""
     x = _rand((M, K), 1.0, 310).bfloat16()
     w = _rand((N, K), 0.03, 311).bfloat16()
@@ -769,11 +739,8 @@ def test_gemm256_persistent_tiles_equal_one_workgroup_per_tile(B, M, N, K, act):
     res = _rand((M, n_out), 1.0, 313).bfloat16()
     outs = []
     for knob in (1, 0):
-        try:
-            B.check(B.lib().vz_tune_set(34, knob))
+        with B.tuned(gemm256_persist=knob):
             outs.append(B.linear(x, w, bias=bias, residual=res, act=act, impl=2))
-        finally:
-            B.check(B.lib().vz_tune_set(34, 1))
     assert torch.isfinite(outs[0].float()).all()
     assert torch.equal(outs[0], outs[1])
     ref = x.float() @ w.float().t()
@@ -795,8 +762,7 @@ def test_gemm256_streamk_two_streams_do_not_share_tickets(B):
     M, N, K = 640, 1100, 4096           # 3 x 5 = 15 tiles on 256 CUs: the whole launch is a stream-K tail when forced
     x1, w1 = _rand((M, K), 1.0, 70).bfloat16(), _rand((N, K), 0.05, 71).bfloat16()
     x2, w2 = _rand((M, K), 1.0, 72).bfloat16(), _rand((N, K), 0.05, 73).bfloat16()
-    try:
-        B.check(B.lib().vz_tune_set(4, 2))
+    with B.tuned(gemm256_streamk=2):
         alone1 = B.linear(x1, w1, out_fp32=True, impl=2)
         alone2 = B.linear(x2, w2, out_fp32=True, impl=2)
         torch.cuda.synchronize()
@@ -812,8 +778,6 @@ def test_gemm256_streamk_two_streams_do_not_share_tickets(B):
             assert B.op_async_error() == 0
         with torch.cuda.stream(s2):
             assert B.op_async_error() == 0
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
     for o in outs1:
         assert torch.equal(o, alone1)
     for o in outs2:
@@ -826,8 +790,7 @@ def test_gemm256_streamk_expired_wait_raises_and_poisons(B):
     stale slots), every other tile is right; reading the error resets the tickets and the next launch is clean."""
     M, N, K = 640, 1100, 4096
     x, w = _rand((M, K), 1.0, 74).bfloat16(), _rand((N, K), 0.05, 75).bfloat16()
-    try:
-        B.check(B.lib().vz_tune_set(4, 2))
+    with B.tuned(gemm256_streamk=2):
         good = B.linear(x, w, out_fp32=True, impl=2)
         assert B.op_async_error() == 0
         B.check(B.lib().vz_test_corrupt_streamk(B.stream_ptr(), 0, 0, 100))
@@ -840,8 +803,6 @@ def test_gemm256_streamk_expired_wait_raises_and_poisons(B):
         assert B.op_async_error() == 0                      # cleared, tickets reset
         again = B.linear(x, w, out_fp32=True, impl=2)
         assert torch.equal(again, good) and B.op_async_error() == 0
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
 
 
 @pytest.mark.parametrize("M,N,K,act", [(33, 6144, 4096, 0), (64, 4096, 4096, 0), (48, 4096, 14336, 0), (64, 28672, 4096, 3), (40, 3584, 4096, 3),
@@ -875,16 +836,13 @@ def test_skinny_tiled_weights_bit_identical(B, M, N, K, act, norm):
     n_out = N // 2 if act == 3 else N
     res = _rand((M, n_out), 1.0, 92).bfloat16()
     nw = (_rand((K,), 0.2, 93) + 1.0) if norm and M <= 16 else None
-    try:
-        B.check(B.lib().vz_tune_set(19, 0))          # 17..64 rows: keep linear_tiled on the MFMA weight stream (not gemm_wide.hip)
+    with B.tuned(wide_mode=0):          # 17..64 rows: keep linear_tiled on the MFMA weight stream (not gemm_wide.hip)
         if nw is not None and M > 2:
             a = B.linear_rmsnorm(x, nw, 1e-5, w, residual=res, act=act)
             b = B.linear_tiled(x, w, wt, residual=res, act=act, norm_w=nw, norm_eps=1e-5)
         else:                                        # (2 rows with a fused norm: the production dispatch is the GEMV)
             a = B.linear(x, w, residual=res, act=act, impl=3)
             b = B.linear_tiled(x, w, wt, residual=res, act=act)
-    finally:
-        B.check(B.lib().vz_tune_set(19, 1))
     assert torch.equal(a, b), f"max diff {float((a.float() - b.float()).abs().max()):.3e}"
 
 
@@ -982,13 +940,10 @@ def test_linear_fp8_mfma(B, M, N, K, act):
     bias = None if act == 3 else _rand((N,), 0.1, 512)
     res = _rand((M, n_out), 0.5, 513).bfloat16()
     ref = _ref_linear(xq, wq, bias, res, act)
-    try:
-        for choice, what in ((1, "two-stage 128^2 kernel"), (2, "256^2 pipeline (gemm256.hip's ring, stream-K tail included)")):
-            B.check(B.lib().vz_tune_set(21, choice))
+    for choice, what in ((1, "two-stage 128^2 kernel"), (2, "256^2 pipeline (gemm256.hip's ring, stream-K tail included)")):
+        with B.tuned(fp8_gemm_choice=choice):
             out32 = B.linear_fp8_mfma(x8, xs, w8.cuda(), ws.cuda(), bias=bias, residual=res, act=act, out_fp32=True)
             check_close(f"fp8 mfma fp32 M{M} N{N} K{K} act{act} {what}", out32, ref, 1e-4, 1e-4)
             out = B.linear_fp8_mfma(x8, xs, w8.cuda(), ws.cuda(), bias=bias, residual=res, act=act)
             check_close(f"fp8 mfma bf16 M{M} N{N} K{K} act{act} {what}", out, ref, BF16_MAX, BF16_L2)
-    finally:
-        B.check(B.lib().vz_tune_set(21, 0))
     assert B.op_async_error() == 0

@@ -1,5 +1,5 @@
 """The persistent decode-token kernel (csrc/decode_persist.hip: batch-1 decode steps as ONE resident grid per token, the 161 launches
-of a step as phases with in-launch hand-offs) against the launch chain (the default; the persistent kernel is opt-in, vz_tune_set(28, 1): it measured slower on MI355X): the same arithmetic in the
+of a step as phases with in-launch hand-offs) against the launch chain (the default; the persistent kernel is opt-in, knob 28 (persist_decode) = 1: it measured slower on MI355X): the same arithmetic in the
 same order, so logits and ids must be EQUAL bit for bit - eager and through the captured per-token graph, at 2 and at 32 layers, short
 and long contexts (1 .. 18 context splits of the attention phase) - and its bounded waits must end the launch and raise
 VZ_ASYNC_PERSIST instead of hanging (hf:models/mistral/modeling_mistral.py:202-241 is the arithmetic of a step; the oracle / reference
@@ -26,15 +26,15 @@ def _model(n_layers, max_ctx, weight_fp8=False, max_batch=1):
 
 
 def _knob(v):
+    """scope with knob 28 (persist_decode) at v"""
     from vz_hip import binding as B
-    B.check(B.lib().vz_tune_set(28, int(v)))
+    return B.tuned(persist_decode=int(v))
 
 
 def _steps(model, emb, n, persist):
     """prefill + n eager decode steps with their logits; (ids [n], logits [n, V], ran on the persistent kernel?)"""
     eng = model.engine
-    _knob(persist)
-    try:
+    with _knob(persist):
         S = emb.shape[1]
         _, last = eng.prefill(emb, [S], all_logits=False, last_logits=True)
         eng.decode_begin(last.argmax(-1).to(torch.int32), [S], [S])
@@ -42,8 +42,6 @@ def _steps(model, emb, n, persist):
         torch.cuda.synchronize()
         eng.check_async()
         return ids[0].clone(), lg[:, 0].clone(), eng.persist_mode()
-    finally:
-        _knob(0)
 
 
 @pytest.fixture(scope="module")
@@ -77,15 +75,12 @@ def test_persistent_graph_replay_equals_launch_chain_and_sampling_tail(small):
     ids = synth.synth_ids(200, cfg.vocab, image_pos=-1, seed=77).unsqueeze(0)
     outs = {}
     for persist in (1, 0):
-        _knob(persist)
-        try:
+        with _knob(persist):
             g = model.generate(input_ids=ids, do_sample=False, max_new_tokens=40, eos_token_id=None)[0].tolist()
             mode = model.engine.persist_mode()
             s_ = model.generate(input_ids=ids, do_sample=True, temperature=0.7, top_k=50, max_new_tokens=24, eos_token_id=None, seed=5)[0].tolist()
             model.engine.check_async()
             outs[persist] = (g, s_, mode)
-        finally:
-            _knob(0)
     if not outs[1][2]:
         pytest.skip("the persistent kernel is not available on this device")
     assert outs[1][0] == outs[0][0] and outs[1][1] == outs[0][1]
@@ -105,15 +100,12 @@ def test_expired_hand_off_ends_the_launch_and_raises(small):
         pytest.skip("the persistent kernel is not available on this device")
     for word, value in ((0, -1000), (8, 1)):
         S = emb.shape[1]
-        _knob(1)
-        try:
+        with _knob(1):
             _, last = eng.prefill(emb, [S], all_logits=False, last_logits=True)
             eng.decode_begin(last.argmax(-1).to(torch.int32), [S], [S])
             eng.persist_poke(word, value)
             eng.decode_steps(1)
             torch.cuda.synchronize()                       # the launch ended (bounded waits): nothing hangs
-        finally:
-            _knob(0)
         with pytest.raises(RuntimeError, match="persistent decode-token kernel"):
             eng.check_async()
         ids2, lg2, _ = _steps(model, emb, 2, persist=1)
@@ -138,7 +130,7 @@ def test_fused_attention_o_launch_on_e4m3_weights(small_fp8, S):
 @pytest.mark.parametrize("S", [5, 127, 300, 1100, 2200])
 def test_fused_attention_o_launch_equals_the_two_launches(small, S):
     """csrc/attn_o_fused.hip (the default batch-1 route: the O projection's workgroups ride in the decode attention's grid and stream
-    their weights under its latency chain) against vz_tune_set(30, 0) (attention kernel, then the O projection's GEMV): the same
+    their weights under its latency chain) against knob 30 (attn_o) = 0 (attention kernel, then the O projection's GEMV): the same
     arithmetic in the same order - logits and ids EQUAL bit for bit, eager and through the captured graph."""
     from vz_hip import binding as B
     cfg, synth, model = small
@@ -146,8 +138,7 @@ def test_fused_attention_o_launch_equals_the_two_launches(small, S):
     emb = eng.embed_tokens(synth.synth_ids(S, cfg.vocab, image_pos=-1, seed=700 + S).unsqueeze(0))
     res = {}
     for fused in (1, 0):
-        B.check(B.lib().vz_tune_set(30, fused))
-        try:
+        with B.tuned(attn_o=fused):
             _, last = eng.prefill(emb, [S], all_logits=False, last_logits=True)
             eng.decode_begin(last.argmax(-1).to(torch.int32), [S], [S])
             ids, lg = eng.decode_steps(5, return_logits=True)
@@ -157,8 +148,6 @@ def test_fused_attention_o_launch_equals_the_two_launches(small, S):
             torch.cuda.synchronize()
             eng.check_async()
             res[fused] = (ids[0].clone(), lg[:, 0].clone(), ids_g[0].clone())
-        finally:
-            B.check(B.lib().vz_tune_set(30, 1))
     for fused in (1,):
         assert torch.isfinite(res[fused][1]).all()
         assert torch.equal(res[fused][0], res[0][0]) and torch.equal(res[fused][2], res[0][2]), fused
@@ -185,8 +174,7 @@ def test_fused_attention_o_launch_with_two_rows(small2, S, short):
     emb = eng.embed_tokens(ids.reshape(-1)).view(2, S, -1)
     res = {}
     for fused in (1, 0):
-        B.check(B.lib().vz_tune_set(30, fused))
-        try:
+        with B.tuned(attn_o=fused):
             _, last = eng.prefill(emb, lens, all_logits=False, last_logits=True)
             eng.decode_begin(last.argmax(-1).to(torch.int32), lens, lens)
             toks, lg = eng.decode_steps(4, return_logits=True)
@@ -196,8 +184,6 @@ def test_fused_attention_o_launch_with_two_rows(small2, S, short):
             torch.cuda.synchronize()
             eng.check_async()
             res[fused] = (toks.clone(), lg.clone(), toks_g.clone())
-        finally:
-            B.check(B.lib().vz_tune_set(30, 1))
     assert torch.isfinite(res[1][1]).all()
     assert torch.equal(res[1][0], res[0][0]) and torch.equal(res[1][2], res[0][2])
     assert torch.equal(res[1][1], res[0][1]), f"S={S}: max |diff| {float((res[1][1] - res[0][1]).abs().max()):.3e}"

@@ -450,16 +450,13 @@ def test_knob_change_captures_again(env, B):
     c1 = cap()
     eng.decode_steps(4, out=buf)
     assert (c1, cap()) == (c0 + 1, c0 + 1)
-    B.check(B.lib().vz_tune_set(9, 0))
-    try:
+    with B.tuned(skinny_mode=0):
         eng.decode_begin(first, [S], [S])
         eng.decode_steps(4, out=buf)
         assert eng.decode_mode()[0] and cap() == c0 + 2, "the knob change did not make the next call capture again"
         eng.decode_begin(first, [S], [S])
         eager, _ = eng.decode_steps(4, return_logits=True)
         assert torch.equal(buf, eager)
-    finally:
-        B.check(B.lib().vz_tune_set(9, 1))
 
 
 def test_colliding_eos_sets_capture_again(env, B):

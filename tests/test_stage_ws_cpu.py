@@ -170,11 +170,8 @@ def test_refused_shapes_and_configs_answer_minus_one(B):
 def test_qformer_follows_the_split_knob(B):
     """knob 23 >= 2 pins the split count: the engine reserves what the launcher then asks for, not the default rule's count"""
     a, cfg = _arch(), _cfg(B, 1)
-    try:
-        B.check(B.lib().vz_tune_set(23, 9))
+    with B.tuned(attn_split=9):
         got = B.stage_ws_bytes(cfg, B.STAGE_QFORMER, 2, 1, 31)
         assert got == _carved(_qformer_takes(a, 2, 1, 31, False, lambda Sk: min(9, _ceil(Sk, 32)) if _ceil(Sk, 32) >= 2 else 0))
-        B.check(B.lib().vz_tune_set(23, 1))
+    with B.tuned(attn_split=1):
         assert B.stage_ws_bytes(cfg, B.STAGE_QFORMER, 2, 1, 31) == _carved(_qformer_takes(a, 2, 1, 31, False, lambda Sk: 0))
-    finally:
-        B.check(B.lib().vz_tune_set(23, 0))

@@ -323,7 +323,7 @@ def test_decode_matches_prefill_logits(env):
 def test_rope_at_the_attention_q_load_is_bit_identical(env):
     """Round 3: the prefill attention rotates the queries as it loads them from the fused QKV row (rope_kv_kernel then only rotates K and
     appends K / V) - the same operation order as the kernel it replaces, so logits and the decode steps that follow are the same BITS as
-    with the rotated copy of Q (vz_tune_set(33, 0)).  Ragged batch with left padding (positions are not row indices there)."""
+    with the rotated copy of Q (knob 33 (rope_in_attn) = 0).  Ragged batch with left padding (positions are not row indices there)."""
     from vz_hip import binding as B
     cfg, model = env["cfg"], env["model"]
     eng = model.engine
@@ -333,14 +333,11 @@ def test_rope_at_the_attention_q_load_is_bit_identical(env):
         emb = eng.embed_tokens(ids).unsqueeze(0)
         got = []
         for knob in (1, 0):
-            try:
-                B.check(B.lib().vz_tune_set(33, knob))
+            with B.tuned(rope_in_attn=knob):
                 full, last = eng.prefill(emb, [S], all_logits=True, last_logits=True)
                 eng.decode_begin(last.argmax(-1).to(torch.int32), [S], [S])
                 toks, lg = eng.decode_steps(3, return_logits=True)
                 got.append((full.clone(), lg.clone(), toks.clone()))
-            finally:
-                B.check(B.lib().vz_tune_set(33, 1))
         assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]) and torch.equal(got[0][2], got[1][2])
     if eng.max_batch >= 2:
         ids = torch.stack([synth.synth_ids(48, cfg.vocab, image_pos=-1, seed=s) for s in (5, 6)])
@@ -348,11 +345,8 @@ def test_rope_at_the_attention_q_load_is_bit_identical(env):
         mask[1, :17] = 0                                     # left padding on the second sample
         outs = []
         for knob in (1, 0):
-            try:
-                B.check(B.lib().vz_tune_set(33, knob))
+            with B.tuned(rope_in_attn=knob):
                 outs.append(model(input_ids=ids.to(model.device), attention_mask=mask.to(model.device)).logits.clone())
-            finally:
-                B.check(B.lib().vz_tune_set(33, 1))
         assert torch.equal(outs[0], outs[1])
 
 
@@ -742,12 +736,9 @@ def test_full_size_request_properties(env):
     # production dispatch: the stream-K tail of the 256x256 GEMM sums K in slices for the rows that fall into the split tiles
     # (fp32 re-association), so a moved tile agrees to bf16 rounding through the 8 Q-Former blocks ...
     check_close("permuted tiles (production dispatch)", b, a[perm].float(), 0.25, 2e-2)
-    try:                                                              # ... and bit for bit with whole tiles only
-        B.check(B.lib().vz_tune_set(4, 0))
+    with B.tuned(gemm256_streamk=0):                                  # ... and bit for bit with whole tiles only
         a0 = model.encode_images(tiles, text, tile_sample=[0] * 5)
         b0 = model.encode_images(tiles[perm], text, tile_sample=[0] * 5)
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
     assert torch.equal(b0, a0[perm])
     # the Q-Former at the full text length (block 0 attends over 32 + 1888 rows) for one tile, against the oracle's band
     O, sd = env["O"], env["sd"]
@@ -836,9 +827,7 @@ def test_continuous_batching_matches_static_batches(env):
     # bf16 bit) on its position in the batch - ids would then agree only up to near-ties.  Whole tiles only (knob 4 = 0) is the
     # batch-invariant kernel choice (as in test_full_size_request_properties): identical samples give identical rows, bit for bit.
     from vz_hip import binding as B
-    try:
-        B.check(B.lib().vz_tune_set(4, 0))
-        B.check(B.lib().vz_tune_set(26, 0))        # and no tile-count-dependent K slices in the CLIP tower's small grids
+    with B.tuned(gemm256_streamk=0, splitk_mid=0):          # and no tile-count-dependent K slices in the CLIP tower's small grids
         free_run = {i: static(i, None) for i in range(len(reqs))}
         # an eos that request 1 emits at its 8th token (mid-chunk with sync_every = 4) and that hits nobody's first token
         eos = free_run[1][7]
@@ -863,9 +852,6 @@ def test_continuous_batching_matches_static_batches(env):
         for i in range(3):
             g1, w = got1[i].tolist(), free_run[i]
             assert g1[0] == w[0] and len(g1) == len(w)           # (a 1-row step runs the GEMV: a near-tie may flip later tokens)
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
-        B.check(B.lib().vz_tune_set(26, 1))
     env["_cb"] = dict(model=model, reqs=reqs, free_run=free_run, tiles=tiles, budgets=budgets)
 
 
@@ -992,29 +978,28 @@ def test_fp8_mfma_prefill_matches_quantized_oracle(env):
     eng.set_prefill_fp8(True)
     short, _ = eng.prefill(emb, [150], all_logits=True, last_logits=False)
     assert torch.equal(short, bf16_prefill)            # below 768 prefill rows the option keeps the bf16 GEMMs (not worth the quantiser launches)
-    B.check(B.lib().vz_tune_set(22, 0))               # ... unless told otherwise: this test runs the fp8 path on 150 rows
-    full, _ = eng.prefill(emb, [150], all_logits=True, last_logits=False)
-    lo_bf, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.BF16), P=O.BF16_FP8ACT)
-    lo_32, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.FP32), P=O.FP32_FP8ACT)
-    band("fp8 MFMA prefill logits", full, lo_bf, lo_32)
-    # what e4m3 activations cost on these (random, worst-case) weights: the distance to the weight-only-quantised model is of the size of
-    # the band itself - two identically quantising implementations already differ by it (a bf16-level difference flips e4m3 roundings)
-    lo_wonly, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.FP32), P=O.FP32)
-    e_act = errs(full, lo_wonly)[1]
-    record("fp8 MFMA prefill: cost of e4m3 activations", hip_vs_weight_only_oracle=e_act, hip_vs_bf16_prefill_same_engine=errs(full, bf16_prefill)[1],
-           oracle_fp8act_vs_weight_only=errs(lo_32, lo_wonly)[1])
-    assert e_act <= 2.0 * errs(lo_32, lo_wonly)[1] + 5e-3
-    # decode continues from the fp8-prefilled cache (bf16 activations from here on): close to the prefill row of the next position
-    S0 = 120
-    _, last = eng.prefill(emb[:, :S0].contiguous(), [S0], all_logits=False, last_logits=True)
-    eng.decode_begin(ids[S0:S0 + 1].to(torch.int32), [S0], [S0])
-    _, lg = eng.decode_steps(1, return_logits=True)
-    e_or = errs(lo_bf, lo_32)[1]
-    check_close("decode step after an fp8 prefill vs the fp8 prefill row", lg[0, 0], full[0, S0], 0.25, 3.0 * e_or + 2e-2)
-    out = model.generate(input_ids=ids[:64].unsqueeze(0), do_sample=False, max_new_tokens=5, eos_token_id=None, pad_token_id=2)
-    assert out.shape == (1, 5)
+    with B.tuned(fp8_prefill_min_rows=0):             # ... unless told otherwise: this test runs the fp8 path on 150 rows
+        full, _ = eng.prefill(emb, [150], all_logits=True, last_logits=False)
+        lo_bf, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.BF16), P=O.BF16_FP8ACT)
+        lo_32, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.FP32), P=O.FP32_FP8ACT)
+        band("fp8 MFMA prefill logits", full, lo_bf, lo_32)
+        # what e4m3 activations cost on these (random, worst-case) weights: the distance to the weight-only-quantised model is of the size of
+        # the band itself - two identically quantising implementations already differ by it (a bf16-level difference flips e4m3 roundings)
+        lo_wonly, _ = O.llm_forward(cfg, sdq, O.embed_tokens(sd, ids.unsqueeze(0), O.FP32), P=O.FP32)
+        e_act = errs(full, lo_wonly)[1]
+        record("fp8 MFMA prefill: cost of e4m3 activations", hip_vs_weight_only_oracle=e_act, hip_vs_bf16_prefill_same_engine=errs(full, bf16_prefill)[1],
+               oracle_fp8act_vs_weight_only=errs(lo_32, lo_wonly)[1])
+        assert e_act <= 2.0 * errs(lo_32, lo_wonly)[1] + 5e-3
+        # decode continues from the fp8-prefilled cache (bf16 activations from here on): close to the prefill row of the next position
+        S0 = 120
+        _, last = eng.prefill(emb[:, :S0].contiguous(), [S0], all_logits=False, last_logits=True)
+        eng.decode_begin(ids[S0:S0 + 1].to(torch.int32), [S0], [S0])
+        _, lg = eng.decode_steps(1, return_logits=True)
+        e_or = errs(lo_bf, lo_32)[1]
+        check_close("decode step after an fp8 prefill vs the fp8 prefill row", lg[0, 0], full[0, S0], 0.25, 3.0 * e_or + 2e-2)
+        out = model.generate(input_ids=ids[:64].unsqueeze(0), do_sample=False, max_new_tokens=5, eos_token_id=None, pad_token_id=2)
+        assert out.shape == (1, 5)
     eng.set_prefill_fp8(False)
-    B.check(B.lib().vz_tune_set(22, 768))
     again, _ = eng.prefill(emb, [150], all_logits=True, last_logits=False)
     assert torch.equal(again, bf16_prefill)
     del model

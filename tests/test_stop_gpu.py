@@ -210,13 +210,8 @@ def pinned_routes():
     """whole tiles only and no row-count-dependent K slices: rows of different batches get the same bits (the setup of
     tests/test_stages_gpu.py::test_continuous_batching_matches_static_batches)"""
     from vz_hip import binding as B
-    B.check(B.lib().vz_tune_set(4, 0))
-    B.check(B.lib().vz_tune_set(26, 0))
-    try:
+    with B.tuned(gemm256_streamk=0, splitk_mid=0):
         yield
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
-        B.check(B.lib().vz_tune_set(26, 1))
 
 
 @pytest.fixture()

@@ -123,17 +123,10 @@ def test_tile_data_parallel_encode_matches_unsharded():
         finally:
             eng.tp_size, eng.tp_rank, eng.all_gather = 1, 0, real_gather
 
-    try:
-        B.check(B.lib().vz_tune_set(1, 1))       # 128x128 kernel only
-        B.check(B.lib().vz_tune_set(4, 0))
-        B.check(B.lib().vz_tune_set(26, 0))      # whole-K tiles whatever the tile count of a rank's share
+    with B.tuned(gemm_choice=1, gemm256_streamk=0, splitk_mid=0):      # 128x128 kernel only, whole-K tiles whatever the tile count of a rank's share
         ref = model.encode_images(tiles, text, tile_sample=tile_sample)
         assert ref.shape == (T, cfg.qf_queries, cfg.hidden)
         assert torch.equal(tile_dp(), ref), "tile-data-parallel encode differs from the unsharded one"
-    finally:
-        B.check(B.lib().vz_tune_set(1, 0))
-        B.check(B.lib().vz_tune_set(4, 1))
-        B.check(B.lib().vz_tune_set(26, 1))
     ref = model.encode_images(tiles, text, tile_sample=tile_sample)
     check_close("tile-DP vs unsharded (production dispatch)", tile_dp(), ref.float(), 0.25, 2e-2)
     # the C-ABI all-gather at tp_size 1 is a device copy into chunk 0
@@ -142,7 +135,7 @@ def test_tile_data_parallel_encode_matches_unsharded():
 
 
 def test_rccl_call_sites_on_one_rank():
-    """The RCCL plumbing on ONE GPU: a tp_size == 1 engine gets a one-rank communicator and vz_tune_set(7, 1) routes its
+    """The RCCL plumbing on ONE GPU: a tp_size == 1 engine gets a one-rank communicator and knob 7 (force_comm) = 1 routes its
     collective call sites through RCCL - 2 bf16 all-reduces per layer in prefill and in every decode step (in place, on the
     engine's stream), the vocab-parallel fp32 all-gather + repack of the logits, and vz_tp_all_gather.  Over one rank
     every collective is the identity, so logits and generated ids must be bit-identical to the plain path."""
@@ -162,29 +155,23 @@ def test_rccl_call_sites_on_one_rank():
 
     ref_logits, ref_ids = run()
     eng.init_comm_single_rank()
-    try:
-        B.check(B.lib().vz_tune_set(7, 1))
+    with B.tuned(force_comm=1):
         logits, new_ids = run()
         # the decode steps ran as ONE captured graph with the RCCL all-reduces / all-gather inside it (not an eager fallback)
         assert eng.decode_mode() == (True, True)
         again = eng.decode_steps(6).clone()          # replay of the same graph object, collectives included
         gathered = eng.all_gather(x[0, :3])
-    finally:
-        B.check(B.lib().vz_tune_set(7, 0))
     assert torch.equal(logits, ref_logits)
     assert torch.equal(new_ids, ref_ids)
     assert again.shape == new_ids.shape
     # The captured TP decode graph holds the gathered-logits buffer: a forward with MORE logits rows between two generates
     # re-allocates it (ensure_gather), so the graph must be dropped and captured again, not replayed on the freed pointer.
-    try:
-        B.check(B.lib().vz_tune_set(7, 1))
+    with B.tuned(force_comm=1):
         _, ids_a = run()
         big = eng.embed_tokens(synth.synth_ids(100, cfg.vocab, image_pos=-1, seed=6)).unsqueeze(0)
         eng.prefill(big, [100], all_logits=True, last_logits=False)          # 100 rows of logits > anything gathered so far
         _, ids_b = run()
         assert eng.decode_mode() == (True, True)
-    finally:
-        B.check(B.lib().vz_tune_set(7, 0))
     assert torch.equal(ids_a, ref_ids) and torch.equal(ids_b, ref_ids)
     assert gathered.shape == (1, 3, cfg.hidden) and torch.equal(gathered[0], x[0, :3])
 
@@ -192,7 +179,7 @@ def test_rccl_call_sites_on_one_rank():
 @pytest.mark.parametrize("world,rank", [(8, 5), (4, 0), (2, 1)])
 def test_one_rank_of_a_tp_engine_runs_its_local_path(world, rank):
     """Shape rehearsal on one GPU: ONE rank of a tp_size = 2 / 4 / 8 engine with the full model loaded (its Zephyr shards, CLIP /
-    Q-Former replicated) runs image -> first token -> a few decode steps with the collectives skipped (vz_tune_set(7, 2)).
+    Q-Former replicated) runs image -> first token -> a few decode steps with the collectives skipped (knob 7 (force_comm) = 2).
     Logits are meaningless without the other ranks' partial sums; what is checked is that every local kernel accepts the
     shard shapes (1792 MLP columns and one KV head at tp 8, tile-DP deal of 5 tiles, vocab shard + repack) and stays finite."""
     from vz_hip import binding as B, synth
@@ -205,8 +192,7 @@ def test_one_rank_of_a_tp_engine_runs_its_local_path(world, rank):
     hf.mm_vision_tower = "openai/clip-vit-large-patch14-336"
     hf.mm_patch_merge_type = "flat"
     hf.mm_hidden_size = 5120
-    try:
-        B.check(B.lib().vz_tune_set(7, 2))
+    with B.tuned(force_comm=2):
         model = VisZephyrForCausalLM(hf, device="cuda:0", max_batch=2, max_ctx=512, max_tiles=5, max_text=64, tp_size=world, tp_rank=rank)
         model.engine.load_synthetic(0)                       # no init_comm: the collectives are skipped in this rehearsal
         model.get_vision_tower().is_loaded = True
@@ -222,5 +208,3 @@ def test_one_rank_of_a_tp_engine_runs_its_local_path(world, rank):
         ids2 = torch.stack([synth.synth_ids(12, cfg.vocab, image_pos=-1, seed=3 + b) for b in range(2)]).to(model.device)
         out2 = model.generate(input_ids=ids2, do_sample=False, max_new_tokens=4, eos_token_id=None, pad_token_id=2)
         assert out2.shape == (2, 4)
-    finally:
-        B.check(B.lib().vz_tune_set(7, 0))

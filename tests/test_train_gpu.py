@@ -117,7 +117,7 @@ def test_arena_is_sized_by_the_step_itself(env):
 
 
 def test_attention_backward_routes_size_their_own_scratch(env):
-    """vz_tune_set(32, 0) sends the Zephyr layers' attention backward through the materialising batched-GEMM route, (32, 1) back to the
+    """knob 32 (flash_bwd) = 0 sends the Zephyr layers' attention backward through the materialising batched-GEMM route, (32, 1) back to the
     tile-resident one.  The route depends on the knob alone and each carves its own scratch: both steps succeed, the materialising
     step's arena is at least the tile-resident step's need, and both losses are the fixture's."""
     from vz_hip import binding as B
@@ -126,16 +126,15 @@ def test_attention_backward_routes_size_their_own_scratch(env):
     ref_loss = float(env["gold"]["loss"])
     tr = Stage1Trainer(env["model"])
     try:
-        B.check(B.lib().vz_tune_set(32, 0))
-        tr.zero_grad()
-        loss_gemm = tr.forward_backward(ids, mask, lab, images)
-        arena_gemm, peak_gemm = tr.ws_info()
-        B.check(B.lib().vz_tune_set(32, 1))
-        tr.zero_grad()
-        loss_flash = tr.forward_backward(ids, mask, lab, images)
-        arena_flash, peak_flash = tr.ws_info()
+        with B.tuned(flash_bwd=0):
+            tr.zero_grad()
+            loss_gemm = tr.forward_backward(ids, mask, lab, images)
+            arena_gemm, peak_gemm = tr.ws_info()
+        with B.tuned(flash_bwd=1):
+            tr.zero_grad()
+            loss_flash = tr.forward_backward(ids, mask, lab, images)
+            arena_flash, peak_flash = tr.ws_info()
     finally:
-        B.check(B.lib().vz_tune_set(32, 1))
         tr.close()
     record("stage1 attention backward routes", loss_batched_gemm=loss_gemm, loss_tile_resident=loss_flash, arena_batched_gemm=arena_gemm,
            peak_tile_resident=peak_flash)
@@ -187,15 +186,12 @@ def test_micro_batches_accumulate_and_one_rank_allreduce(env):
     from vz_hip import binding as B
     # whole-K tiles for both runs: the tile GEMM's K slices follow the tile count (the CLIP tower of one sample takes them, the
     # full batch's does not), which is re-association beyond the micro-batching this test is about
-    B.check(B.lib().vz_tune_set(26, 0))
-    try:
+    with B.tuned(splitk_mid=0):
         tr.zero_grad()
         l_full = tr.forward_backward(ids, mask, lab, images)
         full = {k: v.clone() for k, v in tr.reference_grads().items()}
         tr.zero_grad()
         l_mb = tr.forward_backward(ids, mask, lab, images, micro_batch=1)
-    finally:
-        B.check(B.lib().vz_tune_set(26, 1))
     assert abs(l_mb - l_full) <= 2e-4 * abs(l_full)
     worst = 0.0
     for k, v in tr.reference_grads().items():
@@ -223,8 +219,7 @@ def test_data_parallel_mean_of_rank_gradients(env):
     lab = ids.clone()
     lab[ids == -200] = -100
     images = [synth.synth_tiles(2, seed=43), synth.synth_tiles(1, seed=44)]
-    B.check(B.lib().vz_tune_set(26, 0))           # whole-K tiles on both sides (see the micro-batch test)
-    try:
+    with B.tuned(splitk_mid=0):          # whole-K tiles on both sides (see the micro-batch test)
         per_rank = []
         for b in range(2):
             tr.zero_grad()
@@ -234,8 +229,6 @@ def test_data_parallel_mean_of_rank_gradients(env):
         tr.forward_backward(ids, mask, lab, images)
         both = {k: v.clone() for k, v in tr.reference_grads().items()}
         tr.zero_grad()
-    finally:
-        B.check(B.lib().vz_tune_set(26, 1))
     worst_avg, worst_sum = 0.0, 0.0
     for k in both:
         worst_avg = max(worst_avg, errs(0.5 * (per_rank[0][k] + per_rank[1][k]), both[k])[1])

@@ -166,13 +166,8 @@ def model():
 def pinned_routes():
     """whole tiles only and no row-count-dependent K slices: rows of different batches get the same bits (tests/test_sample_rows_gpu.py)"""
     from vz_hip import binding as B
-    B.check(B.lib().vz_tune_set(4, 0))
-    B.check(B.lib().vz_tune_set(26, 0))
-    try:
+    with B.tuned(gemm256_streamk=0, splitk_mid=0):
         yield
-    finally:
-        B.check(B.lib().vz_tune_set(4, 1))
-        B.check(B.lib().vz_tune_set(26, 1))
 
 
 def _prompt(n, seed):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Stage cycle counts of one wave of the prefill attention kernel (vz_tune_set(16, 1) -> vz_prof_attn_stamps): where the longest causal
+"""Stage cycle counts of one wave of the prefill attention kernel (knob 16 (attn_stamps) = 1 -> vz_prof_attn_stamps): where the longest causal
 workgroup's wave 0 spends its shader cycles per 64-key tile.  python tools/attn_stamps.py [S]"""
 import ctypes as C, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,11 +13,10 @@ q = torch.randn(1, S, Hq, D, device="cuda").bfloat16(); k = torch.randn(1, S, Hk
 for _ in range(3):
     B.attention(q, k, v, D ** -0.5, True, 0, 4096)
 torch.cuda.synchronize()
-B.check(B.lib().vz_tune_set(16, 1))
-B.attention(q, k, v, D ** -0.5, True, 0, 4096)
-st = (C.c_longlong * (16 + 8192))()
-B.check(B.lib().vz_prof_attn_stamps(st))
-B.check(B.lib().vz_tune_set(16, 0))
+with B.tuned(attn_stamps=1):
+    B.attention(q, k, v, D ** -0.5, True, 0, 4096)
+    st = (C.c_longlong * (16 + 8192))()
+    B.check(B.lib().vz_prof_attn_stamps(st))
 names = ["issue K/V global loads", "QK^T (2 halves: frag reads + 32 MFMA issue)", "softmax (incl. wait for the QK^T results)", "PV (tr-reads + 32 MFMA issue)",
          "wait loads + LDS store", "barrier", "-", "loop top"]
 n = max(1, st[8]); tot = sum(st[i] for i in range(8))

@@ -32,7 +32,7 @@ ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--launches", type=int, default=50)
-ap.add_argument("--flash-min-t", type=int, default=-1, help="vz_tune_set(36, .): rows per sample above which the append runs the flash kernel")
+ap.add_argument("--flash-min-t", type=int, default=-1, help="knob 36 (append_flash_min_t): rows per sample above which the append runs the flash kernel")
 ap.add_argument("--ops-only", action="store_true")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
@@ -44,7 +44,7 @@ if not torch.cuda.is_available():
     raise SystemExit("bench_append: needs the GPU (no timing is taken on a CPU)")
 B.load_library()
 if a.flash_min_t >= 0:
-    B.check(B.lib().vz_tune_set(36, a.flash_min_t))
+    B.tune("append_flash_min_t", a.flash_min_t)
 
 
 def timed(fn):

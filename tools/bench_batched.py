@@ -38,9 +38,8 @@ def build(max_batch):
 
 
 model = build(64)
-for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):       # experiments: "knob=value,..." for vz_tune_set
-    from vz_hip import binding as _B
-    _B.check(_B.lib().vz_tune_set(*(int(v) for v in kv.split("="))))
+from vz_hip import binding as _B  # noqa: E402
+_B.tune_from_args(os.environ.get("VZ_TUNE", ""))       # experiments: "knob=value,..." (names or numbers)
 ROWS = [int(v) for v in os.environ.get("VZ_ROWS", "16,64" if SAMPLE else "1,2,4,8,16,32,48,64").split(",")]
 n_new = 64
 

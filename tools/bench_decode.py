@@ -28,10 +28,7 @@ emb = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, [t
 ref_ids = None
 applied = {}
 for setting in (sys.argv[1:] or [""]):
-    for kv in filter(None, setting.split(",")):
-        k, v = (int(t) for t in kv.split("="))
-        B.check(B.lib().vz_tune_set(k, v))
-        applied[k] = v
+    applied.update(B.tune_from_args(setting))
 
     def one():
         tm = {}

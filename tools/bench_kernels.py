@@ -50,10 +50,9 @@ def bench_gemv():
         argl = [(1, B.ptr(x), K, B.ptr(w), K, B.ptr(out), n_out, 1, N, K, None, None, 0, act, int(out32), st) for w in ws]
         for rnd in range(3):
             for v in (1, 2, 3, 4, 5, 6):
-                B.check(B.lib().vz_tune_set(0, v))
-                us = timed(lambda i: fn(*argl[i % pool]), 6 * pool)
+                with B.tuned(gemv_variant=v):
+                    us = timed(lambda i: fn(*argl[i % pool]), 6 * pool)
                 rows.setdefault(v, []).append(us)
-        B.check(B.lib().vz_tune_set(0, 0))
         mb = N * K * 2 / 1e6
         res[name] = {v: (min(t), mb / min(t) * 1e6 / 1e9) for v, t in rows.items()}
         print(f"gemv {name:16s} {mb:7.1f} MB: " + "  ".join(f"v{v}: {min(t):6.1f}us {mb / min(t):5.2f}TB/s" for v, t in rows.items()), flush=True)
@@ -84,9 +83,8 @@ def bench_gemv_fp8():
         rows = {}
         for rnd in range(3):
             for v in (0, 1):
-                B.check(B.lib().vz_tune_set(0, v))
-                rows.setdefault(v, []).append(timed(lambda i: fn(*argl[i % pool]), 6 * pool))
-        B.check(B.lib().vz_tune_set(0, 0))
+                with B.tuned(gemv_variant=v):
+                    rows.setdefault(v, []).append(timed(lambda i: fn(*argl[i % pool]), 6 * pool))
         mb = N * K / 1e6
         print(f"gemv fp8 {name:16s} {mb:7.1f} MB: " + "  ".join(f"{'R2U8' if v == 0 else 'R4U4'}: {min(t):6.1f}us {mb / min(t):5.2f}TB/s" for v, t in rows.items()), flush=True)
         del ws
@@ -140,9 +138,8 @@ def bench_skinny():
             x = torch.randn(M, K, device=dev).bfloat16()
             us = {}
             for mode in (1, 0):
-                B.check(B.lib().vz_tune_set(9, mode))
-                us[mode] = min(timed(lambda i: B.linear(x, ws[i % pool], act=act), 4 * pool) for _ in range(3))
-            B.check(B.lib().vz_tune_set(9, 1))
+                with B.tuned(skinny_mode=mode):
+                    us[mode] = min(timed(lambda i: B.linear(x, ws[i % pool], act=act), 4 * pool) for _ in range(3))
             row.append(f"M{M}: {us[1]:6.1f} (was {us[0]:6.1f}) us")
             if K == 4096 and name != "o":      # the decode step fuses the RMSNorm into these
                 nw = torch.ones(K, device=dev)
@@ -181,21 +178,18 @@ def bench_gemm():
         ws = [torch.randn(N, K, device=dev).bfloat16() * 0.02 for _ in range(3)]
         row = []
         if M <= 512:
-            B.check(B.lib().vz_tune_set(3, 1))
-            us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act, impl=0), 12) for _ in range(3))
-            B.check(B.lib().vz_tune_set(3, 0))
+            with B.tuned(splitk_mode=1):
+                us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act, impl=0), 12) for _ in range(3))
             row.append(f"128 no-splitK: {us:8.1f} us")
         for impl, sk in ((0, 0), (2, 0), (2, 2)):
-            B.check(B.lib().vz_tune_set(4, sk))
-            us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act, impl=impl), 12) for _ in range(3))
+            with B.tuned(gemm256_streamk=sk):
+                us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act, impl=impl), 12) for _ in range(3))
             tf = 2.0 * M * N * K / us / 1e6
             row.append(f"{'128' if impl == 0 else ('256sk' if sk else '256')}: {us:8.1f} us {tf:7.1f} TF ({tf / 2500 * 100:4.1f}%)")
-        B.check(B.lib().vz_tune_set(4, 1))
         us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act), 12) for _ in range(3))
         row.append(f"dispatch: {us:8.1f} us {2.0 * M * N * K / us / 1e6:7.1f} TF")
-        B.check(B.lib().vz_tune_set(11, 1))          # A/B in one process: workgroups wait for their stores before ending
-        us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act), 12) for _ in range(3))
-        B.check(B.lib().vz_tune_set(11, 0))
+        with B.tuned(gemm256_drain=1):          # A/B in one process: workgroups wait for their stores before ending
+            us = min(timed(lambda i: B.linear(x, ws[i % 3], act=act), 12) for _ in range(3))
         row.append(f"drain-wait: {us:8.1f} us")
         print(f"gemm {name:12s} M{M} N{N} K{K}: " + "   ".join(row), flush=True)
 
@@ -210,11 +204,10 @@ def bench_gemm_square():
         ws = [(torch.rand(N, K, device=dev) * 2 - 1).bfloat16() for _ in range(2)]
         row = []
         for impl, ring in ((0, 0), (2, 0), (2, 1)):      # 256 kernel without / with the stream-K tail
-            B.check(B.lib().vz_tune_set(4, ring))
-            us = min(timed(lambda i: B.linear(x, ws[i % 2], act=act, impl=impl), 10) for _ in range(3))
+            with B.tuned(gemm256_streamk=ring):
+                us = min(timed(lambda i: B.linear(x, ws[i % 2], act=act, impl=impl), 10) for _ in range(3))
             tf = 2.0 * M * N * K / us / 1e6
             row.append(f"{'128' if impl == 0 else ('256sk' if ring else '256')}: {us:8.1f} us {tf:7.1f} TF")
-        B.check(B.lib().vz_tune_set(4, 1))
         us = min(timed(lambda i: B.linear(x, ws[i % 2], act=act), 12) for _ in range(3))
         row.append(f"dispatch: {us:8.1f} us {2.0 * M * N * K / us / 1e6:7.1f} TF")
         print(f"gemm {name:12s} M{M} N{N} K{K}: " + "   ".join(row), flush=True)
@@ -230,9 +223,8 @@ def bench_attn():
     res = {1: [], 2: [], 3: []}
     for rnd in range(3):
         for ver in (1, 2, 3):
-            B.check(B.lib().vz_tune_set(2, ver))
-            res[ver].append(timed(lambda i: B.attention(q, k, v, D ** -0.5, True, 0, 4096), 10))
-    B.check(B.lib().vz_tune_set(2, 3))
+            with B.tuned(attn_version=ver):
+                res[ver].append(timed(lambda i: B.attention(q, k, v, D ** -0.5, True, 0, 4096), 10))
     print(f"attn prefill causal S{S}: " + "  ".join(f"v{ver}: {min(t):7.1f} us {fl / min(t) / 1e6:6.1f} TF" for ver, t in res.items()), flush=True)
     kc = torch.randn(1, Hkv, S, D, device=dev).bfloat16()       # cache layout: keys of one head contiguous
     vc = torch.randn(1, Hkv, S, D, device=dev).bfloat16()
@@ -243,10 +235,9 @@ def bench_attn():
     res = {1: [], 2: [], 3: []}
     for rnd in range(3):
         for ver in (1, 2, 3):
-            B.check(B.lib().vz_tune_set(2, ver))
-            res[ver].append(timed(lambda i: B.attention(qkv[:, :, :1024].view(T, 577, 16, 64), qkv[:, :, 1024:2048].view(T, 577, 16, 64),
-                                                        qkv[:, :, 2048:].view(T, 577, 16, 64), 0.125), 10))
-    B.check(B.lib().vz_tune_set(2, 3))
+            with B.tuned(attn_version=ver):
+                res[ver].append(timed(lambda i: B.attention(qkv[:, :, :1024].view(T, 577, 16, 64), qkv[:, :, 1024:2048].view(T, 577, 16, 64),
+                                                            qkv[:, :, 2048:].view(T, 577, 16, 64), 0.125), 10))
     cf = 4.0 * 577 * 577 * 64 * 16 * T
     print(f"attn clip T{T}: " + "  ".join(f"v{ver}: {min(t):7.1f} us {cf / min(t) / 1e6:6.1f} TF" for ver, t in res.items()), flush=True)
     # decode attention at ctx 2048: fused vs two-kernel
@@ -268,8 +259,7 @@ def bench_attn():
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.manual_seed(0)
-    for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):       # experiments: "knob=value,..." for vz_tune_set
-        B.check(B.lib().vz_tune_set(*(int(v) for v in kv.split("="))))
+    B.tune_from_args(os.environ.get("VZ_TUNE", ""))       # experiments: "knob=value,..." (names or numbers)
     if what in ("gemv", "all"):
         bench_gemv()
     if what in ("gemm", "all"):

@@ -43,7 +43,7 @@ DS = [int(v) for v in a.D.split(",")]
 N = a.steps
 MAX_CTX = 4096
 assert a.S + 2 * N * (max(DS) + 1) + max(DS) + 1 <= MAX_CTX, "two calls of N * (D + 1) ids must fit the cache"
-B.check(B.lib().vz_tune_set(10, 32))
+B.tune("attn_nsplit", 32)
 
 
 def make(fp8):

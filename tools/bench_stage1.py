@@ -24,9 +24,7 @@ from vz_hip import synth  # noqa: E402
 from vis_zephyr.model import VisZephyrConfig, VisZephyrForCausalLM  # noqa: E402
 
 from vz_hip import binding as _B  # noqa: E402
-for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):       # experiments: "knob=value,..." for vz_tune_set (32=0: materialising attention backward)
-    _k, _v = (int(t) for t in kv.split("="))
-    _B.check(_B.lib().vz_tune_set(_k, _v))
+_B.tune_from_args(os.environ.get("VZ_TUNE", ""))       # experiments: "knob=value,..." (flash_bwd=0: materialising attention backward)
 nums = [int(a) for a in sys.argv[1:] if a.isdigit()]
 Bn = nums[0] if nums else 64
 layers = nums[1] if len(nums) > 1 else 32

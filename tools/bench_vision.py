@@ -42,15 +42,13 @@ def main():
     for rnd in range(3):
         row = []
         for v in (0, 1):
-            B.check(B.lib().vz_tune_set(26, v))
-            row.append(f"clip {timed(lambda: eng.clip_fused_features(tiles)):6.3f} ms ({'K slices for lone-workgroup grids' if v else 'whole-K tiles only'})")
-        B.check(B.lib().vz_tune_set(26, 1))
-        for name, knobs in (("qformer base (no key split, 4 slices, K|V per block)", ((23, 1), (24, 4), (25, 0))), ("key split", ((23, 0), (24, 4), (25, 0))),
-                            ("+ 8 slices", ((23, 0), (24, 8), (25, 0))), ("+ K|V of all blocks in one GEMM", ((23, 0), (24, 8), (25, 1)))):
-            for k, v in knobs:
-                B.check(B.lib().vz_tune_set(k, v))
-            row.append(f"{name} {timed(lambda: eng.qformer(feats, None, ts)):6.3f} ms")
-        B.check(B.lib().vz_tune_set(23, 0)); B.check(B.lib().vz_tune_set(24, 8)); B.check(B.lib().vz_tune_set(25, 1))
+            with B.tuned(splitk_mid=v):
+                row.append(f"clip {timed(lambda: eng.clip_fused_features(tiles)):6.3f} ms ({'K slices for lone-workgroup grids' if v else 'whole-K tiles only'})")
+        for name, knobs in (("qformer base (no key split, 4 slices, K|V per block)", dict(attn_split=1, splitk_cap=4, qf_kv_all=0)),
+                            ("key split", dict(attn_split=0, splitk_cap=4, qf_kv_all=0)), ("+ 8 slices", dict(attn_split=0, splitk_cap=8, qf_kv_all=0)),
+                            ("+ K|V of all blocks in one GEMM", dict(attn_split=0, splitk_cap=8, qf_kv_all=1))):
+            with B.tuned(**knobs):
+                row.append(f"{name} {timed(lambda: eng.qformer(feats, None, ts)):6.3f} ms")
         print("   ".join(row), flush=True)
 
 

@@ -72,8 +72,7 @@ def run_case(B, name, t):
     res = t["residual"]
     if c.get("inplace"):
         res = res.clone()
-    try:
-        B.check(B.lib().vz_tune_set(9, 0))
+    with B.tuned(skinny_mode=0):
         if c.get("fp8"):
             out = B.linear_fp8(t["x"], t["w8"], t["scale"], bias=t["bias"], residual=res, act=act, out_fp32=fp32,
                                norm_w=t["norm_w"], norm_eps=1e-5)
@@ -87,8 +86,6 @@ def run_case(B, name, t):
             out = res
         else:
             out = B.linear(t["x"], t["w"], bias=t["bias"], residual=res, act=act, out_fp32=fp32, impl=1)
-    finally:
-        B.check(B.lib().vz_tune_set(9, 1))
     torch.cuda.synchronize()
     return out
 

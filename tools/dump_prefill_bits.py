@@ -44,19 +44,19 @@ ENGINES = {
 
 # past: positions each cache row holds before the call (a plain prefill of them is the case's setup), T: rows per sample, new: valid
 # rows per sample (default T).  call: "prefill" | "rows" (prefill_rows into row0 = 1 after `first` filled row 0) | "append".
-# knobs: (vz_tune_set id, value, value it is restored to).  fp8: set_prefill_fp8(True) and knob 22 at 0 around the whole case.
+# knobs: {knob name: value} around the whole case.  fp8: set_prefill_fp8(True) and knob 22 (fp8_prefill_min_rows) at 0 around the whole case.
 CASES = {
     "plain": dict(call="prefill", T=40),
     "plain_ragged": dict(call="prefill", T=96, new=[96, 37], pos_shift=[0, 3]),
     "rows_into_row1": dict(call="rows", T=24, first=40),
-    "plain_ragged_rotated_copy": dict(call="prefill", T=96, new=[96, 37], pos_shift=[0, 3], knobs=[(33, 0, 1)]),
+    "plain_ragged_rotated_copy": dict(call="prefill", T=96, new=[96, 37], pos_shift=[0, 3], knobs=dict(rope_in_attn=0)),
     "fp8_prefill": dict(call="prefill", engine="fp8", T=150, fp8=True),
     "fp8_engine_append": dict(call="append", engine="fp8", past=[37], T=20, fp8=True),
     "append_keysplit": dict(call="append", past=[37], T=20),
     "append_keysplit_ragged_padded": dict(call="append", past=[37, 20], T=20, new=[20, 9]),
     "append_flash_one_run": dict(call="append", past=[37, 37], T=260),
     "append_flash_two_runs": dict(call="append", past=[37, 20], T=260),
-    "append_flash_small_t": dict(call="append", past=[37], T=20, knobs=[(36, 8, 256)]),
+    "append_flash_small_t": dict(call="append", past=[37], T=20, knobs=dict(append_flash_min_t=8)),
 }
 
 
@@ -138,16 +138,13 @@ def _the_call(env, name):
 def _armed(env, name, body):
     from vz_hip import binding as B
     c, eng = CASES[name], env["eng"]
-    knobs = list(c.get("knobs", ())) + ([(22, 0, 768)] if c.get("fp8") else [])
+    knobs = dict(c.get("knobs", {}), **(dict(fp8_prefill_min_rows=0) if c.get("fp8") else {}))
     try:
         if c.get("fp8"):
             eng.set_prefill_fp8(True)
-        for k, v, _ in knobs:
-            B.check(B.lib().vz_tune_set(k, v))
-        return body()
+        with B.tuned(**knobs):
+            return body()
     finally:
-        for k, _, back in knobs:
-            B.check(B.lib().vz_tune_set(k, back))
         if c.get("fp8"):
             eng.set_prefill_fp8(False)
 

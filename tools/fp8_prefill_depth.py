@@ -21,7 +21,7 @@ ids = synth.synth_ids(S, cfg.vocab, image_pos=-1, seed=23).to("cuda:0")
 emb = eng.embed_tokens(ids).unsqueeze(0)
 a, _ = eng.prefill(emb, [S], all_logits=True, last_logits=False)
 eng.set_prefill_fp8(True)
-B.check(B.lib().vz_tune_set(22, 0))
+B.tune("fp8_prefill_min_rows", 0)
 b, _ = eng.prefill(emb, [S], all_logits=True, last_logits=False)
 a, b = a[0].float(), b[0].float()
 rel = float((a - b).norm() / a.norm())

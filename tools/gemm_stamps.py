@@ -21,10 +21,8 @@ x = torch.randn(M, K, device="cuda").bfloat16()
 w = (torch.randn(N, K, device="cuda") * 0.02).bfloat16()
 if os.environ.get("VZ_ZERO", "0") == "1":      # all-zero operands: the clock the chip holds when the data toggles nothing (guide: DVFS give-back item 1)
     x.zero_(); w.zero_()
-B.check(B.lib().vz_tune_set(4, sk))
-for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):       # experiments: "knob=value,..." (34=0: direct fragment-shaped epilogue stores)
-    _k, _v = (int(t) for t in kv.split("="))
-    B.check(B.lib().vz_tune_set(_k, _v))
+B.tune("gemm256_streamk", sk)
+B.tune_from_args(os.environ.get("VZ_TUNE", ""))       # experiments: "knob=value,..." (34=0: direct fragment-shaped epilogue stores)
 ACT = int(os.environ.get("VZ_ACT", "0"))
 import time
 t_end = time.time() + 1.0
@@ -32,14 +30,13 @@ while time.time() < t_end:                 # let DVFS settle under this kernel's
     for _ in range(50):
         B.linear(x, w, impl=2, act=ACT)
     torch.cuda.synchronize()
-B.check(B.lib().vz_tune_set(6, 1))
-for _ in range(3):
-    B.linear(x, w, impl=2, act=ACT)
-torch.cuda.synchronize()
-buf = (C.c_longlong * (4096 * 16))()
-n = C.c_int(0)
-B.check(B.lib().vz_prof_gemm_stamps(buf, 4096, C.byref(n)))
-B.check(B.lib().vz_tune_set(6, 0))
+with B.tuned(gemm256_stamps=1):
+    for _ in range(3):
+        B.linear(x, w, impl=2, act=ACT)
+    torch.cuda.synchronize()
+    buf = (C.c_longlong * (4096 * 16))()
+    n = C.c_int(0)
+    B.check(B.lib().vz_prof_gemm_stamps(buf, 4096, C.byref(n)))
 st = np.ctypeslib.as_array(buf).reshape(4096, 16)[: n.value].astype(np.int64)
 t0 = st[:, 0].min()
 us = lambda a: (a - t0) / 100.0

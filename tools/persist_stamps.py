@@ -16,9 +16,8 @@ from bench import build_model  # noqa: E402
 from vz_hip import binding as B, synth  # noqa: E402
 
 layers = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-B.check(B.load_library().vz_tune_set(28, 1))            # opt in
-for kv in filter(None, os.environ.get("VZ_TUNE", "").split(",")):
-    B.check(B.load_library().vz_tune_set(*(int(v) for v in kv.split("="))))
+B.tune("persist_decode", 1)            # opt in
+B.tune_from_args(os.environ.get("VZ_TUNE", ""))
 S = 2048
 model = build_model(layers, "cuda:0", max_ctx=S + 144)
 eng = model.engine

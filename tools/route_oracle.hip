@@ -25,7 +25,7 @@ static int old_decode_splitk(int N, int K, int act) {
     if (N & 7) return 0;
     const int tiles_n = (N + 127) / 128;
     if (act == VZ_ACT_SWIGLU) return tiles_n < 384 ? 2 : 0;
-    if (K < 8192) return g_decode_sk_short;
+    if (K < 8192) return vz_knob(VZ_KNOB_DECODE_SK_SHORT);
     int sk = (512 + tiles_n - 1) / tiles_n;
     if (sk > 16) sk = 16;
     return sk < 1 ? 1 : sk;
@@ -38,16 +38,16 @@ static bool old_persist_ok(const LinearArgs& a) {
 }
 static Old old_skinny(const LinearArgs& a, int pre, int klass) {
     if (!vz_skinny_ok(a)) return REFUSED;
-    const int w = a.W8 ? LIN_W_E4M3 : (a.N & 15) == 0 && g_skinny_mode != 5 && a.Wt ? LIN_W_BF16_TILED : LIN_W_BF16;
+    const int w = a.W8 ? LIN_W_E4M3 : (a.N & 15) == 0 && vz_knob(VZ_KNOB_SKINNY_MODE) != 5 && a.Wt ? LIN_W_BF16_TILED : LIN_W_BF16;
     if (a.M > 16) return Old{LIN_SKINNY_WIDE, w, pre, a.splitk_hint, klass};
-    if (g_skinny_mode != 2 && old_persist_ok(a) && (a.M >= 3 || g_skinny_mode == 3)) return Old{LIN_SKINNY_PERSIST, w, pre, a.splitk_hint, klass};
+    if (vz_knob(VZ_KNOB_SKINNY_MODE) != 2 && old_persist_ok(a) && (a.M >= 3 || vz_knob(VZ_KNOB_SKINNY_MODE) == 3)) return Old{LIN_SKINNY_PERSIST, w, pre, a.splitk_hint, klass};
     return Old{LIN_SKINNY, w, pre, a.splitk_hint, klass};
 }
 static Old old_tile(LinRoute r, const LinearArgs& a, int pre, int splitk, int klass) {
     return a.norm_w ? REFUSED : Old{r, LIN_W_BF16, pre, splitk, klass};       // "fused RMSNorm prologue exists on the GEMV path only"
 }
 static Old old_launch_linear(const LinearArgs& a, int pre, int klass) {
-    if (g_skinny_mode && vz_skinny_ok(a) && !(a.M == 2 && g_skinny_mode != 7 && vz_gemv_ok(a))) return old_skinny(a, pre, klass);
+    if (vz_knob(VZ_KNOB_SKINNY_MODE) && vz_skinny_ok(a) && !(a.M == 2 && vz_knob(VZ_KNOB_SKINNY_MODE) != 7 && vz_gemv_ok(a))) return old_skinny(a, pre, klass);
     if (vz_gemv_ok(a)) return Old{LIN_GEMV, a.W8 ? LIN_W_E4M3 : LIN_W_BF16, pre, a.splitk_hint, klass};
     if (a.W8) return REFUSED;
     return old_tile(vz_gemm_use256(a) ? LIN_TILE256 : LIN_TILE128, a, pre, a.splitk_hint, klass);
@@ -70,23 +70,23 @@ static Old old_engine_linear(int klass_hint, LinearArgs a, Copies W, int hidden)
         a.W8 = (const unsigned char*)some; a.wscale = some;
         LinearArgs t = a;
         if (M > 16) t.norm_w = nullptr;
-        if (!vz_gemv_ok(t) && !(g_skinny_mode && vz_skinny_ok(t))) { a.W8 = nullptr; a.wscale = nullptr; }
+        if (!vz_gemv_ok(t) && !(vz_knob(VZ_KNOB_SKINNY_MODE) && vz_skinny_ok(t))) { a.W8 = nullptr; a.wscale = nullptr; }
     }
-    if (klass_hint == 1 && M >= 17 && M <= 64 && a.Wt && (!fp8 || M >= std::max(g_decode_tile_rows, 33))) {
+    if (klass_hint == 1 && M >= 17 && M <= 64 && a.Wt && (!fp8 || M >= std::max(vz_knob(VZ_KNOB_DECODE_TILE_ROWS), 33))) {
         LinearArgs t = a;
         t.W8 = nullptr; t.wscale = nullptr;
         if (norm) { t.lda = K; t.norm_w = nullptr; }
         if (vz_wide_ok(t) && vz_wide_splits(t) == 1) return Old{LIN_WIDE_BF16, LIN_W_BF16_TILED, norm, a.splitk_hint, K_GEMV};
     }
-    if (klass_hint == 1 && M >= (fp8 ? std::max(g_decode_tile_rows, 33) : g_decode_tile_rows) && M <= 64 && g_skinny_mode && (K & 63) == 0)
+    if (klass_hint == 1 && M >= (fp8 ? std::max(vz_knob(VZ_KNOB_DECODE_TILE_ROWS), 33) : vz_knob(VZ_KNOB_DECODE_TILE_ROWS)) && M <= 64 && vz_knob(VZ_KNOB_SKINNY_MODE) && (K & 63) == 0)
         return Old{LIN_TILE128, LIN_W_BF16, norm, old_decode_splitk(N, K, a.act), K_GEMV};
-    if (norm && M > 4 && M <= 64 && K == hidden && g_skinny_mode && !(vz_skinny_ok(a) && vz_skinny_fused_norm_ok(a))) {
+    if (norm && M > 4 && M <= 64 && K == hidden && vz_knob(VZ_KNOB_SKINNY_MODE) && !(vz_skinny_ok(a) && vz_skinny_fused_norm_ok(a))) {
         LinearArgs t = a;
         t.lda = K; t.norm_w = nullptr;
         if (vz_skinny_ok(t)) return old_skinny(t, 1, K_GEMV);
     }
     if (norm) return old_launch_linear(a, 0, K_GEMV);
-    return old_launch_linear(a, 0, vz_gemv_ok(a) || (g_skinny_mode && vz_skinny_ok(a)) ? K_GEMV : K_GEMM);
+    return old_launch_linear(a, 0, vz_gemv_ok(a) || (vz_knob(VZ_KNOB_SKINNY_MODE) && vz_skinny_ok(a)) ? K_GEMV : K_GEMM);
 }
 // the op-level entry points (entry = VZ_LINEAR_*); `a` carries what the caller passed
 static Old old_op(int entry, LinearArgs a) {
@@ -94,12 +94,12 @@ static Old old_op(int entry, LinearArgs a) {
     switch (entry) {
     case VZ_LINEAR_OP: return (a.W8 && !a.wscale) ? REFUSED : old_launch_linear(a, 0, 0);
     case VZ_LINEAR_RMSNORM:
-        if (!(a.norm_w && M >= 1 && M <= 16) || !((g_skinny_mode && vz_skinny_ok(a)) || vz_gemv_ok(a))) return REFUSED;
+        if (!(a.norm_w && M >= 1 && M <= 16) || !((vz_knob(VZ_KNOB_SKINNY_MODE) && vz_skinny_ok(a)) || vz_gemv_ok(a))) return REFUSED;
         return old_launch_linear(a, 0, 0);
     case VZ_LINEAR_TILED:
         if (!(a.Wt && a.ldw == K && (N & 15) == 0)) return REFUSED;
         if (M >= 17 && vz_wide_ok(a)) return Old{LIN_WIDE_BF16, LIN_W_BF16_TILED, 0, 0, 0};
-        return g_skinny_mode ? old_skinny(a, 0, 0) : REFUSED;
+        return vz_knob(VZ_KNOB_SKINNY_MODE) ? old_skinny(a, 0, 0) : REFUSED;
     case VZ_LINEAR_TILED_FP8:
         if (!(a.W8t && a.wscale && (N & 127) == 0) || !vz_wide_ok(a)) return REFUSED;
         return Old{LIN_WIDE_E4M3, LIN_W_E4M3_TILED, 0, 0, 0};
@@ -134,10 +134,14 @@ static Old old_route(int entry, unsigned flags, int M, int N, int K, int lda, in
     return old_op(entry, a);
 }
 
+static bool set_knobs(int k9, int k14, int k19) {       // a refused value is reported by the caller's exit status
+    return vz_tune_set(VZ_KNOB_SKINNY_MODE, k9) == VZ_OK && vz_tune_set(VZ_KNOB_DECODE_TILE_ROWS, k14) == VZ_OK && vz_tune_set(VZ_KNOB_WIDE_MODE, k19) == VZ_OK;
+}
+
 static int table() {
     int k9, k14, k19, entry, flags, M, N, K, lda, ldw, act, f32;
     while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d", &k9, &k14, &k19, &entry, &flags, &M, &N, &K, &lda, &ldw, &act, &f32) == 12) {
-        g_skinny_mode = k9; g_decode_tile_rows = k14; g_wide_mode = k19;
+        if (!set_knobs(k9, k14, k19)) return 1;
         printf("%s\n", vz_route_name((LinRoute)old_route(entry, flags, M, N, K, lda, ldw, act, f32, K, 0).route));
     }
     return 0;
@@ -150,7 +154,7 @@ static int grid() {
     const int hidden = 4096;
     long n_engine = 0, n_op = 0, bad = 0;
     for (int k9 = 0; k9 < 8; ++k9) for (int k14 : {29, 17, 65, 40, 8, 1}) for (int k19 : {1, 0}) {
-        g_skinny_mode = k9; g_decode_tile_rows = k14; g_wide_mode = k19;
+        if (!set_knobs(k9, k14, k19)) return 1;
         for (int N : Ns) for (int K : Ks) for (int act : {0, 1, 3}) for (int M = 1; M <= 700; M += (M < 70 ? 1 : 61)) for (int norm : {0, 1}) {
             if (act == VZ_ACT_SWIGLU && (N & 31)) continue;
             const unsigned base = (norm ? VZ_ROUTE_NORM : VZ_ROUTE_RESIDUAL) | (act != VZ_ACT_SWIGLU && N % 3 == 0 ? VZ_ROUTE_BIAS : 0);

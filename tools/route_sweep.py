@@ -39,7 +39,7 @@ F_WT, F_W8, F_W8T, F_NORM, F_BIAS, F_RES, F_DECODE = 1, 2, 4, 8, 16, 32, 64
 E_ENGINE, E_LINEAR, E_RMSNORM, E_TILED, E_TILED_FP8, E_IMPL0 = 0, 1, 2, 3, 4, 8
 
 ROWS = (1, 2, 3, 4, 5, 8, 12, 16, 17, 24, 28, 29, 32, 33, 48, 64)
-KNOB_DEFAULTS = {9: 1, 14: 29, 19: 1}
+ROUTE_KNOBS = (9, 14, 19)      # skinny_mode, decode_tile_rows, wide_mode: what the planner reads; every case sets all three
 KNOB_SETS = [{}] + [{9: v} for v in (0, 2, 3, 5, 7)] + [{19: 0}] + [{14: v} for v in (8, 17, 65)]
 
 # kernel name -> route name of csrc/linear_route.h (splitk_finalize_kernel belongs to the TILE128 launch before it)
@@ -74,6 +74,7 @@ def run(log_path, quick, dry=False):
     B.load_library()
     dev = "cuda:0"
     cases = []
+    base = {k: B.tune_get(k) for k in ROUTE_KNOBS}          # the values the sweep starts from: a case's knobs are these but for what it names
     if not dry:
         mark_x = torch.ones(1, 64, dtype=torch.bfloat16, device=dev)
         mark_w = torch.ones(64, dtype=torch.float32, device=dev)
@@ -82,10 +83,10 @@ def run(log_path, quick, dry=False):
         return hashlib.sha256(t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()
 
     def begin(label, knobs, linears):
-        for k, v in {**KNOB_DEFAULTS, **knobs}.items():
-            B.check(B.lib().vz_tune_set(k, v))
-        case = {"id": len(cases), "label": label, "knobs": {str(k): v for k, v in {**KNOB_DEFAULTS, **knobs}.items()}, "linears": linears,
-                "digests": {}}
+        for k, v in {**base, **knobs}.items():
+            B.tune(k, v)
+        case = {"id": len(cases), "label": label, "knobs": {str(k): v for k, v in {**base, **knobs}.items()}, "named": sorted(knobs),
+                "linears": linears, "digests": {}}
         cases.append(case)
         if not dry:
             B.rmsnorm(mark_x, mark_w, 1e-5)          # the marker launch
@@ -277,7 +278,7 @@ def summarise(trace_csv, log_json):
     for case, recs in zip(cases, per_case):
         h = hashlib.sha256("\n".join(" ".join(r) for r in recs).encode()).hexdigest()
         total.update(h.encode())
-        knobs = " ".join(f"k{k}={v}" for k, v in sorted(case["knobs"].items(), key=lambda kv: int(kv[0])) if KNOB_DEFAULTS[int(k)] != v)
+        knobs = " ".join(f"k{k}={case['knobs'][str(k)]}" for k in case["named"])
         print(f"== case {case['id']}: {case['label']} {knobs}".rstrip())
         print(f"   launches {len(recs)} sha256 {h}")
         prev, count = None, 0

@@ -664,7 +664,6 @@ __global__ __launch_bounds__(HD / 4) void flash_split_combine(FlashParams p, int
     *(uint2*)(p.o + (size_t)b * p.o_bs + (size_t)q * p.o_ss + (size_t)h * p.o_hs + d) = pk;
 }
 
-static int g_attn_version = 3;     // 1 = v1 kernel for every head_dim (tests / A-B), 2 = v2 (head_dim 64 / 128) with the classic online-softmax step, 3 = v2 with the deferred-maximum step (production)
 template <int HD>
 int launch_flash2(const FlashParams& p, hipStream_t s) {
     constexpr int LDS = 2 * 64 * (HD * 2 + HD * 2);
@@ -675,7 +674,7 @@ int launch_flash2(const FlashParams& p, hipStream_t s) {
         VZ_LAUNCH_CHECK();
         return VZ_OK;
     }
-    if (g_attn_version == 2) hipLaunchKernelGGL((flash_attn2_kernel<HD, false, false>), grid, dim3(256), LDS, s, p);
+    if (vz_knob(VZ_KNOB_ATTN_VERSION) == 2) hipLaunchKernelGGL((flash_attn2_kernel<HD, false, false>), grid, dim3(256), LDS, s, p);
     else hipLaunchKernelGGL((flash_attn2_kernel<HD, false, true>), grid, dim3(256), LDS, s, p);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -690,8 +689,6 @@ int launch_flash(const FlashParams& p, hipStream_t s) {
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }
-
-int g_attn_split = 0;              // vz_tune_set(23, v): 0 = automatic key split of few-row head_dim-512 launches, 1 = never, n >= 2 = n splits
 
 // Few query rows against many keys (Q-Former cross-attention, 32 x 576 per tile and head): B * Hq workgroups alone leave most
 // of the chip idle and each one walks its 18 key tiles serially; with a workspace the key tiles are spread over ~one workgroup per CU.
@@ -818,24 +815,21 @@ static int set_flash_attr() {
 }
 
 static long long* g_attn_stamps = nullptr;
-int g_attn_stamp_on = 0;           // vz_tune_set(16, 1)
 int vz_attn_read_stamps(long long* host16) {          // 16 stage words + 2048 x 4 per-workgroup schedule words
     VZ_CHECK_ARG(host16 && g_attn_stamps, "attn stamps: not initialised");
     VZ_CHECK_HIP(hipDeviceSynchronize());
     VZ_CHECK_HIP(hipMemcpy(host16, g_attn_stamps, (16 + 2048 * 4) * sizeof(long long), hipMemcpyDeviceToHost));
     return VZ_OK;
 }
-void vz_set_attn_version(int v) { g_attn_version = v; }
-int vz_attn_version() { return g_attn_version; }
-void vz_set_attn_split(int v) { g_attn_split = v; }
 
 // Key splits of an un-masked head_dim-512 launch with Sq query rows over Sk keys under knob 23 (1 = none).  A function of Sk alone
 // (three 32-key tiles per workgroup): a query row's result never depends on how many tiles or samples share the launch
 // (tests/test_stages_gpu.py::test_continuous_batching_matches_static_batches)
 static int split512(int Sq, int Sk) {
-    if (g_attn_split == 1 || Sq > 64) return 1;
+    const int split = vz_knob(VZ_KNOB_ATTN_SPLIT);
+    if (split == 1 || Sq > 64) return 1;
     const int ntiles = (Sk + 31) / 32;
-    const int nsplit = g_attn_split >= 2 ? std::min(g_attn_split, ntiles) : (ntiles >= 6 ? (ntiles + 2) / 3 : 1);
+    const int nsplit = split >= 2 ? std::min(split, ntiles) : (ntiles >= 6 ? (ntiles + 2) / 3 : 1);
     return nsplit <= 1024 ? nsplit : 1;
 }
 // fp32 scratch (AttnArgs::part) such a launch on (B, Hq, Sq, Sk) wants for its partial softmaxes; 0 = it would not split
@@ -877,10 +871,10 @@ int vz_launch_attention(const AttnArgs& a, hipStream_t s) {
     p.q_bs = a.q_bs; p.q_ss = a.q_ss; p.q_hs = a.q_hs; p.k_bs = a.k_bs; p.k_ss = a.k_ss; p.k_hs = a.k_hs;
     p.v_bs = a.v_bs; p.v_ss = a.v_ss; p.v_hs = a.v_hs; p.o_bs = a.o_bs; p.o_ss = a.o_ss; p.o_hs = a.o_hs;
     p.scale = a.scale; p.causal = a.causal; p.q_pos0 = a.q_pos0; p.window = a.window; p.kv_len = a.kv_len;
-    p.stamps = g_attn_stamp_on ? g_attn_stamps : nullptr;
+    p.stamps = vz_knob(VZ_KNOB_ATTN_STAMPS) ? g_attn_stamps : nullptr;
     p.part = nullptr;
     p.rope_cos = a.rope_cos; p.rope_sin = a.rope_sin; p.rope_pos = a.rope_pos;
-    VZ_CHECK_ARG(!a.rope_cos || (a.head_dim == 128 && a.rope_sin && a.rope_pos && g_attn_version != 1 && !a.part),
+    VZ_CHECK_ARG(!a.rope_cos || (a.head_dim == 128 && a.rope_sin && a.rope_pos && vz_knob(VZ_KNOB_ATTN_VERSION) != 1 && !a.part),
                  "attention: RoPE at the query load is built into the head_dim-128 v2 kernel only");
     if (a.head_dim == 512 && a.part && !a.causal && !a.kv_len) {
         const size_t want = vz_attn_split_floats(a.B, a.Hq, a.Sq, a.Sk);
@@ -889,7 +883,7 @@ int vz_launch_attention(const AttnArgs& a, hipStream_t s) {
             return launch_flash_split<512, 32>(p, split512(a.Sq, a.Sk), s);
         }
     }
-    if (g_attn_version != 1) {
+    if (vz_knob(VZ_KNOB_ATTN_VERSION) != 1) {
         if (a.head_dim == 64) return launch_flash2<64>(p, s);
         if (a.head_dim == 128) return launch_flash2<128>(p, s);
     }

@@ -178,7 +178,6 @@ __global__ __launch_bounds__(256, 3) void attn_o_fused_kernel(AoParams p) {     
 
 }  // namespace
 
-int g_attn_o_delay = 8;       // vz_tune_set(31, n): the O role waits n x ~0.21 us before requesting its weights, so that the attention blocks' K / V loads reach the memory system first (scan at ctx 2048 with the two-trip head, two runs each: 0 -> 372.5-372.7, 4 -> 375.4-377.4, 8 -> 376.5-377.0, 12 -> 373.0-373.6, 16 -> 368.8-370.0 tok/s; against the four-trip head it was 12: 0 -> 344, 8 -> 346, 12 -> 357, 16 -> 352, 24 -> 348)
 int vz_launch_attn_o_fused(const AttnDecodeFusedArgs& a, const bf16_t* o_w, const unsigned char* o_w8, const float* o_scale, bf16_t* att_scratch,
                            bf16_t* x, unsigned* done, const int* step, int layer, int n_layers, int* err, hipStream_t s) {
     VZ_CHECK_ARG((a.B == 1 || a.B == 2) && a.D == D && a.Hq == 32 && a.Hkv == 8 && a.nsplit >= 1 && a.B * a.nsplit <= 32,
@@ -188,7 +187,7 @@ int vz_launch_attn_o_fused(const AttnDecodeFusedArgs& a, const bf16_t* o_w, cons
     p.at.qkv = a.qkv; p.at.kc = a.kc; p.at.vc = a.vc; p.at.o = att_scratch; p.at.part = a.part; p.at.ticket = a.ticket;
     p.at.cosT = a.cosT; p.at.sinT = a.sinT; p.at.pos = a.pos; p.at.slot = a.slot;
     p.at.B = a.B; p.at.Hq = a.Hq; p.at.Hkv = a.Hkv; p.at.max_ctx = a.max_ctx; p.at.nsplit = a.nsplit; p.at.window = a.window; p.at.scale = a.scale;
-    p.o_w = o_w; p.o_w8 = o_w8; p.o_scale = o_scale; p.x = x; p.done = done; p.step = step; p.err = err; p.layer = layer; p.n_layers = n_layers; p.delay = g_attn_o_delay;
+    p.o_w = o_w; p.o_w8 = o_w8; p.o_scale = o_scale; p.x = x; p.done = done; p.step = step; p.err = err; p.layer = layer; p.n_layers = n_layers; p.delay = vz_knob(VZ_KNOB_ATTN_O_DELAY);
     const dim3 grid(a.B * a.nsplit * a.Hkv + O_BLOCKS);
     if (o_w8 && o_scale) {       // e4m3 rows take precedence (as in linear())
         if (a.B == 1) hipLaunchKernelGGL((attn_o_fused_kernel<true, 1>), grid, dim3(256), 0, s, p);

@@ -32,7 +32,7 @@ void vz_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* vz_last_error(void) { return g_err; }
-extern "C" int vz_abi_version(void) { return 11; }
+extern "C" int vz_abi_version(void) { return 12; }
 extern "C" const char* vz_target_arch(void) { return "gfx950"; }
 
 // ------------------------------------------------------------------------------------------------
@@ -47,7 +47,6 @@ static LinearArgs mk_linear(const void* A, int lda, const void* W, int ldw, void
     return a;
 }
 
-static int g_fp8_prefill_min_rows = 768;   // vz_tune_set(22, rows): fewest prefill rows that take the fp8 MFMA path of a prefill_fp8 engine
 
 // The op-level linear entry points: each names the kernels it exists for as the routes it admits (include/viszephyr.h: VZ_LINEAR_*); the
 // route itself is the planner's.  vz_op_linear_route asks the same function, so what it reports is what the entry point runs.
@@ -688,7 +687,6 @@ extern "C" int vz_clip_fused_features(vz_engine* e, const void* d_images, int T,
 // ------------------------------------------------------------------------------------------------
 // a11: Q-Former
 // ------------------------------------------------------------------------------------------------
-static int g_qf_kv_all = 1;     // vz_tune_set(25, 0): the Q-Former's cross-attention K|V projections one block at a time (A/B)
 int qf_attn(vz_engine* e, const bf16_t* q, long q_bs, long q_ss, const bf16_t* k, const bf16_t* v, long kv_bs, long kv_ss,
             bf16_t* o, int B, int Sq, int Sk, hipStream_t s, float* part, size_t part_floats) {
     ProfScope ps(e, K_ATTN, s);
@@ -712,7 +710,7 @@ static bool qf_shape_ok(const vz_config& c, int T, int n_samples, int Lmax) {
 // rounds of the 256^2 kernel, no stream-K tail (8 x 217 us -> one launch).  The [T * P, blocks * 2H] result is capped at 2 GiB;
 // larger tile batches fill the chip per block anyway.
 static bool qf_kv_all(const vz_config& c, int T, bool contig) {
-    return contig && (size_t)T * qf_visual_tokens(c) * c.qf_blocks * 2 * c.hidden * sizeof(bf16_t) <= ((size_t)2 << 30) && g_qf_kv_all;
+    return contig && (size_t)T * qf_visual_tokens(c) * c.qf_blocks * 2 * c.hidden * sizeof(bf16_t) <= ((size_t)2 << 30) && vz_knob(VZ_KNOB_QF_KV_ALL);
 }
 struct QfWs { bf16_t *fn, *ckv, *x0, *y0, *kv0, *q0, *a0, *xs, *x, *y, *qkv, *att, *ff; float* part; size_t part_floats; };
 static QfWs carve_qformer(Carver& m, const vz_config& c, int T, int n_samples, int Lmax, bool kv_all) {
@@ -815,23 +813,15 @@ extern "C" int vz_embed_splice(vz_engine* e, const int* d_kind, const int* d_idx
 // Self-test (vz_tune_set(7, 1)): an engine with tp_size == 1 that has been given a one-rank communicator routes the same
 // call sites through RCCL (all-reduce over one rank = identity, all-gather = copy), so the collective plumbing - library,
 // dtypes, in-place buffers, stream order, the vocab-parallel gather + repack - runs on a single GPU.
-static int g_force_comm = 0;
-static int g_rope_in_attn = 1;     // vz_tune_set(33, 0): the prefill writes a rotated copy of Q (rope_kv_kernel) for the attention again (A/B; bit-identical)
-static unsigned g_tune_epoch = 0;  // successful vz_tune_set calls so far: a captured decode step froze the routes the knobs chose, so it is part of the graph key
-static int g_attn_o = 1;           // vz_tune_set(30, 0): batch-1 decode attention and O projection as two launches again (attn_o_fused.hip off)
-static int g_persist_decode = 0;   // vz_tune_set(28, 1): batch-1 decode steps as one resident grid per token (decode_persist.hip) instead of the launch chain.
-                                   // Off by default: measured 282 vs 339 tok/s (profiles/r03_persist_stamps.txt: the phase edges + the attention phase leave HBM idle longer than the launch boundaries they replace)
-static int g_attn_nsplit = 0;   // vz_tune_set(10, n): context splits of the fused decode attention (0 = engine default)
-static inline bool tp_local(const vz_engine* e) { return e->tp == 1 && !(g_force_comm && e->comm); }
+static inline bool tp_local(const vz_engine* e) { return e->tp == 1 && !(vz_knob(VZ_KNOB_FORCE_COMM) && e->comm); }
 
 // vz_tune_set(7, 2): shape rehearsal of ONE rank of a tp_size > 1 engine on a single GPU - every collective is skipped (the
 // partial sums / vocab shard are left as they are), so all local kernels run with that rank's shard shapes; results are
 // meaningless as logits, the point is that nothing on the local path rejects the shapes of tp 2 / 4 / 8.
-static inline bool tp_skip(const vz_engine* e) { return e->tp > 1 && g_force_comm == 2; }
+static inline bool tp_skip(const vz_engine* e) { return e->tp > 1 && vz_knob(VZ_KNOB_FORCE_COMM) == 2; }
 
-static int g_oneshot = 1;        // vz_tune_set(29, 0): keep RCCL for the decode step's all-reduces although peer areas are attached
 static int tp_allreduce_bf16(vz_engine* e, bf16_t* buf, size_t count, hipStream_t s, bool decode = false) {
-    if (decode && g_oneshot && e->os_ranks == e->tp && e->tp > 1 && (int)count <= vz_engine::OS_MAX_ELEMS && (count & 1) == 0 && !tp_skip(e)) {
+    if (decode && vz_knob(VZ_KNOB_ONESHOT) && e->os_ranks == e->tp && e->tp > 1 && (int)count <= vz_engine::OS_MAX_ELEMS && (count & 1) == 0 && !tp_skip(e)) {
         ProfScope ps(e, K_COMM, s);
         return vz_launch_allreduce_oneshot(e->os_areas, e->rank, e->tp, vz_engine::OS_MAX_ELEMS, buf, buf, (int)count, e->os_seq, e->d_ferr, s);
     }
@@ -995,12 +985,8 @@ static int rows_entry_check(vz_engine* e, const char* who, char dim, bool pointe
     return VZ_OK;
 }
 
-// More new rows per sample than this run the append on the prefill's flash kernel with a scalar q_pos0, once per run of cache rows with
-// equal past; at or below it the key-split kernel of attn_append.hip.  Measured behind 2048 cached positions (profiles/append.txt): the
-// key-split kernel + combine take 48 us against 67 at T = 256, 61 against 68 at 320, 76 against 71 at 384 and 87 against 74 at 512: the
-// crossover lies between 320 and 384, and 256 sits inside the range it wins by a clear margin.
-// vz_tune_set(36, rows).
-static int g_append_flash_min_t = 256;
+// More new rows per sample than knob 36 (VZ_KNOB_APPEND_FLASH_MIN_T; tune.h has the measurement) run the append on the prefill's flash
+// kernel with a scalar q_pos0, once per run of cache rows with equal past; at or below it the key-split kernel of attn_append.hip.
 
 // One call: T embed rows per sample; sample b's first h_new[b] rows are valid and go behind the h_past[b] positions cache row row0 + b
 // keeps (slots past + t).  The plain prefill is the call with past = 0 everywhere.
@@ -1022,10 +1008,10 @@ static int llm_rows_forward(vz_engine* e, const RowsWs& w, const RowsCall& k, bo
     const bool lead = e->rank == 0;   // the row-parallel partial sums carry the residual on one rank only
     bf16_t *x = w.x, *y = w.y, *qkv = w.qkv, *q = w.q, *att = w.att, *act = w.act, *ylast = w.ylast;
     // The attention, chosen once: the key-split kernel (short appends), or flash launches over runs of cache rows with equal past.  The
-    // plain prefill is one such run at past 0, and the only one whose flash launch may rotate Q in its own load (g_rope_in_attn; the
+    // plain prefill is one such run at past 0, and the only one whose flash launch may rotate Q in its own load (knob 33; the
     // others read the rotated copy q that rope_kv writes).
-    const bool keysplit = append && !(T > g_append_flash_min_t);
-    const bool rope_q_late = !append && g_rope_in_attn && D == 128 && vz_attn_version() != 1;
+    const bool keysplit = append && !(T > vz_knob(VZ_KNOB_APPEND_FLASH_MIN_T));
+    const bool rope_q_late = !append && vz_knob(VZ_KNOB_ROPE_IN_ATTN) && D == 128 && vz_knob(VZ_KNOB_ATTN_VERSION) != 1;
     int* d_slot = w.ints;
     int* d_len = w.ints + rows;
     int kv_max = 0;
@@ -1046,7 +1032,7 @@ static int llm_rows_forward(vz_engine* e, const RowsWs& w, const RowsCall& k, bo
     // (below ~768 rows the quantiser launches and the shallow grids cost more than the fp8 MFMA saves: 330 rows 20.4 vs 18.6 ms, 1320 rows 37.5 vs 43.6)
     // The plain prefill only: carve_append takes no q8 / qs, and nobody has measured or tested an append on the fp8 route - on a
     // prefill_fp8 engine it keeps the bf16 linears.
-    const bool f8 = !append && e->prefill_fp8 && rows >= g_fp8_prefill_min_rows && tp_local(e) && vz_gemm_fp8_ok(rows, QKV, H, H, H) && vz_gemm_fp8_ok(rows, H, I, I, I) && vz_gemm_fp8_ok(rows, H, A, A, A);
+    const bool f8 = !append && e->prefill_fp8 && rows >= vz_knob(VZ_KNOB_FP8_PREFILL_MIN_ROWS) && tp_local(e) && vz_gemm_fp8_ok(rows, QKV, H, H, H) && vz_gemm_fp8_ok(rows, H, I, I, I) && vz_gemm_fp8_ok(rows, H, A, A, A);
     // norm_w != null: Ain is the residual stream and the RMSNorm belongs to this linear (fp8: norm + quantiser in one launch)
     auto plin = [&](const bf16_t* Ain, const float* norm_w, const LinW& W, int N, int K, void* Cout, int ldc, const bf16_t* res, int act) -> int {
         if (f8) {
@@ -1322,7 +1308,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(st.cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
             const LlmLayerW& W = e->llm[i];
-            const bool fuse_ao = !spec && g_attn_o && (B == 1 || (B == 2 && g_attn_o >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
+            const bool fuse_ao = !spec && vz_knob(VZ_KNOB_ATTN_O) && (B == 1 || (B == 2 && vz_knob(VZ_KNOB_ATTN_O) >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
             RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
             if (spec) {
@@ -2046,7 +2032,7 @@ static bool decode_step_past_16_row_kernels(vz_engine* e, int B) {
 static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids) {
     DecodeGraphKey k;
     memset(&k, 0, sizeof(k));          // padding, and the modes that are off, compare equal
-    k.B = e->dec_B; k.n = n; k.nsplit = e->dec_nsplit; k.use_tok = e->use_tok; k.kind = tail_kind(e); k.tune_epoch = g_tune_epoch;
+    k.B = e->dec_B; k.n = n; k.nsplit = e->dec_nsplit; k.use_tok = e->use_tok; k.kind = tail_kind(e); k.tune_epoch = vz_tune_epoch();
     k.out = d_out_ids; k.arena = e->arena; k.ring = e->ring.p; k.ring_n = e->ring.n;
     switch (k.kind) {
     case TAIL_SPEC: k.spec = e->spec.a; break;
@@ -2107,7 +2093,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     // vz_tune_set(28, 1) - batch 1, one GPU, bf16 weights, Zephyr-7B geometry on a 256-CU device: the steps run as ONE resident grid
     // per token (decode_persist.hip) instead of the launch chain.  Its pointer table is (re)built here, never inside a capture.
     e->use_tok = false;
-    if (g_persist_decode && B == 1 && e->tp == 1 && tp_local(e) && !c.weight_fp8 && c.hidden == 4096 && c.inter == 14336 && c.n_heads == 32 &&
+    if (vz_knob(VZ_KNOB_PERSIST_DECODE) && B == 1 && e->tp == 1 && tp_local(e) && !c.weight_fp8 && c.hidden == 4096 && c.inter == 14336 && c.n_heads == 32 &&
         c.n_kv_heads == 8 && c.head_dim == 128 && c.vocab >= 256 && vz_decode_persist_supported()) {
         if (!e->tok) {
             std::vector<VzTokLayerHost> lt(c.n_layers);
@@ -2161,12 +2147,12 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         // (config-5 miniature, e4m3, ctx ~330: 64 rows x 3 splits -> x 1: decode 627 -> 597 ms per batch; 32 rows x 3 -> x 2: 459 -> 448) -
         // rows x KV heads x splits is held to ~512 workgroups; 1..2 rows keep every split (batch-1 numbers unchanged)
         if (!spec) ns = std::min(ns, std::max(1, 512 / std::max(1, B * e->Hkv_l)));      // (a verify step's rows share one cache row and its workgroups)
-        e->dec_nsplit = g_attn_nsplit > 0 ? g_attn_nsplit : ns;
+        e->dec_nsplit = vz_knob(VZ_KNOB_ATTN_NSPLIT) > 0 ? vz_knob(VZ_KNOB_ATTN_NSPLIT) : ns;
         if (spec) {
             // the split positions follow the BUCKET, not the exact bound: one graph per bucket, as for the plain step
             int chunks = need;
             for (int bk : buckets) if (bk >= need) { chunks = bk; break; }
-            e->spec.a.key_bound = g_attn_nsplit > 0 ? c.max_ctx : std::min(chunks * 128, c.max_ctx);       // (a pinned split count: splits over the whole cache, one graph)
+            e->spec.a.key_bound = vz_knob(VZ_KNOB_ATTN_NSPLIT) > 0 ? c.max_ctx : std::min(chunks * 128, c.max_ctx);       // (a pinned split count: splits over the whole cache, one graph)
             // worst case of the device-side state after these n steps (the device keeps the exact one): n x R positions, inside the budget
             const int adv = std::min(e->h_len[0] - e->spec.base_len + n * B, e->spec.a.budget);
             for (int b = 0; b < B; ++b) { e->h_len[b] = e->spec.base_len + adv + b; e->h_pos[b] = e->spec.base_pos + adv + b; }
@@ -2306,36 +2292,7 @@ extern "C" int vz_test_corrupt_streamk(vz_stream stream, int tile, int arrive, i
     return vz_gemm256_corrupt_tickets((hipStream_t)stream, tile, arrive, ready);
 }
 
-extern int g_attn_o_delay;
-extern int g_skinny_even;
-extern int g_flash_bwd;      // train_engine.hip
-extern int g_gemm256_streamk, g_gemm256_skew, g_gemm256_stamps, g_gemm256_drain, g_gemm256_persist, g_attn_stamp_on, g_fp8_gemm_choice;
 int vz_gemm256_read_stamps(long long* host, int max_wgs, int* n_wgs);
-static int tune_set(int knob, int value) {
-    if (knob == 10) { if (value < 0 || value > 64) { vz_set_error("tune_set: decode attention splits must be 0..64"); return VZ_ERR_ARG; } g_attn_nsplit = value; return VZ_OK; }
-    // knob number -> the int it sets, or its setter
-    static const struct { int knob; int* var; void (*set)(int); } knobs[] = {
-        {0, nullptr, vz_set_gemv_variant}, {1, nullptr, vz_set_gemm_choice}, {2, nullptr, vz_set_attn_version}, {3, nullptr, vz_set_splitk_mode},
-        {4, &g_gemm256_streamk}, {5, &g_gemm256_skew}, {6, &g_gemm256_stamps}, {7, &g_force_comm}, {9, &g_skinny_mode},
-        {11, &g_gemm256_drain}, {14, &g_decode_tile_rows}, {15, &g_decode_sk_short}, {16, &g_attn_stamp_on}, {19, &g_wide_mode}, {21, &g_fp8_gemm_choice},
-        {22, &g_fp8_prefill_min_rows}, {23, nullptr, vz_set_attn_split}, {24, nullptr, vz_set_splitk_cap}, {25, &g_qf_kv_all}, {26, nullptr, vz_set_splitk_mid},
-        {27, &g_wide_fp8_splits}, {28, &g_persist_decode}, {29, &g_oneshot}, {30, &g_attn_o}, {31, &g_attn_o_delay}, {32, &g_flash_bwd}, {33, &g_rope_in_attn},
-        {34, &g_gemm256_persist}, {35, &g_skinny_even}, {36, &g_append_flash_min_t},
-    };
-    for (const auto& k : knobs) {
-        if (k.knob != knob) continue;
-        if (k.var) *k.var = value; else k.set(value);
-        return VZ_OK;
-    }
-    vz_set_error("tune_set: unknown knob %d", knob);
-    return VZ_ERR_ARG;
-}
-extern "C" int vz_tune_set(int knob, int value) {
-    const int r = tune_set(knob, value);
-    if (r == VZ_OK) ++g_tune_epoch;          // the next vz_llm_decode_steps captures again
-    return r;
-}
-
 int vz_attn_read_stamps(long long* host16);
 extern "C" int vz_prof_attn_stamps(long long* host16) { return vz_attn_read_stamps(host16); }
 extern "C" int vz_prof_gemm_stamps(long long* host_out, int max_wgs, int* n_wgs) {

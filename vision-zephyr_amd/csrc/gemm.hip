@@ -444,15 +444,6 @@ int vz_init_gemm_kernels() {
     return VZ_OK;
 }
 
-static int g_gemm_choice = 0;
-void vz_set_gemm_choice(int v) { g_gemm_choice = v; }
-static int g_splitk_mode = 0;          // 0 auto, 1 never (A/B knob 3)
-void vz_set_splitk_mode(int v) { g_splitk_mode = v; }
-static int g_splitk_mid = 1;           // 1: K slices for grids of fewer than 256 tiles with M > 512 (A/B knob 26)
-void vz_set_splitk_mid(int v) { g_splitk_mid = v; }
-static int g_splitk_cap = 8;           // most K slices of a weight-streaming (M <= 512) product (A/B knob 24; 4 -> 8: Q-Former 3.87 -> 3.80 ms)
-void vz_set_splitk_cap(int v) { g_splitk_cap = v < 1 ? 1 : (v > 16 ? 16 : v); }
-
 // Tile choice: the 256x256 8-phase kernel runs one workgroup per CU, so it needs enough 256^2 tiles to fill the
 // 256 CUs several times over (>= 512 tiles: measured cross-over on MI355X, tools/bench_kernels.py); smaller grids keep the
 // 128x128 kernel (2 workgroups per CU, 4x the tiles).
@@ -461,7 +452,7 @@ bool vz_gemm_use256(const LinearArgs& a) {
     // measured on MI355X (tools/bench_kernels.py gemm): the 256^2 kernel wins once it has >= 160 tiles (QKV 192: 100 vs 118 us,
     // gate-up 896: 373 vs 506 us) or, with its stream-K tail, >= 96 tiles of long K (down-proj 128 tiles x 224 K-tiles:
     // 190 vs 252 us); the 128^2 kernel keeps short K (CLIP, K = 1024) and small grids (O-proj 128 tiles x 64: 68 vs 80 us)
-    return g_gemm_choice == 2 || (g_gemm_choice == 0 && a.K >= 1024 && (t256 >= 160 || (t256 >= 96 && a.K >= 8192)));
+    return vz_knob(VZ_KNOB_GEMM_CHOICE) == 2 || (vz_knob(VZ_KNOB_GEMM_CHOICE) == 0 && a.K >= 1024 && (t256 >= 160 || (t256 >= 96 && a.K >= 8192)));
 }
 
 int vz_launch_gemm128(const LinearArgs& a, hipStream_t s) {
@@ -483,18 +474,18 @@ int vz_launch_gemm128(const LinearArgs& a, hipStream_t s) {
     // The factor depends on N and K only, never on M: a row's result must not change with the number of rows beside it
     // (the Q-Former computes block 0's self-attention once per sample and relies on it being bit-identical to the
     // per-tile computation, tests/test_stages_gpu.py::test_qformer).
-    if (g_splitk_mode != 1 && a.M <= 512 && p.tiles_n < 128 && a.act != VZ_ACT_SWIGLU && (a.N & 3) == 0) {
+    if (vz_knob(VZ_KNOB_SPLITK_MODE) != 1 && a.M <= 512 && p.tiles_n < 128 && a.act != VZ_ACT_SWIGLU && (a.N & 3) == 0) {
         // ~256 workgroups per row tile, rounded DOWN: two row tiles (the Q-Former's 160 rows) then fit the 512 slots in one round
         // (N = 12288: 96 column tiles x 3 slices x 2 row tiles = 576 workgroups ran a second round - 57 us; x 2 slices: 47 us)
         splitk = std::max(1, 256 / p.tiles_n);
-        if (splitk > g_splitk_cap) splitk = g_splitk_cap;
+        if (splitk > vz_knob(VZ_KNOB_SPLITK_CAP)) splitk = vz_knob(VZ_KNOB_SPLITK_CAP);
         while (splitk > 1 && nk / splitk < 8) --splitk;
     }
     // A grid that leaves the CUs a single workgroup each (or none) is cut along K until ~512 workgroups exist: a lone workgroup has nobody to
     // hide its LDS / barrier latency behind (CLIP fc2 at 5 tiles: 184 tiles x K = 4096, 50 -> 31 us; CLIP tower 4.99 -> 4.54 ms at 5 tiles,
     // 3.78 -> 2.8 at 1; tools/bench_vision.py).  Short K (1024: CLIP QKV / out) only pays on very small grids.  The factor follows the tile
     // count, i.e. M: like the 128^2 / 256^2 choice it is not batch-invariant (knob 26 = 0 switches it off; the invariance tests do).
-    if (g_splitk_mid && splitk == 1 && a.M > 512 && a.act != VZ_ACT_SWIGLU && (a.N & 3) == 0 &&
+    if (vz_knob(VZ_KNOB_SPLITK_MID) && splitk == 1 && a.M > 512 && a.act != VZ_ACT_SWIGLU && (a.N & 3) == 0 &&
         ((tiles < 256 && nk >= 32) || (tiles <= 128 && nk >= 16))) {
         splitk = std::min(4, 512 / tiles);
         while (splitk > 1 && nk / splitk < 8) --splitk;

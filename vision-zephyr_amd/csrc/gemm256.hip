@@ -661,12 +661,6 @@ int sk_state_for(hipStream_t s, SkState** out) {
 
 }  // namespace
 
-int g_gemm256_streamk = 1;   // vz_tune_set(4, v): 1 = stream-K tail (default), 0 = whole tiles only
-int g_gemm256_stamps = 0;    // vz_tune_set(6, v): 1 = record in-kernel phase stamps (vz_prof_gemm_stamps)
-int g_gemm256_drain = 0;     // vz_tune_set(11, v)
-int g_gemm256_persist = 1;   // vz_tune_set(34, v)
-int g_gemm256_skew = 2;      // vz_tune_set(5, v): K-tiles by which even / odd stream-K workgroups lead / lag
-
 int vz_init_gemm256_kernel() {
     static VzDeviceOnce once;
     if (!vz_device_first(once)) return VZ_OK;
@@ -690,8 +684,8 @@ static int plan_and_launch(Gemm256Params& p, int nk, int* err_word, bool fp8, hi
     const int rem = T % P;
     // a last round that fills at most half of the CUs is cut along K instead.  Measured (S=2048): down-proj (128 tiles,
     // K=14336) 250 -> 190 us, Q-Former cross-attention K/V (384 tiles) 227 -> 214 us; a fuller tail (QKV, 192 tiles) does
-    // not pay for the 256 KiB-per-tile fix-up (100 -> 117 us).  g_gemm256_streamk = 2 forces it for any tail (tests).
-    if (g_gemm256_streamk && rem > 0 && (rem * 2 <= P || g_gemm256_streamk == 2)) {
+    // not pay for the 256 KiB-per-tile fix-up (100 -> 117 us).  knob 4 = 2 forces it for any tail (tests).
+    if (vz_knob(VZ_KNOB_GEMM256_STREAMK) && rem > 0 && (rem * 2 <= P || vz_knob(VZ_KNOB_GEMM256_STREAMK) == 2)) {
         const long units = (long)rem * nk;
         long wgs = units / SK_MIN_UNITS;
         if (wgs > P) wgs = P;
@@ -702,7 +696,7 @@ static int plan_and_launch(Gemm256Params& p, int nk, int* err_word, bool fp8, hi
             { int r = sk_state_for(s, &st); if (r) return r; }
             if (st && (size_t)(wgs + rem) * TILE_FLOATS * sizeof(float) <= st->ws_bytes && 2 * rem <= st->n_tickets) {
                 p.n_full = T - rem; p.n_rem = rem; p.sk_wgs = (int)wgs; p.units_per_wg = U;
-                p.sk_skew = U >= 24 ? g_gemm256_skew : 0;
+                p.sk_skew = U >= 24 ? vz_knob(VZ_KNOB_GEMM256_SKEW) : 0;
                 p.ws = st->ws; p.tickets = st->tickets; p.err = err_word ? err_word : st->err;
             }
         }
@@ -712,9 +706,9 @@ static int plan_and_launch(Gemm256Params& p, int nk, int* err_word, bool fp8, hi
     // process (tools/bench_kernels.py gemmsq): Stage-1 gate|up (12736 rows, 5600 tiles) 2344 -> 2240 us, Stage-1 QKV 509 -> 496, CLIP fc1 at 64 x 577 rows
     // 392 -> 376, 4 rounds of Zephyr tiles 446 -> 432; one-round shapes unchanged.  Also built: requesting the NEXT tile's first two K-tiles before the
     // current tile's epilogue (their HBM latency under the store drain) - no gain over plain persistence (2261 / 503 / 382 / 446 us): removed.
-    p.n_pers = (g_gemm256_persist && p.n_full > P) ? P : p.n_full;
-    p.stamps = nullptr; p.drain = g_gemm256_drain;
-    if (g_gemm256_stamps && p.n_pers + p.sk_wgs <= 4096) {
+    p.n_pers = (vz_knob(VZ_KNOB_GEMM256_PERSIST) && p.n_full > P) ? P : p.n_full;
+    p.stamps = nullptr; p.drain = vz_knob(VZ_KNOB_GEMM256_DRAIN);
+    if (vz_knob(VZ_KNOB_GEMM256_STAMPS) && p.n_pers + p.sk_wgs <= 4096) {
         p.stamps = g_stamps; g_stamp_wgs = p.n_pers + p.sk_wgs;
         VZ_CHECK_HIP(hipMemsetAsync(g_stamps, 0, (size_t)g_stamp_wgs * 16 * sizeof(long long), s));
     }

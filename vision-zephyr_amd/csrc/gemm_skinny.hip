@@ -20,7 +20,6 @@
 //     fragments in registers (exact) and the row's power-of-two scale multiplies the fp32 result once.
 #include "linear_route.h"
 
-int g_skinny_even = 1;          // vz_tune_set(35, 0): one persistent workgroup per CU whatever the group count (A/B)
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -529,13 +528,13 @@ template <bool SWIGLU, bool FP8>
 int launch_persist(const SkinnyParams& p, int n_groups, size_t lds, hipStream_t s) {
     // ONE workgroup per CU even where LDS would hold two (5..7 rows): measured 3.85 / 3.88 / 3.94 ms per 5 / 6 / 7-row step
     // against 3.98 / 4.03 / 4.08 with two (knob 9 = SKINNY_PERSIST_2_PER_CU) - the eight waves' synchronised bursts again
-    const int per_cu = g_skinny_mode == SKINNY_PERSIST_2_PER_CU ? ((160 * 1024) / (int)lds >= 2 ? 2 : 1) : 1;
+    const int per_cu = vz_knob(VZ_KNOB_SKINNY_MODE) == SKINNY_PERSIST_2_PER_CU ? ((160 * 1024) / (int)lds >= 2 ? 2 : 1) : 1;
     const int cap = g_num_cu_skinny * per_cu;
     // the launch lasts as long as its busiest workgroup: ceil(n_groups / cap) groups.  With that many groups on EVERY workgroup fewer of them
     // are needed (QKV: 384 groups = 2 per workgroup on 192 CUs instead of 2 on 128 + 1 on 128; the waves' bursts then share HBM with fewer
     // others): same summation per group, bit-identical
     const int rounds = (n_groups + cap - 1) / cap;
-    const int grid = g_skinny_even ? (n_groups + rounds - 1) / rounds : (n_groups < cap ? n_groups : cap);
+    const int grid = vz_knob(VZ_KNOB_SKINNY_EVEN) ? (n_groups + rounds - 1) / rounds : (n_groups < cap ? n_groups : cap);
     vz_launch_timed(skinny_persist_kernel<SWIGLU, FP8>, dim3(grid), dim3(512), lds, s, p, n_groups);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
@@ -565,10 +564,9 @@ int launch(const SkinnyParams& p, int blocks, size_t lds, hipStream_t s) {
 
 }  // namespace
 
-int g_skinny_mode = SKINNY_ON;   // vz_tune_set(9, v): SkinnyMode (linear_route.h)
 
 // 5..16 rows with the RMSNorm fused: only the persistent form holds the normalised rows in LDS at one workgroup per CU
-bool vz_skinny_fused_norm_ok(const LinearArgs& a) { return g_skinny_mode != SKINNY_NO_PERSIST && a.M >= 2 && a.M <= 16 && skinny_persist_ok(a); }
+bool vz_skinny_fused_norm_ok(const LinearArgs& a) { return vz_knob(VZ_KNOB_SKINNY_MODE) != SKINNY_NO_PERSIST && a.M >= 2 && a.M <= 16 && skinny_persist_ok(a); }
 
 bool vz_skinny_ok(const LinearArgs& a) {
     if (a.M < 2 || a.M > 64 || (a.K & 63) != 0 || a.K < 512) return false;
@@ -617,7 +615,7 @@ int vz_launch_tile_weights(const bf16_t* W, int N, int K, int ldw, bf16_t* Wt, h
 // 3.59 / 3.61 vs 3.69 / 3.68 ms per step on the tiled weights), from 2 with SKINNY_PERSIST_FROM_2, never with SKINNY_NO_PERSIST
 LinRoute vz_skinny_route(const LinearArgs& a) {
     if (a.M > 16) return LIN_SKINNY_WIDE;
-    if (g_skinny_mode != SKINNY_NO_PERSIST && skinny_persist_ok(a) && (a.M >= 3 || g_skinny_mode == SKINNY_PERSIST_FROM_2)) return LIN_SKINNY_PERSIST;
+    if (vz_knob(VZ_KNOB_SKINNY_MODE) != SKINNY_NO_PERSIST && skinny_persist_ok(a) && (a.M >= 3 || vz_knob(VZ_KNOB_SKINNY_MODE) == SKINNY_PERSIST_FROM_2)) return LIN_SKINNY_PERSIST;
     return LIN_SKINNY;
 }
 

@@ -466,18 +466,16 @@ int pick_splits(int row_blocks, int chunks, bool fp8 = false) {
 
 }  // namespace
 
-int g_wide_mode = 1;       // vz_tune_set(19, v): 0 = off (17..64-row decode steps keep the earlier routes)
-int g_wide_fp8_splits = 0; // vz_tune_set(27, P): force the K split of the e4m3 stream (0 = pick_splits; A/B)
 
 int vz_wide_splits(const LinearArgs& a) {
     const int rbs = a.N >> 7, chunks = a.K >> 9;
     const bool f8 = a.W8t != nullptr;
-    if (f8 && g_wide_fp8_splits > 0 && chunks % g_wide_fp8_splits == 0 && ((chunks / g_wide_fp8_splits) & 1) == 0) return g_wide_fp8_splits;
+    if (f8 && vz_knob(VZ_KNOB_WIDE_FP8_SPLITS) > 0 && chunks % vz_knob(VZ_KNOB_WIDE_FP8_SPLITS) == 0 && ((chunks / vz_knob(VZ_KNOB_WIDE_FP8_SPLITS)) & 1) == 0) return vz_knob(VZ_KNOB_WIDE_FP8_SPLITS);
     return pick_splits(rbs, chunks, f8);
 }
 
 bool vz_wide_ok(const LinearArgs& a) {
-    if (!g_wide_mode || a.norm_w || !a.rows_free) return false;
+    if (!vz_knob(VZ_KNOB_WIDE_MODE) || a.norm_w || !a.rows_free) return false;
     if (a.W8t) { if (!a.wscale || ((uintptr_t)a.W8t & 15) != 0 || ((uintptr_t)a.wscale & 15) != 0 || ((a.K >> 9) & 1)) return false; }
     else if (!a.Wt || a.W8) return false;
     if (a.M < 17 || a.M > 64 || (a.N & 127) != 0 || (a.K & 511) != 0 || a.ldw != a.K) return false;

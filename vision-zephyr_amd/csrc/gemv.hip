@@ -35,8 +35,6 @@
 
 namespace {
 
-int g_gemv_variant = 0;   // 0 = production choice; >0 = tuning variants (tools/bench_kernels.py)
-
 // The operand-free form of the stream (gemv_bf16_noepi_kernel): one kernel per K shape, chosen here as gemv_bf16_kernel chooses its body.
 template <int MB, int R, int U, bool NT, int NW, int MODE, int G>
 int launch_noepi_form(const GemvParams& p, int blocks, hipStream_t s, size_t lds) {
@@ -69,7 +67,8 @@ int launch_variant(const GemvParams& p0, hipStream_t s, size_t lds) {
     p.units = p.act == VZ_ACT_SWIGLU ? p.N / R : (p.N + R - 1) / R;     // SwiGLU: R/2 outputs of N/2 per unit
     int blocks = (p.units + NW - 1) / NW;
     int cap = NW == 4 ? 2048 : 512;
-    if (g_gemv_variant >= 7 && g_gemv_variant <= 10) cap = (g_gemv_variant & 1) ? 256 : 512;      // experiments: one / two workgroups per CU
+    const int variant = vz_knob(VZ_KNOB_GEMV_VARIANT);
+    if (variant >= 7 && variant <= 10) cap = (variant & 1) ? 256 : 512;      // experiments: one / two workgroups per CU
     if (blocks > cap) blocks = cap;
     // neither bias nor residual (QKV, gate|up, lm_head of the decode step): the form without the epilogue's operands; routed forms only
     if constexpr (MB <= 2 && !FP8 && R == 2 && U == 8 && NT) {
@@ -114,15 +113,15 @@ int launch_mb(const GemvParams& p, hipStream_t s, size_t lds) {
     if constexpr (MB <= 4) {
         const int units = p.act == VZ_ACT_SWIGLU ? p.N / 2 : (p.N + 1) / 2;
         const int b8 = (units + 7) / 8;
-        fat = g_gemv_variant == 0 && (b8 >= 512 || b8 % 256 == 0);
+        fat = vz_knob(VZ_KNOB_GEMV_VARIANT) == 0 && (b8 >= 512 || b8 % 256 == 0);
     }
     if (p.W8) {       // 2 rows x up to 8 chunks of 1024 k per wave (measured faster than 4 rows x 4: 13.5 vs 15.3 us on down-proj)
-        if (g_gemv_variant == 1) return launch_variant<MB, 4, 4, true, true>(p, s, lds);
+        if (vz_knob(VZ_KNOB_GEMV_VARIANT) == 1) return launch_variant<MB, 4, 4, true, true>(p, s, lds);
         if constexpr (MB <= 4) { if (fat) return launch_variant<MB, 2, 8, true, true, 8>(p, s, lds); }
         return launch_variant<MB, 2, 8, true, true>(p, s, lds);
     }
     if constexpr (MB <= 4) { if (fat) return launch_variant<MB, 2, 8, true, false, 8>(p, s, lds); }
-    switch (g_gemv_variant) {
+    switch (vz_knob(VZ_KNOB_GEMV_VARIANT)) {
         case 1: return launch_variant<MB, 2, 4, false>(p, s, lds);
         case 2: return launch_variant<MB, 2, 8, false>(p, s, lds);
         case 3: return launch_variant<MB, 2, 8, true>(p, s, lds);
@@ -136,8 +135,6 @@ int launch_mb(const GemvParams& p, hipStream_t s, size_t lds) {
 }
 
 }  // namespace
-
-void vz_set_gemv_variant(int v) { g_gemv_variant = v; }
 
 bool vz_gemv_ok(const LinearArgs& a) {
     if (a.M > 8 || (a.K % (a.W8 ? 1024 : 512)) != 0) return false;

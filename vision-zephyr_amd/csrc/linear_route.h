@@ -23,7 +23,7 @@ constexpr unsigned lin_bit(LinRoute r) { return 1u << r; }
 // the representation of W the kernel reads
 enum LinWeights { LIN_W_BF16, LIN_W_BF16_TILED, LIN_W_E4M3, LIN_W_E4M3_TILED };
 
-// vz_tune_set(9, v): the values of g_skinny_mode
+// the values of knob 9 (VZ_KNOB_SKINNY_MODE)
 enum SkinnyMode {
     SKINNY_OFF = 0,              // no MFMA weight stream: GEMV up to 8 rows, tile GEMMs beyond (the routes before gemm_skinny.hip)
     SKINNY_ON = 1,               // default: 2..64 independent rows stream the weights through MFMAs; persistent fused-norm form from 3 rows
@@ -70,5 +70,3 @@ int vz_run_route(const LinPlan& p, const LinearArgs& a, const bf16_t* xnorm, hip
 
 // gemm_skinny.hip: which of its three forms takes these arguments (the launcher and the planner both ask here)
 LinRoute vz_skinny_route(const LinearArgs& a);
-
-extern int g_decode_tile_rows, g_decode_sk_short;      // vz_tune_set(14 / 15)

@@ -3,10 +3,6 @@
 
 #include "linear_route.h"
 
-// vz_tune_set(14, rows): from this many rows on a decode step's linears run on the 128^2 tile GEMM (65 = never)
-int g_decode_tile_rows = 29;      // measured cross-over on the tiled weight copies (profiles/r02_rows.txt): MFMA weight stream 4.42 ms per step at 25 rows, 4.74 at 32; tile route 4.56 / 4.64
-int g_decode_sk_short = 8;        // vz_tune_set(15, v): split-K factor of the K = 4096 decode projections (QKV, O) on the tile-GEMM route
-
 const char* vz_route_name(LinRoute r) {
     static const char* const names[] = {"GEMV", "SKINNY", "SKINNY_PERSIST", "SKINNY_WIDE", "WIDE_BF16", "WIDE_E4M3", "TILE128", "TILE256"};
     return r >= LIN_GEMV && r <= LIN_TILE256 ? names[r] : "NONE";
@@ -19,7 +15,7 @@ static int vz_decode_splitk(int N, int K, int act) {
     if (N & 7) return 0;
     const int tiles_n = (N + 127) / 128;
     if (act == VZ_ACT_SWIGLU) return tiles_n < 384 ? 2 : 0;
-    if (K < 8192) return g_decode_sk_short;
+    if (K < 8192) return vz_knob(VZ_KNOB_DECODE_SK_SHORT);
     int sk = (512 + tiles_n - 1) / tiles_n;
     if (sk > 16) sk = 16;
     return sk < 1 ? 1 : sk;
@@ -60,7 +56,7 @@ LinPlan vz_plan_linear(const LinearArgs& a, LinCaller c) {
     // columns (they all have K = hidden); below 17 rows the stand-alone norm is only tried where the columns are known to match
     const bool pre = a.norm_w && (c.rows == LIN_ROWS_DECODE ? c.xnorm_cols > 0 : c.xnorm_cols == a.K);
     const bool pre_k = a.norm_w && c.xnorm_cols == a.K;
-    const bool stream = g_skinny_mode != SKINNY_OFF;
+    const bool stream = vz_knob(VZ_KNOB_SKINNY_MODE) != SKINNY_OFF;
     auto plan = [&](LinRoute r, LinWeights w, bool pre_norm, int splitk, int klass) { return LinPlan{r, w, pre_norm, splitk, klass, rows_free}; };
     auto probe = [&](LinWeights w, bool pre_norm) { return as_launched(a, plan(LIN_NONE, w, pre_norm, a.splitk_hint, K_GEMV), a.A); };
     auto allowed = [&](LinRoute r) { return (c.allow & lin_bit(r)) != 0; };
@@ -82,11 +78,11 @@ LinPlan vz_plan_linear(const LinearArgs& a, LinCaller c) {
         use8 = vz_gemv_ok(t) || (stream && vz_skinny_ok(t));
     }
     // what a GEMV / MFMA-stream launch reads (knob 9 = 5: the row-major weights although a tiled copy exists, A/B)
-    const LinWeights ws = use8 ? LIN_W_E4M3 : has_wt && (a.N & 15) == 0 && g_skinny_mode != SKINNY_IGNORE_TILED ? LIN_W_BF16_TILED : LIN_W_BF16;
+    const LinWeights ws = use8 ? LIN_W_E4M3 : has_wt && (a.N & 15) == 0 && vz_knob(VZ_KNOB_SKINNY_MODE) != SKINNY_IGNORE_TILED ? LIN_W_BF16_TILED : LIN_W_BF16;
 
     // e4m3 engines leave the e4m3 streams for the bf16 tile route where the row-major e4m3 stream stops being ahead (32 rows); bf16
     // engines at the measured cross-over of knob 14
-    const int tile_rows = e4m3 ? std::max(g_decode_tile_rows, 33) : g_decode_tile_rows;
+    const int tile_rows = e4m3 ? std::max(vz_knob(VZ_KNOB_DECODE_TILE_ROWS), 33) : vz_knob(VZ_KNOB_DECODE_TILE_ROWS);
 
     // ---- 17..64 independent rows: the tiled streams of gemm_wide.hip ----
     if (rows_free && a.M >= 17 && a.M <= 64) {
@@ -127,7 +123,7 @@ LinPlan vz_plan_linear(const LinearArgs& a, LinCaller c) {
     // 2 rows: the GEMV with both rows in LDS streams the weights like the 1-row launch (3.12 vs 3.48 ms per 2-row step; knob 9 = 7: the
     // MFMA stream); 3..64 independent rows: one MFMA per KiB of weights.  Both fuse the norm.
     const bool gemv = vz_gemv_ok(a0) && allowed(LIN_GEMV);
-    if (stream && vz_skinny_ok(a0) && allowed(vz_skinny_route(a0)) && !(a.M == 2 && g_skinny_mode != SKINNY_2_ROWS && gemv))
+    if (stream && vz_skinny_ok(a0) && allowed(vz_skinny_route(a0)) && !(a.M == 2 && vz_knob(VZ_KNOB_SKINNY_MODE) != SKINNY_2_ROWS && gemv))
         return plan(vz_skinny_route(a0), ws, false, a.splitk_hint, K_GEMV);
     if (gemv) return plan(LIN_GEMV, use8 ? LIN_W_E4M3 : LIN_W_BF16, false, a.splitk_hint, K_GEMV);
     if (use8) return none;                                     // e4m3 rows and no weight-stream kernel for them

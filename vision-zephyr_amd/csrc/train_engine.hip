@@ -22,7 +22,6 @@
 
 #include "engine_internal.h"
 
-int g_flash_bwd = 1;        // vz_tune_set(32, 0): the step's head-128 attention backward through the materialising batched-GEMM route again (A/B)
 
 struct ProjParam { std::string name; int dtype; long n; size_t off; void* work; };
 
@@ -448,7 +447,7 @@ static int attn_bwd_one(Step& cx, const AttnBwdArgs& a) {
     return VZ_OK;
 }
 static int attn_bwd(Step& cx, const AttnBwdArgs& a0) {
-    if (g_flash_bwd && vz_flash_bwd_ok(a0)) {
+    if (vz_knob(VZ_KNOB_FLASH_BWD) && vz_flash_bwd_ok(a0)) {
         Frame fr(cx.m);
         const size_t bytes = vz_flash_bwd_scratch_bytes(a0.B, a0.Sq, a0.Hq);
         char* ws = cx.m.take<char>(bytes);

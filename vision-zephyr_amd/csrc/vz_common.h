@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/viszephyr.h"
+#include "tune.h"      // vz_knob(): the tune knobs the launchers, the planner and the engines read
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -177,18 +178,14 @@ int vz_wide_splits(const LinearArgs& a);         // K splits a launch on these a
 int vz_launch_wide(const LinearArgs& a, hipStream_t s);
 int vz_launch_tile_weights_fp8(const unsigned char* W8, int N, int K, int ldw, unsigned char* W8t, hipStream_t s);
 int vz_wide_reserve(hipStream_t s);             // K-split scratch of a stream, allocated outside a capture
-extern int g_wide_fp8_splits;
 int vz_init_wide_kernels();
-extern int g_wide_mode;
 int vz_linear_check_common(const LinearArgs& a);
 bool vz_gemv_ok(const LinearArgs& a);
 bool vz_skinny_ok(const LinearArgs& a);      // 2..16 rows: MFMA weight stream (gemm_skinny.hip)
 int vz_launch_skinny(const LinearArgs& a, hipStream_t s);
 int vz_init_skinny_kernels();
-extern int g_skinny_mode;                    // vz_tune_set(9, v): SkinnyMode (linear_route.h)
 bool vz_skinny_fused_norm_ok(const LinearArgs& a);
 int vz_init_gemv_kernels();
-void vz_set_gemv_variant(int v);
 // Profiling classes of vz_prof_enable / vz_prof_read
 enum { K_GEMM = 0, K_GEMV = 1, K_ATTN = 2, K_ATTN_DEC = 3, K_NORM = 4, K_OTHER = 5, K_FUSED = 6, K_COMM = 7 };
 // Profiling: when set, the next GEMM/GEMV launch is issued through hipExtLaunchKernelGGL with these events, which
@@ -218,10 +215,6 @@ int vz_launch_gemm256(const LinearArgs& a, hipStream_t s);
 int vz_init_gemm256_kernel();
 int vz_gemm256_async_error(hipStream_t s, int* err, bool reset_only);
 int vz_gemm256_corrupt_tickets(hipStream_t s, int tr, int arrive, int ready);
-void vz_set_gemm_choice(int v);  // 0 auto, 1 force 128x128, 2 force 256x256
-void vz_set_splitk_mode(int v);
-void vz_set_splitk_cap(int v);
-void vz_set_splitk_mid(int v);   // 1: K slices for small grids with M > 512 (default), 0 off
 
 int vz_launch_layernorm(const bf16_t* x, int ldx, bf16_t* y, int ldy, const float* w, const float* b, int rows,
                         int cols, float eps, hipStream_t s);
@@ -247,9 +240,6 @@ struct AttnArgs {
 };
 int vz_launch_attention(const AttnArgs& a, hipStream_t s);
 size_t vz_attn_split_floats(int B, int Hq, int Sq, int Sk);      // `part` floats a head_dim-512 key-split launch wants under knob 23; 0 = no split
-void vz_set_attn_version(int v);
-int vz_attn_version();
-void vz_set_attn_split(int v);
 
 // append attention (attn_append.hip): nnew[b] query tokens of cache row b behind past[b] cached positions whose K / V are in the cache
 struct AttnAppendArgs {

@@ -6,6 +6,7 @@ torch.cuda.current_stream()).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -20,7 +21,7 @@ VZ_ASYNC_STREAMK = 2
 VZ_ASYNC_PERSIST = 3
 VZ_ASYNC_ONESHOT = 4
 VZ_ASYNC_ATTN_O = 5
-ABI_VERSION = 11
+ABI_VERSION = 12
 SCORE_REC, SCORE_WARPED, SCORE_RAW = 1, 2, 4          # vz_llm_decode_scores `what`
 SPEC_CTL_WRITE, SPEC_CTL_HIST, SPEC_CTL_DONE, SPEC_CTL_DRAFTED, SPEC_CTL_STEPS, SPEC_CTL_IDS, SPEC_CTL_WORDS = 0, 1, 2, 3, 4, 8, 16
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF, ACT_SWIGLU = 0, 1, 2, 3
@@ -125,6 +126,8 @@ SYMBOLS = {
     "vz_comm_oneshot_attach": (_I, [_P, _P, _I]),
     "vz_engine_async_error": (_I, [_P, _P]),
     "vz_tune_set": (_I, [_I, _I]),
+    "vz_tune_get": (_I, [_I, C.POINTER(_I)]),
+    "vz_tune_info": (_I, [_I, C.POINTER(_I), C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vz_engine_resize_vocab": (_I, [_P, _I]),
     "vz_op_resample_u8": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "vz_op_anyres_tiles": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -245,6 +248,82 @@ def check(rc: int):
     if rc == VZ_ERR_UNSUPPORTED:
         raise NotImplementedError(msg)
     raise VzError(f"libviszephyr_hip error {rc}: {msg}")
+
+
+# ---- the tune knobs (csrc/tune.h): names, a scope that restores what it found ----
+_knobs: Optional[dict] = None
+
+
+def knobs() -> dict:
+    """{name: (number, default, lo, hi)} of every knob, in table order: read once from vz_tune_info, never copied here"""
+    global _knobs
+    if _knobs is None:
+        table, i = {}, 0
+        k, name, d, lo, hi = C.c_int(), C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+        while lib().vz_tune_info(i, C.byref(k), C.byref(name), C.byref(d), C.byref(lo), C.byref(hi)) == VZ_OK:
+            table[name.value.decode()] = (k.value, d.value, lo.value, hi.value)
+            i += 1
+        _knobs = table
+    return _knobs
+
+
+def _knob_number(knob) -> int:
+    """a knob's number from its name, its number or either as a string; an unknown NAME raises KeyError (an unknown number is the library's to refuse)"""
+    if isinstance(knob, str) and not knob.lstrip("-").isdigit():
+        if knob not in knobs():
+            raise KeyError(f"unknown tune knob {knob!r}; known: {', '.join(knobs())}")
+        return knobs()[knob][0]
+    return int(knob)
+
+
+def tune(knob, value):
+    """vz_tune_set by name or number, for as long as the process lives (a tool's own setting); tests use tuned()"""
+    check(lib().vz_tune_set(_knob_number(knob), int(value)))
+
+
+def tune_get(knob) -> int:
+    v = C.c_int()
+    check(lib().vz_tune_get(_knob_number(knob), C.byref(v)))
+    return v.value
+
+
+@contextlib.contextmanager
+def tuned(*pairs, **values):
+    """Scope with knobs set: tuned(splitk_mid=0, gemm256_streamk=0), or tuned((26, 0), (4, 0)) where the knob is a number or a variable.
+    On entry each knob's current value is read, then the new one set; on exit - exception or not - what was read is set again, in reverse
+    order.  Scopes nest."""
+    found = []
+    try:
+        for knob, value in list(pairs) + list(values.items()):
+            number = _knob_number(knob)
+            was = tune_get(number)
+            tune(number, value)
+            found.append((number, was))
+        yield
+    finally:
+        for number, was in reversed(found):
+            tune(number, was)
+
+
+def _knob_args(settings):
+    """[(knob, value)] of a tool's --knob / VZ_TUNE settings: a list of "k=v" (k a name or a number), or one string of them joined by commas"""
+    if isinstance(settings, str):
+        settings = settings.split(",")
+    return [tuple(kv.split("=", 1)) for kv in settings if kv]
+
+
+def tuned_from_args(settings):
+    """tuned() over "k=v" settings"""
+    return tuned(*_knob_args(settings))
+
+
+def tune_from_args(settings):
+    """tune() over "k=v" settings: a tool's knobs for its whole life; returns {number: value} of what it set"""
+    done = {}
+    for knob, value in _knob_args(settings):
+        tune(knob, value)
+        done[_knob_number(knob)] = int(value)
+    return done
 
 
 def ptr(t: Optional[torch.Tensor]):
