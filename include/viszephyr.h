@@ -472,6 +472,44 @@ typedef struct vz_logits_proc_params {
 int vz_llm_decode_logits_proc(vz_engine* e, const vz_logits_proc_params* p, vz_stream stream);
 int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len,
                          const vz_logits_proc_params* p, vz_stream stream);
+/* Per-row logits processors (csrc/logits_proc.hip: logits_process_rows_kernel): the rows of a continuous batch are
+ * independent requests, so each row takes its processors from its own record of a table in device memory - the per-row tail's form
+ * (vz_llm_decode_sampling_rows) carried to the processors.  The record, 32 ints = 128 bytes, by byte offset:
+ *     0  repetition_penalty   float, > 0, 1 = off
+ *     4  no_repeat_ngram      0..8, 0 = off
+ *     8  min_new_tokens       >= 0: the eos ids are -inf while fewer ids were generated
+ *    12  n_eos                0..4
+ *    16  eos[4]
+ *    32  n_suppress           0..16
+ *    36  suppress[16]
+ *   100  n_seq                0..64 id sequences of sequence_bias / bad_words_ids in the row's region of the sequence table
+ *   104  active               0 = the row is not processed: no logit touched, nothing appended to its history (the other fields are not read)
+ *   108  reserved[5]
+ * The id sequences of row r are entries [0, n_seq) of region r of a per-row table [max_batch][64][12] ints, each entry as in
+ * vz_logits_proc_params.seq.  Same arithmetic, order and limits as vz_llm_decode_logits_proc: bit-identical to it row by row.
+ * vz_llm_decode_logits_proc_rows(enable = 1): arms the launch where the call-level one sits - behind the guidance combine and the raw-row
+ * recorder, in front of the argmax / the sampler / the per-row tail - with every record inactive and every history empty (stream-ordered).
+ * VZ_ERR_ARG together with vz_llm_decode_logits_proc (whichever is armed second); vz_llm_decode_steps refuses it with the beam or the
+ * speculative tail; tensor-parallel engines: VZ_ERR_UNSUPPORTED.  enable = 0: off, no launch is added to the step.
+ * vz_llm_decode_set_row_logits_proc: stream-ordered like vz_llm_decode_set_row - uploads row `row`'s record and its n_seq (= rec->n_seq)
+ * sequences h_seq [n_seq][12] and sets the row's history length and seeded-id count to 0; rec = NULL: the row becomes inactive.  The
+ * whole record and the sequences are checked before the device is touched (VZ_ERR_ARG).  The captured step reads the tables through
+ * pointers: the call changes no kernel argument and captures nothing (vz_llm_decode_info).
+ * vz_op_logits_process_rows: the same kernel on caller-owned fp32 logits [rows <= 64, cols] and histories, row r by h_rows[r]; its
+ * sequences are entries [h_nseq_off[r], h_nseq_off[r + 1]) of h_seq [.][12] (h_nseq_off: rows + 1 ints; NULL when no row has any).
+ * Nothing is appended (the first token of an admitted request: its prefill logits row with an empty history; tests). */
+typedef struct vz_proc_row {
+    float repetition_penalty;
+    int no_repeat_ngram, min_new_tokens;
+    int n_eos, eos[4];
+    int n_suppress, suppress[16];
+    int n_seq, active;
+    int reserved[5];
+} vz_proc_row;
+int vz_llm_decode_logits_proc_rows(vz_engine* e, int enable, vz_stream stream);
+int vz_llm_decode_set_row_logits_proc(vz_engine* e, int row, const vz_proc_row* rec, const int* h_seq, int n_seq, vz_stream stream);
+int vz_op_logits_process_rows(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, const vz_proc_row* h_rows,
+                              const int* h_seq, const int* h_nseq_off, vz_stream stream);
 /* how the last vz_llm_decode_steps ran: *graph = 1 when a captured hipGraph was replayed; *comm_in_graph = 1 when the RCCL
  * collectives of a tensor-parallel engine are part of that graph (0 = eager steps, e.g. after RCCL refused the capture) */
 int vz_llm_decode_mode(vz_engine* e, int* graph, int* comm_in_graph);
@@ -601,6 +639,18 @@ int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, int emb_rows,
                        const int* h_target, const int* h_seq, int n_seq, vz_stream stream);
 int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const int* d_first_ids, vz_stream stream);
 int vz_llm_decode_stop_read(vz_engine* e, int row0, int rows, int* d_at, vz_stream stream);
+/* Per-row stop sequences: the id-sequence rule of the matcher reads row r's sequences from region r of an
+ * engine-owned table [max_batch][VZ_STOP_MAX_SEQ][VZ_STOP_SEQ_STRIDE] and their count from a per-row word; the stop strings stay
+ * call-level and shared.  vz_llm_decode_stop_row_seqs(enable = 1): arms the mode behind vz_llm_decode_stop, or on its own - no stop
+ * string and no call-level sequence at all is allowed here, a row with nothing to match is never a hit.  Every row's region starts as
+ * the call-level sequences and, as with every arming, no row is watched.  While the mode is armed vz_llm_decode_stop is VZ_ERR_ARG
+ * (disarm the mode first); refusals otherwise as for vz_llm_decode_stop.  enable = 0: off (with the matcher off too, no launch is added).
+ * vz_llm_decode_stop_set_row_seqs: stream-ordered - row `row`'s region becomes the call-level sequences followed by its own n_seq
+ * sequences h_seq [n_seq][VZ_STOP_SEQ_STRIDE] ([len, start, the ids newest first]); together they must fit VZ_STOP_MAX_SEQ (VZ_ERR_ARG,
+ * checked before the device is touched).  It captures nothing.  vz_llm_decode_stop_rows keeps its meaning: the row starts clean and its
+ * first token goes through the kernel - call it behind this one. */
+int vz_llm_decode_stop_row_seqs(vz_engine* e, int enable, vz_stream stream);
+int vz_llm_decode_stop_set_row_seqs(vz_engine* e, int row, const int* h_seq, int n_seq, vz_stream stream);
 /* Seeded histories (a generate() call that continues on a kept cache; host ids, stream-ordered; behind the arming, in front of
  * vz_llm_decode_begin / vz_llm_decode_stop_rows).  vz_llm_decode_stop_seed: the last min(n, 63) of the n ids fed before generation begins
  * enter row `row`'s ring in front of its first generated token, so a stop string may begin in them as in the tail of HF's input_ids; the

@@ -465,6 +465,9 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->beam.d) hipFree(e->beam.d);
     if (e->proc.d) hipFree(e->proc.d);
     if (e->proc.d_seq) hipFree(e->proc.d_seq);
+    if (e->proc.d_rows) hipFree(e->proc.d_rows);
+    if (e->proc.d_rowseq) hipFree(e->proc.d_rowseq);
+    if (e->stop.d_rowseq) hipFree(e->stop.d_rowseq);
     if (e->score.d_slot) hipFree(e->score.d_slot);
     if (e->stop.d_state) hipFree(e->stop.d_state);
     if (e->stop.d_tab) hipFree(e->stop.d_tab);
@@ -1243,6 +1246,11 @@ static int* proc_base(const vz_engine* e) { return e->proc.d + proc_len_ints(e->
 static int* proc_hist(const vz_engine* e) { return e->proc.d + 2 * proc_len_ints(e->c); }
 // the stop matcher's per-row count of ids its ring was seeded with (vz_llm_decode_stop_seed): behind the rows' states
 static int* stop_pre(const vz_engine* e) { return e->stop.d_state + (size_t)e->c.max_batch * VZ_STOP_ROW; }
+// the per-row stop sequences (vz_llm_decode_stop_row_seqs): the rows' regions, then the rows' counts; null while the mode is off
+static constexpr size_t STOP_REGION_INTS = (size_t)VZ_STOP_MAX_SEQ * VZ_STOP_SEQ_STRIDE;
+static const int* stop_row_seq(const vz_engine* e, int row0 = 0) { return e->stop.rows_on ? e->stop.d_rowseq + row0 * STOP_REGION_INTS : nullptr; }
+static const int* stop_row_nseq(const vz_engine* e, int row0 = 0) { return e->stop.rows_on ? e->stop.d_rowseq + e->c.max_batch * STOP_REGION_INTS + row0 : nullptr; }
+static bool stop_armed(const vz_engine* e) { return e->stop.on || e->stop.rows_on; }
 // the id-sequence table of sequence_bias / bad_words_ids as the entry points take it (vz_common.h: ProcArgs)
 static int proc_seq_check(const int* h_seq, int n_seq) {
     VZ_CHECK_ARG(n_seq >= 0 && n_seq <= VZ_PROC_MAX_SEQ && (n_seq == 0 || h_seq), "logits_proc: 0..%d id sequences expected, got %d", VZ_PROC_MAX_SEQ, n_seq);
@@ -1370,6 +1378,8 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
             // logits_proc.hip: st.cur still holds the token the previous tail published - the kernel appends it to the row's history itself
             RC(vz_launch_logits_process(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.a, e->proc.a.n_seq ? e->proc.d_seq : nullptr, s, proc_base(e)));
         }
+        // the per-row form: every row by its own record; a row whose record is inactive is left alone
+        if (e->proc.rows_on) RC(vz_launch_logits_process_rows(e->d_logits, B, c.vocab, proc_hist(e), c.max_ctx, e->proc.d, st.cur, e->proc.d_rows, e->proc.d_rowseq, proc_base(e), s));
         if (beam_lp && br.scores) RC(vz_launch_score_raw_rows(e->d_logits, B, c.vocab, br.scores, beam_view(e->beam.d).hidx, br.cap, s));
         switch (tail) {
         case TAIL_SPEC: {
@@ -1411,7 +1421,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
                                       (e->score.what & VZ_SCORE_WARPED) ? e->score.warped : nullptr, e->score.d_slot, e->score.cap, s));
         }
         // stop.hip: the token the tail just left in st.cur through the rows' stop conditions (writes its own state only)
-        if (e->stop.on) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s, stop_pre(e))); }      // (its own profiling scope: one more counted launch)
+        if (stop_armed(e)) { ProfScope pm(e, K_OTHER, s); RC(vz_launch_stop_match(e->stop.a, e->stop.d_state, B, st.cur, 0, s, stop_pre(e), stop_row_seq(e), stop_row_nseq(e))); }      // (its own profiling scope: one more counted launch)
         // guidance.hip: the unconditional rows take the tokens the conditional rows just chose and move on as they did
         if (e->cfg.on) RC(vz_launch_cfg_follow(st.cur, st.pos, st.slot, st.len, B, c.max_ctx, e->rope_max, s));
         RC(vz_launch_step_advance(st.step, e->score.what ? e->score.d_slot : nullptr, s));
@@ -1452,6 +1462,26 @@ static int row_samples_to_device(const char* who, const vz_sample_params* h_rows
     return VZ_OK;
 }
 
+// every arming of the matcher starts with no row watched (stream-ordered behind the steps of an earlier arming): a row is matched from its
+// vz_llm_decode_stop_rows on, never from what an earlier call left in its state
+static int stop_state_unwatched(vz_engine* e, hipStream_t s) {
+    const int mb = e->c.max_batch;
+    if (!e->stop.d_state) {
+        e->stop.h_init.assign((size_t)mb * VZ_STOP_ROW + mb, 0);          // the rows' states, then the rows' seeded-id counts (stop_pre)
+        for (int r = 0; r < mb; ++r) e->stop.h_init[(size_t)r * VZ_STOP_ROW + 1] = VZ_STOP_UNARMED;
+        VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_state, e->stop.h_init.size() * sizeof(int)));
+    }
+    VZ_CHECK_HIP(hipMemcpyAsync(e->stop.d_state, e->stop.h_init.data(), e->stop.h_init.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    return VZ_OK;
+}
+static int stop_seq_check(const char* who, const int* h_seq, int n_seq) {
+    VZ_CHECK_ARG(n_seq == 0 || h_seq, "%s: id sequences without their table", who);
+    for (int k = 0; k < n_seq; ++k)
+        VZ_CHECK_ARG(h_seq[k * VZ_STOP_SEQ_STRIDE] >= 1 && h_seq[k * VZ_STOP_SEQ_STRIDE] <= VZ_STOP_MAX_SEQ_LEN && h_seq[k * VZ_STOP_SEQ_STRIDE + 1] >= 0,
+                     "%s: id sequence %d of %d ids from %d (1..%d ids, start >= 0)", who, k, h_seq[k * VZ_STOP_SEQ_STRIDE], h_seq[k * VZ_STOP_SEQ_STRIDE + 1], VZ_STOP_MAX_SEQ_LEN);
+    return VZ_OK;
+}
+
 // The stop matcher (stop.hip: stop_match_kernel): armed, every decode step whose tail is the argmax, the sampler or the
 // per-row tail passes, behind that tail (and the recorder) and inside the per-token hipGraph, the token each row just chose through the
 // row's stop conditions and records the index of the token at which one first held.  The tables are copied into the engine's own device
@@ -1459,6 +1489,7 @@ static int row_samples_to_device(const char* who, const vz_sample_params* h_rows
 extern "C" int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, int emb_rows, int vec, int n_str, int max_pos, int max_end, int window,
                                   const int* h_target, const int* h_seq, int n_seq, vz_stream stream) {
     NEED_READY();
+    VZ_CHECK_ARG(!e->stop.rows_on, "decode_stop: the per-row stop sequences are armed over the call-level set (vz_llm_decode_stop_row_seqs(0) first)");
     if (!enable) { e->stop.on = 0; memset(&e->stop.a, 0, sizeof(e->stop.a)); return VZ_OK; }
     if (e->tp > 1) { vz_set_error("decode_stop: the stop matcher on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(n_str >= 0 && n_str <= VZ_STOP_MAX_STR && n_seq >= 0 && n_seq <= VZ_STOP_MAX_SEQ && n_str + n_seq >= 1,
@@ -1467,20 +1498,9 @@ extern "C" int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, in
                                 max_pos <= VZ_STOP_MAX_POS && max_end >= 1 && max_end <= VZ_STOP_MAX_END && window >= 1 && window <= VZ_STOP_W),
                  "decode_stop: stop-string tables outside the matcher's limits (rows %d, vec %d, max_valid_positions %d <= %d, max_valid_end_lens %d <= %d, "
                  "maximum_token_len %d <= %d)", emb_rows, vec, max_pos, VZ_STOP_MAX_POS, max_end, VZ_STOP_MAX_END, window, VZ_STOP_W);
-    VZ_CHECK_ARG(n_seq == 0 || h_seq, "decode_stop: id sequences without their table");
-    for (int k = 0; k < n_seq; ++k)
-        VZ_CHECK_ARG(h_seq[k * VZ_STOP_SEQ_STRIDE] >= 1 && h_seq[k * VZ_STOP_SEQ_STRIDE] <= VZ_STOP_MAX_SEQ_LEN && h_seq[k * VZ_STOP_SEQ_STRIDE + 1] >= 0,
-                     "decode_stop: id sequence %d of %d ids from %d (1..%d ids, start >= 0)", k, h_seq[k * VZ_STOP_SEQ_STRIDE], h_seq[k * VZ_STOP_SEQ_STRIDE + 1], VZ_STOP_MAX_SEQ_LEN);
+    RC(stop_seq_check("decode_stop", h_seq, n_seq));
     hipStream_t s = (hipStream_t)stream;
-    const int mb = e->c.max_batch;
-    if (!e->stop.d_state) {
-        e->stop.h_init.assign((size_t)mb * VZ_STOP_ROW + mb, 0);          // the rows' states, then the rows' seeded-id counts (stop_pre)
-        for (int r = 0; r < mb; ++r) e->stop.h_init[(size_t)r * VZ_STOP_ROW + 1] = VZ_STOP_UNARMED;
-        VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_state, e->stop.h_init.size() * sizeof(int)));
-    }
-    // every arming starts with no row watched (stream-ordered behind the steps of an earlier arming): a row is matched from its
-    // vz_llm_decode_stop_rows on, never from what an earlier call left in its state
-    VZ_CHECK_HIP(hipMemcpyAsync(e->stop.d_state, e->stop.h_init.data(), e->stop.h_init.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    RC(stop_state_unwatched(e, s));
     const size_t emb_ints = n_str ? (size_t)emb_rows * vec : 0, tgt_ints = VZ_STOP_MAX_STR, seq_ints = (size_t)VZ_STOP_MAX_SEQ * VZ_STOP_SEQ_STRIDE;
     const size_t need = emb_ints + tgt_ints + seq_ints;
     std::vector<int> tab(need, 0);                  // [emb | target | seq], as the device holds it
@@ -1512,9 +1532,48 @@ extern "C" int vz_llm_decode_stop(vz_engine* e, int enable, const int* h_emb, in
 // kernel: one implementation, no host mirror
 extern "C" int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const int* d_first_ids, vz_stream stream) {
     NEED_READY();
-    VZ_CHECK_ARG(e->stop.on, "decode_stop_rows: the stop matcher is off (vz_llm_decode_stop)");
+    VZ_CHECK_ARG(stop_armed(e), "decode_stop_rows: the stop matcher is off (vz_llm_decode_stop)");
     VZ_CHECK_ARG(row0 >= 0 && rows >= 1 && row0 + rows <= e->c.max_batch && d_first_ids, "decode_stop_rows: rows [%d, %d) outside max_batch = %d", row0, row0 + rows, e->c.max_batch);
-    return vz_launch_stop_match(e->stop.a, e->stop.d_state + (size_t)row0 * VZ_STOP_ROW, rows, d_first_ids, 1, (hipStream_t)stream, stop_pre(e) + row0);
+    return vz_launch_stop_match(e->stop.a, e->stop.d_state + (size_t)row0 * VZ_STOP_ROW, rows, d_first_ids, 1, (hipStream_t)stream, stop_pre(e) + row0,
+                                stop_row_seq(e, row0), stop_row_nseq(e, row0));
+}
+
+// Per-row stop sequences: rule 2 of the matcher by row.  Arming fills every row's region with the call-level
+// sequences of the armed matcher (none when it is off) and starts, as every arming does, with no row watched.
+extern "C" int vz_llm_decode_stop_row_seqs(vz_engine* e, int enable, vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->stop.rows_on = 0; e->stop.h_call.clear(); return VZ_OK; }
+    if (e->tp > 1) { vz_set_error("decode_stop_row_seqs: the stop matcher on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    const int mb = e->c.max_batch, n_call = e->stop.on ? e->stop.a.n_seq : 0;
+    RC(stop_state_unwatched(e, s));
+    if (!e->stop.d_rowseq) VZ_CHECK_HIP(hipMalloc((void**)&e->stop.d_rowseq, (mb * STOP_REGION_INTS + mb) * sizeof(int)));
+    // the call-level sequences as the armed matcher holds them: the tail of its table image [emb | target | seq]
+    e->stop.h_call.assign(STOP_REGION_INTS, 0);
+    if (n_call) memcpy(e->stop.h_call.data(), e->stop.h_tab.data() + (e->stop.h_tab.size() - STOP_REGION_INTS), (size_t)n_call * VZ_STOP_SEQ_STRIDE * sizeof(int));
+    std::vector<int> img(mb * STOP_REGION_INTS + mb, 0);
+    for (int r = 0; r < mb; ++r) {
+        memcpy(img.data() + r * STOP_REGION_INTS, e->stop.h_call.data(), STOP_REGION_INTS * sizeof(int));
+        img[mb * STOP_REGION_INTS + r] = n_call;
+    }
+    RC(upload_ints(e, img.data(), img.size(), e->stop.d_rowseq, s));
+    e->stop.rows_on = 1;
+    return VZ_OK;
+}
+
+extern "C" int vz_llm_decode_stop_set_row_seqs(vz_engine* e, int row, const int* h_seq, int n_seq, vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(e->stop.rows_on, "decode_stop_set_row_seqs: the per-row stop sequences are off (vz_llm_decode_stop_row_seqs)");
+    const int n_call = e->stop.on ? e->stop.a.n_seq : 0;
+    VZ_CHECK_ARG(row >= 0 && row < e->c.max_batch && n_seq >= 0 && n_call + n_seq <= VZ_STOP_MAX_SEQ, "decode_stop_set_row_seqs: row %d outside max_batch = %d, or %d "
+                 "call-level + %d own id sequences, more than %d", row, e->c.max_batch, n_call, n_seq, VZ_STOP_MAX_SEQ);
+    RC(stop_seq_check("decode_stop_set_row_seqs", h_seq, n_seq));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> img(e->stop.h_call);                                 // the call-level sequences in front of the row's own
+    if (n_seq) memcpy(img.data() + (size_t)n_call * VZ_STOP_SEQ_STRIDE, h_seq, (size_t)n_seq * VZ_STOP_SEQ_STRIDE * sizeof(int));
+    const int total = n_call + n_seq;
+    RC(upload_ints(e, img.data(), img.size(), e->stop.d_rowseq + row * STOP_REGION_INTS, s));
+    return upload_ints(e, &total, 1, e->stop.d_rowseq + e->c.max_batch * STOP_REGION_INTS + row, s);
 }
 
 // Seeds row `row`'s ring with the last ids that were fed before generation begins (a call that continues on a kept cache), newest last:
@@ -1522,7 +1581,7 @@ extern "C" int vz_llm_decode_stop_rows(vz_engine* e, int row0, int rows, const i
 // only.  Behind the arming (which clears every row), in front of vz_llm_decode_stop_rows (which keeps the ring); stream-ordered.
 extern "C" int vz_llm_decode_stop_seed(vz_engine* e, int row, const int* h_ids, int n, vz_stream stream) {
     NEED_READY();
-    VZ_CHECK_ARG(e->stop.on && e->stop.d_state, "decode_stop_seed: the stop matcher is off (vz_llm_decode_stop)");
+    VZ_CHECK_ARG(stop_armed(e) && e->stop.d_state, "decode_stop_seed: the stop matcher is off (vz_llm_decode_stop)");
     VZ_CHECK_ARG(row >= 0 && row < e->c.max_batch && n >= 0 && (h_ids || n == 0), "decode_stop_seed: row %d outside max_batch = %d, or %d ids", row, e->c.max_batch, n);
     int img[VZ_STOP_W + 1] = {0};
     const int k = std::min(n, VZ_STOP_W - 1);
@@ -1680,6 +1739,7 @@ extern "C" int vz_llm_decode_logits_proc(vz_engine* e, const vz_logits_proc_para
     if (!p) { e->proc.on = 0; return VZ_OK; }
     const vz_config& c = e->c;
     if (e->tp > 1) { vz_set_error("decode_logits_proc: logits processors on a tensor-parallel engine are not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(!e->proc.rows_on, "decode_logits_proc: the per-row logits processors are armed (vz_llm_decode_logits_proc_rows): one of the two forms at a time");
     ProcArgs a;
     RC(proc_args_of(*p, &a));
     VZ_CHECK_ARG(c.vocab <= 65536, "decode_logits_proc: vocabulary of %d, the kernel's bitmaps hold 65536", c.vocab);
@@ -1735,6 +1795,84 @@ extern "C" int vz_op_logits_process(float* d_logits, int rows, int cols, int* d_
         VZ_CHECK_HIP(hipMemcpy(d_seq, p->seq, (size_t)a.n_seq * VZ_PROC_SEQ_STRIDE * sizeof(int), hipMemcpyHostToDevice));
     }
     return vz_launch_logits_process(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, a, (const int*)d_seq, s);
+}
+
+// Per-row logits processors (logits_proc.hip: logits_process_rows_kernel).  One record per row of the decode batch in
+// device memory, every one inactive after the arming; the histories are the call-level form's buffer (the two forms exclude each other).
+static constexpr size_t PROC_REGION_INTS = (size_t)VZ_PROC_MAX_SEQ * VZ_PROC_SEQ_STRIDE;
+static int proc_row_of(const vz_proc_row* rec, const int* h_seq, int n_seq, ProcRow* out) {
+    memset(out, 0, sizeof(*out));
+    if (!rec || !rec->active) return VZ_OK;          // inactive: the other fields are neither read nor kept
+    memcpy(out, rec, sizeof(*out));
+    out->active = 1; memset(out->pad, 0, sizeof(out->pad));
+    RC(vz_proc_row_check(*out));
+    VZ_CHECK_ARG(n_seq == out->n_seq, "logits_proc rows: the record names %d id sequences, %d were handed over", out->n_seq, n_seq);
+    RC(proc_seq_check(h_seq, n_seq));
+    for (int i = 0; i < 4; ++i) if (i >= out->eos.n) out->eos.id[i] = -1;
+    for (int i = 0; i < 16; ++i) if (i >= out->n_suppress) out->suppress[i] = -1;
+    return VZ_OK;
+}
+
+extern "C" int vz_llm_decode_logits_proc_rows(vz_engine* e, int enable, vz_stream stream) {
+    NEED_READY();
+    if (!enable) { e->proc.rows_on = 0; return VZ_OK; }
+    const vz_config& c = e->c;
+    if (e->tp > 1) { vz_set_error("decode_logits_proc_rows: logits processors on a tensor-parallel engine are not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(!e->proc.on, "decode_logits_proc_rows: the call-level logits processors are armed (vz_llm_decode_logits_proc): one of the two forms at a time");
+    VZ_CHECK_ARG(c.vocab <= 65536, "decode_logits_proc_rows: vocabulary of %d, the kernel's bitmaps hold 65536", c.vocab);
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->proc.d) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d, (2 * proc_len_ints(c) + (size_t)c.max_batch * c.max_ctx) * sizeof(int)));
+    if (!e->proc.d_rows) VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d_rows, (size_t)c.max_batch * sizeof(ProcRow)));
+    if (!e->proc.d_rowseq) {          // (zeroed once: the kernel requests a row's whole region before it knows how much of it counts)
+        VZ_CHECK_HIP(hipMalloc((void**)&e->proc.d_rowseq, (size_t)c.max_batch * PROC_REGION_INTS * sizeof(int)));
+        VZ_CHECK_HIP(hipMemsetAsync(e->proc.d_rowseq, 0, (size_t)c.max_batch * PROC_REGION_INTS * sizeof(int), s));
+    }
+    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d, 0, 2 * proc_len_ints(c) * sizeof(int), s));
+    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d_rows, 0, (size_t)c.max_batch * sizeof(ProcRow), s));      // every record inactive
+    e->proc.rows_on = 1;
+    return VZ_OK;
+}
+
+extern "C" int vz_llm_decode_set_row_logits_proc(vz_engine* e, int row, const vz_proc_row* rec, const int* h_seq, int n_seq, vz_stream stream) {
+    NEED_READY();
+    const vz_config& c = e->c;
+    VZ_CHECK_ARG(e->proc.rows_on, "decode_set_row_logits_proc: the per-row logits processors are off (vz_llm_decode_logits_proc_rows)");
+    VZ_CHECK_ARG(row >= 0 && row < c.max_batch, "decode_set_row_logits_proc: row %d outside max_batch = %d", row, c.max_batch);
+    ProcRow pr;
+    RC(proc_row_of(rec, h_seq, n_seq, &pr));
+    hipStream_t s = (hipStream_t)stream;
+    // the sequences first, the record behind them (stream order: a step between the two copies cannot be - they are enqueued back to
+    // back), then the row's history restarts: length and seeded-id count 0
+    if (pr.active && pr.n_seq) RC(upload_ints(e, h_seq, (size_t)pr.n_seq * VZ_PROC_SEQ_STRIDE, e->proc.d_rowseq + row * PROC_REGION_INTS, s));
+    RC(upload_ints(e, (const int*)&pr, sizeof(pr) / sizeof(int), (int*)(e->proc.d_rows + row), s));
+    VZ_CHECK_HIP(hipMemsetAsync(e->proc.d + row, 0, sizeof(int), s));
+    VZ_CHECK_HIP(hipMemsetAsync(proc_base(e) + row, 0, sizeof(int), s));
+    return VZ_OK;
+}
+
+// the same kernel on caller-owned logits and histories, row r by h_rows[r]; the records and the rows' sequence regions go through this
+// (device, stream)'s own scratch.  Nothing is appended.
+extern "C" int vz_op_logits_process_rows(float* d_logits, int rows, int cols, int* d_hist, int hist_stride, int* d_hist_len, const vz_proc_row* h_rows,
+                                         const int* h_seq, const int* h_nseq_off, vz_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    VZ_CHECK_ARG(d_logits && d_hist && d_hist_len && h_rows && rows >= 1 && rows <= 64 && cols >= 1 && hist_stride >= 1, "logits_process_rows: bad argument (1..64 rows)");
+    const size_t rec_ints = sizeof(ProcRow) / sizeof(int);
+    std::vector<int> img((rec_ints + PROC_REGION_INTS) * rows, 0);       // [records | regions]
+    for (int r = 0; r < rows; ++r) {
+        const int k0 = h_nseq_off ? h_nseq_off[r] : 0, k1 = h_nseq_off ? h_nseq_off[r + 1] : 0;
+        VZ_CHECK_ARG(k0 >= 0 && k1 >= k0 && (k1 == k0 || h_seq), "logits_process_rows: row %d takes the id sequences [%d, %d) of a table", r, k0, k1);
+        const int* q = k1 > k0 ? h_seq + (size_t)k0 * VZ_PROC_SEQ_STRIDE : nullptr;
+        ProcRow* pr = (ProcRow*)(img.data() + rec_ints * r);
+        RC(proc_row_of(h_rows + r, q, k1 - k0, pr));
+        if (pr->active && pr->n_seq) memcpy(img.data() + rec_ints * rows + PROC_REGION_INTS * r, q, (size_t)pr->n_seq * VZ_PROC_SEQ_STRIDE * sizeof(int));
+    }
+    void* d = nullptr; size_t have = 0;
+    const size_t need = (rec_ints + PROC_REGION_INTS) * 64 * sizeof(int);
+    RC(vz_stream_ws(8, s, need, false, &d, &have));
+    VZ_CHECK_ARG(d && have >= need, "logits_process_rows: first use of a stream inside a capture (call it once before capturing)");
+    VZ_CHECK_HIP(hipStreamSynchronize(s));          // an earlier call's kernel has read its tables
+    VZ_CHECK_HIP(hipMemcpy(d, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice));
+    return vz_launch_logits_process_rows(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, (const ProcRow*)d, (const int*)d + rec_ints * rows, nullptr, s);
 }
 
 // Classifier-free guidance in the step (hf:generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor; guidance.hip;
@@ -2041,7 +2179,8 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     case TAIL_ROWS: case TAIL_GREEDY: break;
     }
     if (e->proc.on) { k.proc_on = 1; k.proc = e->proc.a; k.proc_hist = e->proc.d; k.proc_seq = e->proc.a.n_seq ? e->proc.d_seq : nullptr; }
-    if (e->stop.on) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
+    if (stop_armed(e)) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
+    k.proc_rows_on = e->proc.rows_on; k.stop_rows_on = e->stop.rows_on;
     if (e->cfg.on) { k.cfg_scale = e->cfg.scale; k.cfg_pairs = e->cfg.pairs; }
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
@@ -2078,8 +2217,10 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
                  "together with the beam or the speculative tail, nor on a tensor-parallel engine");
     VZ_CHECK_ARG(!e->score.what || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the step recorder (vz_llm_decode_scores) runs behind the "
                  "argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
-    VZ_CHECK_ARG(!e->stop.on || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the stop matcher (vz_llm_decode_stop) runs behind the "
+    VZ_CHECK_ARG(!stop_armed(e) || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the stop matcher (vz_llm_decode_stop) runs behind the "
                  "argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
+    VZ_CHECK_ARG(!e->proc.rows_on || (tail != TAIL_BEAM && tail != TAIL_SPEC), "decode_steps: the per-row logits processors (vz_llm_decode_logits_proc_rows) run in "
+                 "front of the argmax, the sampler or the per-row tail only, not with the beam or the speculative tail");
     VZ_CHECK_ARG(!e->score.what || n <= e->score.cap, "decode_steps: %d steps, the step recorder's rings hold cap_steps = %d", n, e->score.cap);
     DecodeWs w;
     RC(carve_stage(e, "decode", [&](Carver& m) { return carve_decode(m, c, Shard{e->Hq_l, e->Hkv_l, e->I_l}, B, spec); }, &w));

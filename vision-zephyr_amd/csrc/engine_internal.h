@@ -76,8 +76,9 @@ struct DecodeGraphKey {
     int* stop_state; StopArgs stop;      // the stop matcher behind the tail: its state, tables and dims (zero when off)
     BeamRowsArgs beam_rows;              // the beam tail's row recorder: its rings (zero when off)
     float cfg_scale; int cfg_pairs;      // classifier-free guidance between the logits and the processors (zero when off)
+    int proc_rows_on, stop_rows_on;      // the per-row processors / per-row stop sequences: mode bits only - their tables are engine-owned, stable device memory read through pointers
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 + 2 * 4 &&
               sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos) + sizeof(RowSample), "padding in the graph key");
 
@@ -138,14 +139,20 @@ struct vz_engine {
     // of the argmax / the sampler.  d = [hist_len: max_batch ints, padded to 64 | hist: max_batch x max_ctx ints], its own allocation
     // d_seq / h_seq = the id-sequence table of sequence_bias / bad_words_ids (VZ_PROC_MAX_SEQ entries) and its host image: an arming
     // with an equal table uploads nothing; seq_epoch counts the uploads
-    struct { int on = 0; ProcArgs a{}; int* d = nullptr; int* d_seq = nullptr; std::vector<int> h_seq; int seq_epoch = 0; } proc;
+    // rows_on (vz_llm_decode_logits_proc_rows): the per-row launch instead, over the same histories - d_rows = max_batch
+    // records, d_rowseq = max_batch regions of VZ_PROC_MAX_SEQ sequence entries; allocated once, never moved
+    struct { int on = 0; ProcArgs a{}; int* d = nullptr; int* d_seq = nullptr; std::vector<int> h_seq; int seq_epoch = 0;
+             int rows_on = 0; ProcRow* d_rows = nullptr; int* d_rowseq = nullptr; } proc;
     // step recorder (vz_llm_decode_scores; sampling.hip: token_scores_kernel): behind the tail, a record per row and step into the caller's
     // rings of `cap` steps; d_slot = the steps launched since vz_llm_decode_begin (one word of its own, counted by the step-advance launch)
     struct { unsigned what = 0; float *rec = nullptr, *warped = nullptr, *raw = nullptr; int cap = 0; int* d_slot = nullptr; } score;
     // stop matcher (vz_llm_decode_stop; stop.hip: stop_match_kernel): behind the tail and the recorder.  d_state = max_batch rows of VZ_STOP_ROW
     // ints [n | at | ring]; d_tab = the tables of the armed stop set [emb | target | seq] (a.emb / a.target / a.seq point into it)
     // h_tab = the host image of d_tab (an arming with the same stop set uploads nothing); h_init = the state with no row watched
-    struct { int on = 0; StopArgs a{}; int* d_state = nullptr; int* d_tab = nullptr; size_t tab_ints = 0; std::vector<int> h_tab, h_init; } stop;
+    // rows_on (vz_llm_decode_stop_row_seqs): rule 2 reads d_rowseq = max_batch regions of VZ_STOP_MAX_SEQ entries, then
+    // max_batch counts; h_call = the call-level sequences every region starts with (a.n_seq entries; the matcher may be off: none)
+    struct { int on = 0; StopArgs a{}; int* d_state = nullptr; int* d_tab = nullptr; size_t tab_ints = 0; std::vector<int> h_tab, h_init;
+             int rows_on = 0; int* d_rowseq = nullptr; std::vector<int> h_call; } stop;
     // classifier-free guidance (vz_llm_decode_guidance; guidance.hip): orthogonal to the tail - armed, the decode batch is 2 * pairs rows
     // (row r < pairs a prompt, row pairs + r its negative prompt) and everything behind the logits runs on the first `pairs` rows
     struct { int on = 0, pairs = 0; float scale = 1.f; } cfg;

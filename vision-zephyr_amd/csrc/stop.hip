@@ -12,13 +12,16 @@
 // The common step - no stop string can end in the new token, no sequence ends in it - is two memory round trips: the new token with the
 // state, then the token's table entry with the target lengths and the sequences' heads; the ring slot and n are written, done.  When a walk is needed the table
 // rows of all older window tokens are requested as batches of 8 independent loads per lane into LDS and the walks then run in LDS.
+// Per-row mode: rule 2 takes row r's sequences and their count from region r of a per-row table instead of the shared
+// one - the call-level sequences are copied in front of every row's own by whoever fills it; rule 1 stays shared.
 // The kernel writes the state only: never a word the step reads.
 #include "vz_common.h"
 
 #define STOP_MAX_VEC (VZ_STOP_MAX_STR * (VZ_STOP_MAX_POS + VZ_STOP_MAX_END) + 1)
 
 __global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restrict__ state, const int* __restrict__ ids, int reset,
-                                                        const int* __restrict__ pre) {
+                                                        const int* __restrict__ pre, const int* __restrict__ row_seq,
+                                                        const int* __restrict__ row_nseq) {
     __shared__ int rowsL[(VZ_STOP_W - 1) * STOP_MAX_VEC];
     const int lane = threadIdx.x;
     int* st = state + (size_t)blockIdx.x * VZ_STOP_ROW;
@@ -35,9 +38,13 @@ __global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restr
         end_len = a.emb[(size_t)ct * a.vec + a.n_str * a.max_pos + lane];
         target = a.target[s_idx];
     }
-    const int* sq = a.seq + lane * VZ_STOP_SEQ_STRIDE;      // [len, start, ids newest first]
+    // per-row mode (row_seq): the row's own region and count; the count is requested beside the heads, not in front of them - the region
+    // holds VZ_STOP_MAX_SEQ entries whatever the count is
+    const int* sq = (row_seq ? row_seq + (size_t)blockIdx.x * VZ_STOP_MAX_SEQ * VZ_STOP_SEQ_STRIDE : a.seq) + lane * VZ_STOP_SEQ_STRIDE;      // [len, start, ids newest first]
     int len = 0, start = 0, head = 0;
-    if (lane < a.n_seq) { len = sq[0]; start = sq[1]; head = sq[2]; }
+    int n_seq = row_seq ? row_nseq[blockIdx.x] : a.n_seq;
+    if (lane < (row_seq ? VZ_STOP_MAX_SEQ : a.n_seq)) { len = sq[0]; start = sq[1]; head = sq[2]; }
+    n_seq = min(max(__builtin_amdgcn_readfirstlane(n_seq), 0), VZ_STOP_MAX_SEQ);
     n = __builtin_amdgcn_readfirstlane(n);
     at = __builtin_amdgcn_readfirstlane(at);
     if (at != -1) return;                                   // stopped already (sticky), or not armed
@@ -45,7 +52,7 @@ __global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restr
     if (lane == (n & (VZ_STOP_W - 1))) { ringv = tok; st[2 + lane] = tok; }
 
     // rule 2: the newest id first, the rest only for a sequence that ends in it
-    bool ok2 = lane < a.n_seq && len >= 1 && len <= VZ_STOP_MAX_SEQ_LEN && n1 >= start + len && head == tok;
+    bool ok2 = lane < n_seq && len >= 1 && len <= VZ_STOP_MAX_SEQ_LEN && n1 >= start + len && head == tok;
     if (__any(ok2)) {
         // the older ids of every sequence whose head matched, requested as one batch (the table row holds VZ_STOP_MAX_SEQ_LEN ids whatever
         // len is), then compared in registers against ring values moved by __shfl: no dependent load per id
@@ -106,8 +113,8 @@ __global__ __launch_bounds__(64) void stop_match_kernel(StopArgs a, int* __restr
     }
 }
 
-static int stop_args_ok(const StopArgs& a) {
-    VZ_CHECK_ARG(a.n_str >= 0 && a.n_str <= VZ_STOP_MAX_STR && a.n_seq >= 0 && a.n_seq <= VZ_STOP_MAX_SEQ && a.n_str + a.n_seq >= 1,
+static int stop_args_ok(const StopArgs& a, bool per_row) {
+    VZ_CHECK_ARG(a.n_str >= 0 && a.n_str <= VZ_STOP_MAX_STR && a.n_seq >= 0 && a.n_seq <= VZ_STOP_MAX_SEQ && (per_row || a.n_str + a.n_seq >= 1),
                  "stop_match: %d stop strings (0..%d), %d id sequences (0..%d), at least one of either", a.n_str, VZ_STOP_MAX_STR, a.n_seq, VZ_STOP_MAX_SEQ);
     if (a.n_str) {
         VZ_CHECK_ARG(a.emb && a.target && a.emb_rows >= 1, "stop_match: stop strings without their tables");
@@ -121,10 +128,11 @@ static int stop_args_ok(const StopArgs& a) {
     return VZ_OK;
 }
 
-int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre) {
-    VZ_CHECK_ARG(state && ids && rows >= 1, "stop_match: bad argument");
-    { int r = stop_args_ok(a); if (r) return r; }
-    hipLaunchKernelGGL(stop_match_kernel, dim3(rows), dim3(64), 0, s, a, state, ids, reset, pre);
+int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre, const int* row_seq,
+                         const int* row_nseq) {
+    VZ_CHECK_ARG(state && ids && rows >= 1 && (row_seq == nullptr) == (row_nseq == nullptr), "stop_match: bad argument");
+    { int r = stop_args_ok(a, row_seq != nullptr); if (r) return r; }
+    hipLaunchKernelGGL(stop_match_kernel, dim3(rows), dim3(64), 0, s, a, state, ids, reset, pre, row_seq, row_nseq);
     VZ_LAUNCH_CHECK();
     return VZ_OK;
 }

@@ -404,7 +404,10 @@ int vz_launch_score_raw_rows(const float* logits, int rows, int cols, float* raw
 struct StopArgs { const int* emb; const int* target; const int* seq; int emb_rows, vec, n_str, max_pos, max_end, window, n_seq, pad; };
 static_assert(sizeof(StopArgs) == 3 * 8 + 8 * 4, "padding in StopArgs");
 // one new id per row (ids[row]) through the matcher; reset != 0: the rows start clean (n = 0, at = -1) and are armed
-int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre = nullptr);
+// row_seq != null: rule 2 reads row r's sequences from region r of row_seq [rows][VZ_STOP_MAX_SEQ][VZ_STOP_SEQ_STRIDE] and
+// their count from row_nseq[r] instead of a.seq / a.n_seq (then a.n_str = a.n_seq = 0 is allowed: a row with nothing to match is never a hit)
+int vz_launch_stop_match(const StopArgs& a, int* state, int rows, const int* ids, int reset, hipStream_t s, const int* pre = nullptr,
+                         const int* row_seq = nullptr, const int* row_nseq = nullptr);
 // beam search (beam.hip): K = max(2, 1 + n_eos) * nb candidates per group, as hf:generation/utils.py `_beam_search` keeps
 struct BeamEos { int n; int id[4]; };
 int vz_beam_k(int nb, int n_eos);
@@ -422,6 +425,18 @@ static_assert(sizeof(ProcArgs) == 6 * 4 + sizeof(BeamEos) + 16 * 4, "padding in 
 // appended first (saturating at hist_stride); base != null: base[row] ids of the history were seeded, min_new counts those behind them
 int vz_launch_logits_process(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
                              const ProcArgs& a, const int* seqtab, hipStream_t s, const int* base = nullptr);
+// the per-row form: record r of a table in device memory arms row r (vz_proc_row of the C ABI, 32 ints; active = 0:
+// the row's workgroup leaves behind the record), region r of d_seqtab [rows][VZ_PROC_MAX_SEQ][VZ_PROC_SEQ_STRIDE] holds its id sequences
+struct ProcRow { float penalty; int ngram, min_new; BeamEos eos; int n_suppress; int suppress[16]; int n_seq, active; int pad[5]; };
+static_assert(sizeof(ProcRow) == 128 && sizeof(vz_proc_row) == sizeof(ProcRow) && offsetof(vz_proc_row, repetition_penalty) == offsetof(ProcRow, penalty) &&
+              offsetof(vz_proc_row, no_repeat_ngram) == offsetof(ProcRow, ngram) && offsetof(vz_proc_row, min_new_tokens) == offsetof(ProcRow, min_new) &&
+              offsetof(vz_proc_row, n_eos) == offsetof(ProcRow, eos.n) && offsetof(vz_proc_row, eos) == offsetof(ProcRow, eos.id) &&
+              offsetof(vz_proc_row, n_suppress) == offsetof(ProcRow, n_suppress) && offsetof(vz_proc_row, suppress) == offsetof(ProcRow, suppress) &&
+              offsetof(vz_proc_row, n_seq) == offsetof(ProcRow, n_seq) && offsetof(vz_proc_row, active) == offsetof(ProcRow, active),
+              "vz_proc_row is the table entry");
+int vz_proc_row_check(const ProcRow& a);      // vz_launch_logits_process's limits on one record (an inactive one passes)
+int vz_launch_logits_process_rows(float* logits, int rows, int cols, int* hist, int hist_stride, int* hist_len, const int* cur,
+                                  const ProcRow* d_records, const int* d_seqtab, const int* base, hipStream_t s);
 int vz_launch_beam_select(const float* logits, int rows, int cols, int nb_in, int nb_out, const BeamEos& eos, const float* scores_in,
                           float* cand_s, int* cand_t, int* hist, const int* hidx, int hist_cap, int* next_tok, float* next_score,
                           int* next_parent, const RowEmit& emit, bool on_rows, hipStream_t s);      // on_rows: `logits` are log-prob rows already

@@ -891,7 +891,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     # ---- continuous batching: the 23 K-item eval loop without waiting for a batch's longest answer ----
     @torch.no_grad()
     def generate_stream(self, requests, max_new_tokens: int = 128, eos_token_id=None, rows: Optional[int] = None, sync_every: int = 16,
-                        admit: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_sequences=None):
+                        admit: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_sequences=None, per_request: bool = False):
         """Generation over an iterable of requests - dicts with `input_ids` [1, L] (IMAGE_TOKEN_INDEX sentinels allowed),
         optional `images` ([N,3,336,336]) / `images_size`, optional `max_new_tokens`, optional sampling parameters `do_sample`,
         `temperature`, `top_p`, `top_k`, `seed` (read as `generate` reads them; greedy without them) - with CONTINUOUS batching: up to `rows`
@@ -910,7 +910,8 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         its prefill logits with draw counter 0 and its row then steps with the per-row tail (csrc/sampling.hip: sample_rows_kernel)
         under the request's own seed and counter, whichever cache row it lands in.  The per-row tail is armed when the first sampled
         request is admitted; a call in which no request samples runs as it always did.  `repetition_penalty`, `no_repeat_ngram_size`,
-        `min_new_tokens` and `suppress_tokens` in a request raise NotImplementedError.
+        `min_new_tokens` and `suppress_tokens` in a request raise NotImplementedError (so do `sequence_bias`, `bad_words_ids` and
+        `stop_token_sequences`) unless the call opts in with `per_request=True`, below.
 
         Admissions are BATCHED when the engine has cache rows to spare (`max_batch > rows`): all requests entering at one sync
         share one Zephyr prefill (right-padded, up to `admit` = min(max_batch - rows, 16) sequences) into the spare rows, one
@@ -928,14 +929,32 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         admission, and decides them on the device behind every step's tail; where each row stopped rides with the chunk's ids.  A
         stopped request is yielded inclusive of its stopping token and its row parked at that sync.  A stop set beyond the matcher's
         limits raises (NotImplementedError for stop strings, ValueError for more than 16 or malformed `stop_token_sequences`) before
-        anything runs: this loop has no per-token host path, and a stop condition is never dropped.  Per-request stop sets are not built."""
+        anything runs: this loop has no per-token host path, and a stop condition is never dropped.
+
+        `per_request=True` (opt-in, as `beam_extended` is for the beam path): a request may carry its own logits processors -
+        `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`, `suppress_tokens`, `sequence_bias`, `bad_words_ids`, read by
+        vz_hip.logits_proc.parse with the call's eos ids and the model's vocabulary (HF's ValueErrors, the kernel's limits) - and its own
+        `stop_token_sequences`, matched behind the call's (together at most 16).  Up to the same kernel-route re-association every
+        request gets the tokens `generate(input_ids, <its own keywords>)` gives it alone; one that stops on a sequence is yielded
+        inclusive of the stopping token.  Both modes are armed once, before the first admission: every step then
+        runs the per-row processor kernel (csrc/logits_proc.hip: logits_process_rows_kernel; a row whose request names no key has an
+        inactive record and is left alone) and the stop matcher in its per-row mode, their tables written per row at admission with no
+        re-capture.  A request's first token goes through `binding.logits_process_rows` on its prefill logits row with an empty history;
+        when its row is parked its record is deactivated.  A stream in which no request names a key yields the ids of the same stream
+        with the flag off.  Per-request stop strings, guidance and eos ids are not built; tensor-parallel engines: NotImplementedError."""
         from vz_hip import binding as B
+        from vz_hip import logits_proc as LP
         from vz_hip import sample_rows as SR
         from vz_hip import scores as SC
         from vz_hip import stop as ST
         stop, host_stop = ST.parse(stop_strings, tokenizer, None, self.generation_config, True, stop_token_sequences)
         if host_stop is not None or (stop is not None and self.engine.tp_size > 1):
             raise NotImplementedError("generate_stream: these stop strings are beyond what the device matcher takes (vz_hip.stop.parse)")
+        if per_request and self.engine.tp_size > 1:
+            raise NotImplementedError("generate_stream: per_request=True on a tensor-parallel engine is not built")
+        watched = stop is not None or per_request          # the stop matcher runs: rows are watched from their admission on
+        n_call = len(stop.seqs) if stop is not None else 0
+        own = {}                                            # per_request: request index -> (its ProcConfig or None, its own stop sequences)
         self._kv_epoch += 1
         self._ensure_ready()
         eng = self.engine
@@ -974,9 +993,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             S = emb.shape[1]
             if S + budget > eng.max_ctx:
                 raise ValueError(f"request {idx}: prompt ({S}) + max_new_tokens ({budget}) exceeds the engine's max_ctx ({eng.max_ctx})")
-            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed), SC.wants_logprobs(req)
+            if per_request:
+                own[idx] = (LP.parse_request(req, sorted(eos), self.config.vocab_size), ST.parse_row_sequences(req.get("stop_token_sequences"), n_call))
+            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed, per_request), SC.wants_logprobs(req)
 
-        def first_tokens(logits, params, want):     # one launch and one readback for the group: argmax, or each row by its own parameters
+        def first_tokens(logits, params, want, cfgs=None):     # one launch and one readback for the group: argmax, or each row by its own parameters
+            if cfgs is not None and any(c is not None for c in cfgs):      # each row's own processors over an empty history, in place
+                B.logits_process_rows(logits, cfgs)
             ids = B.argmax(logits) if not any(p.sample for p in params) else B.sample_rows(logits, params)
             if not any(want):
                 return ids.tolist(), None
@@ -984,6 +1007,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             return ids.tolist(), (x - lse).tolist()
 
         try:
+            if per_request:                         # every record inactive, every row's stop sequences the call's: armed once
+                eng.set_logits_proc_rows(True)
+                eng.set_stop_row_seqs(True)
             while True:
                 while not exhausted:                # admit requests into free rows
                     free = [r for r in range(n_rows) if slots[r] is None]
@@ -1000,15 +1026,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     if not group:
                         break
                     want = [g[5] for g in group]
+                    cfgs = [own[g[0]][0] for g in group] if per_request else None
                     if len(group) == 1:             # straight into the free row
                         idx, emb, S, budget, par, _ = group[0]
-                        firsts, lp0 = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par], want)
+                        firsts, lp0 = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par], want, cfgs)
                     else:                           # one prefill for the group in the spare rows, one readback
                         Smax = max(g[2] for g in group)
                         pad = torch.zeros(len(group), Smax, group[0][1].shape[-1], dtype=torch.bfloat16, device=self.device)
                         for j, g in enumerate(group):
                             pad[j, :g[2]] = g[1][0]
-                        firsts, lp0 = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group], want)
+                        firsts, lp0 = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group], want, cfgs)
                     moves = []
                     if not scored and any(want):
                         eng.set_scores(max(1, int(sync_every)), n_rows)      # records only; restarts the ring between two chunks
@@ -1030,12 +1057,17 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                             moves.append((n_rows + j, r, S))
                         slots[r] = [idx, [first], budget, [lp0[j]] if wants else None]
                         group[j] = (idx, None, S, budget, par, r, first)
+                    for g in group:
+                        own.pop(g[0], None) if len(g) != 7 else None      # (ended at its first token: nothing to write)
                     if moves:
                         eng.kv_move_rows([m[0] for m in moves], [m[1] for m in moves], [m[2] for m in moves])
                     for g in group:
                         if len(g) == 7:
                             eng.decode_set_row(g[5], g[6], g[2], g[2])
-                            if stop is not None:        # the row starts clean and its first token goes through the matcher
+                            if per_request:             # the row's own record (its history restarts empty) and stop sequences
+                                eng.decode_set_row_logits_proc(g[5], own[g[0]][0])
+                                eng.decode_set_row_stop_seqs(g[5], own[g[0]][1])
+                            if watched:                 # the row starts clean and its first token goes through the matcher
                                 eng.stop_rows(g[5], torch.tensor([g[6]], dtype=torch.int32))
                             if armed:                   # the row's second token is draw 1 of the request's own stream
                                 eng.decode_set_row_sampling(g[5], g[4].at(1))
@@ -1043,7 +1075,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                     return
                 n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
                 chunk = eng.decode_steps(n)
-                at = eng.stop_at(0, n_rows) if stop is not None else None
+                at = eng.stop_at(0, n_rows) if watched else None
                 chunk = chunk.cpu()                                         # [rows, n]; the only host sync of the chunk
                 at = None if at is None else at.tolist()
                 lps = None
@@ -1068,8 +1100,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                         else:
                             yield st[0], torch.tensor(st[1], dtype=torch.long)
                         eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
+                        if per_request:
+                            eng.decode_set_row_logits_proc(r, None)          # a parked row costs the step one record read
+                            own.pop(st[0], None)
                         slots[r] = None
         finally:
+            if per_request:
+                eng.set_stop_row_seqs(False)
+                eng.set_logits_proc_rows(False)
             if stop is not None:
                 eng.set_stop(None)
             if scored:

@@ -64,6 +64,16 @@ class VzLogitsProcParams(C.Structure):
     ]
 
 
+class VzProcRow(C.Structure):
+    """vz_proc_row: one row's logits processors (128 bytes, the entry of the per-row table in device memory; vz_hip.logits_proc.pack_row
+    writes the same bytes)"""
+    _fields_ = [
+        ("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int), ("min_new_tokens", C.c_int),
+        ("n_eos", C.c_int), ("eos", C.c_int * 4), ("n_suppress", C.c_int), ("suppress", C.c_int * 16),
+        ("n_seq", C.c_int), ("active", C.c_int), ("reserved", C.c_int * 5),
+    ]
+
+
 # every symbol include/viszephyr.h declares: (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SYMBOLS = {
@@ -174,6 +184,11 @@ SYMBOLS = {
     "vz_op_stop_match": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vz_llm_decode_logits_proc": (_I, [_P, _P, _P]),
     "vz_op_logits_process": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    "vz_llm_decode_logits_proc_rows": (_I, [_P, _I, _P]),
+    "vz_llm_decode_set_row_logits_proc": (_I, [_P, _I, _P, _P, _I, _P]),
+    "vz_op_logits_process_rows": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "vz_llm_decode_stop_row_seqs": (_I, [_P, _I, _P]),
+    "vz_llm_decode_stop_set_row_seqs": (_I, [_P, _I, _P, _I, _P]),
     "vz_llm_decode_guidance": (_I, [_P, _I, _F, _I, _P]),
     "vz_op_cfg_combine": (_I, [_P, _P, _I, _I, _F, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
@@ -786,6 +801,36 @@ def logits_process(logits, cfg, hist=None, hist_len=None):
     assert hist.device == logits.device and hist_len.device == logits.device
     check(lib().vz_op_logits_process(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), C.byref(proc_params(cfg)),
                                      stream_ptr(logits.device)))
+    return logits
+
+
+def proc_row(cfg):
+    """the vz_proc_row record of a vz_hip.logits_proc config; None: an inactive record"""
+    from . import logits_proc as LP
+    return VzProcRow.from_buffer_copy(LP.pack_row(cfg))
+
+
+def logits_process_rows(logits, cfgs, hist=None, hist_len=None):
+    """the per-row form of `logits_process` (logits_proc.hip: logits_process_rows_kernel) IN PLACE on fp32 logits [rows <= 64, V]: row r by
+    cfgs[r] (a vz_hip.logits_proc config; None: the row is left alone), over the histories hist int32 [rows, stride] of hist_len int32
+    [rows] ids each (None = empty: the first token of an admitted request).  Nothing is appended.  Returns `logits`."""
+    _need_cuda(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous() and len(cfgs) == logits.shape[0]
+    rows = logits.shape[0]
+    if hist is None:
+        hist = torch.zeros(rows, 1, dtype=torch.int32, device=logits.device)
+        hist_len = torch.zeros(rows, dtype=torch.int32, device=logits.device)
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.is_contiguous() and hist.shape[0] == rows and hist.shape[1] >= 1
+    assert hist_len.dtype == torch.int32 and hist_len.is_contiguous() and hist_len.numel() == rows
+    assert hist.device == logits.device and hist_len.device == logits.device
+    recs = (VzProcRow * rows)(*[proc_row(c) for c in cfgs])
+    seq, off = [], [0]
+    for c in cfgs:
+        seq += c.seq_table() if c is not None and c.seq else []
+        off.append(len(seq) // 12)
+    ints = lambda v: (C.c_int * len(v))(*v) if v else None      # noqa: E731
+    check(lib().vz_op_logits_process_rows(ptr(logits), rows, logits.shape[1], ptr(hist), hist.shape[1], ptr(hist_len), recs, ints(seq),
+                                          ints(off) if seq else None, stream_ptr(logits.device)))
     return logits
 
 

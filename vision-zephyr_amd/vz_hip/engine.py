@@ -712,6 +712,30 @@ class Engine:
             return
         B.check(self.lib.vz_llm_decode_logits_proc(self.h, C.byref(B.proc_params(cfg)), self._s()))
 
+    def set_logits_proc_rows(self, on: bool):
+        """the per-row logits processors (logits_proc.hip: logits_process_rows_kernel): armed, every decode step runs each row's logits
+        through that row's own record of a device table, in front of the argmax / the sampler / the per-row tail.  Arming leaves every
+        record inactive and every history empty; `decode_set_row_logits_proc` arms a row.  Not together with `set_logits_proc`."""
+        B.check(self.lib.vz_llm_decode_logits_proc_rows(self.h, int(bool(on)), self._s()))
+
+    def decode_set_row_logits_proc(self, row: int, cfg=None):
+        """one row's record and id sequences (cfg = vz_hip.logits_proc.parse(...); None: the row is left alone from now on), stream-ordered
+        like `decode_set_row`; the row's history restarts empty.  Captures nothing."""
+        seq = cfg.seq_table() if cfg is not None and cfg.seq else []
+        B.check(self.lib.vz_llm_decode_set_row_logits_proc(self.h, int(row), C.byref(B.proc_row(cfg)) if cfg is not None else None,
+                                                           (C.c_int * len(seq))(*seq) if seq else None, len(seq) // 12, self._s()))
+
+    def set_stop_row_seqs(self, on: bool):
+        """per-row stop sequences (stop.hip): armed - behind `set_stop(plan)`, or on its own - the matcher's id-sequence rule reads each
+        row's own sequences; every row starts with the call's (`plan.seqs`) and unwatched.  Disarm it before `set_stop` is called again."""
+        B.check(self.lib.vz_llm_decode_stop_row_seqs(self.h, int(bool(on)), self._s()))
+
+    def decode_set_row_stop_seqs(self, row: int, seqs=()):
+        """one row's own stop sequences (id lists; behind the call's, together at most 16), stream-ordered; call `stop_rows` behind it"""
+        from . import stop as ST
+        tab = ST.row_seq_table(seqs).contiguous() if seqs else None
+        B.check(self.lib.vz_llm_decode_stop_set_row_seqs(self.h, int(row), B.ptr(tab), len(seqs), self._s()))
+
     def set_guidance(self, cfg=None):
         """HF's classifier-free guidance in every decode step (guidance.hip; cfg = vz_hip.guidance.GuidanceConfig, None = off): the NEXT
         `decode_begin` takes 2 * cfg.pairs rows - row r < pairs a prompt, row pairs + r its negative prompt - and every step combines each

@@ -29,6 +29,36 @@ class ProcConfig:
         return out
 
 
+# vz_proc_row (include/viszephyr.h): one row's record of the per-row table, 32 little-endian 32-bit words by byte offset -
+#   0 repetition_penalty (fp32) | 4 no_repeat_ngram | 8 min_new_tokens | 12 n_eos | 16 eos[4] | 32 n_suppress | 36 suppress[16] |
+#   100 n_seq | 104 active | 108 reserved[5]
+ROW_RECORD_BYTES = 128
+REQUEST_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens", "sequence_bias", "bad_words_ids")
+
+
+def pack_row(cfg: Optional[ProcConfig]) -> bytes:
+    """the vz_proc_row record of a config as the device table holds it (unused list slots -1); None: an inactive record, all zeros"""
+    if cfg is None:
+        return bytes(ROW_RECORD_BYTES)
+    pad = lambda ids, n: (list(ids) + [-1] * n)[:n]      # noqa: E731  (a list beyond its slots keeps its count: the entry points refuse the record)
+    rec = struct.pack("<f3i4ii16i2i5i", float(cfg.penalty), int(cfg.ngram), int(cfg.min_new), len(cfg.eos), *pad(cfg.eos, MAX_EOS),
+                      len(cfg.suppress), *pad(cfg.suppress, MAX_SUPPRESS), len(cfg.seq), 1, 0, 0, 0, 0, 0)
+    assert len(rec) == ROW_RECORD_BYTES
+    return rec
+
+
+def pack_row_seqs(cfg: Optional[ProcConfig]) -> list:
+    """what a row's region of the per-row sequence table [max_batch][MAX_SEQ][SEQ_STRIDE] starts with: the config's own table"""
+    return [] if cfg is None else cfg.seq_table()
+
+
+def parse_request(req, eos: Optional[Sequence[int]] = None, vocab: Optional[int] = None) -> Optional[ProcConfig]:
+    """the processor keys of one `generate_stream(per_request=True)` request (REQUEST_KEYS, read as `generate` reads its keywords) with the
+    call's eos ids and the model's vocabulary: `parse`'s config, None for a request that names none of them"""
+    return parse(req.get("repetition_penalty"), req.get("no_repeat_ngram_size"), req.get("min_new_tokens"), req.get("suppress_tokens"),
+                 eos, req.get("sequence_bias"), req.get("bad_words_ids"), vocab)
+
+
 def _check_sequence_bias(sequence_bias) -> dict:
     """hf:SequenceBiasLogitsProcessor._validate_arguments and _convert_list_arguments_into_dict: {tuple of ids: bias}"""
     sb = sequence_bias

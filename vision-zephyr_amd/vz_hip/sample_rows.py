@@ -79,13 +79,17 @@ def row_params(do_sample, temperature, top_k, top_p, seed: Optional[int], gen, d
     return RowParams(True, float(temperature), top_k, top_p, int(draw_seed() if seed is None else seed), 0, **warp)
 
 
-def parse_request(req: Mapping, gen, draw_seed: Callable[[], int]) -> RowParams:
+def parse_request(req: Mapping, gen, draw_seed: Callable[[], int], per_request: bool = False) -> RowParams:
     """the sampling parameters of one `generate_stream` request (keys do_sample, temperature, top_p, top_k, seed, min_p, typical_p,
     epsilon_cutoff, eta_cutoff; defaults as `generate`'s, `gen` = the model's generation config).
-    Logits processors per request are not built: a row's processor history would have to restart at admission."""
-    for k in UNBUILT_REQUEST_KEYS:
+    Logits processors and stop sequences per request need the stream's `per_request=True` (the per-row tables of DESIGN.md section 6m;
+    vz_hip.logits_proc.parse_request and vz_hip.stop.parse_row_sequences read those keys): without it a request that names one raises,
+    it is never dropped."""
+    for k in () if per_request else UNBUILT_REQUEST_KEYS:
         if req.get(k) is not None:
             raise NotImplementedError(f"generate_stream: `{k}` in a request is not built (logits processors run over a whole batch: generate())")
+    if not per_request and req.get("stop_token_sequences") is not None:
+        raise NotImplementedError("generate_stream: `stop_token_sequences` in a request needs per_request=True (without it the stop set is the call's)")
     return row_params(req.get("do_sample", False), req.get("temperature", 1.0), req.get("top_k", -1), req.get("top_p"), req.get("seed"),
                       gen, draw_seed, req.get("min_p"), req.get("typical_p"), req.get("epsilon_cutoff"), req.get("eta_cutoff"))
 

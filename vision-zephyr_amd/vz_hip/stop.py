@@ -46,6 +46,26 @@ class Plan:
         return t
 
 
+def parse_row_sequences(token_sequences, n_call: int = 0) -> List[List[int]]:
+    """the `stop_token_sequences` of one `generate_stream(per_request=True)` request, checked as `parse` checks the call-level ones (1..32
+    ids each); with the call's own `n_call` sequences, which the matcher copies in front of every row's, they must fit MAX_SEQ:
+    ValueError otherwise.  None / empty: []."""
+    out = []
+    for ids in token_sequences or []:
+        ids = [int(t) for t in ids]
+        if not 1 <= len(ids) <= MAX_SEQ_LEN:
+            raise ValueError(f"a stop token sequence holds 1..{MAX_SEQ_LEN} ids, got {len(ids)}")
+        out.append(ids)
+    if int(n_call) + len(out) > MAX_SEQ:
+        raise ValueError(f"at most {MAX_SEQ} stop token sequences for a request, the call's own included: got {n_call} + {len(out)}")
+    return out
+
+
+def row_seq_table(seqs: Sequence[Sequence[int]]) -> torch.Tensor:
+    """a request's own sequences as the matcher's per-row table takes them (Plan.seq_table's entries, start 0)"""
+    return Plan(seqs=[(list(ids), 0) for ids in seqs]).seq_table()
+
+
 def _string_tables(crit) -> Optional[dict]:
     """HF's StopStringCriteria -> its tables, or None beyond the matcher's limits"""
     emb = crit.embedding_vec.detach().to("cpu", torch.int32).contiguous()
