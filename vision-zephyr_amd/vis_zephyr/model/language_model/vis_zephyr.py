@@ -942,39 +942,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         re-capture.  A request's first token goes through `binding.logits_process_rows` on its prefill logits row with an empty history;
         when its row is parked its record is deactivated.  A stream in which no request names a key yields the ids of the same stream
         with the flag off.  Per-request stop strings, guidance and eos ids are not built; tensor-parallel engines: NotImplementedError."""
-        from vz_hip import binding as B
-        from vz_hip import logits_proc as LP
-        from vz_hip import sample_rows as SR
-        from vz_hip import scores as SC
         from vz_hip import stop as ST
+        from vz_hip import stream
         stop, host_stop = ST.parse(stop_strings, tokenizer, None, self.generation_config, True, stop_token_sequences)
         if host_stop is not None or (stop is not None and self.engine.tp_size > 1):
             raise NotImplementedError("generate_stream: these stop strings are beyond what the device matcher takes (vz_hip.stop.parse)")
         if per_request and self.engine.tp_size > 1:
             raise NotImplementedError("generate_stream: per_request=True on a tensor-parallel engine is not built")
-        watched = stop is not None or per_request          # the stop matcher runs: rows are watched from their admission on
-        n_call = len(stop.seqs) if stop is not None else 0
-        own = {}                                            # per_request: request index -> (its ProcConfig or None, its own stop sequences)
         self._kv_epoch += 1
         self._ensure_ready()
-        eng = self.engine
         eos = DL.resolve_defaults(self.generation_config, eos_token_id, max_new_tokens).eos
-        draw_seed = lambda: int(torch.randint(0, 2 ** 62, (1,)).item())      # noqa: E731  (as generate draws its seed)
-        armed = False                           # the per-row tail: from the first sampled request on
-        scored = False                          # the step recorder: from the first request with logprobs=True on
-        n_rows = min(eng.max_batch, 64) if rows is None else int(rows)
-        if not 1 <= n_rows <= min(eng.max_batch, 64):
-            raise ValueError(f"rows must be in [1, {min(eng.max_batch, 64)}]")
-        spare = eng.max_batch - n_rows
-        width = min(spare, 16) if admit is None else int(admit)
-        if not 0 <= width <= min(spare, 16):
-            raise ValueError(f"admit must be in [0, {min(spare, 16)}] (max_batch {eng.max_batch} - rows {n_rows} spare cache rows)")
-        it = iter(enumerate(requests))
-        slots = [None] * n_rows                 # per row: [request index, tokens so far, budget]
-        eng.decode_begin(torch.zeros(n_rows, dtype=torch.int32), [0] * n_rows, [0] * n_rows)       # every row parked
-        if stop is not None:
-            eng.set_stop(stop)                  # no row is watched until a request lands in it (stop_rows)
-        exhausted = False
 
         def embed(idx, req):
             if req.get("guidance_scale") is not None or req.get("negative_prompt_ids") is not None:
@@ -983,137 +960,15 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             ids = req["input_ids"]
             ids = ids if ids.dim() == 2 else ids.unsqueeze(0)
             images = req.get("images")
-            budget = int(req.get("max_new_tokens", max_new_tokens))
-            if images is not None:
-                images = images if isinstance(images, (list, tuple)) else [images]
-                emb = self.prepare_inputs_labels_for_multimodal(ids.to(self.device), None, None, None, None, images,
-                                                                req.get("images_size"))[4]
-            else:
-                emb = eng.embed_tokens(ids.to(self.device))
-            S = emb.shape[1]
-            if S + budget > eng.max_ctx:
-                raise ValueError(f"request {idx}: prompt ({S}) + max_new_tokens ({budget}) exceeds the engine's max_ctx ({eng.max_ctx})")
-            if per_request:
-                own[idx] = (LP.parse_request(req, sorted(eos), self.config.vocab_size), ST.parse_row_sequences(req.get("stop_token_sequences"), n_call))
-            return emb, S, budget, SR.parse_request(req, self.generation_config, draw_seed, per_request), SC.wants_logprobs(req)
+            if images is None:
+                return self.engine.embed_tokens(ids.to(self.device))
+            images = images if isinstance(images, (list, tuple)) else [images]
+            return self.prepare_inputs_labels_for_multimodal(ids.to(self.device), None, None, None, None, images, req.get("images_size"))[4]
 
-        def first_tokens(logits, params, want, cfgs=None):     # one launch and one readback for the group: argmax, or each row by its own parameters
-            if cfgs is not None and any(c is not None for c in cfgs):      # each row's own processors over an empty history, in place
-                B.logits_process_rows(logits, cfgs)
-            ids = B.argmax(logits) if not any(p.sample for p in params) else B.sample_rows(logits, params)
-            if not any(want):
-                return ids.tolist(), None
-            x, lse, _, _ = SC.unpack(B.token_scores(logits, ids, params))
-            return ids.tolist(), (x - lse).tolist()
-
-        try:
-            if per_request:                         # every record inactive, every row's stop sequences the call's: armed once
-                eng.set_logits_proc_rows(True)
-                eng.set_stop_row_seqs(True)
-            while True:
-                while not exhausted:                # admit requests into free rows
-                    free = [r for r in range(n_rows) if slots[r] is None]
-                    if not free:
-                        break
-                    group = []
-                    while len(group) < (min(len(free), width) if width >= 2 else 1):
-                        try:
-                            idx, req = next(it)
-                        except StopIteration:
-                            exhausted = True
-                            break
-                        group.append((idx,) + embed(idx, req))
-                    if not group:
-                        break
-                    want = [g[5] for g in group]
-                    cfgs = [own[g[0]][0] for g in group] if per_request else None
-                    if len(group) == 1:             # straight into the free row
-                        idx, emb, S, budget, par, _ = group[0]
-                        firsts, lp0 = first_tokens(eng.prefill_rows(free[0], emb, [S]), [par], want, cfgs)
-                    else:                           # one prefill for the group in the spare rows, one readback
-                        Smax = max(g[2] for g in group)
-                        pad = torch.zeros(len(group), Smax, group[0][1].shape[-1], dtype=torch.bfloat16, device=self.device)
-                        for j, g in enumerate(group):
-                            pad[j, :g[2]] = g[1][0]
-                        firsts, lp0 = first_tokens(eng.prefill_rows(n_rows, pad, [g[2] for g in group]), [g[4] for g in group], want, cfgs)
-                    moves = []
-                    if not scored and any(want):
-                        eng.set_scores(max(1, int(sync_every)), n_rows)      # records only; restarts the ring between two chunks
-                        scored = True
-                    if not armed and any(g[4].sample for g in group):
-                        # the table the running batch uploaded holds every row greedy: rows keep their ids when the tail changes under them
-                        eng.set_sampling_rows([])
-                        armed = True
-                    for j, (idx, emb, S, budget, par, wants) in enumerate(group):
-                        first = int(firsts[j])
-                        if first in eos or budget <= 1:
-                            if wants:
-                                yield idx, torch.tensor([first], dtype=torch.long), torch.tensor([lp0[j]], dtype=torch.float32)
-                            else:
-                                yield idx, torch.tensor([first], dtype=torch.long)
-                            continue
-                        r = free.pop(0)
-                        if len(group) > 1:
-                            moves.append((n_rows + j, r, S))
-                        slots[r] = [idx, [first], budget, [lp0[j]] if wants else None]
-                        group[j] = (idx, None, S, budget, par, r, first)
-                    for g in group:
-                        own.pop(g[0], None) if len(g) != 7 else None      # (ended at its first token: nothing to write)
-                    if moves:
-                        eng.kv_move_rows([m[0] for m in moves], [m[1] for m in moves], [m[2] for m in moves])
-                    for g in group:
-                        if len(g) == 7:
-                            eng.decode_set_row(g[5], g[6], g[2], g[2])
-                            if per_request:             # the row's own record (its history restarts empty) and stop sequences
-                                eng.decode_set_row_logits_proc(g[5], own[g[0]][0])
-                                eng.decode_set_row_stop_seqs(g[5], own[g[0]][1])
-                            if watched:                 # the row starts clean and its first token goes through the matcher
-                                eng.stop_rows(g[5], torch.tensor([g[6]], dtype=torch.int32))
-                            if armed:                   # the row's second token is draw 1 of the request's own stream
-                                eng.decode_set_row_sampling(g[5], g[4].at(1))
-                if all(s is None for s in slots):
-                    return
-                n = min([sync_every] + [s[2] - len(s[1]) for s in slots if s is not None])
-                chunk = eng.decode_steps(n)
-                at = eng.stop_at(0, n_rows) if watched else None
-                chunk = chunk.cpu()                                         # [rows, n]; the only host sync of the chunk
-                at = None if at is None else at.tolist()
-                lps = None
-                if scored:
-                    x, lse, _, _ = SC.unpack(eng.scores_steps(n)[0].cpu())  # [n, rows]
-                    lps = (x - lse).transpose(0, 1).tolist()
-                for r, st in enumerate(slots):
-                    if st is None:
-                        continue
-                    cut = at[r] + 1 if at is not None and at[r] >= 0 else st[2]      # tokens the row keeps if its stop condition held
-                    for i, t in enumerate(chunk[r].tolist()):
-                        if len(st[1]) >= cut:
-                            break
-                        st[1].append(int(t))
-                        if st[3] is not None:
-                            st[3].append(lps[r][i])
-                        if int(t) in eos or len(st[1]) >= st[2]:
-                            break
-                    if st[1][-1] in eos or len(st[1]) >= min(st[2], cut):
-                        if st[3] is not None:
-                            yield st[0], torch.tensor(st[1], dtype=torch.long), torch.tensor(st[3], dtype=torch.float32)
-                        else:
-                            yield st[0], torch.tensor(st[1], dtype=torch.long)
-                        eng.decode_set_row(r, 0, 0, 0)                       # park until the next request arrives
-                        if per_request:
-                            eng.decode_set_row_logits_proc(r, None)          # a parked row costs the step one record read
-                            own.pop(st[0], None)
-                        slots[r] = None
-        finally:
-            if per_request:
-                eng.set_stop_row_seqs(False)
-                eng.set_logits_proc_rows(False)
-            if stop is not None:
-                eng.set_stop(None)
-            if scored:
-                eng.set_scores(None)
-            if armed:
-                eng.set_sampling_rows(None)
+        # the scheduler (vz_hip/stream.py): admit, step, harvest until the requests and the rows run out.  The vocabulary is what a request's
+        # own processors are checked against: only a per_request call reads it
+        yield from stream.run(self.engine, requests, embed, gen=self.generation_config, vocab=self.config.vocab_size if per_request else None,
+                              eos=eos, max_new=max_new_tokens, stop=stop, per_request=per_request, rows=rows, admit=admit, sync_every=sync_every)
 
     def _token_ring(self, n: int = 8) -> torch.Tensor:
         """pinned host buffer the step tails write their tokens to (device-visible: hipHostMalloc memory is mapped)."""

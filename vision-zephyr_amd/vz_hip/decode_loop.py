@@ -98,6 +98,29 @@ def chunk_recorder(sink, rows: int, sync_every: int, max_new: int):
     return None if sink is None else (max(1, min(sync_every, max_new - 1)), rows, sink.warped, sink.raw)
 
 
+class arming:
+    """The scope every decode route arms the engine's step modes through: `arm(name, args, off)` calls `eng.name(*args)` at any time inside
+    it and, once that call has returned, owes `eng.name(*off)`; on the way out, whatever happened, exactly what was armed is disarmed, last
+    first.  `has(name)`: is that mode armed by now?"""
+
+    def __init__(self, eng):
+        self.eng, self.undo = eng, []
+
+    def arm(self, name, args, off):
+        getattr(self.eng, name)(*args)
+        self.undo.append((name, off))
+
+    def has(self, name) -> bool:
+        return any(n == name for n, _ in self.undo)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for name, off in reversed(self.undo):
+            getattr(self.eng, name)(*off)
+
+
 @contextmanager
 def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None, guidance=None,
           history=None):
@@ -111,18 +134,13 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
     whatever happened (a failed arming included), exactly what was armed is disarmed, last first.  None = not asked for: not called.
     history (a call that continues on a kept cache): per row the ids fed before the first token - the processors' histories and the stop
     matcher's rings start from them (`Engine.seed_history`)."""
-    undo = []
-
-    def arm(name, args, off):
-        getattr(eng, name)(*args)
-        undo.append((name, off))
-
     def begin(first, next_pos, ctx_len):
         eng.decode_begin(first if guidance is None else torch.cat([first, first]), next_pos, ctx_len)
         if stop is not None:
             eng.stop_rows(0, first)
 
-    try:
+    with arming(eng) as scope:
+        arm = scope.arm
         if proc is not None:
             arm("set_logits_proc", (proc,), (None,))
             if history is not None:
@@ -146,9 +164,6 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
         if beam is not None:
             arm("set_beam", beam, (False,))
         yield begin
-    finally:
-        for name, off in reversed(undo):
-            getattr(eng, name)(*off)
 
 
 def decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk=None, stop: bool = False) -> torch.Tensor:
