@@ -920,6 +920,32 @@ int vz_llm_decode_beam_rows(vz_engine* e, float* d_scores, float* d_raw, int cap
 int vz_llm_decode_guidance(vz_engine* e, int enable, float scale, int pairs, vz_stream stream);
 int vz_op_cfg_combine(float* d_logits_cond, const float* d_logits_uncond, int pairs, int cols, float scale, vz_stream stream);
 
+/* ---- shared-prefix decode attention (csrc/attn_shared.hip) ----
+ * n samples of one prompt read the prompt's K / V once.  Rows come in groups of n adjacent rows, group g = rows g*n .. g*n + n - 1;
+ * d_shared[g] (int32, device) leading cache slots of the group live in cache row g*n only.  Row r sees the slots [0, shared[g]) of cache
+ * row g*n and the slots [shared[g], slot[r]] of its own row, slot[r] being the slot of the token just appended (window > 0: only the
+ * slots > slot[r] - window of that union); a row with slot[r] < shared[g] shares nothing and sees its own slots [0, slot[r]].  No other
+ * slot is read.
+ * vz_op_attention_shared: d_q_rot rotated bf16 [R][Hq][128], caches [rows >= R][Hkv][max_ctx][128], d_o bf16 [R][Hq][128], d_slot int32 [R].
+ *   Two launches: one stacked pass per (group, KV head) over the shared slots, split over nsplit workgroups along the keys (0 = chosen
+ *   from shared_max = max_g shared[g], given on the host, 1 <= shared_max <= max_ctx; >= 1 forced, cut to the 64-key tiles of shared_max
+ *   and to 64), which leaves fp32 partials in the workspace; then one workgroup per (row, KV head) for the row's own slots and the merge.
+ *   2 <= n <= 64, R a multiple of n, head_dim 128.  The workspace needs R * Hq * nsplit * 132 floats;
+ *   vz_op_attention_shared_ws_floats(R, n, Hq, Hkv, max_ctx) covers every split the rule can choose for shared_max <= max_ctx (pure host
+ *   arithmetic; 0 = a shape the op refuses).
+ * vz_llm_decode_share(n, h_shared[groups], groups): arms the NEXT decode batch (vz_llm_decode_begin) as groups x n rows whose attention
+ *   is the op above behind the stand-alone RoPE + append launch, for every tail but the speculative one; n = 0 disarms.  2 <= n <= 64,
+ *   groups * n <= min(max_batch, 64), 1 <= h_shared[g] <= max_ctx; VZ_ERR_UNSUPPORTED on a tensor-parallel engine.  While armed:
+ *   vz_llm_decode_begin with another row count, vz_llm_decode_set_row to a context shorter than the group's shared slots (parking
+ *   included), vz_llm_kv_move_rows into a group's first row, and vz_llm_decode_steps with guidance, the speculative tail or the persistent
+ *   token kernel are refused.  n, the split and the table's address are part of what a captured step freezes.  With nothing armed the
+ *   step is launch for launch what it is without this entry. */
+int vz_op_attention_shared(const void* d_q_rot, const void* d_kcache, const void* d_vcache, void* d_o, const int* d_shared, const int* d_slot,
+                           int R, int n, int Hq, int Hkv, int head_dim, int max_ctx, int shared_max, float scale, int window, int nsplit,
+                           float* d_workspace, long workspace_floats, vz_stream stream);
+long vz_op_attention_shared_ws_floats(int R, int n, int Hq, int Hkv, int max_ctx);
+int vz_llm_decode_share(vz_engine* e, int n, const int* h_shared, int groups, vz_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

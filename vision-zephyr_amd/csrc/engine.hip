@@ -217,6 +217,20 @@ extern "C" int vz_op_attention_append(const void* q, const void* kc, const void*
 extern "C" long vz_op_attention_append_ws_floats(int B, int T, int Hq, int Hkv, int max_ctx) {
     return (long)vz_attn_append_ws_floats(B, T, Hq, Hkv, max_ctx);
 }
+extern "C" int vz_op_attention_shared(const void* q, const void* kc, const void* vc, void* o, const int* d_shared, const int* d_slot, int R, int n,
+                                      int Hq, int Hkv, int head_dim, int max_ctx, int shared_max, float scale, int window, int nsplit, float* ws,
+                                      long ws_floats, vz_stream s) {
+    VZ_CHECK_ARG(ws && ws_floats > 0, "attention_shared: bad workspace");
+    AttnSharedArgs a;
+    a.q = (const bf16_t*)q; a.kc = (const bf16_t*)kc; a.vc = (const bf16_t*)vc; a.o = (bf16_t*)o; a.part = ws; a.part_floats = (size_t)ws_floats;
+    a.shared = d_shared; a.slot = d_slot;
+    a.R = R; a.n = n; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = head_dim; a.max_ctx = max_ctx; a.window = window; a.shared_max = shared_max; a.nsplit = nsplit;
+    a.scale = scale;
+    return vz_launch_attention_shared(a, (hipStream_t)s);
+}
+extern "C" long vz_op_attention_shared_ws_floats(int R, int n, int Hq, int Hkv, int max_ctx) {
+    return (long)vz_attn_shared_ws_floats(R, n, Hq, Hkv, max_ctx);
+}
 // two helpers of the training step at op level (parity tests): dst[c][r] = src[r][c], and out[c] += sum_r y[r][c] through `part`
 extern "C" int vz_op_transpose(const void* src, long src_ld, void* dst, long dst_ld, int R, int C, vz_stream s) {
     return vz_launch_transpose((const bf16_t*)src, src_ld, 0, 0, (bf16_t*)dst, dst_ld, 0, 0, R, C, 1, 1, 0, (hipStream_t)s);
@@ -463,6 +477,9 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->d_ferr) hipFree(e->d_ferr);
     if (e->d_xnorm) hipFree(e->d_xnorm);
     if (e->beam.d) hipFree(e->beam.d);
+    if (e->share.d_tab) hipFree(e->share.d_tab);
+    if (e->share.q_rot) hipFree(e->share.q_rot);
+    if (e->share.ws) hipFree(e->share.ws);
     if (e->proc.d) hipFree(e->proc.d);
     if (e->proc.d_seq) hipFree(e->proc.d_seq);
     if (e->proc.d_rows) hipFree(e->proc.d_rows);
@@ -1171,6 +1188,8 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     const vz_config& c = e->c;
     hipStream_t s = (hipStream_t)stream;
     VZ_CHECK_ARG(decode_shape_ok(c, B, false) && d_first_ids && h_next_pos && h_ctx_len, "decode_begin: B=%d unsupported (1..min(64,max_batch))", B);
+    VZ_CHECK_ARG(!e->share.on || B == e->share.groups * e->share.n, "decode_begin: the shared-prefix attention (vz_llm_decode_share) is armed for %d x %d rows, "
+                 "the batch has %d", e->share.groups, e->share.n, B);
     const int mb = c.max_batch;
     std::vector<int> h(DecodeState::ints(mb), 0);       // host image of the state: everything behind `cur` goes up in one copy
     const DecodeState hs = decode_state(h.data(), mb), ds = decode_state(e->d_state, mb);
@@ -1201,6 +1220,10 @@ extern "C" int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_
     const vz_config& c = e->c;
     VZ_CHECK_ARG(e->dec_B >= 1 && row >= 0 && row < e->dec_B, "decode_set_row: row %d outside the running batch of %d", row, e->dec_B);
     VZ_CHECK_ARG(ctx_len >= 0 && ctx_len < c.max_ctx && next_pos >= 0, "decode_set_row: ctx_len %d / pos %d outside [0,%d)", ctx_len, next_pos, c.max_ctx);
+    // shared-prefix attention armed: the slots [0, shared) of a group are its first row's - a row set in front of them would append into them
+    VZ_CHECK_ARG(!e->share.on || (row < e->share.groups * e->share.n && ctx_len >= e->share.h_shared[row / e->share.n]),
+                 "decode_set_row: row %d to context %d, in front of the %d slots its group shares (vz_llm_decode_share is armed: a row is neither parked nor "
+                 "moved into the shared slots)", row, ctx_len, e->share.on && row < e->share.groups * e->share.n ? e->share.h_shared[row / e->share.n] : 0);
     const DecodeState ds = decode_state(e->d_state, c.max_batch);
     const int h[DecodeState::ROW_ARRAYS] = {token, next_pos, ctx_len, ctx_len + 1};     // cur | pos | slot | len: one int in each of the four state arrays
     e->h_len[row] = ctx_len + 1; e->h_pos[row] = next_pos; e->h_parked[row] = ctx_len == 0 && next_pos == 0;
@@ -1228,6 +1251,8 @@ extern "C" int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const 
         // the keys that row keeps attending to
         VZ_CHECK_ARG(h_src[i] >= e->dec_B || e->h_parked[h_src[i]], "kv_move_rows: source row %d belongs to the running decode batch", h_src[i]);
         VZ_CHECK_ARG(h_dst[i] >= e->dec_B || e->h_parked[h_dst[i]], "kv_move_rows: destination row %d is a live row of the running decode batch (park it first)", h_dst[i]);
+        VZ_CHECK_ARG(!e->share.on || h_dst[i] >= e->share.groups * e->share.n || h_dst[i] % e->share.n != 0, "kv_move_rows: destination row %d holds the slots its group "
+                     "shares (vz_llm_decode_share is armed)", h_dst[i]);
     }
     for (int i0 = 0; i0 < n; i0 += 16) {
         KvMoves mv;
@@ -1316,7 +1341,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(st.cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
             const LlmLayerW& W = e->llm[i];
-            const bool fuse_ao = !spec && vz_knob(VZ_KNOB_ATTN_O) && (B == 1 || (B == 2 && vz_knob(VZ_KNOB_ATTN_O) >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
+            const bool fuse_ao = !spec && !e->share.on && vz_knob(VZ_KNOB_ATTN_O) && (B == 1 || (B == 2 && vz_knob(VZ_KNOB_ATTN_O) >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
             RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
             if (spec) {
@@ -1329,6 +1354,17 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
                 a.R = B; a.Hq = Hq; a.Hkv = Hkv; a.max_ctx = c.max_ctx; a.nsplit = e->dec_nsplit; a.key_bound = e->spec.a.key_bound;
                 a.window = c.sliding_window; a.scale = ATTN_SCALE;
                 RC(vz_launch_spec_verify_attn(a, s));
+            } else if (e->share.on) {
+                // shared-prefix step (attn_shared.hip): RoPE + append of every row to its own cache row (the stand-alone
+                // kernel), one stacked pass per group over the slots its rows share, then each row's own slots and the merge
+                ProfScope ps(e, K_ATTN_DEC, s);
+                RC(vz_launch_rope_kv(qkv, QKV, e->share.q_rot, kc_of(e, i), vc_of(e, i), e->cosT, e->sinT, st.pos, st.slot, B, 1, Hq, Hkv, D, c.max_ctx, s));
+                AttnSharedArgs a;
+                a.q = e->share.q_rot; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->share.ws; a.part_floats = e->share.ws_floats;
+                a.shared = e->share.d_tab; a.slot = st.slot;
+                a.R = B; a.n = e->share.n; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D; a.max_ctx = c.max_ctx; a.window = c.sliding_window;
+                a.shared_max = e->share.shared_max; a.nsplit = 0; a.scale = ATTN_SCALE;
+                RC(vz_launch_attention_shared(a, s));
             } else {
                 ProfScope ps(e, K_ATTN_DEC, s);
                 AttnDecodeFusedArgs a;
@@ -1875,6 +1911,40 @@ extern "C" int vz_op_logits_process_rows(float* d_logits, int rows, int cols, in
     return vz_launch_logits_process_rows(d_logits, rows, cols, d_hist, hist_stride, d_hist_len, nullptr, (const ProcRow*)d, (const int*)d + rec_ints * rows, nullptr, s);
 }
 
+// Shared-prefix decode attention (attn_shared.hip; include/viszephyr.h has the contract): the next decode batch is
+// `groups` groups of n adjacent rows, and the rows of group g read their first h_shared[g] cache slots from cache row g * n.  n = 0: off.
+extern "C" int vz_llm_decode_share(vz_engine* e, int n, const int* h_shared, int groups, vz_stream stream) {
+    NEED_READY();
+    if (n == 0) { e->share.on = 0; e->share.n = 0; e->share.groups = 0; e->share.shared_max = 0; e->share.h_shared.clear(); return VZ_OK; }
+    const vz_config& c = e->c;
+    if (e->tp > 1) { vz_set_error("decode_share: the shared-prefix attention on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    VZ_CHECK_ARG(n >= 2 && n <= 64 && groups >= 1 && h_shared && (long)groups * n <= std::min(c.max_batch, 64), "decode_share: 2 <= n (%d) <= 64 rows per group and "
+                 "groups (%d) x n <= min(max_batch = %d, 64) expected", n, groups, c.max_batch);
+    VZ_CHECK_ARG(c.head_dim == 128 && vz_attn_shared_ws_floats(groups * n, n, e->Hq_l, e->Hkv_l, c.max_ctx) > 0, "decode_share: head_dim %d, %d query / %d KV heads unsupported",
+                 c.head_dim, e->Hq_l, e->Hkv_l);
+    int smax = 0;
+    for (int g = 0; g < groups; ++g) {
+        VZ_CHECK_ARG(h_shared[g] >= 1 && h_shared[g] <= c.max_ctx, "decode_share: shared[%d] = %d outside [1, max_ctx = %d]", g, h_shared[g], c.max_ctx);
+        smax = std::max(smax, h_shared[g]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->share.d_tab) {
+        // the largest workspace any arming of this engine can ask for: every (groups, n) with groups x n <= min(max_batch, 64)
+        size_t ws = 0;
+        const int rows_max = std::min(c.max_batch, 64);
+        for (int nn = 2; nn <= rows_max; ++nn)
+            for (int gg = 1; gg * nn <= rows_max; ++gg) ws = std::max(ws, vz_attn_shared_ws_floats(gg * nn, nn, e->Hq_l, e->Hkv_l, c.max_ctx));
+        VZ_CHECK_HIP(hipMalloc((void**)&e->share.ws, ws * sizeof(float)));
+        e->share.ws_floats = ws;
+        VZ_CHECK_HIP(hipMalloc((void**)&e->share.q_rot, (size_t)64 * e->Hq_l * c.head_dim * sizeof(bf16_t)));
+        VZ_CHECK_HIP(hipMalloc((void**)&e->share.d_tab, 64 * sizeof(int)));
+    }
+    RC(upload_ints(e, h_shared, groups, e->share.d_tab, s));
+    e->share.on = 1; e->share.n = n; e->share.groups = groups; e->share.shared_max = smax;
+    e->share.h_shared.assign(h_shared, h_shared + groups);
+    return VZ_OK;
+}
+
 // Classifier-free guidance in the step (hf:generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor; guidance.hip;
 // DESIGN.md section 6k): after vz_llm_decode_guidance(enable=1) a decode batch is 2 * pairs rows - row r < pairs a prompt, row pairs + r
 // its negative prompt - that share every weight sweep; behind the logits, row r's become scale * (lc - lu) + lu (lc / lu = the
@@ -2182,6 +2252,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     if (stop_armed(e)) { k.stop_state = e->stop.d_state; k.stop = e->stop.a; }
     k.proc_rows_on = e->proc.rows_on; k.stop_rows_on = e->stop.rows_on;
     if (e->cfg.on) { k.cfg_scale = e->cfg.scale; k.cfg_pairs = e->cfg.pairs; }
+    if (e->share.on) { k.share_n = e->share.n; k.share_nsplit = vz_attn_shared_nsplit(e->share.groups, e->share.n, e->Hq_l, e->Hkv_l, e->share.shared_max); k.share_tab = e->share.d_tab; }
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
 }
@@ -2195,6 +2266,14 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     const int B = e->dec_B;
     const TailKind tail = tail_kind(e);
     const bool spec = tail == TAIL_SPEC;
+    if (e->share.on) {
+        VZ_CHECK_ARG(B == e->share.groups * e->share.n, "decode_steps: the shared-prefix attention (vz_llm_decode_share) is armed for %d x %d rows, the batch has %d",
+                     e->share.groups, e->share.n, B);
+        if (e->cfg.on || tail == TAIL_SPEC) {
+            vz_set_error("decode_steps: the shared-prefix attention (vz_llm_decode_share) does not run with guidance or the speculative tail");
+            return VZ_ERR_UNSUPPORTED;
+        }
+    }
     if (e->cfg.on) {
         if (tail == TAIL_BEAM || tail == TAIL_SPEC) {
             vz_set_error("decode_steps: guidance (vz_llm_decode_guidance) runs in front of the argmax, the sampler or the per-row tail only, not with the "
@@ -2249,6 +2328,10 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
         RC(vz_decode_persist_reset(e->tok, s));         // arrival counters restart with the step counter
         if (e->tok_poke_word >= 0) { RC(vz_decode_persist_poke(e->tok, e->tok_poke_word, e->tok_poke_value, s)); e->tok_poke_word = -1; }
         e->use_tok = true;
+    }
+    if (e->share.on && e->use_tok) {      // (an armed batch has >= 2 rows, the resident grid takes one)
+        vz_set_error("decode_steps: the shared-prefix attention (vz_llm_decode_share) on the persistent decode-token kernel is not built");
+        return VZ_ERR_UNSUPPORTED;
     }
     if (e->cfg.on && e->use_tok) {      // (a guided batch has >= 2 rows, the resident grid takes one: kept so that widening either shows up here)
         vz_set_error("decode_steps: guidance (vz_llm_decode_guidance) on the persistent decode-token kernel is not built");

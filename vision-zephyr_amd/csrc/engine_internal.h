@@ -77,8 +77,9 @@ struct DecodeGraphKey {
     BeamRowsArgs beam_rows;              // the beam tail's row recorder: its rings (zero when off)
     float cfg_scale; int cfg_pairs;      // classifier-free guidance between the logits and the processors (zero when off)
     int proc_rows_on, stop_rows_on;      // the per-row processors / per-row stop sequences: mode bits only - their tables are engine-owned, stable device memory read through pointers
+    int share_n, share_nsplit; const int* share_tab;      // the shared-prefix attention (vz_llm_decode_share): rows per group, key splits, the `shared` table (zero when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 + 2 * 4 &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 + 2 * 4 + 2 * 4 + 8 &&
               sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos) + sizeof(RowSample), "padding in the graph key");
 
@@ -156,6 +157,11 @@ struct vz_engine {
     // classifier-free guidance (vz_llm_decode_guidance; guidance.hip): orthogonal to the tail - armed, the decode batch is 2 * pairs rows
     // (row r < pairs a prompt, row pairs + r its negative prompt) and everything behind the logits runs on the first `pairs` rows
     struct { int on = 0, pairs = 0; float scale = 1.f; } cfg;
+    // shared-prefix decode attention (vz_llm_decode_share; attn_shared.hip): the decode batch is groups x n rows and
+    // the rows of a group read h_shared[g] leading slots from cache row g * n.  d_tab = the `shared` table (64 ints), q_rot = the rotated
+    // queries [64][Hq][D], ws = the prefix partials - the engine's own allocations, made on the first arming, never carved from the arena
+    struct { int on = 0, n = 0, groups = 0, shared_max = 0; std::vector<int> h_shared; int* d_tab = nullptr; bf16_t* q_rot = nullptr;
+             float* ws = nullptr; size_t ws_floats = 0; } share;
     struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)

@@ -260,6 +260,25 @@ int vz_launch_attention_append(const AttnAppendArgs& a, hipStream_t s);
 int vz_attn_append_nsplit(int B, int T, int Hq, int Hkv, int kv_max);
 size_t vz_attn_append_ws_floats(int B, int T, int Hq, int Hkv, int max_ctx);
 
+// shared-prefix decode attention (attn_shared.hip): R rows in groups of n adjacent rows; row r sees the slots
+// [0, shared[r / n]) of cache row (r / n) * n and the slots [shared[r / n], slot[r]] of its own row
+struct AttnSharedArgs {
+    const bf16_t* q;      // rotated queries [R, Hq, D]
+    const bf16_t* kc;     // cache base of row 0: [rows][Hkv][max_ctx][D]
+    const bf16_t* vc;
+    bf16_t* o;            // [R, Hq, D]
+    float* part;          // fp32 workspace of part_floats elements (vz_attn_shared_ws_floats)
+    size_t part_floats;
+    const int *shared, *slot;   // device int32 [R / n], [R]
+    int R, n, Hq, Hkv, head_dim, max_ctx, window;
+    int shared_max;       // host: max over the groups of shared (chooses the key split)
+    int nsplit;           // 0 = the host rule, n >= 1 forced
+    float scale;
+};
+int vz_launch_attention_shared(const AttnSharedArgs& a, hipStream_t s);
+int vz_attn_shared_nsplit(int groups, int n, int Hq, int Hkv, int shared_max);
+size_t vz_attn_shared_ws_floats(int R, int n, int Hq, int Hkv, int max_ctx);
+
 // decode attention: one query token per slot against the KV cache; lengths live on the device
 struct AttnDecodeArgs {
     const bf16_t* q;      // [B, Hq, D]

@@ -335,6 +335,12 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, images=None, images_size=None, **kwargs):
         self._ensure_ready()
+        if kwargs.get("share_prompt_kv"):      # what the shared-prefix route does not build is refused here, before anything runs
+            from vz_hip import share as SH
+            scale = kwargs.get("guidance_scale", getattr(self.generation_config, "guidance_scale", None))
+            SH.check_call(kwargs.get("num_return_sequences"), kwargs.get("num_beams"),
+                          (scale is not None and scale != 1) or kwargs.get("negative_prompt_ids") is not None,
+                          kwargs.get("past_key_values") is not None, kwargs.get("prompt_lookup_num_tokens"), self.engine.tp_size)
         if kwargs.get("past_key_values") is not None:
             return self._generate_continue(input_ids, kwargs.pop("past_key_values"), kwargs)
         kwargs.pop("past_key_values", None)
@@ -455,7 +461,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                               output_logprobs: bool = False, stop_strings=None, tokenizer=None, device_stop: bool = True,
                               min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
                               eta_cutoff: Optional[float] = None, sequence_bias=None, bad_words_ids=None, beam_extended: bool = False,
-                              _guidance=None, _append=None, _prompt_rows=None, **unused):
+                              _guidance=None, _append=None, _prompt_rows=None, share_prompt_kv: bool = False, **unused):
         """`return_dict_in_generate=True` returns HF's `GenerateDecoderOnlyOutput` (a subclass with two more fields; `sequences` = the
         generated ids as the plain call returns them - generation starts from embeddings, so there are no prompt ids in front).  With
         `output_scores` / `output_logits` (HF's: tuples of [rows, V] fp32 per step, the processed and warped scores / the raw logits) or
@@ -525,7 +531,16 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         ids as HF's see a prompt's, a stop string may begin in them, host-side criteria get them in front of the new ids; `min_new_tokens`
         and the id-sequence stops count generated ids only.  `num_beams > 1`, guidance, `num_return_sequences > 1`, more rows than
         `max_batch`, tensor-parallel engines and a sampled or per-token batch of several rows raise NotImplementedError - all before the
-        handle goes stale; `prompt_lookup_num_tokens` takes the plain path."""
+        handle goes stale; `prompt_lookup_num_tokens` takes the plain path.
+
+        Shared prompt KV (vz_hip/share.py; csrc/attn_shared.hip): `share_prompt_kv=True` with `do_sample=True` and
+        `num_return_sequences = n >= 2` keeps each prompt's KV in the one cache row it was prefilled into - no copy into the other n - 1
+        rows - and every step's attention reads those slots once per (prompt, KV head) for all n rows as one stacked MFMA pass, each row
+        adding only its own generated slots.  The logits differ from the copy route's to bf16 rounding (another summation order), so ids
+        under one seed can differ at a near-tie; processors, per-row sampling, scores / log-probs and device stops work as on the copy
+        route.  Opt-in: absent or False, the call is the copy route, untouched.  With `num_beams > 1`, `guidance_scale`,
+        `past_key_values`, `prompt_lookup_num_tokens`, a tensor-parallel engine or `num_return_sequences == 1` the keyword raises
+        NotImplementedError before anything runs."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
         from vz_hip import stop as ST
@@ -598,7 +613,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
             self._kv_epoch += 1
         if nrs > 1:                          # n samples of every prompt decode together, each row on its own seed (the per-row tail)
             return done(self._generate_samples(inputs_embeds, seqlens, position_ids, nrs, max_new_tokens, temperature, top_k, top_p, seed, eos,
-                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp, neg=neg))
+                                               pad_token_id, sync_every, timing, proc, sink=sink, stop=stop, warp=warp, neg=neg, share=bool(share_prompt_kv)))
         if prompt_lookup_num_tokens and _spec_history is not None and proc is None and sink is None and stop is None and neg is None and app is None:      # (with processors, scores, device stops or guidance: the plain / guided greedy path)
             # HF's prompt lookup decoding: the ids the call yields anyway - the argmax, or in a sampled call the draw of each position under
             # the call's seed - several per weight sweep when the continuation repeats the context (vz_hip/spec.py)
@@ -715,12 +730,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
 
     # ---- n samples per prompt (hf:generation/utils.py `_sample` with num_return_sequences; csrc/sampling.hip: sample_rows_kernel) ----
     def _generate_samples(self, embeds, seqlens, position_ids, n, max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every,
-                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None, warp=None, neg=None) -> torch.Tensor:
+                          timing=None, proc=None, prompt0: int = 0, sink=None, stop=None, warp=None, neg=None, share: bool = False) -> torch.Tensor:
         """`n` sampled sequences of every prompt: [Bsz * n, T] in HF's order (prompt-major, a prompt's samples adjacent).  Each prompt is
         prefilled once into its first cache row, its prompt KV copied into its other n - 1 rows, its n first tokens drawn from the one
         row of prefill logits, and then all rows step together with the per-row tail: row j of prompt b draws under seed
         `seed + b * n + j` (vz_hip.sample_rows.row_seed) with its own counter, so it gets the tokens that seed gives it alone.  `neg`
-        (vz_hip.guidance.Negative): each negative prompt is prefilled once as well and spread over the n unconditional rows of its prompt."""
+        (vz_hip.guidance.Negative): each negative prompt is prefilled once as well and spread over the n unconditional rows of its prompt.
+        `share` (generate's `share_prompt_kv`; vz_hip/share.py): no copy - the prompt's KV stays in its first row and the armed step's
+        attention reads it from there for all n rows."""
         from vz_hip import sample_rows as SR
         eng = self.engine
         if eng.tp_size > 1:
@@ -734,10 +751,14 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if Bsz > G:
             part = lambda lo, hi, tm: self._generate_samples(embeds[lo:hi], seqlens[lo:hi], None if position_ids is None else position_ids[lo:hi], n,      # noqa: E731
                                                              max_new, temperature, top_k, top_p, seed, eos, pad_token_id, sync_every, tm, proc,
-                                                             prompt0 + lo, sink, stop, warp, None if neg is None else neg.rows(lo, hi))
+                                                             prompt0 + lo, sink, stop, warp, None if neg is None else neg.rows(lo, hi), share)
             return DL.run_parts(part, Bsz, G, pad_token_id, self.device, timing)
         if max(seqlens) + max_new > eng.max_ctx:
             raise ValueError(f"prompt ({max(seqlens)}) + max_new_tokens ({max_new}) exceeds the engine's max_ctx ({eng.max_ctx})")
+        plan = None
+        if share:
+            from vz_hip import share as SH
+            plan = SH.plan(seqlens, n, max_new, eng.max_ctx, getattr(self.config, "sliding_window", 0) or 0, eng.max_batch)
         R = Bsz * n
         uncond = None
         if neg is None:
@@ -749,9 +770,9 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
                                SR.row_seed(seed, prompt0 + r // n, n, r % n), 0, **(warp or {})) for r in range(R)]
         first, first_cpu, blk = DL.first_tokens(last, params, proc, sink, timing, uncond=uncond)
         if neg is None:
-            next_pos, ctx_len = DL.fan_spread(eng, seqlens, position_ids, n)
+            next_pos, ctx_len = (DL.fan_share if share else DL.fan_spread)(eng, seqlens, position_ids, n)
         with DL.armed(eng, proc=proc, sampling_rows=[p.at(1) for p in params], scores=DL.chunk_recorder(sink, R, sync_every, max_new),
-                      stop=stop, guidance=None if neg is None else neg.config(R)) as begin:
+                      stop=stop, guidance=None if neg is None else neg.config(R), share=plan) as begin:
             begin(first, next_pos, ctx_len)
             return DL.decode_rows(eng, first_cpu, max_new, eos, pad_token_id, sync_every, blk, stop is not None).to(self.device)
 

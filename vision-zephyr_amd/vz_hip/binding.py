@@ -100,6 +100,8 @@ SYMBOLS = {
     "vz_op_colsum_groups": (_I, [_L]),
     "vz_op_attention_append": (_I, [_P] * 6 + [_I] * 7 + [_L] * 6 + [_F, _I, _I, _P, _L, _P]),
     "vz_op_attention_append_ws_floats": (_L, [_I] * 5),
+    "vz_op_attention_shared": (_I, [_P] * 6 + [_I] * 7 + [_F, _I, _I, _P, _L, _P]),
+    "vz_op_attention_shared_ws_floats": (_L, [_I] * 5),
     "vz_op_attention_bwd": (_I, [_P] * 7 + [_I] * 7 + [_F, _I, _I, _P, _P, _L, _P]),
     "vz_op_attention_split": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I] + [_L] * 12 + [_F, _I, _I, _I, _P, _P, _L, _P]),
     "vz_op_argmax": (_I, [_P, _I, _I, _P, _P]),
@@ -190,6 +192,7 @@ SYMBOLS = {
     "vz_llm_decode_stop_row_seqs": (_I, [_P, _I, _P]),
     "vz_llm_decode_stop_set_row_seqs": (_I, [_P, _I, _P, _I, _P]),
     "vz_llm_decode_guidance": (_I, [_P, _I, _F, _I, _P]),
+    "vz_llm_decode_share": (_I, [_P, _I, _P, _I, _P]),
     "vz_op_cfg_combine": (_I, [_P, _P, _I, _I, _F, _P]),
     "vz_llm_decode_beam": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "vz_op_beam_select": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
@@ -1018,6 +1021,31 @@ def attention_append(q, kcache, vcache, past, new, scale, kv_max, window=0, nspl
     check(lib().vz_op_attention_append(ptr(q), ptr(kcache), ptr(vcache), ptr(o), ptr(past), ptr(new), B, T, Hq, Hkv, D, max_ctx, int(kv_max),
                                        q.stride(0), q.stride(1), q.stride(2), o.stride(0), o.stride(1), o.stride(2),
                                        float(scale), window, nsplit, ptr(ws), ws.numel(), stream_ptr(q.device)))
+    return o
+
+
+def attention_shared_ws_floats(R, n, Hq, Hkv, max_ctx) -> int:
+    """fp32 workspace elements that cover every key split vz_op_attention_shared's host rule can choose; 0 = a refused shape; needs no GPU."""
+    return lib().vz_op_attention_shared_ws_floats(R, n, Hq, Hkv, max_ctx)
+
+
+def attention_shared(q, kcache, vcache, shared, slot, n, scale, shared_max, window=0, nsplit=0, out=None, ws=None):
+    """Shared-prefix decode attention (attn_shared.hip; DESIGN.md section 6n).  q rotated bf16 [R,Hq,128]; caches [rows >= R,Hkv,max_ctx,128];
+    shared int32 [R / n], slot int32 [R] on the device: row r sees the slots [0, shared[r // n]) of cache row (r // n) * n and the slots
+    [shared[r // n], slot[r]] of its own row; shared_max = max(shared) (host) -> o [R,Hq,128] (`out` or a new tensor).  nsplit 0 = the
+    host rule, >= 1 forced; ws: the fp32 workspace (default: one that covers the call)."""
+    _need_cuda(q, kcache, vcache, shared, slot)
+    R, Hq, D = q.shape
+    Hkv, max_ctx = kcache.shape[1], kcache.shape[2]
+    assert q.dtype == torch.bfloat16 and q.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous() and kcache.shape[0] >= R
+    assert shared.dtype == torch.int32 and slot.dtype == torch.int32 and slot.numel() == R and shared.numel() * n == R
+    o = torch.empty(R, Hq, D, dtype=torch.bfloat16, device=q.device) if out is None else out
+    assert o.dtype == torch.bfloat16 and o.is_contiguous() and tuple(o.shape) == (R, Hq, D)
+    if ws is None:
+        floats = max(attention_shared_ws_floats(R, n, Hq, Hkv, max_ctx), R * Hq * min(max(nsplit, 1), 64) * (D + 4), 1)
+        ws = torch.empty(floats, dtype=torch.float32, device=q.device)
+    check(lib().vz_op_attention_shared(ptr(q), ptr(kcache), ptr(vcache), ptr(o), ptr(shared), ptr(slot), R, int(n), Hq, Hkv, D, max_ctx,
+                                       int(shared_max), float(scale), int(window), int(nsplit), ptr(ws), ws.numel(), stream_ptr(q.device)))
     return o
 
 

@@ -123,13 +123,14 @@ class arming:
 
 @contextmanager
 def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=None, stop=None, beam=None, beam_rows=None, guidance=None,
-          history=None):
+          history=None, share=None):
     """Arms what the call asked for in the one order the engine requires - logits processors, classifier-free guidance (`guidance`: a
     vz_hip.guidance.GuidanceConfig; `begin` then takes the first tokens of the conditional rows and the positions of all 2 * pairs rows,
     and hands each first token to both rows of its pair), the step's tail (`sampling`: the arguments
     of `set_sampling`, or `sampling_rows`: the per-row table), the host token ring, the step recorder (`scores`: the arguments of
     `set_scores`), the stop matcher, the beam tail's row recorder (`beam_rows`: the arguments of `set_beam_rows`), the beam tail (`beam`:
-    the arguments of `set_beam`) - all in front of the batch's `decode_begin`,
+    the arguments of `set_beam`), the shared-prefix attention (`share`: a vz_hip.share.Plan - the batch `begin` starts is its groups x n
+    rows) - all in front of the batch's `decode_begin`,
     and yields `begin(first, next_pos, ctx_len)`: `decode_begin`, then the matcher takes the rows' first tokens.  On the way out,
     whatever happened (a failed arming included), exactly what was armed is disarmed, last first.  None = not asked for: not called.
     history (a call that continues on a kept cache): per row the ids fed before the first token - the processors' histories and the stop
@@ -163,6 +164,8 @@ def armed(eng, proc=None, sampling=None, sampling_rows=None, ring=None, scores=N
             arm("set_beam_rows", beam_rows, (None,))
         if beam is not None:
             arm("set_beam", beam, (False,))
+        if share is not None:
+            arm("set_share", (share,), (None,))
         yield begin
 
 
@@ -239,6 +242,16 @@ def fan_spread(eng, seqlens, position_ids, n: int):
     src = [g * n for g in range(G) for _ in range(1, n)]
     dst = [g * n + j for g in range(G) for j in range(1, n)]
     eng.kv_move_rows(src, dst, [seqlens[d // n] for d in dst])
+    ctx_len = [int(seqlens[r // n]) for r in range(G * n)]
+    next_pos = list(ctx_len) if position_ids is None else [int(position_ids[r // n, ctx_len[r] - 1]) + 1 for r in range(G * n)]
+    return next_pos, ctx_len
+
+
+def fan_share(eng, seqlens, position_ids, n: int):
+    """`fan_spread` without the copies: the prompt's KV stays in its first row alone and the rows of a prompt read it from there
+    (`armed(share=)`).  Returns (next_pos, ctx_len) per row for `begin` - every row appends behind the prompt in
+    its own cache row."""
+    G = len(seqlens)
     ctx_len = [int(seqlens[r // n]) for r in range(G * n)]
     next_pos = list(ctx_len) if position_ids is None else [int(position_ids[r // n, ctx_len[r] - 1]) + 1 for r in range(G * n)]
     return next_pos, ctx_len

@@ -748,6 +748,16 @@ class Engine:
         B.check(self.lib.vz_llm_decode_guidance(self.h, 1, float(cfg.scale), int(cfg.pairs), self._s()))
         self._guid = cfg
 
+    def set_share(self, plan=None):
+        """Shared-prefix decode attention (attn_shared.hip; plan = vz_hip.share.Plan, None = off): the NEXT
+        `decode_begin` takes len(plan.shared) * plan.n rows, and the n adjacent rows of group g read their first plan.shared[g] cache slots
+        from cache row g * n - nothing is copied into the other rows.  Armed, the engine refuses what would write into those slots."""
+        if plan is None:
+            B.check(self.lib.vz_llm_decode_share(self.h, 0, None, 0, self._s()))
+            return
+        tab = (C.c_int * len(plan.shared))(*[int(v) for v in plan.shared])
+        B.check(self.lib.vz_llm_decode_share(self.h, int(plan.n), tab, len(plan.shared), self._s()))
+
     def set_ring(self, ring: Optional[torch.Tensor]):
         """host-visible (pinned) int32 ring the step tails write their tokens to: [slots] for a one-row batch or [rows, slots]
         (slot = draw counter mod slots); None = off.  decode_steps refuses a batch with more rows than the ring has."""
