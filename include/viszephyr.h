@@ -686,6 +686,32 @@ int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, 
  * size (d_out = NULL: the size only).  Tests. */
 int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, size_t* bytes, vz_stream stream);
 
+/* ---- opt-in e4m3 mirror of the KV cache that the decode attention streams (csrc/attn_decode_kv8.hip; vz_hip/kv8.py) ----
+ * The bf16 cache stays: prefill writes it, the prefill and append-prefill attention read it.  Beside it the mirror holds every cache row as OCP
+ * e4m3 bytes with ONE fp32 power-of-two scale per (cache row, KV head, slot), for K (after RoPE) and for V, each 128-value row quantised as
+ * vz_hip/quant.py::quantize_rows quantises a weight row - +50 % KV memory.  Writers: the prefills (slots [0, past + new) of the rows they touch,
+ * every layer), vz_llm_kv_move_rows (slots [0, len) of the destination rows) and the decode step itself (the new token's row).
+ * vz_engine_kv_fp8(e, 1) allocates the mirror and marks every row invalid until one of the first two writers has rebuilt it:
+ * vz_llm_decode_begin / vz_llm_decode_set_row return VZ_ERR_STATE for a row with ctx_len > 0 whose mirror is invalid.  While on, the decode
+ * step runs the kv8 attention for every batch size (no attention + O fusion, no persistent token kernel) and vz_llm_decode_spec,
+ * vz_llm_decode_share, vz_llm_decode_beam and vz_llm_kv_beam_reorder return VZ_ERR_UNSUPPORTED.  VZ_ERR_UNSUPPORTED on tp_size > 1.
+ * vz_engine_kv_fp8(e, 0) (the default state) frees it: every call is the plain engine's.  Not inside a capture.
+ * vz_llm_kv8_copy_out (tests): the mirror's bytes [layer][K|V][max_batch][kv head][max_ctx][head_dim] into d_q and its fp32 scales
+ * [layer][K|V][max_batch][kv head][max_ctx] into d_scales; *q_bytes / *scale_floats = the sizes (d_q = d_scales = NULL: the sizes only).
+ * vz_op_kv8_mirror_rows: the writer on caller buffers - slots [0, h_len[i]) of rows h_row[i] (n <= 64) of d_kcache / d_vcache bf16
+ * [R][Hkv][max_ctx][128] into d_k8 / d_v8 (same shape, bytes) and d_ks / d_vs fp32 [R][Hkv][max_ctx]; other slots are left untouched.
+ * vz_op_attention_decode_kv8: vz_op_attention_decode_fused over the mirror - slots < d_slot[b] are read from d_k8 / d_v8 with their scales,
+ * the new token's row is used in bf16 and appended to the bf16 caches and, quantised, to the mirror; B <= 64, nsplit <= 32. */
+int vz_engine_kv_fp8(vz_engine* e, int enable);
+int vz_llm_kv8_copy_out(vz_engine* e, void* d_q, size_t max_q_bytes, float* d_scales, size_t max_scale_floats, size_t* q_bytes,
+                        size_t* scale_floats, vz_stream stream);
+int vz_op_kv8_mirror_rows(const void* d_kcache, const void* d_vcache, void* d_k8, void* d_v8, float* d_ks, float* d_vs, int n,
+                          const int* h_row, const int* h_len, int Hkv, int head_dim, int max_ctx, vz_stream stream);
+int vz_op_attention_decode_kv8(const void* d_qkv, void* d_kcache, void* d_vcache, void* d_k8, void* d_v8, float* d_ks, float* d_vs,
+                               void* d_o, float* d_workspace, unsigned* d_ticket, const float* d_cos, const float* d_sin,
+                               const int* d_pos, const int* d_slot, int B, int Hq, int Hkv, int head_dim, int max_ctx, int nsplit,
+                               int window, float scale, vz_stream stream);
+
 /* ---- prompt-lookup speculative decoding of one greedy sequence (hf:generation/candidate_generator.py PromptLookupCandidateGenerator;
  * csrc/spec.hip; vz_hip/spec.py) ----
  * A verify step carries R = D + 1 rows (D in 1..7) of ONE sequence in cache row 0: row 0 = the last emitted token, rows 1..D = guessed

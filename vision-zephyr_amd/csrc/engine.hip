@@ -334,6 +334,25 @@ extern "C" int vz_op_attention_decode_fused(const void* qkv, void* kc, void* vc,
     a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.max_ctx = max_ctx; a.nsplit = nsplit; a.window = window; a.scale = scale;
     return vz_launch_attn_decode_fused(a, (hipStream_t)s);
 }
+extern "C" int vz_op_attention_decode_kv8(const void* qkv, void* kc, void* vc, void* k8, void* v8, float* ks, float* vs, void* o, float* ws, unsigned* ticket,
+                                          const float* cosT, const float* sinT, const int* pos, const int* slot, int B, int Hq,
+                                          int Hkv, int D, int max_ctx, int nsplit, int window, float scale, vz_stream s) {
+    VZ_CHECK_ARG(qkv && kc && vc && k8 && v8 && ks && vs && o && ws && ticket && cosT && sinT && pos && slot && B > 0, "attention_decode_kv8: bad argument");
+    AttnDecodeKv8Args a;
+    a.qkv = (const bf16_t*)qkv; a.kc = (bf16_t*)kc; a.vc = (bf16_t*)vc; a.k8 = (unsigned char*)k8; a.v8 = (unsigned char*)v8; a.ks = ks; a.vs = vs;
+    a.o = (bf16_t*)o; a.part = ws; a.ticket = ticket; a.cosT = cosT; a.sinT = sinT; a.pos = pos; a.slot = slot;
+    a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.max_ctx = max_ctx; a.nsplit = nsplit; a.window = window; a.scale = scale;
+    return vz_launch_attn_decode_kv8(a, (hipStream_t)s);
+}
+extern "C" int vz_op_kv8_mirror_rows(const void* kc, const void* vc, void* k8, void* v8, float* ks, float* vs, int n, const int* h_row, const int* h_len,
+                                     int Hkv, int D, int max_ctx, vz_stream s) {
+    VZ_CHECK_ARG(kc && vc && k8 && v8 && ks && vs && h_row && h_len && n >= 1 && n <= 64 && D == 128, "kv8_mirror_rows: bad argument (1..64 rows, head_dim 128)");
+    Kv8MirrorArgs a;
+    a.src[0] = (const bf16_t*)kc; a.src[1] = (const bf16_t*)vc; a.q[0] = (unsigned char*)k8; a.q[1] = (unsigned char*)v8; a.sc[0] = ks; a.sc[1] = vs;
+    a.layer_elems = 0; a.n_layers = 1; a.Hkv = Hkv; a.max_ctx = max_ctx; a.n = n;
+    for (int i = 0; i < n; ++i) { a.row[i] = h_row[i]; a.len[i] = h_len[i]; }
+    return vz_launch_kv8_mirror_rows(a, (hipStream_t)s);
+}
 extern "C" int vz_op_argmax(const float* logits, int rows, int cols, int* ids, vz_stream s) {
     return vz_launch_argmax(logits, rows, cols, ids, {}, (hipStream_t)s);
 }
@@ -480,6 +499,8 @@ extern "C" int vz_engine_destroy(vz_engine* e) {
     if (e->share.d_tab) hipFree(e->share.d_tab);
     if (e->share.q_rot) hipFree(e->share.q_rot);
     if (e->share.ws) hipFree(e->share.ws);
+    if (e->kv8.q) hipFree(e->kv8.q);
+    if (e->kv8.sc) hipFree(e->kv8.sc);
     if (e->proc.d) hipFree(e->proc.d);
     if (e->proc.d_seq) hipFree(e->proc.d_seq);
     if (e->proc.d_rows) hipFree(e->proc.d_rows);
@@ -965,6 +986,24 @@ extern "C" int vz_tp_all_gather(vz_engine* e, const void* d_send, void* d_recv, 
 static bf16_t* kc_of(vz_engine* e, int layer) { return e->kv + (size_t)layer * e->kv_layer_elems; }
 static bf16_t* vc_of(vz_engine* e, int layer) { return kc_of(e, layer) + e->kv_layer_elems / 2; }
 
+// (re)build slots [0, h_len[i]) of cache rows h_row[i] in the e4m3 mirror from the bf16 cache, layers [layer0, layer0 + n_layers), and mark
+// the rows valid (attn_decode_kv8.hip: kv8_mirror_rows_kernel, 64 rows per launch)
+static int kv8_mirror(vz_engine* e, int layer0, int n_layers, const int* h_row, const int* h_len, int n, hipStream_t s) {
+    const vz_config& c = e->c;
+    const size_t half = e->kv_layer_elems / 2, l0 = (size_t)layer0 * e->kv_layer_elems;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        Kv8MirrorArgs a;
+        a.src[0] = e->kv + l0; a.src[1] = e->kv + l0 + half;
+        a.q[0] = e->kv8.q + l0; a.q[1] = e->kv8.q + l0 + half;
+        a.sc[0] = e->kv8.sc + l0 / c.head_dim; a.sc[1] = e->kv8.sc + (l0 + half) / c.head_dim;
+        a.layer_elems = e->kv_layer_elems; a.n_layers = n_layers; a.Hkv = e->Hkv_l; a.max_ctx = c.max_ctx; a.n = std::min(64, n - i0);
+        for (int i = 0; i < a.n; ++i) { a.row[i] = h_row[i0 + i]; a.len[i] = h_len[i0 + i]; }
+        RC(vz_launch_kv8_mirror_rows(a, s));
+    }
+    for (int i = 0; i < n; ++i) e->kv8.valid[h_row[i]] = 1;
+    return VZ_OK;
+}
+
 static bool rows_shape_ok(const vz_config& c, int row0, int B, int T) { return B >= 1 && row0 >= 0 && row0 + B <= c.max_batch && T >= 1 && T <= c.max_ctx; }
 // q8, qs: carve_prefill only; part, part_floats: carve_append only
 struct RowsWs { bf16_t *x, *y, *qkv, *q, *att, *act; int* ints; bf16_t* ylast; unsigned char* q8 = nullptr; float* qs = nullptr; float* part = nullptr; size_t part_floats = 0; };
@@ -1036,6 +1075,8 @@ static int llm_rows_forward(vz_engine* e, const RowsWs& w, const RowsCall& k, bo
     int* d_len = w.ints + rows;
     int kv_max = 0;
     bool padded = false;
+    std::vector<int> kv8_row(B), kv8_len(B);      // the e4m3 mirror on: every layer rebuilds slots [0, past + new) of the rows this call touches
+    for (int b = 0; b < B; ++b) { kv8_row[b] = k.row0 + b; kv8_len[b] = k.h_past[b] + k.h_new[b]; }
     {
         std::vector<int> h(rows + (keysplit ? 3 : 1) * B);          // slot[rows] | kv_len[B], and for the key-split kernel | past[B] | new[B]
         for (int b = 0; b < B; ++b) {
@@ -1079,6 +1120,7 @@ static int llm_rows_forward(vz_engine* e, const RowsWs& w, const RowsCall& k, bo
         RC(plin(x, W.in_norm, W.qkv, QKV, H, qkv, QKV, nullptr, VZ_ACT_NONE));
         // RoPE of K + the KV append at slot past + t; the rotated copy q of the queries unless the attention rotates them in its own load
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_rope_kv(qkv, QKV, rope_q_late ? nullptr : q, kc, vc, e->cosT, e->sinT, k.d_pos, d_slot, B, T, Hq, Hkv, D, c.max_ctx, s)); }
+        if (e->kv8.on) { ProfScope ps(e, K_OTHER, s); RC(kv8_mirror(e, i, 1, kv8_row.data(), kv8_len.data(), B, s)); }
         if (keysplit) {
             ProfScope ps(e, K_ATTN, s);
             AttnAppendArgs a;
@@ -1195,6 +1237,11 @@ extern "C" int vz_llm_decode_begin(vz_engine* e, int B, const int* d_first_ids, 
     const DecodeState hs = decode_state(h.data(), mb), ds = decode_state(e->d_state, mb);
     for (int b = 0; b < B; ++b) {
         VZ_CHECK_ARG(h_ctx_len[b] >= 0 && h_ctx_len[b] < c.max_ctx, "decode_begin: ctx_len[%d]=%d outside [0,%d)", b, h_ctx_len[b], c.max_ctx);
+        if (e->kv8.on && h_ctx_len[b] > 0 && !e->kv8.valid[b]) {
+            vz_set_error("decode_begin: row %d has %d cached positions but no e4m3 mirror of them (vz_engine_kv_fp8 is on: prefill the row, or move KV "
+                         "into it, after enabling)", b, h_ctx_len[b]);
+            return VZ_ERR_STATE;
+        }
         hs.pos[b] = h_next_pos[b];
         hs.slot[b] = h_ctx_len[b];         // slot the next token is written to
         hs.len[b] = h_ctx_len[b] + 1;      // keys visible to the next token
@@ -1224,6 +1271,11 @@ extern "C" int vz_llm_decode_set_row(vz_engine* e, int row, int token, int next_
     VZ_CHECK_ARG(!e->share.on || (row < e->share.groups * e->share.n && ctx_len >= e->share.h_shared[row / e->share.n]),
                  "decode_set_row: row %d to context %d, in front of the %d slots its group shares (vz_llm_decode_share is armed: a row is neither parked nor "
                  "moved into the shared slots)", row, ctx_len, e->share.on && row < e->share.groups * e->share.n ? e->share.h_shared[row / e->share.n] : 0);
+    if (e->kv8.on && ctx_len > 0 && !e->kv8.valid[row]) {
+        vz_set_error("decode_set_row: row %d has %d cached positions but no e4m3 mirror of them (vz_engine_kv_fp8 is on: prefill the row, or move KV "
+                     "into it, after enabling)", row, ctx_len);
+        return VZ_ERR_STATE;
+    }
     const DecodeState ds = decode_state(e->d_state, c.max_batch);
     const int h[DecodeState::ROW_ARRAYS] = {token, next_pos, ctx_len, ctx_len + 1};     // cur | pos | slot | len: one int in each of the four state arrays
     e->h_len[row] = ctx_len + 1; e->h_pos[row] = next_pos; e->h_parked[row] = ctx_len == 0 && next_pos == 0;
@@ -1260,6 +1312,8 @@ extern "C" int vz_llm_kv_move_rows(vz_engine* e, int n, const int* h_src, const 
         for (int i = 0; i < mv.n; ++i) { mv.src[i] = h_src[i0 + i]; mv.dst[i] = h_dst[i0 + i]; mv.len[i] = h_len[i0 + i]; }
         int r = vz_launch_kv_move_rows(e->kv, e->kv_layer_elems, c.n_layers, c.max_batch, e->Hkv_l, c.max_ctx, c.head_dim, mv, (hipStream_t)stream);
         if (r) return r;
+        // the e4m3 mirror of the destination rows: re-quantised from the moved bf16 rows, every layer (the mirror is a function of the cache)
+        if (e->kv8.on) RC(kv8_mirror(e, 0, c.n_layers, mv.dst, mv.len, mv.n, (hipStream_t)stream));
     }
     return VZ_OK;
 }
@@ -1341,7 +1395,7 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
         { ProfScope ps(e, K_OTHER, s); RC(vz_launch_embed_tokens(st.cur, B, H, e->top.embed, x, s)); }
         for (int i = 0; i < c.n_layers; ++i) {
             const LlmLayerW& W = e->llm[i];
-            const bool fuse_ao = !spec && !e->share.on && vz_knob(VZ_KNOB_ATTN_O) && (B == 1 || (B == 2 && vz_knob(VZ_KNOB_ATTN_O) >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
+            const bool fuse_ao = !spec && !e->share.on && !e->kv8.on && vz_knob(VZ_KNOB_ATTN_O) && (B == 1 || (B == 2 && vz_knob(VZ_KNOB_ATTN_O) >= 1 && 2 * e->dec_nsplit <= 32)) && e->tp == 1 && tp_local(e) && H == 4096 && A == 4096 && Hq == 32 && Hkv == 8 &&
                                  D == 128 && e->dec_nsplit <= 32 && e->d_ao_done;
             RC(linear(e, 1, x, H, W.qkv, H, qkv, QKV, B, QKV, H, nullptr, 0, VZ_ACT_NONE, 0, s, W.in_norm, c.rms_eps));
             if (spec) {
@@ -1365,6 +1419,18 @@ static int decode_step_launch(vz_engine* e, const DecodeWs& w, int* d_out_ids, i
                 a.R = B; a.n = e->share.n; a.Hq = Hq; a.Hkv = Hkv; a.head_dim = D; a.max_ctx = c.max_ctx; a.window = c.sliding_window;
                 a.shared_max = e->share.shared_max; a.nsplit = 0; a.scale = ATTN_SCALE;
                 RC(vz_launch_attention_shared(a, s));
+            } else if (e->kv8.on) {
+                // the e4m3 mirror on (attn_decode_kv8.hip): the same step with the cached slots read from the mirror, for
+                // every batch size; the new row goes to the bf16 cache and to the mirror
+                ProfScope ps(e, K_ATTN_DEC, s);
+                const size_t l0 = (size_t)i * e->kv_layer_elems, half = e->kv_layer_elems / 2;
+                AttnDecodeKv8Args a;
+                a.qkv = qkv; a.kc = kc_of(e, i); a.vc = vc_of(e, i); a.o = att; a.part = e->d_part; a.ticket = e->d_ticket;
+                a.k8 = e->kv8.q + l0; a.v8 = e->kv8.q + l0 + half; a.ks = e->kv8.sc + l0 / D; a.vs = e->kv8.sc + (l0 + half) / D;
+                a.cosT = e->cosT; a.sinT = e->sinT; a.pos = st.pos; a.slot = st.slot;
+                a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.max_ctx = c.max_ctx; a.nsplit = std::min(e->dec_nsplit, 32); a.window = c.sliding_window;
+                a.scale = ATTN_SCALE;
+                RC(vz_launch_attn_decode_kv8(a, s));
             } else {
                 ProfScope ps(e, K_ATTN_DEC, s);
                 AttnDecodeFusedArgs a;
@@ -1917,6 +1983,7 @@ extern "C" int vz_llm_decode_share(vz_engine* e, int n, const int* h_shared, int
     NEED_READY();
     if (n == 0) { e->share.on = 0; e->share.n = 0; e->share.groups = 0; e->share.shared_max = 0; e->share.h_shared.clear(); return VZ_OK; }
     const vz_config& c = e->c;
+    if (e->kv8.on) { vz_set_error("decode_share: not available while the e4m3 KV mirror is on (vz_engine_kv_fp8): its attention reads the bf16 cache and its writes would leave the mirror stale"); return VZ_ERR_UNSUPPORTED; }
     if (e->tp > 1) { vz_set_error("decode_share: the shared-prefix attention on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(n >= 2 && n <= 64 && groups >= 1 && h_shared && (long)groups * n <= std::min(c.max_batch, 64), "decode_share: 2 <= n (%d) <= 64 rows per group and "
                  "groups (%d) x n <= min(max_batch = %d, 64) expected", n, groups, c.max_batch);
@@ -1994,6 +2061,7 @@ extern "C" int vz_llm_decode_beam(vz_engine* e, int enable, int nb, int groups, 
     NEED_READY();
     if (!enable) { e->beam.on = 0; e->beam.a.hist = nullptr; return VZ_OK; }
     const vz_config& c = e->c;
+    if (e->kv8.on) { vz_set_error("decode_beam: not available while the e4m3 KV mirror is on (vz_engine_kv_fp8): its attention reads the bf16 cache and its writes would leave the mirror stale"); return VZ_ERR_UNSUPPORTED; }
     if (e->tp > 1) { vz_set_error("decode_beam: beam search on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(nb >= 2 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, BEAM_ROWS) && h_base && d_scores &&
                  d_hist && hist_steps >= 1, "decode_beam: %d groups x %d beams (2..16) must fit min(max_batch %d, 64) rows; base, scores and "
@@ -2074,6 +2142,7 @@ extern "C" int vz_llm_decode_beam_rows(vz_engine* e, float* d_scores, float* d_r
 extern "C" int vz_llm_kv_beam_reorder(vz_engine* e, int nb, int groups, const int* h_base, const int* h_end, const int* d_parent, vz_stream stream) {
     NEED_READY();
     const vz_config& c = e->c;
+    if (e->kv8.on) { vz_set_error("kv_beam_reorder: not available while the e4m3 KV mirror is on (vz_engine_kv_fp8): its attention reads the bf16 cache and its writes would leave the mirror stale"); return VZ_ERR_UNSUPPORTED; }
     VZ_CHECK_ARG(nb >= 1 && nb <= 16 && groups >= 1 && nb * groups <= std::min(c.max_batch, BEAM_ROWS) && h_base && h_end && d_parent,
                  "kv_beam_reorder: %d groups x %d rows must fit min(max_batch %d, 64)", groups, nb, c.max_batch);
     for (int g = 0; g < groups; ++g)
@@ -2097,6 +2166,7 @@ extern "C" int vz_llm_decode_spec(vz_engine* e, int enable, int D, int max_ngram
     NEED_READY();
     if (!enable) { e->spec.on = 0; e->spec.a.samp = ROW_GREEDY; return VZ_OK; }
     const vz_config& c = e->c;
+    if (e->kv8.on) { vz_set_error("decode_spec: not available while the e4m3 KV mirror is on (vz_engine_kv_fp8): its attention reads the bf16 cache and its writes would leave the mirror stale"); return VZ_ERR_UNSUPPORTED; }
     if (e->tp > 1) { vz_set_error("decode_spec: speculative decoding on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
     const int R = D + 1;
     VZ_CHECK_ARG(D >= 1 && D <= 7 && R <= c.max_batch && e->dec_B == R, "decode_spec: D = %d draft slots (1..7) need a running decode batch of D + 1 rows "
@@ -2215,6 +2285,23 @@ extern "C" int vz_llm_kv_copy_out(vz_engine* e, void* d_out, size_t max_bytes, s
     return VZ_OK;
 }
 
+// The same for the e4m3 mirror (vz_engine_kv_fp8; tests): the bytes [layer][K|V][max_batch][kv head][max_ctx][head_dim] into d_q and the fp32
+// scales [layer][K|V][max_batch][kv head][max_ctx] into d_scales; *q_bytes / *scale_floats receive the sizes; d_q = d_scales = NULL only asks.
+extern "C" int vz_llm_kv8_copy_out(vz_engine* e, void* d_q, size_t max_q_bytes, float* d_scales, size_t max_scale_floats, size_t* q_bytes, size_t* scale_floats,
+                                   vz_stream stream) {
+    NEED_READY();
+    VZ_CHECK_ARG(q_bytes && scale_floats, "kv8_copy_out: null size");
+    if (!e->kv8.on) { vz_set_error("kv8_copy_out: the e4m3 KV mirror is off (vz_engine_kv_fp8)"); return VZ_ERR_STATE; }
+    *q_bytes = e->kv_layer_elems * e->c.n_layers;
+    *scale_floats = *q_bytes / e->c.head_dim;
+    if (!d_q && !d_scales) return VZ_OK;
+    VZ_CHECK_ARG(d_q && d_scales && max_q_bytes >= *q_bytes && max_scale_floats >= *scale_floats, "kv8_copy_out: %zu bytes / %zu floats do not hold the %zu-byte mirror and its "
+                 "%zu scales", max_q_bytes, max_scale_floats, *q_bytes, *scale_floats);
+    VZ_CHECK_HIP(hipMemcpyAsync(d_q, e->kv8.q, *q_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    VZ_CHECK_HIP(hipMemcpyAsync(d_scales, e->kv8.sc, *scale_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return VZ_OK;
+}
+
 // Does a linear of the B-row step decode_step_launch is about to issue (its four projections, the lm_head) leave the <= 16-row
 // weight-stream kernels?  Those routes - the tile GEMMs, gemm_wide.hip and the 17..64-row kernel beside them - are the ones whose launches
 // may take per-stream split-K scratch, which cannot be allocated inside a capture.
@@ -2253,6 +2340,7 @@ static DecodeGraphKey decode_graph_key(const vz_engine* e, int n, int* d_out_ids
     k.proc_rows_on = e->proc.rows_on; k.stop_rows_on = e->stop.rows_on;
     if (e->cfg.on) { k.cfg_scale = e->cfg.scale; k.cfg_pairs = e->cfg.pairs; }
     if (e->share.on) { k.share_n = e->share.n; k.share_nsplit = vz_attn_shared_nsplit(e->share.groups, e->share.n, e->Hq_l, e->Hkv_l, e->share.shared_max); k.share_tab = e->share.d_tab; }
+    if (e->kv8.on) k.kv8 = e->kv8.q;
     if (e->score.what) { k.sc_what = e->score.what; k.sc_cap = e->score.cap; k.sc_rec = e->score.rec; k.sc_warped = e->score.warped; k.sc_raw = e->score.raw; }
     return k;
 }
@@ -2273,6 +2361,10 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
             vz_set_error("decode_steps: the shared-prefix attention (vz_llm_decode_share) does not run with guidance or the speculative tail");
             return VZ_ERR_UNSUPPORTED;
         }
+    }
+    if (e->kv8.on && (e->share.on || tail == TAIL_BEAM || tail == TAIL_SPEC)) {
+        vz_set_error("decode_steps: the e4m3 KV mirror (vz_engine_kv_fp8) runs the plain step only, not the shared-prefix attention, the beam or the speculative tail");
+        return VZ_ERR_UNSUPPORTED;
     }
     if (e->cfg.on) {
         if (tail == TAIL_BEAM || tail == TAIL_SPEC) {
@@ -2313,7 +2405,7 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
     // vz_tune_set(28, 1) - batch 1, one GPU, bf16 weights, Zephyr-7B geometry on a 256-CU device: the steps run as ONE resident grid
     // per token (decode_persist.hip) instead of the launch chain.  Its pointer table is (re)built here, never inside a capture.
     e->use_tok = false;
-    if (vz_knob(VZ_KNOB_PERSIST_DECODE) && B == 1 && e->tp == 1 && tp_local(e) && !c.weight_fp8 && c.hidden == 4096 && c.inter == 14336 && c.n_heads == 32 &&
+    if (vz_knob(VZ_KNOB_PERSIST_DECODE) && !e->kv8.on && B == 1 && e->tp == 1 && tp_local(e) && !c.weight_fp8 && c.hidden == 4096 && c.inter == 14336 && c.n_heads == 32 &&
         c.n_kv_heads == 8 && c.head_dim == 128 && c.vocab >= 256 && vz_decode_persist_supported()) {
         if (!e->tok) {
             std::vector<VzTokLayerHost> lt(c.n_layers);
@@ -2428,6 +2520,43 @@ extern "C" int vz_llm_decode_steps(vz_engine* e, int n, int* d_out_ids, float* d
 extern "C" int vz_engine_prefill_fp8(vz_engine* e, int enable) {
     VZ_CHECK_ARG(e && (!enable || e->c.weight_fp8), "prefill_fp8: needs an engine created with weight_fp8 = 1");
     e->prefill_fp8 = enable ? 1 : 0;
+    return VZ_OK;
+}
+
+// The opt-in e4m3 mirror of the KV cache for the decode attention.  1: allocates the mirror (1 byte per cache element + one
+// fp32 scale per 128: +50 % KV memory next to the bf16 cache, which stays) and marks every row's mirror invalid - a row decodes again once a
+// prefill (vz_llm_prefill_rows / vz_llm_prefill_append) or vz_llm_kv_move_rows has rebuilt it.  0 (default): frees it; every call is the
+// plain engine's.  Never inside a capture: the captured step is dropped.
+extern "C" int vz_engine_kv_fp8(vz_engine* e, int enable) {
+    VZ_CHECK_ARG(e, "kv_fp8: null engine");
+    if (enable && e->tp > 1) { vz_set_error("kv_fp8: the e4m3 KV mirror on a tensor-parallel engine is not built"); return VZ_ERR_UNSUPPORTED; }
+    if (enable && (e->share.on || e->beam.on || e->spec.on)) {
+        vz_set_error("kv_fp8: disarm the shared-prefix attention, the beam and the speculative tail first (they read and write the bf16 cache only)");
+        return VZ_ERR_STATE;
+    }
+    VZ_CHECK_HIP(hipDeviceSynchronize());
+    RC(drop_decode_graph(e));
+    if (!enable) {
+        if (e->kv8.q) VZ_CHECK_HIP(hipFree(e->kv8.q));
+        if (e->kv8.sc) VZ_CHECK_HIP(hipFree(e->kv8.sc));
+        e->kv8.q = nullptr; e->kv8.sc = nullptr; e->kv8.on = 0; e->kv8.valid.clear();
+        return VZ_OK;
+    }
+    const size_t bytes = e->kv_layer_elems * e->c.n_layers;
+    if (!e->kv8.q) {
+        hipError_t er = hipMalloc((void**)&e->kv8.q, bytes);
+        if (er == hipSuccess) er = hipMalloc((void**)&e->kv8.sc, bytes / e->c.head_dim * sizeof(float));
+        if (er != hipSuccess) {
+            if (e->kv8.q) (void)hipFree(e->kv8.q);
+            e->kv8.q = nullptr; e->kv8.sc = nullptr; e->kv8.on = 0;
+            vz_set_error("kv_fp8: hipMalloc of the %zu-byte mirror failed: %s", bytes + bytes / e->c.head_dim * sizeof(float), hipGetErrorString(er));
+            return VZ_ERR_HIP;
+        }
+    }
+    VZ_CHECK_HIP(hipMemset(e->kv8.q, 0, bytes));
+    VZ_CHECK_HIP(hipMemset(e->kv8.sc, 0, bytes / e->c.head_dim * sizeof(float)));
+    e->kv8.valid.assign(e->c.max_batch, 0);
+    e->kv8.on = 1;
     return VZ_OK;
 }
 

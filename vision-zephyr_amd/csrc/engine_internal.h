@@ -78,8 +78,9 @@ struct DecodeGraphKey {
     float cfg_scale; int cfg_pairs;      // classifier-free guidance between the logits and the processors (zero when off)
     int proc_rows_on, stop_rows_on;      // the per-row processors / per-row stop sequences: mode bits only - their tables are engine-owned, stable device memory read through pointers
     int share_n, share_nsplit; const int* share_tab;      // the shared-prefix attention (vz_llm_decode_share): rows per group, key splits, the `shared` table (zero when off)
+    const unsigned char* kv8;            // the e4m3 KV mirror the decode attention streams (vz_engine_kv_fp8; null when off)
 };
-static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 + 2 * 4 + 2 * 4 + 8 &&
+static_assert(sizeof(DecodeGraphKey) == 6 * 4 + 3 * 8 + 4 + sizeof(SampleArgs) + sizeof(BeamArgs) + sizeof(SpecArgs) + 2 * 8 + sizeof(ProcArgs) + 4 + 3 * 8 + 2 * 4 + 8 + sizeof(StopArgs) + sizeof(BeamRowsArgs) + 2 * 4 + 2 * 4 + 2 * 4 + 8 + 8 &&
               sizeof(BeamRowsArgs) == 2 * 8 + 2 * 4 &&
               sizeof(BeamArgs) == 8 + 3 * 4 + sizeof(BeamEos) && sizeof(SpecArgs) == 5 * 8 + 7 * 4 + sizeof(BeamEos) + sizeof(RowSample), "padding in the graph key");
 
@@ -162,6 +163,10 @@ struct vz_engine {
     // queries [64][Hq][D], ws = the prefix partials - the engine's own allocations, made on the first arming, never carved from the arena
     struct { int on = 0, n = 0, groups = 0, shared_max = 0; std::vector<int> h_shared; int* d_tab = nullptr; bf16_t* q_rot = nullptr;
              float* ws = nullptr; size_t ws_floats = 0; } share;
+    // e4m3 mirror of the KV cache for the decode attention (vz_engine_kv_fp8; attn_decode_kv8.hip): q = the cache's rows
+    // as bytes at the bf16 cache's element offsets, sc = one fp32 power-of-two scale per 128-value row (offset / 128); the engine's own
+    // allocations.  valid[row] = the row's mirror was (re)built by a prefill or a kv_move since the mirror was enabled
+    struct { int on = 0; unsigned char* q = nullptr; float* sc = nullptr; std::vector<char> valid; } kv8;
     struct { int* p = nullptr; int n = 0, rows = 0; } ring;   // host-visible token ring of the streamer path (vz_llm_decode_ring): [rows][n]
     hipStream_t last_stream = nullptr;   // stream of the last stage call (vz_engine_async_error resets that stream's stream-K tickets)
     int dec_captures = 0;        // graphs captured since the engine was created (vz_llm_decode_info)

@@ -347,6 +347,30 @@ size_t vz_attn_decode_part_floats(int B, int Hkv, int nsplit);   // [B][Hkv][nsp
 // `step` = the decode call's device-side step counter
 int vz_launch_attn_o_fused(const AttnDecodeFusedArgs& a, const bf16_t* o_w, const unsigned char* o_w8, const float* o_scale, bf16_t* att_scratch,
                            bf16_t* x, unsigned* done, const int* step, int layer, int n_layers, int* err, hipStream_t s);
+// attn_decode_kv8.hip: the same step over the e4m3 mirror of the cache - slots < slot from k8 / v8 [B][Hkv][max_ctx][D]
+// bytes with the scales ks / vs [B][Hkv][max_ctx], the new token's row in bf16; the new row is appended to the bf16 cache AND to the mirror
+struct AttnDecodeKv8Args {
+    const bf16_t* qkv;
+    bf16_t *kc, *vc, *o;
+    unsigned char *k8, *v8;
+    float *ks, *vs;
+    float* part;           // vz_attn_decode_part_floats
+    unsigned* ticket;      // [B*Hkv], zeroed once
+    const float *cosT, *sinT;
+    const int *pos, *slot;
+    int B, Hq, Hkv, D, max_ctx, nsplit, window;
+    float scale;
+};
+int vz_launch_attn_decode_kv8(const AttnDecodeKv8Args& a, hipStream_t s);
+// the mirror's writer: slots [0, len[i]) of cache row row[i], i < n <= 64, n_layers layers (layer_elems elements apart), K (index 0) and V (1).
+// src = the bf16 rows [.][Hkv][max_ctx][128], q = their e4m3 bytes at the same offsets, sc = one fp32 scale per 128-value row
+struct Kv8MirrorArgs {
+    const bf16_t* src[2]; unsigned char* q[2]; float* sc[2];
+    size_t layer_elems;
+    int n_layers, Hkv, max_ctx, n;
+    int row[64], len[64];
+};
+int vz_launch_kv8_mirror_rows(const Kv8MirrorArgs& a, hipStream_t s);
 
 
 int vz_launch_rope_kv(const bf16_t* qkv, int ld, bf16_t* q_out, bf16_t* kc, bf16_t* vc, const float* cosT,

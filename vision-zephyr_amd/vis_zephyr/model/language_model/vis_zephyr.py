@@ -114,13 +114,13 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
 
     def __init__(self, config, device: Union[str, torch.device] = "cuda:0", max_batch: int = 1,
                  max_ctx: int = 4096, max_tiles: int = 8, max_text: int = 2048, engine: Optional[Engine] = None,
-                 tp_size: int = 1, tp_rank: int = 0, weight_fp8: bool = False, weight_nf4: bool = False):
+                 tp_size: int = 1, tp_rank: int = 0, weight_fp8: bool = False, weight_nf4: bool = False, kv_fp8: bool = False):
         self.config = config
         self.arch = arch_from_config(config)
         self.engine = engine if engine is not None else Engine(self.arch, device=device, max_batch=max_batch,
                                                                max_ctx=max_ctx, max_tiles=max_tiles,
                                                                max_text=max_text, tp_size=tp_size, tp_rank=tp_rank,
-                                                               weight_fp8=weight_fp8, weight_nf4=weight_nf4)
+                                                               weight_fp8=weight_fp8, weight_nf4=weight_nf4, kv_fp8=kv_fp8)
         self.device = self.engine.device
         self.dtype = torch.bfloat16
         self.model = VisZephyrModel(config, self)
@@ -164,7 +164,7 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         if isinstance(device_map, dict) and "" in device_map:          # ref builder.py:29-31: device_map = {"": device}
             device = device_map[""]
         dev = "cuda:0" if str(device) == "cuda" else device
-        engine_kw = {k: kw.pop(k) for k in ("max_batch", "max_ctx", "max_tiles", "max_text", "tp_size", "tp_rank", "weight_fp8", "weight_nf4") if k in kw}
+        engine_kw = {k: kw.pop(k) for k in ("max_batch", "max_ctx", "max_tiles", "max_text", "tp_size", "tp_rank", "weight_fp8", "weight_nf4", "kv_fp8") if k in kw}
         model = cls(config, device=dev, **engine_kw)
         for name, t in W.iter_backbone(path):
             model.engine.add_weight(name, t)
@@ -335,6 +335,11 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, images=None, images_size=None, **kwargs):
         self._ensure_ready()
+        if self.engine.kv_fp8:      # the e4m3 KV mirror (vz_hip/kv8.py): what its step does not build is refused before anything runs
+            from vz_hip import kv8 as KV8
+            KV8.check_call(kwargs.get("num_beams"), bool(kwargs.get("share_prompt_kv")))
+            if "prompt_lookup_num_tokens" in kwargs:      # without effect: the plain path
+                kwargs["prompt_lookup_num_tokens"] = KV8.lookup_effective(True, kwargs["prompt_lookup_num_tokens"])
         if kwargs.get("share_prompt_kv"):      # what the shared-prefix route does not build is refused here, before anything runs
             from vz_hip import share as SH
             scale = kwargs.get("guidance_scale", getattr(self.generation_config, "guidance_scale", None))
@@ -540,7 +545,11 @@ class VisZephyrForCausalLM(VisZephyrMetaForCausalLM):
         under one seed can differ at a near-tie; processors, per-row sampling, scores / log-probs and device stops work as on the copy
         route.  Opt-in: absent or False, the call is the copy route, untouched.  With `num_beams > 1`, `guidance_scale`,
         `past_key_values`, `prompt_lookup_num_tokens`, a tensor-parallel engine or `num_return_sequences == 1` the keyword raises
-        NotImplementedError before anything runs."""
+        NotImplementedError before anything runs.
+
+        A model built with `kv_fp8=True` (vz_hip/kv8.py; csrc/attn_decode_kv8.hip) decodes from the e4m3 mirror of
+        its KV cache: `num_beams > 1` and `share_prompt_kv=True` raise NotImplementedError before anything runs,
+        `prompt_lookup_num_tokens` takes the plain path, every other keyword works as without it."""
         from vz_hip import logits_proc, sample_rows
         from vz_hip import scores as SC
         from vz_hip import stop as ST

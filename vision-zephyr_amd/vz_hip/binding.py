@@ -108,6 +108,10 @@ SYMBOLS = {
     "vz_op_rope_kv": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vz_op_attention_decode": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "vz_op_attention_decode_fused": (_I, [_P] * 10 + [_I] * 7 + [_F, _P]),
+    "vz_op_attention_decode_kv8": (_I, [_P] * 14 + [_I] * 7 + [_F, _P]),
+    "vz_op_kv8_mirror_rows": (_I, [_P] * 6 + [_I, _P, _P, _I, _I, _I, _P]),
+    "vz_engine_kv_fp8": (_I, [_P, _I]),
+    "vz_llm_kv8_copy_out": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _P]),
     "vz_engine_create": (_I, [C.POINTER(VzConfig), C.POINTER(_P)]),
     "vz_engine_destroy": (_I, [_P]),
     "vz_engine_ws_info": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -1071,6 +1075,43 @@ def attention_decode_fused(qkv, kcache, vcache, cos, sin, pos, slot, Hq, scale, 
     check(lib().vz_op_attention_decode_fused(ptr(qkv), ptr(kcache), ptr(vcache), ptr(o), ptr(ws), ptr(ticket), ptr(cos),
                                              ptr(sin), ptr(pos), ptr(slot), Bn, Hq, Hkv, D, max_ctx, nsplit, window,
                                              float(scale), stream_ptr(qkv.device)))
+    return o, ticket
+
+
+def kv8_mirror_rows(kcache, vcache, k8, v8, ks, vs, rows, lens):
+    """The e4m3 mirror's writer on caller buffers (attn_decode_kv8.hip): slots [0, lens[i]) of cache rows rows[i] (<= 64 of them) of the bf16
+    caches [R,Hkv,max_ctx,128] are quantised into k8 / v8 uint8 (same shape) and ks / vs fp32 [R,Hkv,max_ctx], in place; every other slot
+    is left untouched."""
+    _need_cuda(kcache, vcache, k8, v8, ks, vs)
+    R, Hkv, max_ctx, D = kcache.shape
+    rows, lens = [int(r) for r in rows], [int(n) for n in lens]
+    assert kcache.dtype == torch.bfloat16 and vcache.dtype == torch.bfloat16 and kcache.is_contiguous() and vcache.is_contiguous() and vcache.shape == kcache.shape
+    assert k8.dtype == torch.uint8 and v8.dtype == torch.uint8 and k8.is_contiguous() and v8.is_contiguous() and k8.shape == kcache.shape and v8.shape == kcache.shape
+    assert ks.dtype == torch.float32 and vs.dtype == torch.float32 and ks.is_contiguous() and vs.is_contiguous() and tuple(ks.shape) == (R, Hkv, max_ctx) and vs.shape == ks.shape
+    assert len(rows) == len(lens) and 1 <= len(rows) <= 64 and all(0 <= r < R for r in rows) and all(0 <= n <= max_ctx for n in lens)
+    arr = lambda v: (C.c_int * len(v))(*v)    # noqa: E731
+    check(lib().vz_op_kv8_mirror_rows(ptr(kcache), ptr(vcache), ptr(k8), ptr(v8), ptr(ks), ptr(vs), len(rows), arr(rows), arr(lens), Hkv, D, max_ctx,
+                                      stream_ptr(kcache.device)))
+
+
+def attention_decode_kv8(qkv, kcache, vcache, k8, v8, ks, vs, cos, sin, pos, slot, Hq, scale, nsplit=32, window=0, ticket=None, out=None):
+    """attention_decode_fused over the e4m3 mirror (attn_decode_kv8.hip): qkv bf16 [B,(Hq+2Hkv)*D] -> o [B,Hq,D].  Slots < slot[b] are read
+    from k8 / v8 uint8 [B,Hkv,max_ctx,128] with the scales ks / vs fp32 [B,Hkv,max_ctx]; the new token's row is used in bf16 and appended
+    to the bf16 caches and, quantised, to the mirror, in place."""
+    _need_cuda(qkv, kcache, vcache, k8, v8, ks, vs, cos, sin, pos, slot)
+    Bn, Hkv, max_ctx, D = kcache.shape
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and tuple(qkv.shape) == (Bn, (Hq + 2 * Hkv) * D)
+    assert kcache.dtype == torch.bfloat16 and kcache.is_contiguous() and vcache.is_contiguous() and vcache.shape == kcache.shape
+    assert k8.dtype == torch.uint8 and v8.dtype == torch.uint8 and k8.is_contiguous() and v8.is_contiguous() and k8.shape == kcache.shape and v8.shape == kcache.shape
+    assert ks.dtype == torch.float32 and vs.dtype == torch.float32 and ks.is_contiguous() and vs.is_contiguous() and tuple(ks.shape) == (Bn, Hkv, max_ctx) and vs.shape == ks.shape
+    assert pos.dtype == torch.int32 and slot.dtype == torch.int32 and pos.numel() == Bn and slot.numel() == Bn
+    ws = torch.empty(Bn * Hkv * nsplit * (4 * D + 32), dtype=torch.float32, device=qkv.device)
+    if ticket is None:
+        ticket = torch.zeros(Bn * Hkv, dtype=torch.int32, device=qkv.device)
+    o = torch.empty(Bn, Hq, D, dtype=torch.bfloat16, device=qkv.device) if out is None else out
+    assert o.dtype == torch.bfloat16 and o.is_contiguous() and tuple(o.shape) == (Bn, Hq, D)
+    check(lib().vz_op_attention_decode_kv8(ptr(qkv), ptr(kcache), ptr(vcache), ptr(k8), ptr(v8), ptr(ks), ptr(vs), ptr(o), ptr(ws), ptr(ticket), ptr(cos),
+                                           ptr(sin), ptr(pos), ptr(slot), Bn, Hq, Hkv, D, max_ctx, nsplit, window, float(scale), stream_ptr(qkv.device)))
     return o, ticket
 
 

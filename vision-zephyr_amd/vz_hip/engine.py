@@ -40,7 +40,7 @@ def rope_tables(cfg: ArchConfig, max_pos: int) -> Tuple[torch.Tensor, torch.Tens
 class Engine:
     def __init__(self, cfg: ArchConfig, device="cuda:0", max_batch: int = 1, max_ctx: int = 4096,
                  max_tiles: int = 8, max_text: int = 2048, tp_size: int = 1, tp_rank: int = 0, weight_fp8: bool = False,
-                 weight_nf4: bool = False):
+                 weight_nf4: bool = False, kv_fp8: bool = False):
         self.lib = B.load_library()            # raises when the HIP library is absent: no fallback
         self._qf_kv_pool = {}
         if not torch.cuda.is_available():
@@ -81,6 +81,35 @@ class Engine:
         self._score = None                     # the step recorder's rings and step count while armed (set_scores)
         self._guid = None                      # the armed vz_hip.guidance.GuidanceConfig (set_guidance)
         self._beam_rows = None                 # the beam tail's row rings while armed (set_beam_rows)
+        self.kv_fp8 = False
+        if kv_fp8:
+            self.set_kv_fp8(True)
+
+    def set_kv_fp8(self, on: bool = True):
+        """The opt-in e4m3 mirror of the KV cache (vz_hip.kv8): on, the decode attention streams one byte per cached K / V
+        element plus one scale per 128 instead of two bytes, at +50 % KV memory (the bf16 cache stays for the prefills).  Switching it on
+        invalidates every row's mirror: a row decodes again after a prefill or a kv_move_rows into it.  Beams, share_prompt_kv and
+        speculative steps are refused while it is on.  Off by default: every call is the plain engine's."""
+        from . import kv8 as KV8
+        if on:
+            KV8.check_engine(self.tp_size)
+        B.check(self.lib.vz_engine_kv_fp8(self.h, int(bool(on))))
+        self.kv_fp8 = bool(on)
+
+    def kv8_mirror(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """a copy of the whole e4m3 mirror: (uint8 [n_layers, 2 (K|V), max_batch, kv heads, max_ctx, head_dim], fp32 scales
+        [n_layers, 2, max_batch, kv heads, max_ctx]) (tests)."""
+        from . import kv8 as KV8
+        if not self.kv_fp8:
+            raise RuntimeError("kv8_mirror: the e4m3 KV mirror is off (Engine(kv_fp8=True) / set_kv_fp8)")
+        qs, ss = KV8.mirror_shape(self.cfg, self.max_batch, self.max_ctx, self.tp_size)
+        q = torch.empty(qs, dtype=torch.uint8, device=self.device)
+        sc = torch.empty(ss, dtype=torch.float32, device=self.device)
+        nq, ns = C.c_size_t(0), C.c_size_t(0)
+        B.check(self.lib.vz_llm_kv8_copy_out(self.h, None, 0, None, 0, C.byref(nq), C.byref(ns), self._s()))
+        assert q.numel() == nq.value and sc.numel() == ns.value
+        B.check(self.lib.vz_llm_kv8_copy_out(self.h, B.ptr(q), nq.value, B.ptr(sc), ns.value, C.byref(nq), C.byref(ns), self._s()))
+        return q, sc
 
     def set_prefill_fp8(self, on: bool = True):
         """weight_fp8 engines: run the Zephyr prefill linears on the fp8 MFMA (activations quantised to e4m3 per row on the device,
